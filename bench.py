@@ -9,6 +9,7 @@ is copied back and compared with the CPU oracle; a mismatch fails the run.  The 
 and BASELINE config 2 (grayscale + blur) are measured next to it as extra keys.
 
   python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ what the last timed step returned, as DIR/*.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  Images are independent, so ranks never exchange pixels (weak
@@ -263,6 +264,46 @@ def verify_sample(fl, st, src, dst, out_stride, results, params, plan, fe_name, 
     return len(picks), None, off / max(total, 1)
 
 
+DUMP_BUDGET = 64 << 20    # bytes --dump-outputs may write in all
+DUMP_SAMPLE = 256         # images of the batch whose output bytes are written
+DUMP_SEED = 0xD0A7
+
+
+def dump_outputs(out_dir, dsts_c, row):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in `out_dir` (bench inputs are seeded, so
+    two builds run with the same arguments can be compared file for file):
+      output_bytes.npy  float64 [n]     bytes written for every image of the batch (flgpu_image.bytes)
+      output_meta.npy   float64 [n, 4]  width, height, channels and FLGPU_IMG_* flags of every result
+      sample_index.npy  float64 [k]     the sampled images: a permutation of the batch seeded by DUMP_SEED, cut where the next
+                                        image's bytes would exceed the budget (at most DUMP_SAMPLE images)
+      outputs.npy       float32 [total] the sampled images' output bytes (JPEG streams, or pixels without a front end),
+                                        concatenated in sample order; output_bytes[sample_index] cuts them apart
+    `row(i)` returns image i's destination as a 1-D uint8 tensor.  Returns the number of images sampled."""
+    import numpy as np
+    n = len(dsts_c)
+    nbytes = np.array([d.bytes for d in dsts_c], dtype=np.float64)
+    meta = np.array([(d.width, d.height, d.channels, d.flags) for d in dsts_c], dtype=np.float64).reshape(n, 4)
+    room = (DUMP_BUDGET - 4 * 128 - nbytes.nbytes - meta.nbytes - 8 * DUMP_SAMPLE) // 4   # (128 = an .npy header)
+    picks, used = [], 0
+    for i in np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_SAMPLE]:
+        if used + int(nbytes[i]) > room:
+            break
+        picks.append(int(i))
+        used += int(nbytes[i])
+    data = np.empty(used, dtype=np.float32)
+    at = 0
+    for i in picks:
+        b = int(nbytes[i])
+        data[at:at + b] = row(i)[:b].cpu().numpy()
+        at += b
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output_bytes.npy"), nbytes)
+    np.save(os.path.join(out_dir, "output_meta.npy"), meta)
+    np.save(os.path.join(out_dir, "sample_index.npy"), np.array(picks, dtype=np.float64))
+    np.save(os.path.join(out_dir, "outputs.npy"), data)
+    return len(picks)
+
+
 def synthetic_jpeg_files(count=4):
     """Photo-like 1920x1080 baseline JPEGs (quality 85, 4:2:0 -- what a web origin typically serves) for the JPEG-source
     latency probe; written to a temporary directory."""
@@ -471,7 +512,7 @@ def main_one_context(args):
     out_stride = (int(plan.max_out_bytes) + 255) // 256 * 256
     shapes = [(SRC_H, SRC_W, SRC_C)] * n
     shard_of, shard_bytes = fl.plan_shards(N, shapes, params)
-    srcp, dstp, keep = [0] * n, [0] * n, []
+    srcp, dstp, keep, row_of = [0] * n, [0] * n, [], [None] * n
     for k in range(N):
         idx = [i for i in range(n) if int(shard_of[i]) == k]
         dev = torch.device("cuda", devices[k])
@@ -485,6 +526,7 @@ def main_one_context(args):
         for j, i in enumerate(idx):
             srcp[i] = s_k.data_ptr() + j * src_bytes
             dstp[i] = d_k.data_ptr() + j * out_stride
+            row_of[i] = (d_k, j)
     st = fl.State(devices=devices, profile=True) if N > 1 else fl.State(device=devices[0], profile=True)
     run = st.prepared_batch(srcp, shapes, params, dstp, [out_stride] * n)
 
@@ -505,6 +547,7 @@ def main_one_context(args):
     ok, err = 1, None
     srcs_c, dsts_c, _ = run._keep   # (collected whatever the front end: a device-side failure of the batch comes back here)
     fl._check(st._lib.flgpu_batch_results(st._ctx, n, dsts_c), st._ctx)
+    dumped = dump_outputs(args.dump_outputs, dsts_c, lambda i: row_of[i][0][row_of[i][1]]) if args.dump_outputs else None
     if fe == fl.FE_JPEG and any(d.bytes == 0 for d in dsts_c):
         ok, err = 0, "an encoded stream did not fit its destination"
     launches = max(int(stats["resample_launches"]), 1)
@@ -532,6 +575,8 @@ def main_one_context(args):
                                                               "jpeg": fe == fl.FE_JPEG, "quality": args.quality}, args.cpu_threads)
     if err:
         line["error"] = err
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "images": n, "sampled_images": dumped}
     print(json.dumps(line), flush=True)
     st.close()
     if not ok:
@@ -566,7 +611,12 @@ def main():
     ap.add_argument("--config3-share", type=int, default=8192, help="pictures of BASELINE config 3's per-GPU share run as one device batch (an `extra` entry; 0 = skip)")
     ap.add_argument("--queue-lanes", type=int, default=0, help="batches the request queue keeps in flight (0 = library default)")
     ap.add_argument("--queue-max-batch", type=int, default=0, help="largest batch the request queue forms (0 = library default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's batch; a seeded sample of its bytes, "
+                         "at most 64 MB) to DIR/*.npy, see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.one_context:
         return main_one_context(args)
 
@@ -656,6 +706,7 @@ def main():
     # kernel's bounded LDS waits -- comes back as FLGPU_ERR_DEVICE)
     srcs_c, dsts_c, _ = run._keep
     fl._check(st._lib.flgpu_batch_results(st._ctx, n, dsts_c), st._ctx)
+    dumped = dump_outputs(args.dump_outputs, dsts_c, lambda i: dst[i]) if args.dump_outputs and rank == 0 else None
     if fe == fl.FE_JPEG:
         results = [(d.flags, d.bytes) for d in dsts_c]
         if any(b == 0 for _, b in results):
@@ -781,6 +832,8 @@ def main():
         }
         if verr:
             line["error"] = verr
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "images": n, "sampled_images": dumped}
         if results is not None:
             line["mean_stream_bytes"] = sum(b for _, b in results) / max(len(results), 1)
         line["roofline"]["traffic"] = measured_traffic(line["config"]["workload"])

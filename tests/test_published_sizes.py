@@ -1,16 +1,15 @@
 """The only output facts the reference publishes (README.md:111-127): mean response sizes of
 `GET /lenna.jpg?w=300&h=200` (JPEG, 16,021 B) and `...&webp=true&quality=20` (lossy WebP, 2,684 B).  They depend on
 the whole chain -- decode, Lanczos3 resize to 200x200, letterbox to 300x200, encoder -- so they make a coarse but
-independent anchor for the oracle's restatement of that chain.  Runs only where the reference checkout (its
-images/lenna.jpg) is present, i.e. in the build container; never on the GPU box."""
+independent anchor for the oracle's restatement of that chain.  The picture is the committed copy of the reference's
+images/lenna.jpg (tests/golden/lenna_reference.jpg; test_jpeg_decode.py pins its hash)."""
 import os
 
 import numpy as np
 import pytest
 
-LENNA = "/root/reference/images/lenna.jpg"
+LENNA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lenna_reference.jpg")
 PIL = pytest.importorskip("PIL.Image")
-pytestmark = pytest.mark.skipif(not os.path.exists(LENNA), reason="reference checkout not present")
 
 
 @pytest.fixture(scope="module")

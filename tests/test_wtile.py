@@ -1,6 +1,6 @@
 """The window-tile matrix-pipe kernel (csrc/fl_wtile.h): mild down-scales and Gaussian blurs at the full-width arithmetic.
 Reference: image 0.25.6 imageops/sample.rs vertical_sample + horizontal_sample behind resize_exact and blur
-(/root/reference/src/handler.rs:229-255).
+(the reference's src/handler.rs:229-255).
 
 Without a device: the kernel's own tables, run operand for operand on the host (oracle/wtile_model.cpp), against the oracle --
 that pins the table builder (windows, f16 terms, byte digits, strips) and the arithmetic's error budget.  With a device: the
