@@ -7,14 +7,15 @@
 // all sampling factors 1x1, Annex K quantisation tables scaled by quality, Annex K Huffman tables.
 //
 // Two kernels per batch:
-//   jpeg_dct_quant_kernel   one wave per 8x8 block (a wave walks through 8 consecutive blocks): the 64 lanes are the
-//                           64 samples / coefficients.  The integer DCT of transform.rs (IJG jfdctint) is linear up
-//                           to the final shift of each pass, so a lane computes ITS coefficient as an 8-term integer
-//                           dot product with a constant matrix derived at compile time from the butterfly itself
-//                           (int32 wrap-around arithmetic is a ring: the sums are identical bit for bit).  The same
-//                           wave then Huffman-codes the block's AC coefficients: lane k = zig-zag coefficient k, a
-//                           ballot gives every lane its zero run, a DPP prefix sum places the code words, LDS
-//                           atomics assemble them.  Out: quantised DC, AC bit count, AC bits (from bit 0).
+//   jpeg_dct_quant_kernel   one wave per 16 consecutive blocks, in two phases.  Transform: block after block, the 64
+//                           lanes are the 64 samples / coefficients.  The integer DCT of transform.rs (IJG jfdctint) is
+//                           linear up to the final shift of each pass, so a lane computes ITS coefficient as an 8-term
+//                           integer dot product with a constant matrix derived at compile time from the butterfly itself
+//                           (int32 wrap-around arithmetic is a ring: the sums are identical bit for bit); lane k owns
+//                           zig-zag coefficient k, so the quantised units land in LDS in coding order, with a ballot of
+//                           their non-zero AC terms.  Coding: each lane Huffman-codes whole units on its own, walking
+//                           the set bits of the unit's mask (lane 16 k + b: component k of block b).
+//                           Out: quantised DC, AC bit count, AC bits (from bit 0).
 //   jpeg_pack_kernel        one workgroup per picture: DC code sizes (they need the previous block) + AC sizes ->
 //                           exclusive scan -> bit offset of every block; the blocks' bits are shifted into place in an
 //                           LDS window of the stream (atomics), then pad_byte, 0xFF -> 0xFF00 stuffing by a second
@@ -101,10 +102,16 @@ __device__ __forceinline__ int32_t dot8_i16(const uint32_t m[4], const uint4 v)
     return __builtin_amdgcn_sdot2(as_i16x2(m[3]), as_i16x2(v.w), p, false);
 }
 
-// natural index -> zig-zag position (inverse of encoder.rs UNZIGZAG)
-__constant__ uint8_t kZigzagPos[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
-                                       41, 43, 9,  11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38,
-                                       46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+// zig-zag position -> natural index (encoder.rs UNZIGZAG): the transform gives lane k the sample and coefficient of natural
+// index kNatural[k], so that its quantised result is zig-zag coefficient k without an exchange
+struct NaturalOrder { uint8_t n[64]; };
+constexpr NaturalOrder make_natural()
+{
+    NaturalOrder t{};
+    for (int k = 0; k < 64; ++k) t.n[k] = kUnzigzag[k];
+    return t;
+}
+__constant__ NaturalOrder kNatural = make_natural();
 
 // Annex K Huffman tables (fl_jpeg_tables.h) expanded to (length << 16 | code) at compile time -- encoder.rs build_huff_lut
 struct HuffLut { uint32_t e[256]; };
@@ -182,156 +189,121 @@ __device__ __forceinline__ uint32_t coef_size(int32_t v) // encode_coefficient: 
     return mag ? 32u - (uint32_t)__clz(mag) : 0u;
 }
 
-// Huffman coding of one block's AC coefficients by one wave (BitWriter::write_block without the DC term): lane k
-// holds zig-zag coefficient k (lane 0, the DC term, does not take part).  A non-zero lane emits its (run, size)
-// code and value bits, preceded by ZRL codes when the zero run in front of it exceeds 15; lane 63 emits the
-// end-of-block code when coefficient 63 is zero.  The code words are OR-ed into `tu` (LDS, zero on entry) from
-// bit 0, most significant bit first.  Returns the number of bits.  ac = the component's 256-entry table in LDS;
-// lt_lo / lt_hi = mask of the lanes below this one.
-__device__ __forceinline__ uint32_t code_ac_block(int32_t zv, uint32_t lane, uint32_t lt_lo, uint32_t lt_hi, const uint32_t *ac,
-                                                  uint32_t *tu)
-{
-    const bool nz = zv != 0 && lane != 0u;
-    const uint64_t mask = __ballot(nz);
-    const uint32_t eob = ac[0];
-    if (mask == 0ull) { // DC-only block (wave-uniform): just the end-of-block code
-        if (lane == 0u) tu[0] = (eob & 0xffffu) << (32u - (eob >> 16));
-        return eob >> 16;
-    }
-    const uint32_t mag = (uint32_t)(zv < 0 ? -zv : zv);
-    const uint32_t size = mag ? 32u - (uint32_t)__clz(mag) : 0u;               // encode_coefficient
-    const uint32_t value = (uint32_t)(zv + (zv >> 31)) & ((1u << size) - 1u);  // negative: (v - 1) & mask
-    const uint32_t lo = (uint32_t)mask & lt_lo, hi = (uint32_t)(mask >> 32) & lt_hi;
-    const uint32_t prev = hi ? 63u - (uint32_t)__clz(hi) : (lo ? 31u - (uint32_t)__clz(lo) : 0u); // previous coded coefficient
-    const uint32_t run = lane - prev - 1u;
-    uint32_t nb = 0, code = 0;
-    if (nz) {
-        const uint32_t e = ac[((run & 15u) << 4) | size];
-        nb = (e >> 16) + size;                       // <= 16 + 10
-        code = ((e & 0xffffu) << size) | value;
-    } else if (lane == 63u) {
-        nb = eob >> 16;
-        code = eob & 0xffffu;
-    }
-    if (__ballot(nz && run > 15u) == 0ull) {
-        // common case, no ZRL anywhere in the block: every lane's code fits one 32-bit word
-        const uint32_t inc = wave_inclusive_scan(nb, lane);
-        if (nb) {
-            const uint32_t p = inc - nb, wi = p >> 5, sh = p & 31u;
-            const uint32_t left = code << (32u - nb);
-            const uint32_t w1 = (left << 1) << (31u - sh);
-            atomicOr(&tu[wi], left >> sh);
-            if (w1) atomicOr(&tu[wi + 1u], w1);
-        }
-        return (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-    }
-    // "while zero_run > 15 { huffman_encode(0xF0) }": up to three ZRL codes in front, 59 bits in all
-    uint64_t bits = code;
-    if (nz) {
-        const uint32_t zrl = ac[0xF0], zl = zrl >> 16, zc = zrl & 0xffffu;
-        uint64_t pre = 0;
-        uint32_t pl = 0;
-        for (uint32_t i = 0; i < (run >> 4); ++i) { pre = (pre << zl) | zc; pl += zl; }
-        bits |= pre << nb;
-        nb += pl;
-    }
-    const uint32_t inc = wave_inclusive_scan(nb, lane);
-    if (nb) {
-        const uint32_t p = inc - nb, wi = p >> 5, sh = p & 31u;
-        const uint64_t left = bits << (64u - nb);
-        const uint64_t a = left >> sh;
-        const uint32_t w0 = (uint32_t)(a >> 32), w1 = (uint32_t)a, w2 = sh ? (uint32_t)((left << (64u - sh)) >> 32) : 0u;
-        if (w0) atomicOr(&tu[wi], w0);
-        if (w1) atomicOr(&tu[wi + 1u], w1);
-        if (w2) atomicOr(&tu[wi + 2u], w2);
-    }
-    return (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-}
+// ---------------------------------------------------------------- kernel 1: colour + FDCT + quantise + AC Huffman coding --
 
-// ---------------------------------------------------------------- kernel 1: colour + FDCT + quantise (+ AC bit count) --
+// Blocks per wave: 16 (lanes 16 k + b code component k of block b) or 32 (lanes b / 32 + b: block b's Y / Cb + Cr units).
+// 32 uses every lane in the coding phase but needs 13.5 KB of LDS per wave (2.5 waves per SIMD); 16 needs half of that and took
+// 307 us against 394 us per 1024 pictures (profiles/pr_jpeg_unit_coder.txt).  `make EXTRA="-DFL_JPEG_BPW=32 ..."` for the A/B.
+#ifndef FL_JPEG_BPW
+#define FL_JPEG_BPW 16
+#define FL_JPEG_WPG 2
+#define FL_JPEG_PREFETCH 3
+#endif
+constexpr uint32_t kBlocksPerWave = FL_JPEG_BPW;
+constexpr uint32_t kWavesPerWg = FL_JPEG_WPG;
+constexpr uint32_t kPrefetch = FL_JPEG_PREFETCH;       // blocks whose pixels are loaded ahead
+static_assert(kBlocksPerWave == 32u || kBlocksPerWave == 16u, "the coding phase's lane mapping");
+constexpr uint32_t kJpegThreads = 64u * kWavesPerWg;
+constexpr uint32_t kBlocksPerWg = kWavesPerWg * kBlocksPerWave;
+constexpr uint32_t kUnitsPerWave = 3u * kBlocksPerWave;
 
-constexpr int kBlocksPerWave = 8;                       // consecutive blocks one wave walks through
-constexpr int kBlocksPerWg = 4 * kBlocksPerWave;
+// The longest AC code of a unit: 63 non-zero coefficients, each a (run, size) code of at most 16 bits and at most 10 value bits
+// (|AC| <= 1023 for 8-bit samples), no end-of-block code behind coefficient 63.  Fewer coefficients are shorter: a ZRL (10-11
+// bits) stands for 16 zero positions and an end-of-block code (2-4 bits) only follows a zero coefficient 63.
+static_assert(63u * (16u + 10u) <= kAcWordsPerUnit * 32u, "a unit's AC code must fit its acbits slot");
+
+// Per wave: the quantised coefficients of kBlocksPerWave blocks (zig-zag order, DC first) and their non-zero AC masks, written
+// by the transform phase and read by the coding phase; the transform's two exchange buffers for the three components.
+struct WaveLds {
+    int16_t coef[kUnitsPerWave][64];
+    uint64_t nz[kUnitsPerWave];                          // bit k: zig-zag coefficient k (k >= 1) is not zero
+    __attribute__((aligned(16))) int16_t smp[3][64];     // samples, natural order
+    __attribute__((aligned(16))) int16_t p1[3][64];      // pass-1 results, transposed
+};
 
 __device__ __forceinline__ void stage_ac_luts(uint32_t *s_ac)
 {
-    for (uint32_t i = threadIdx.x; i < 512u; i += 256u) s_ac[i] = kHuff.ac[i >> 8].e[i & 255u];
+    for (uint32_t i = threadIdx.x; i < 512u; i += kJpegThreads) s_ac[i] = kHuff.ac[i >> 8].e[i & 255u];
     __syncthreads();
 }
 
+// kRgba: every letterboxed picture, 4 channels at a 4-byte aligned address: one dword per pixel and no branch, so that the loads
+// of the blocks ahead stay in flight (behind the channel-count branches of load_rgba the compiler waits for every load at once)
+template <bool kRgba>
 __device__ __forceinline__ uint32_t block_pixel(const JpegJob &jb, uint32_t brow, uint32_t bcol, uint32_t r, uint32_t c)
 {
     // copy_blocks_ycbcr / pixel_at_or_near: pixels past the right / bottom edge repeat the last column / row
     uint32_t px = bcol * 8u + c, py = brow * 8u + r;
     px = px < jb.w ? px : jb.w - 1u;
     py = py < jb.h ? py : jb.h - 1u;
-    if (jb.c == 4u && (reinterpret_cast<uintptr_t>(jb.src) & 3u) == 0u) // every letterboxed picture: one dword per pixel
-        return reinterpret_cast<const uint32_t *>(jb.src)[(size_t)py * jb.w + px] & 0xffffffu;
+    // (a global, not a flat, load: a flat load also counts against the LDS waits, so each of them would wait for the pixels too;
+    // the caller drops the alpha byte when it takes the value, which keeps the load in flight until then)
+    if constexpr (kRgba) return ((const __attribute__((address_space(1))) uint32_t *)jb.src)[(size_t)py * jb.w + px];
     uint32_t pr, pg, pb, pa;
     load_rgba(jb.src + ((size_t)py * jb.w + px) * jb.c, jb.c, pr, pg, pb, pa);
     return pr | (pg << 8) | (pb << 16);
 }
 
-// Forward DCT + quantisation of one component of one block: lane (r, c) in, lane k = zig-zag coefficient k out.
-__device__ __forceinline__ int32_t dct_quant_unit(uint32_t sample, uint32_t lane, uint32_t r, uint32_t c, const uint32_t (&m1)[4], const uint32_t (&m2)[4],
-                                                  uint4 k1, uint32_t q, uint32_t magic, uint32_t zz, int16_t *ta16, int16_t *tb16, int32_t *ta)
+// Forward DCT + quantisation of the three components of one block, interleaved so that the LDS round trips of one component
+// overlap the arithmetic of the others.  Lane k holds the sample at natural index (r, c) = kNatural[k] and returns the
+// quantised coefficient of that index, i.e. zig-zag coefficient k.
+__device__ __forceinline__ void dct_quant_block(const uint32_t (&smp)[3], uint32_t nat, uint32_t r, uint32_t c, const uint32_t (&m1)[4],
+                                                const uint32_t (&m2)[4], uint4 k1, const uint32_t (&q)[3], const uint32_t (&magic)[3],
+                                                WaveLds &w, int32_t (&qv)[3])
 {
-    ta16[lane] = (int16_t)sample;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w.smp[k][nat] = (int16_t)smp[k];
     wave_lds_sync();
     // Pass 1 (rows): lane (r, c) produces horizontal frequency c of row r
-    const int32_t p = dot8_i16(m1, *reinterpret_cast<const uint4 *>(ta16 + r * 8)); // one 16-byte read: the row's 8 samples
-    // transform.rs: c = 0: (p - 8 * 128) << PASS1_BITS (level shift folded in), c = 4: p << PASS1_BITS, else (p + 2^10) >> 11
-    // (CONST_BITS - PASS1_BITS).  One form for all lanes, (p << s1 + a1) >> 11 with per-lane s1 = 13 or 0 (the sums of columns 0
-    // and 4 are below 2^12, so nothing is shifted out): no lane-dependent branches in a kernel whose time is its vector instructions.
-    const int32_t v1 = ((p << k1.x) + (int32_t)k1.y) >> 11;
-    tb16[c * 8 + r] = (int16_t)v1;                // |v1| <= 255 * 8 * 4; transposed: the column pass reads 8 consecutive values
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int32_t p = dot8_i16(m1, *reinterpret_cast<const uint4 *>(w.smp[k] + r * 8)); // one 16-byte read: the row's 8 samples
+        // transform.rs: c = 0: (p - 8 * 128) << PASS1_BITS (level shift folded in), c = 4: p << PASS1_BITS, else (p + 2^10) >> 11
+        // (CONST_BITS - PASS1_BITS).  One form for all lanes, (p << s1 + a1) >> 11 with per-lane s1 = 13 or 0 (the sums of columns 0
+        // and 4 are below 2^12, so nothing is shifted out): no lane-dependent branches.
+        const int32_t v1 = ((p << k1.x) + (int32_t)k1.y) >> 11;
+        w.p1[k][c * 8 + r] = (int16_t)v1;                 // |v1| <= 255 * 8 * 4; transposed: the column pass reads 8 consecutive values
+    }
     wave_lds_sync();
-    // Pass 2 (columns): lane (r, c) produces vertical frequency r of column c: rows 0 and 4 (p2 + 2) >> 2, else (p2 + 2^14) >> 15
-    const int32_t p2 = dot8_i16(m2, *reinterpret_cast<const uint4 *>(tb16 + c * 8));
-    const int32_t d = (p2 + (int32_t)k1.z) >> k1.w;
-    // encode_rgb "Quantization": ((d / 8) as f32 / f32::from(q)).round() as i32.  |d / 8| <= 2048 and q <= 255,
-    // so the f32 quotient cannot round onto or across a half (nearest miss: 1 / (2q) >= 2^-9 away, f32 error
-    // <= 2^-14): it equals the exact round-half-away  sign(n) * floor((2|n| + q) / 2q), taken with the
-    // per-coefficient reciprocal ceil(2^32 / 2q) from the table block (exact for 2|n| + q < 2^13).
-    // i32 division truncates toward zero: |d / 8| = |d| >> 3, and the sign of a non-zero quotient is d's.
-    const int32_t sg = d >> 31;
-    const uint32_t an = (uint32_t)((d ^ sg) - sg) >> 3;
-    const uint32_t rq = __umulhi(2u * an + q, magic);
-    const int32_t qv = ((int32_t)rq ^ sg) - sg;
-    // natural -> zig-zag order through LDS: lane k then owns zig-zag coefficient k
-    ta[zz] = qv;
-    wave_lds_sync();
-    const int32_t zv = ta[lane];
-    wave_lds_sync();
-    return zv;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // Pass 2 (columns): lane (r, c) produces vertical frequency r of column c: rows 0 and 4 (p2 + 2) >> 2, else (p2 + 2^14) >> 15
+        const int32_t p2 = dot8_i16(m2, *reinterpret_cast<const uint4 *>(w.p1[k] + c * 8));
+        const int32_t d = (p2 + (int32_t)k1.z) >> k1.w;
+        // encode_rgb "Quantization": ((d / 8) as f32 / f32::from(q)).round() as i32.  |d / 8| <= 2048 and q <= 255,
+        // so the f32 quotient cannot round onto or across a half (nearest miss: 1 / (2q) >= 2^-9 away, f32 error
+        // <= 2^-14): it equals the exact round-half-away  sign(n) * floor((2|n| + q) / 2q), taken with the
+        // per-coefficient reciprocal ceil(2^32 / 2q) from the table block (exact for 2|n| + q < 2^13).
+        // i32 division truncates toward zero: |d / 8| = |d| >> 3, and the sign of a non-zero quotient is d's.
+        const int32_t sg = d >> 31;
+        const uint32_t an = (uint32_t)((d ^ sg) - sg) >> 3;
+        const uint32_t rq = __umulhi(2u * an + q[k], magic[k]);
+        qv[k] = ((int32_t)rq ^ sg) - sg;
+    }
 }
 
-// One wave per block; the three components of a block are transformed one after the other, then Huffman-coded TOGETHER:
-// the kernel is bound by vector-instruction issue (97 % VALU, profiles/r03_jpeg_pmc.txt), a block's three 64-coefficient
-// units rarely hold more than a few dozen non-zero coefficients between them, and coding works on non-zero coefficients
-// only -- so they are compacted into one list (rank of a lane among its unit's non-zero lanes = v_mbcnt of the ballot), one
-// lane per code word: (run, size) lookup, value bits, ZRL prefixes, a segmented prefix sum for the bit positions and the LDS
-// ORs then run once per block instead of once per component.  A block with more than 64 code words (non-zero coefficients
-// plus end-of-block codes) takes the per-component path, code_ac_block, which is also what every stream is checked against
-// (the oracle encoder codes blocks the reference's way, one BitWriter call after the other).
-__global__ __launch_bounds__(256) void jpeg_dct_quant_kernel(const JpegJob *__restrict__ jobs, const uint32_t *__restrict__ arena,
-                                                             uint32_t job_base)
+typedef __attribute__((address_space(1))) uint32_t global_u32; // (global, not flat, stores: they do not count against the LDS waits)
+
+// Appends the `len` (<= 26) low bits of `code` to a lane's unit: full 32-bit words go to out[wi++], most significant bit first.
+struct UnitBits {
+    uint64_t acc;   // the low `pend` bits are pending (pend < 32 between calls)
+    uint32_t pend, total, wi;
+    global_u32 *out;
+    __device__ __forceinline__ void put(uint32_t code, uint32_t len)
+    {
+        acc = (acc << len) | code;
+        pend += len;
+        total += len;
+        if (pend >= 32u) { pend -= 32u; out[wi++] = (uint32_t)(acc >> pend); }
+    }
+};
+
+// The transform phase of jpeg_dct_quant_kernel: blocks first .. first + count - 1 into the wave's LDS.
+template <bool kRgba>
+__device__ __forceinline__ void transform_blocks(const JpegJob &jb, const uint32_t *__restrict__ arena, uint32_t first, uint32_t count,
+                                                 uint32_t lane, WaveLds &w)
 {
-    __shared__ int32_t s_a[4][64];                       // zig-zag exchange
-    __shared__ __attribute__((aligned(16))) int16_t s_a16[4][64], s_b16[4][64]; // samples / pass-1 results (both fit 16 bits)
-    __shared__ uint32_t s_ac[512], s_u[4][3][64];        // AC code tables (luma, chroma); per wave and component: the unit's AC bits
-    __shared__ uint32_t s_ent[4][72];                    // per wave: [0] a pad entry, then the block's compacted code-word list
-    const JpegJob jb = jobs[job_base + blockIdx.y];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, r = lane >> 3, c = lane & 7u;
-    const uint32_t nblocks = jb.bx * jb.by;
-    if (blockIdx.x * kBlocksPerWg >= nblocks) return; // whole workgroup idle (uniform)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s_u[wave][k][lane] = 0u;
-    if (lane == 0) s_ent[wave][0] = 7u << 24;          // (component 7: no real entry continues it)
-    stage_ac_luts(s_ac);
-    const uint32_t first = blockIdx.x * kBlocksPerWg + wave * kBlocksPerWave;
-    if (first >= nblocks) return;                      // wave-uniform; from here on waves never synchronise with each other
-    const uint32_t last = min(first + (uint32_t)kBlocksPerWave, nblocks);
+    const uint32_t nat = kNatural.n[lane], r = nat >> 3, c = nat & 7u;
     uint32_t m1[4], m2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -339,144 +311,130 @@ __global__ __launch_bounds__(256) void jpeg_dct_quant_kernel(const JpegJob *__re
         m2[j] = pack_i16(kFdct.a[r][2 * j], kFdct.a[r][2 * j + 1]);
     }
     const uint8_t *qt = reinterpret_cast<const uint8_t *>(arena + jb.tab_off) + 624;
-    const uint32_t ql = qt[lane], qc = qt[64 + lane];
-    const uint32_t *magic = reinterpret_cast<const uint32_t *>(qt + 128);
-    const uint32_t ml = magic[lane], mc = magic[64 + lane];
-    const uint32_t lt_lo = lane >= 32u ? 0xffffffffu : (1u << lane) - 1u, lt_hi = lane >= 32u ? (1u << (lane - 32u)) - 1u : 0u;
-    const uint32_t zz = kZigzagPos[lane];
-    // per-lane shift / rounding constants of the two passes (see dct_quant_unit)
+    const uint32_t *mg = reinterpret_cast<const uint32_t *>(qt + 128);
+    const uint32_t q[3] = {qt[nat], qt[64 + nat], qt[64 + nat]};
+    const uint32_t magic[3] = {mg[nat], mg[64 + nat], mg[64 + nat]};
+    // per-lane shift / rounding constants of the two passes (see dct_quant_block)
     const uint4 k1 = {(c == 0u || c == 4u) ? 13u : 0u, c == 0u ? (uint32_t)(-(8 * 128) * 8192) : (c == 4u ? 0u : 1u << 10),
                       (r == 0u || r == 4u) ? 2u : 1u << 14, (r == 0u || r == 4u) ? 2u : 15u};
-    int32_t *ta = s_a[wave];
-    int16_t *ta16 = s_a16[wave], *tb16 = s_b16[wave];
-    uint32_t *ent = s_ent[wave];
     uint32_t brow = first / jb.bx, bcol = first - brow * jb.bx; // (one division per wave; the walk below steps them)
-    uint32_t rgb = block_pixel(jb, brow, bcol, r, c);
-    for (uint32_t blk = first; blk < last; ++blk) {
+    // the pixels of the next kPrefetch blocks are in flight while a block is transformed (block_pixel clamps to the picture,
+    // so the loads past the wave's last block need no condition -- a condition would make the compiler wait for all of them)
+    uint32_t ahead[kPrefetch];
+#pragma unroll
+    for (uint32_t j = 0; j < kPrefetch; ++j) {
+        ahead[j] = block_pixel<kRgba>(jb, brow, bcol, r, c);
+        if (++bcol == jb.bx) { bcol = 0; ++brow; }
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t rgb = kRgba ? ahead[0] & 0xffffffu : ahead[0];
+#pragma unroll
+        for (uint32_t j = 0; j + 1u < kPrefetch; ++j) ahead[j] = ahead[j + 1u];
+        ahead[kPrefetch - 1u] = block_pixel<kRgba>(jb, brow, bcol, r, c);
+        if (++bcol == jb.bx) { bcol = 0; ++brow; }
         uint32_t smp[3];
         jfif_px(rgb, smp[0], smp[1], smp[2]);
         // a block of one colour (the fill frame of a letterboxed picture: 75 of the 950 blocks of config 1, 31 % of config 0's)
         const bool flat = __ballot(rgb != (uint32_t)__builtin_amdgcn_readfirstlane((int)rgb)) == 0ull;
-        if (++bcol == jb.bx) { bcol = 0; ++brow; }
-        if (blk + 1u < last) rgb = block_pixel(jb, brow, bcol, r, c); // in flight while this block is transformed
         if (flat) {
             // Both passes of the transform are linear up to their final shifts and every row of the matrix but the first sums to zero:
             // a constant block s has pass-1 column 0 = 4 (8 s - 1024) in every row, nothing else, and pass 2 turns that into
             // d[0] = (32 (8 s - 1024) + 2) >> 2 = 64 (s - 128); all other d are (0 + rounding) >> shift = 0.  The DC term goes through
-            // the quantiser of dct_quant_unit, each component's AC code is its end-of-block code alone.
-            const uint32_t q0l = (uint32_t)__builtin_amdgcn_readfirstlane((int)ql), q0c = (uint32_t)__builtin_amdgcn_readfirstlane((int)qc);
-            const uint32_t m0l = (uint32_t)__builtin_amdgcn_readfirstlane((int)ml), m0c = (uint32_t)__builtin_amdgcn_readfirstlane((int)mc);
+            // the quantiser of dct_quant_block (lane 0 holds natural index 0), the AC masks are empty.
+            if (lane == 0u) {
 #pragma unroll
-            for (int comp = 0; comp < 3; ++comp) {
-                const int32_t d = 64 * ((int32_t)smp[comp] - 128);
-                const int32_t sg = d >> 31;
-                const uint32_t an = (uint32_t)((d ^ sg) - sg) >> 3;
-                const uint32_t rq = __umulhi(2u * an + (comp ? q0c : q0l), comp ? m0c : m0l);
-                const int32_t qv = ((int32_t)rq ^ sg) - sg;
-                const uint32_t e = s_ac[comp ? 256u : 0u]; // (run 0, size 0): end of block
-                if (lane == 0u) {
-                    const uint32_t unit = blk * 3u + (uint32_t)comp;
-                    jb.acbits[(size_t)unit * kAcWordsPerUnit] = (e & 0xffffu) << (32u - (e >> 16));
-                    jb.meta[unit] = ((uint32_t)qv & 0xffffu) | ((e >> 16) << 16);
+                for (int k = 0; k < 3; ++k) {
+                    const int32_t d = 64 * ((int32_t)smp[k] - 128);
+                    const int32_t sg = d >> 31;
+                    const uint32_t an = (uint32_t)((d ^ sg) - sg) >> 3;
+                    const uint32_t rq = __umulhi(2u * an + q[k], magic[k]);
+                    w.coef[i * 3u + k][0] = (int16_t)(((int32_t)rq ^ sg) - sg);
+                    w.nz[i * 3u + k] = 0ull;
                 }
             }
             continue;
         }
-        int32_t zv[3];
+        int32_t qv[3];
+        dct_quant_block(smp, nat, r, c, m1, m2, k1, q, magic, w, qv);
 #pragma unroll
-        for (int comp = 0; comp < 3; ++comp) zv[comp] = dct_quant_unit(smp[comp], lane, r, c, m1, m2, k1, comp ? qc : ql, comp ? mc : ml, zz, ta16, tb16, ta);
-        // ---- the block's code words: per component its non-zero AC coefficients in zig-zag order, then an end-of-block code
-        // unless coefficient 63 is coded (BitWriter::write_block) ----
-        uint64_t mask[3];
-        uint32_t base[3], total = 0;
-#pragma unroll
-        for (int comp = 0; comp < 3; ++comp) {
-            mask[comp] = __ballot(zv[comp] != 0 && lane != 0u);
-            base[comp] = total;
-            total += (uint32_t)__popcll(mask[comp]) + ((mask[comp] >> 63) ? 0u : 1u);
+        for (int k = 0; k < 3; ++k) {
+            w.coef[i * 3u + k][lane] = (int16_t)qv[k];
+            const uint64_t nz = __ballot(qv[k] != 0) & ~1ull;
+            if (lane == 0u) w.nz[i * 3u + k] = nz;
         }
-        uint32_t ac_bits[3];
-        if (total <= 64u) {
-#pragma unroll
-            for (int comp = 0; comp < 3; ++comp) {
-                const uint32_t lo = (uint32_t)mask[comp], hi = (uint32_t)(mask[comp] >> 32);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u)); // non-zero lanes below this one
-                if (zv[comp] != 0 && lane != 0u) ent[1u + base[comp] + rank] = ((uint32_t)zv[comp] & 0xffffu) | (lane << 16) | ((uint32_t)comp << 24); // value, zig-zag position, component
-                if (lane == 0u && !(mask[comp] >> 63)) ent[base[comp] + (uint32_t)__popcll(mask[comp]) + 1u] = (64u << 16) | ((uint32_t)comp << 24); // position 64: end of block
-            }
-            wave_lds_sync();
-            const bool act = lane < total;
-            const uint32_t prev = ent[lane], cur = act ? ent[lane + 1u] : (64u << 16);
-            wave_lds_sync();
-            const uint32_t comp = (cur >> 24) & 3u, pos = (cur >> 16) & 127u;
-            const bool is_eob = pos == 64u;
-            const uint32_t prevpos = ((prev ^ cur) >> 24) ? 0u : ((prev >> 16) & 127u); // a unit's first code word: its run starts behind the DC term
-            const uint32_t run = pos - prevpos - 1u;
-            const int32_t v = (int32_t)(int16_t)(cur & 0xffffu);
-            const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-            const uint32_t size = is_eob ? 0u : 32u - (uint32_t)__clz(mag | 1u); // encode_coefficient (a listed coefficient is not zero)
-            const uint32_t value = (uint32_t)(v + (v >> 31)) & ((1u << size) - 1u);                 // negative: (v - 1) & mask
-            const uint32_t *tab = s_ac + (comp ? 256u : 0u);
-            const uint32_t e = tab[is_eob ? 0u : (((run & 15u) << 4) | size)];
-            uint32_t nb = act ? (e >> 16) + size : 0u;              // <= 16 + 10
-            const uint32_t code = ((e & 0xffffu) << size) | value;
-            const uint32_t nzrl = (act && !is_eob) ? run >> 4 : 0u; // "while zero_run > 15 { huffman_encode(0xF0) }": up to three in front
-            uint32_t *tuc = s_u[wave][comp];
-            uint32_t inc, pbit;
-            if (__ballot(nzrl != 0u) == 0ull) {
-                // no ZRL anywhere in the block: every code word fits one 32-bit word
-                inc = wave_inclusive_scan(nb, lane);
-                const uint32_t s1 = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)base[1] - 1), s2 = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)base[2] - 1);
-                pbit = inc - nb - (comp == 0u ? 0u : (comp == 1u ? s1 : s2));
-                if (nb) {
-                    const uint32_t wi = pbit >> 5, sh = pbit & 31u;
-                    const uint32_t left = code << (32u - nb);
-                    const uint32_t w1 = (left << 1) << (31u - sh);
-                    atomicOr(&tuc[wi], left >> sh);
-                    if (w1) atomicOr(&tuc[wi + 1u], w1);
-                }
-                ac_bits[0] = s1; ac_bits[1] = s2 - s1;
-            } else {
-                const uint32_t zrl = tab[0xF0], zl = zrl >> 16, zc = zrl & 0xffffu;
-                uint64_t pre = 0;
-#pragma unroll
-                for (uint32_t i = 0; i < 3; ++i) if (i < nzrl) pre = (pre << zl) | zc;
-                const uint64_t bits = (pre << nb) | code; // <= 3 * 16 + 26 bits
-                nb += nzrl * zl;
-                inc = wave_inclusive_scan(nb, lane);
-                const uint32_t s1 = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)base[1] - 1), s2 = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)base[2] - 1);
-                pbit = inc - nb - (comp == 0u ? 0u : (comp == 1u ? s1 : s2));
-                if (nb) {
-                    const uint32_t wi = pbit >> 5, sh = pbit & 31u;
-                    const uint64_t left = bits << (64u - nb);
-                    const uint64_t a2 = left >> sh;
-                    const uint32_t w0 = (uint32_t)(a2 >> 32), w1 = (uint32_t)a2, w2 = sh ? (uint32_t)((left << (64u - sh)) >> 32) : 0u;
-                    if (w0) atomicOr(&tuc[wi], w0);
-                    if (w1) atomicOr(&tuc[wi + 1u], w1);
-                    if (w2) atomicOr(&tuc[wi + 2u], w2);
-                }
-                ac_bits[0] = s1; ac_bits[1] = s2 - s1;
-            }
-            ac_bits[2] = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63) - ac_bits[0] - ac_bits[1];
-            wave_lds_sync();
-        } else {
-            // more code words than lanes: component by component, as the reference writes them
-#pragma unroll
-            for (int comp = 0; comp < 3; ++comp) {
-                ac_bits[comp] = code_ac_block(zv[comp], lane, lt_lo, lt_hi, s_ac + (comp ? 256 : 0), s_u[wave][comp]);
-                wave_lds_sync();
-            }
+    }
+}
+
+// Two phases per wave.  Transform: one block after the other, the 64 lanes are the 64 samples / coefficients of a block
+// (dct_quant_block); each unit's quantised coefficients go to LDS in zig-zag order, with a ballot of their non-zero AC terms.
+// A block of one colour skips the transform.  Coding: every lane codes whole units by itself (BitWriter::write_block without
+// the DC term) -- lane 16 k + b component k of block b (see kBlocksPerWave) -- walking the set bits of the
+// unit's mask: one code word per step, however many coefficients its neighbours' units hold.  Out: quantised DC, AC bit count,
+// AC bits (from bit 0, the last word padded with zeros).
+__global__ __launch_bounds__(kJpegThreads) void jpeg_dct_quant_kernel(const JpegJob *__restrict__ jobs, const uint32_t *__restrict__ arena,
+                                                                      uint32_t job_base)
+{
+    __shared__ WaveLds s_w[kWavesPerWg];
+    __shared__ uint32_t s_ac[512];                       // AC code tables (luma, chroma)
+    const JpegJob jb = jobs[job_base + blockIdx.y];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t nblocks = jb.bx * jb.by;
+    if (blockIdx.x * kBlocksPerWg >= nblocks) return;    // whole workgroup idle (uniform)
+    stage_ac_luts(s_ac);
+    const uint32_t first = blockIdx.x * kBlocksPerWg + wave * kBlocksPerWave;
+    if (first >= nblocks) return;                        // wave-uniform; from here on waves never synchronise with each other
+    const uint32_t count = min(kBlocksPerWave, nblocks - first);
+    WaveLds &w = s_w[wave];
+
+    // ---- transform phase ----
+    if (jb.c == 4u && (reinterpret_cast<uintptr_t>(jb.src) & 3u) == 0u) transform_blocks<true>(jb, arena, first, count, lane, w);
+    else transform_blocks<false>(jb, arena, first, count, lane, w);
+    wave_lds_sync();
+
+    // ---- coding phase: one lane per unit ----
+    uint32_t b, u, u_end;
+    bool chroma;
+    if constexpr (kBlocksPerWave == 32u) { // lane b: block b's Y unit; lane 32 + b: its Cb, then its Cr unit
+        b = lane & 31u;
+        chroma = lane >= 32u;
+        u = b * 3u + (chroma ? 1u : 0u);
+        u_end = b * 3u + (chroma ? 3u : 1u);
+    } else {                               // lane 16 k + b: component k of block b (lanes 48-63 idle)
+        b = lane & 15u;
+        chroma = lane >= 16u;
+        u = b * 3u + (lane >> 4);
+        u_end = lane >= 48u ? u : u + 1u;
+    }
+    if (b >= count) return;
+    const uint32_t *tab = s_ac + (chroma ? 256u : 0u);
+    const uint32_t eob = tab[0], zrl = tab[0xF0];
+    for (; u < u_end; ++u) {
+        const uint32_t unit = first * 3u + u;
+        const int16_t *cf = w.coef[u];
+        uint64_t m = w.nz[u];
+        UnitBits ub{0ull, 0u, 0u, unit * kAcWordsPerUnit, (global_u32 *)jb.acbits};
+        uint32_t prev = 0;
+        // the next coefficient is read one step ahead, so that a step waits for one LDS round trip (the table entry), not two
+        uint32_t pos = (uint32_t)__builtin_ctzll(m | (1ull << 63));
+        int32_t v = cf[pos];
+        while (m) {
+            const uint32_t cpos = pos;
+            const int32_t cv = v;
+            m &= m - 1ull;
+            pos = (uint32_t)__builtin_ctzll(m | (1ull << 63));
+            v = cf[pos];
+            uint32_t run = cpos - prev - 1u;
+            prev = cpos;
+            while (run > 15u) { ub.put(zrl & 0xffffu, zrl >> 16); run -= 16u; } // "while zero_run > 15 { huffman_encode(0xF0) }"
+            const uint32_t mag = (uint32_t)(cv < 0 ? -cv : cv);
+            const uint32_t size = 32u - (uint32_t)__clz(mag);                 // encode_coefficient (cv is not zero)
+            const uint32_t value = (uint32_t)(cv + (cv >> 31)) & ((1u << size) - 1u); // negative: (v - 1) & mask
+            const uint32_t e = tab[(run << 4) | size];
+            ub.put(((e & 0xffffu) << size) | value, (e >> 16) + size);          // <= 16 + 10 bits
         }
-        // ---- out: the units' AC bits (from bit 0 of their own buffers: the pack kernel shifts them into place), quantised DC, AC bit count
-#pragma unroll
-        for (int comp = 0; comp < 3; ++comp) {
-            const uint32_t unit = blk * 3u + (uint32_t)comp;
-            uint32_t *tu = s_u[wave][comp];
-            const uint32_t nw = (ac_bits[comp] + 31u) >> 5;          // <= 52 words: 63 * 26 bits
-            if (lane < nw) { jb.acbits[(size_t)unit * kAcWordsPerUnit + lane] = tu[lane]; tu[lane] = 0u; }
-            if (lane == 0u) jb.meta[unit] = ((uint32_t)zv[comp] & 0xffffu) | (ac_bits[comp] << 16); // quantised DC, AC bit count
-        }
-        wave_lds_sync();
+        if (prev != 63u) ub.put(eob & 0xffffu, eob >> 16);
+        if (ub.pend) ub.out[ub.wi] = (uint32_t)(ub.acc << (32u - ub.pend));            // the last word, padded with zeros
+        jb.meta[unit] = ((uint32_t)(uint16_t)cf[0]) | (ub.total << 16);         // quantised DC, AC bit count
     }
 }
 
@@ -644,7 +602,7 @@ hipError_t launch_jpeg_encode(const JpegJob *jobs, const uint32_t *arena, uint32
                               hipStream_t st)
 {
     if (!njobs || !max_blocks) return hipSuccess;
-    hipLaunchKernelGGL(jpeg_dct_quant_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, njobs), dim3(256), 0, st, jobs, arena, job_base);
+    hipLaunchKernelGGL(jpeg_dct_quant_kernel, dim3((max_blocks + kBlocksPerWg - 1) / kBlocksPerWg, njobs), dim3(kJpegThreads), 0, st, jobs, arena, job_base);
     FL_LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_pack_kernel, dim3(njobs), dim3(kPackThreads), 0, st, jobs, arena, job_base);
     FL_LAUNCH_CHECK();
