@@ -36,6 +36,7 @@ struct Work {
     bool unaligned = false;
     size_t jpeg_coef_off = 0, jpeg_off_off = 0, jpeg_raw_off = 0; // FE_JPEG scratch (bytes)
     uint32_t jpeg_tab = 0;
+    size_t png_filt_off = 0; uint32_t png_row0 = 0, png_seg0 = 0, png_nseg = 0; // FE_PNG scratch: filtered rows (bytes), flat row / segment numbers
     uint32_t orient = 0, raw_w = 0, raw_h = 0; // EXIF orientation pre-pass (2..8), source size before it
     size_t orient_off = 0;
     uint32_t tile_w = 0;        // S1_TILE: output columns per tile (power of two)
@@ -545,7 +546,7 @@ int entropy_failures(flgpu_ctx *c, size_t n, std::vector<uint8_t> &bad, hipStrea
 
 uint64_t staged_out_bytes(const flgpu_params &p, const flgpu_plan &plan, uint64_t)
 {
-    return p.front_end == FLGPU_FE_JPEG ? plan.max_out_bytes : plan.out_bytes;
+    return fe_encoded(p.front_end) ? plan.max_out_bytes : plan.out_bytes;
 }
 
 int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, bool same_params,
@@ -561,7 +562,8 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     // ---- plan every image ------------------------------------------------
     std::unique_ptr<RoctxRange> range_plan(new RoctxRange("flgpu plan + tables"));
     std::vector<Work> work(n);
-    size_t tmp_a_bytes = 0, tmp_b_bytes = 0, tmp_o_bytes = 0, tmp_al_bytes = 0, jpeg_coef_bytes = 0, jpeg_off_bytes = 0, jpeg_raw_bytes = 0;
+    size_t tmp_a_bytes = 0, tmp_b_bytes = 0, tmp_o_bytes = 0, tmp_al_bytes = 0, jpeg_coef_bytes = 0, jpeg_off_bytes = 0, jpeg_raw_bytes = 0, png_filt_bytes = 0;
+    uint32_t png_rows = 0, png_segs = 0;
     for (size_t i = 0; i < n; ++i) {
         Work &w = work[i];
         const flgpu_image &s = srcs[i];
@@ -619,10 +621,21 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
             w.jpeg_off_off = jpeg_off_bytes; jpeg_off_bytes += align_up((units + 1) * sizeof(uint32_t), 256);
             w.jpeg_raw_off = jpeg_raw_bytes; jpeg_raw_bytes += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
         }
+        if (w.p->front_end == FLGPU_FE_PNG) {
+            const uint64_t fb = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
+            if ((uint64_t)png_rows + pl.out_h >= (1ull << 31) || (uint64_t)png_segs + png_segments(fb) >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
+            w.png_filt_off = png_filt_bytes; png_filt_bytes += align_up(fb, 256);
+            w.png_row0 = png_rows; png_rows += pl.out_h;
+            w.png_seg0 = png_segs; w.png_nseg = (uint32_t)png_segments(fb); png_segs += w.png_nseg;
+        }
     }
     FL_HIP(c, c->d_jpeg_coef.reserve(jpeg_coef_bytes), "JPEG coefficient scratch");
     FL_HIP(c, c->d_jpeg_off.reserve(jpeg_off_bytes), "JPEG offset scratch");
     FL_HIP(c, c->d_jpeg_raw.reserve(jpeg_raw_bytes), "JPEG bit-stream scratch");
+    FL_HIP(c, c->d_png_filt.reserve(png_filt_bytes), "PNG filtered-row scratch");
+    FL_HIP(c, c->d_png_chunks.reserve((size_t)png_segs * kPngSegOutBytes), "PNG chunk scratch");
+    FL_HIP(c, c->d_png_syms.reserve((size_t)png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
+    FL_HIP(c, c->d_png_recs.reserve((size_t)png_segs * 4u * sizeof(uint32_t)), "PNG segment records");
     FL_HIP(c, c->d_tmp_o.reserve(tmp_o_bytes), "orientation scratch");
     for (auto &w : work)
         if (w.orient) { w.raw_src = w.src; w.src = static_cast<uint8_t *>(c->d_tmp_o.p) + w.orient_off; }
@@ -1013,11 +1026,33 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     for (auto &L : s1_launches) has_err_word |= (L.k.kind & 255u) == S1_MFMA;
     // (they live at the end of the batch's descriptor block and arrive zeroed with it: a clear of their own was two fill kernels
     // and two engine switches between one batch's last kernel and the next one's first)
-    std::vector<size_t> jjob_idx, fjob_idx; // image of every encoder / front-end job: its result words are addressed once the block's place is known
+    std::vector<size_t> jjob_idx, fjob_idx, pjob_idx; // image of every encoder / front-end job: its result words are addressed once the block's place is known
     const uint32_t mfma_spin_limit = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_MFMA_SPIN_LIMIT)); // tests: 0 = every bounded wait expires
     std::vector<JpegJob> jjobs;
+    std::vector<PngJob> pjobs;
     uint32_t jpeg_max_blocks = 0;
     for (auto &kv : fe_groups) {
+        if (kv.first.kind == FLGPU_FE_PNG) {
+            for (size_t idx : kv.second) {
+                const Work &w = work[idx];
+                const flgpu_plan &pl = w.plan;
+                PngJob j; memset(&j, 0, sizeof(j));
+                j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
+                j.dst = w.final_dst;
+                j.filt = static_cast<uint8_t *>(c->d_png_filt.p) + w.png_filt_off;
+                j.chunks = static_cast<uint8_t *>(c->d_png_chunks.p) + (size_t)w.png_seg0 * kPngSegOutBytes;
+                j.syms = static_cast<uint16_t *>(c->d_png_syms.p) + (size_t)w.png_seg0 * kPngSegBytes;
+                j.recs = static_cast<uint32_t *>(c->d_png_recs.p) + (size_t)w.png_seg0 * 4u;
+                j.result = nullptr; pjob_idx.push_back(idx);
+                j.w = pl.out_w; j.h = pl.out_h; j.c = pl.out_c;
+                j.row0 = w.png_row0; j.seg0 = w.png_seg0; j.nseg = w.png_nseg;
+                j.level = png_level(w.p->quality);
+                j.dst_cap = (uint32_t)std::min<uint64_t>(dsts[idx].capacity, 0xffffffffull);
+                j.fbytes = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
+                pjobs.push_back(j);
+            }
+            continue;
+        }
         if (kv.first.kind == FLGPU_FE_JPEG) {
             for (size_t idx : kv.second) {
                 const Work &w = work[idx];
@@ -1077,14 +1112,17 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     // one staging slot: [jobs][items][fjobs][jjobs][mitems][mreqs][mwg]
     const size_t jobs_b = align_up(jobs.size() * sizeof(Job), 256), items_b = align_up(items.size() * sizeof(StreamItem), 256),
                  fjobs_b = align_up(fjobs.size() * sizeof(FrontendJob), 256), jjobs_b = align_up(jjobs.size() * sizeof(JpegJob), 256),
-                 mitems_b = align_up(mitems.size() * sizeof(MfmaItem), 256), mreqs_b = align_up(mreqs.size() * sizeof(MfmaReq), 256), mwg_b = align_up(mwg.size() * sizeof(uint32_t), 256);
-    const size_t stat_off = jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b + mwg_b, stat_b = (has_results || has_err_word) ? align_up(n * 8 + 8, 256) : 0;
+                 mitems_b = align_up(mitems.size() * sizeof(MfmaItem), 256), mreqs_b = align_up(mreqs.size() * sizeof(MfmaReq), 256), mwg_b = align_up(mwg.size() * sizeof(uint32_t), 256),
+                 pjobs_b = align_up(pjobs.size() * sizeof(PngJob), 256);
+    const size_t pjobs_off = jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b + mwg_b;
+    const size_t stat_off = pjobs_off + pjobs_b, stat_b = (has_results || has_err_word) ? align_up(n * 8 + 8, 256) : 0;
     const size_t desc_b = stat_off + stat_b;
     uint32_t *status_dev = nullptr;
     const Job *d_jobs = nullptr; const StreamItem *d_items = nullptr; const FrontendJob *d_fjobs = nullptr; const JpegJob *d_jjobs = nullptr;
     const MfmaItem *d_mitems = nullptr;
     const MfmaReq *d_mreqs = nullptr;
     const uint32_t *d_mwg = nullptr;
+    const PngJob *d_pjobs = nullptr;
     DescSlot *slot = nullptr;
     if (desc_b) {
         slot = &c->slots[c->next_slot];
@@ -1099,6 +1137,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
             memset(hp + stat_off, 0, stat_b);
             for (size_t k = 0; k < jjobs.size(); ++k) jjobs[k].result = status_dev + 2 * jjob_idx[k];
             for (size_t k = 0; k < fjobs.size(); ++k) fjobs[k].status = status_dev + 2 * fjob_idx[k];
+            for (size_t k = 0; k < pjobs.size(); ++k) pjobs[k].result = status_dev + 2 * pjob_idx[k];
         }
         if (!jobs.empty()) memcpy(hp, jobs.data(), jobs.size() * sizeof(Job));
         if (!items.empty()) memcpy(hp + jobs_b, items.data(), items.size() * sizeof(StreamItem));
@@ -1107,6 +1146,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         if (!mitems.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b, mitems.data(), mitems.size() * sizeof(MfmaItem));
         if (!mreqs.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b, mreqs.data(), mreqs.size() * sizeof(MfmaReq));
         if (!mwg.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b, mwg.data(), mwg.size() * sizeof(uint32_t));
+        if (!pjobs.empty()) memcpy(hp + pjobs_off, pjobs.data(), pjobs.size() * sizeof(PngJob));
         // While a previous batch is still running, the block goes up on the context's upload stream: the slot is free (its last
         // batch has ended, see above), so the copy runs under that batch's kernels, and this batch's first kernel follows its
         // last one without a copy engine in between.  A lone request on an idle device sends the block down its own stream (no
@@ -1130,6 +1170,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         d_mitems = reinterpret_cast<const MfmaItem *>(dp + jobs_b + items_b + fjobs_b + jjobs_b);
         d_mreqs = reinterpret_cast<const MfmaReq *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b);
         d_mwg = reinterpret_cast<const uint32_t *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b);
+        d_pjobs = reinterpret_cast<const PngJob *>(dp + pjobs_off);
     }
 
     range_plan.reset();
@@ -1232,6 +1273,11 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         FL_HIP(c, launch_jpeg_encode(d_jjobs, c->d_arena, 0, (uint32_t)jjobs.size(), jpeg_max_blocks, st), "JPEG encode");
         c->stats.frontend_launches++;
     }
+    if (!pjobs.empty()) {
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_png_encode(d_pjobs, (uint32_t)pjobs.size(), png_rows, png_segs, st), "PNG encode");
+        c->stats.frontend_launches++;
+    }
     // plain copies for requests that change nothing
     for (size_t i = 0; i < n; ++i) {
         const Work &w = work[i];
@@ -1247,8 +1293,8 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         const flgpu_plan &pl = work[i].plan;
         dsts[i].width = pl.out_w; dsts[i].height = pl.out_h; dsts[i].channels = pl.out_c;
         const uint32_t fe = work[i].p->front_end;
-        dsts[i].flags = fe == FLGPU_FE_JPEG ? FLGPU_IMG_ENCODED : (fe != FLGPU_FE_NONE ? FLGPU_IMG_FRONTEND_PLANES : 0u);
-        dsts[i].bytes = fe == FLGPU_FE_JPEG ? 0 : pl.out_bytes; // an encoded stream's length is a result word: flgpu_batch_results
+        dsts[i].flags = fe_encoded(fe) ? FLGPU_IMG_ENCODED : (fe != FLGPU_FE_NONE ? FLGPU_IMG_FRONTEND_PLANES : 0u);
+        dsts[i].bytes = fe_encoded(fe) ? 0 : pl.out_bytes; // an encoded stream's length is a result word: flgpu_batch_results
     }
     c->last_n = n;
     c->last_status_dev = status_dev;
@@ -1280,7 +1326,7 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st)
     int rc = FLGPU_OK;
     for (size_t i = 0; i < n; ++i) {
         if (c->last_fe[i] == FLGPU_FE_WEBP420 && (r[2 * i] & 1u)) dsts[i].flags |= FLGPU_IMG_HAS_ALPHA;
-        if (c->last_fe[i] == FLGPU_FE_JPEG) {
+        if (fe_encoded(c->last_fe[i])) {
             dsts[i].bytes = r[2 * i + 1];
             if (!r[2 * i + 1]) { c->set_error("encoded stream does not fit the destination"); rc = FLGPU_ERR_BUFFER_TOO_SMALL; }
         }
@@ -1325,7 +1371,7 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
             sb = used;
         } else
         if (srcs[i].capacity < sb) return FLGPU_ERR_INVALID_ARG;
-        if (dsts[i].capacity < plans[i].out_bytes && ps[i].front_end != FLGPU_FE_JPEG) return FLGPU_ERR_BUFFER_TOO_SMALL;
+        if (dsts[i].capacity < plans[i].out_bytes && !fe_encoded(ps[i].front_end)) return FLGPU_ERR_BUFFER_TOO_SMALL;
         dsrc[i] = srcs[i]; ddst[i] = dsts[i];
         dsrc[i].data = reinterpret_cast<uint8_t *>(in_b); dsrc[i].capacity = sb; in_b += align_up(sb, 256);
         const uint64_t ob = plans[i].max_out_bytes; // JPEG: the format's worst case, so the device side never overflows

@@ -30,6 +30,7 @@
 #include "fl_jpegdec.h"
 #include "fl_kernels.h"
 #include "fl_mfma.h"
+#include "fl_png.h"
 #include "fl_tables.h"
 #include "fl_wtile.h"
 
@@ -213,6 +214,7 @@ struct flgpu_ctx {
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
+    fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front
     // end, FL_JPEG_RESULT_OVERFLOW), [2i + 1] bytes of an encoded stream
@@ -339,6 +341,8 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
 // room to give an encoded result on the device: the planning bound, or the format's worst case if the caller offers it
 uint64_t staged_out_bytes(const flgpu_params &p, const flgpu_plan &plan, uint64_t dst_capacity);
+// front ends whose output is an encoded stream: its length is a result word, known once the batch has run
+inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG; }
 // JPEG sources of a batch: dsrc[i].data = DEVICE copy of the coefficient blob whose header (host copy) is hdrs[i], or
 // hdrs[i] == nullptr for ordinary pixel sources.  Runs the decode kernels into scratch and points dsrc[i] at the pixels.
 struct JpegSrc {

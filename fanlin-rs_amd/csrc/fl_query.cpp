@@ -13,6 +13,7 @@
 
 #include "../../include/fanlin_gpu.h"
 #include "fl_abi.h"
+#include "fl_png.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_mfma.h"
@@ -245,8 +246,10 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
             p->front_end = qc == 100 ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
         }
     }
+    /* a PNG that stays PNG: the finished image/png body (handler.rs:264-273) when the caller opts in */
+    if (input_format == FLGPU_IN_PNG && fmt == FLGPU_OUT_KEEP && (accept_flags & FLGPU_ENCODE_PNG)) p->front_end = FLGPU_FE_PNG;
     if (out_format) *out_format = fmt;
-    *result_kind = p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
     return flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
 }
 
@@ -363,7 +366,7 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    if (p->front_end > FLGPU_FE_JPEG || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST) return FLGPU_ERR_INVALID_ARG;
+    if (p->front_end > FLGPU_FE_PNG || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST) return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
     if (p->orientation >= 5) { const uint32_t t = sw; sw = sh; sh = t; }
@@ -433,6 +436,13 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->chroma_h = plan->plane_h;
         plan->out_bytes = 3ull * plan->plane_w * plan->plane_h + 1024ull;
         plan->max_out_bytes = 1024ull + 2ull * fl::kJpegMaxUnitBytes * 3ull * (plan->plane_w / 8u) * (plan->plane_h / 8u);
+        break;
+    case FLGPU_FE_PNG:
+        // out_bytes: a planning bound, the filtered rows (what an incompressible picture's stream comes close to).
+        // max_out_bytes: the format's worst case (fl_png.h): every segment falls back to stored blocks rather than grow, so a
+        // dst of this capacity is never too small.
+        plan->out_bytes = fl::png_filtered_bytes(plan->out_w, plan->out_h, plan->out_c);
+        plan->max_out_bytes = fl::png_max_out_bytes(plan->out_bytes);
         break;
     case FLGPU_FE_WEBP420:
         plan->plane_w = plan->out_w;

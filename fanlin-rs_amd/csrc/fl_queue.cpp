@@ -154,11 +154,11 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
     // per batch spent issuing copies with the device idle, tools/experiments/jh_hiptrace.sh.)
     constexpr uint64_t kSpecBytes = 32u << 10;
     bool encoded = false;
-    for (size_t i = 0; i < n; ++i) encoded |= ps[i].front_end == FLGPU_FE_JPEG;
+    for (size_t i = 0; i < n; ++i) encoded |= fe_encoded(ps[i].front_end);
     std::vector<uint64_t> spec(n, 0);
     if (encoded) {
         for (size_t i = 0; i < n; ++i) {
-            if (ps[i].front_end != FLGPU_FE_JPEG) continue;
+            if (!fe_encoded(ps[i].front_end)) continue;
             spec[i] = std::min<uint64_t>({kSpecBytes, dev_out[i], batch[i]->out_bytes});
             if (spec[i]) FL_HIP(c, hipMemcpyAsync(batch[i]->out.p, ddst[i].data, spec[i], hipMemcpyDeviceToHost, st), "D2H");
         }
@@ -170,9 +170,9 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
     if (rrc == FLGPU_ERR_DEVICE) return rrc;
     bool more = false;
     for (size_t i = 0; i < n; ++i) {
-        const bool jpeg = ps[i].front_end == FLGPU_FE_JPEG;
-        const uint64_t nb = jpeg ? ddst[i].bytes : batch[i]->out_bytes;
-        if (jpeg && nb > batch[i]->out_bytes) { batch[i]->status = FLGPU_ERR_BUFFER_TOO_SMALL; ddst[i].bytes = 0; continue; } // the caller's dst really is too small
+        const bool enc = fe_encoded(ps[i].front_end);
+        const uint64_t nb = enc ? ddst[i].bytes : batch[i]->out_bytes;
+        if (enc && nb > batch[i]->out_bytes) { batch[i]->status = FLGPU_ERR_BUFFER_TOO_SMALL; ddst[i].bytes = 0; continue; } // the caller's dst really is too small
         if (nb > spec[i]) {
             FL_HIP(c, hipMemcpyAsync(static_cast<uint8_t *>(batch[i]->out.p) + spec[i], ddst[i].data + spec[i], nb - spec[i], hipMemcpyDeviceToHost, st), "D2H");
             more = true;
@@ -184,7 +184,7 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
         batch[i]->dst->width = ddst[i].width; batch[i]->dst->height = ddst[i].height;
         batch[i]->dst->channels = ddst[i].channels; batch[i]->dst->flags = ddst[i].flags;
         batch[i]->dst->bytes = ddst[i].bytes;
-        if (ps[i].front_end == FLGPU_FE_JPEG && !ddst[i].bytes && batch[i]->status == FLGPU_OK) batch[i]->status = FLGPU_ERR_BUFFER_TOO_SMALL;
+        if (fe_encoded(ps[i].front_end) && !ddst[i].bytes && batch[i]->status == FLGPU_OK) batch[i]->status = FLGPU_ERR_BUFFER_TOO_SMALL;
     }
     if (rrc == FLGPU_ERR_DEVICE) return rrc; // the device error word: no result of this batch is valid
     {   // requests whose file the device entropy decoder gave up on go back to their callers, who decode on the host and queue again
@@ -464,15 +464,15 @@ try {
         const int prc = jpeg_source_precheck(c, src, jinfo); // before any block is reserved on the file's say-so
         if (prc) return prc;
     } else if (src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
-    const bool jpeg = p->front_end == FLGPU_FE_JPEG;
-    if (!jpeg && dst->capacity < plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const bool enc = fe_encoded(p->front_end);
+    if (!enc && dst->capacity < plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
     Request r{};
     r.src = src; r.p = p; r.dst = dst;
     r.src_bytes = (uint64_t)src->width * src->height * src->channels;
     r.weight = r.src_bytes + plan.out_bytes;
     // an encoded stream is staged with the format's worst case on the device, so only the caller's own capacity can be
     // too small, and that is known once the stream's length is (JpegEncoder into a Vec never fails, handler.rs:274-278)
-    r.out_bytes = jpeg ? std::min<uint64_t>(dst->capacity, plan.max_out_bytes) : plan.out_bytes;
+    r.out_bytes = enc ? std::min<uint64_t>(dst->capacity, plan.max_out_bytes) : plan.out_bytes;
     if (r.out_bytes == 0) return FLGPU_ERR_BUFFER_TOO_SMALL;
     {
         const uint32_t limit = 4u * lanes_per_device(c) * batch_per_device(c) * c->n_dev();

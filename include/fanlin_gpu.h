@@ -27,6 +27,8 @@
  *                                       webp::Encoder::encode, src/handler.rs:295-297
  *   front_end = FLGPU_FE_JPEG           the whole jpeg::JpegEncoder::new_with_quality(q).encode_image(&img),
  *                                       src/handler.rs:274-278 (FDCT, quantiser, Huffman coder, framing)
+ *   front_end = FLGPU_FE_PNG            the whole PngEncoder::new_with_quality(ct, FilterType::Adaptive) +
+ *                                       img.write_with_encoder, src/handler.rs:264-273 (row filters, deflate, framing)
  *   params.filter = NEAREST             the per-frame pipeline of process_gif, src/handler.rs:327-353
  *   flgpu_process_image                 State::process_image after the decoder as one call, src/handler.rs:198-308
  *   flgpu_ycck_to_cmyk                  the YCCK loop of convert_jpeg_color_if_needed, src/handler.rs:423-438
@@ -90,13 +92,20 @@ typedef enum flgpu_front_end {
     FLGPU_FE_JFIF444 = 1,  /* dst = Y | Cb | Cr, each plane_w x plane_h (multiples of 8, edge replicated) */
     FLGPU_FE_WEBP420 = 2,  /* dst = Y (w x h) | U | V (each ceil(w/2) x ceil(h/2)) | A (w x h), BT.601 limited range: what
                               libwebp's WebPPictureARGBToYUVA makes of the RGBA picture, alpha-weighted chroma included */
-    FLGPU_FE_JPEG = 3      /* dst = the finished JFIF stream of JpegEncoder::new_with_quality(q).encode_image(&img)
+    FLGPU_FE_JPEG = 3,     /* dst = the finished JFIF stream of JpegEncoder::new_with_quality(q).encode_image(&img)
                               (src/handler.rs:274-278): baseline, 3 components, 4:4:4; dst->bytes long */
+    FLGPU_FE_PNG = 4       /* dst = the finished PNG file of PngEncoder (src/handler.rs:264-273): signature, IHDR, IDAT...,
+                              IEND; 8-bit samples, colour type 0 / 4 / 2 / 6 for out_c 1 / 2 / 3 / 4, no interlace; row
+                              filters by the png crate's adaptive rule; compression from quality (< 50 best, < 85 default,
+                              otherwise fast); decodes to exactly the FLGPU_FE_NONE pixels; dst->bytes long */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
 #define FLGPU_ACCEPT_WEBP 1u
 #define FLGPU_ACCEPT_AVIF 2u
+/* Not a content::Format bit: the caller wants the library to finish image/png bodies (FLGPU_FE_PNG,
+ * FLGPU_RESULT_PNG_STREAM) for PNG inputs that stay PNG.  Without it such requests return pixels, as before. */
+#define FLGPU_ENCODE_PNG 0x100u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -141,11 +150,14 @@ typedef struct flgpu_plan {
     uint32_t chroma_w, chroma_h;       /* front end chroma plane size */
     uint64_t pixel_bytes;              /* out_w * out_h * out_c */
     uint64_t out_bytes;                /* bytes the call writes to dst (pixels or planes); for FLGPU_FE_JPEG a planning bound
-                                          (about 1 byte per sample) that ordinary pictures stay far below */
+                                          (about 1 byte per sample) that ordinary pictures stay far below; for FLGPU_FE_PNG
+                                          the filtered rows, out_h * (1 + out_w * out_c) */
     uint64_t max_out_bytes;            /* FLGPU_FE_JPEG: the worst case of the format (every 8x8 block of every component at its
                                           longest code, every byte stuffed): a dst of this capacity can never be too small, as
-                                          JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).  Otherwise
-                                          equal to out_bytes. */
+                                          JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).
+                                          FLGPU_FE_PNG: the worst case of the format, every 32 KB segment of the filtered rows
+                                          as stored blocks: 63 + sum over segments of (L + 5 * ceil(L / 65535) + 5 + 12).
+                                          Otherwise equal to out_bytes. */
 } flgpu_plan;
 
 #define FLGPU_MAX_DEVICES 8
@@ -284,12 +296,14 @@ int flgpu_transform(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *
  * said.  The outcome is one of flgpu_result_kind:
  *   AS_IS         params.as_is() (handler.rs:202-204): nothing was done, serve the original bytes
  *   JPEG_STREAM   input was JPEG and no other container was negotiated: dst holds the finished "image/jpeg" body
+ *   PNG_STREAM    input was PNG, no other container was negotiated and accept_flags has FLGPU_ENCODE_PNG: dst holds the
+ *                 finished "image/png" body (handler.rs:264-273), dst->bytes long
  *   WEBP_PLANES   lossy WebP was negotiated (handler.rs:286-297): dst holds Y | U | V for WebPEncode
- *   PIXELS        everything else (PNG, AVIF, lossless WebP, GIF frames, ...): dst holds the DynamicImage pixels for
+ *   PIXELS        everything else (PNG without FLGPU_ENCODE_PNG, AVIF, lossless WebP, GIF frames, ...): dst holds the DynamicImage pixels for
  *                 the crate's own encoder; *out_format says which container was negotiated
  * Errors: FLGPU_ERR_PARSE where axum answers 400 (bad query, or the size gate of src/main.rs:134-138). */
 typedef enum flgpu_input_format { FLGPU_IN_OTHER = 0, FLGPU_IN_JPEG = 1, FLGPU_IN_PNG = 2, FLGPU_IN_WEBP = 3, FLGPU_IN_GIF_FRAME = 4 } flgpu_input_format;
-typedef enum flgpu_result_kind { FLGPU_RESULT_AS_IS = 0, FLGPU_RESULT_JPEG_STREAM = 1, FLGPU_RESULT_WEBP_PLANES = 2, FLGPU_RESULT_PIXELS = 3 } flgpu_result_kind;
+typedef enum flgpu_result_kind { FLGPU_RESULT_AS_IS = 0, FLGPU_RESULT_JPEG_STREAM = 1, FLGPU_RESULT_WEBP_PLANES = 2, FLGPU_RESULT_PIXELS = 3, FLGPU_RESULT_PNG_STREAM = 4 } flgpu_result_kind;
 int flgpu_process_image(flgpu_ctx *ctx, const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string,
                         uint32_t accept_flags, int input_format, flgpu_image *dst, flgpu_plan *plan, int *result_kind,
                         int *out_format);
@@ -345,7 +359,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS

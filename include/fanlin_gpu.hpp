@@ -77,6 +77,8 @@ public:
     bool webp_accepted() const { return (flags_ & FLGPU_ACCEPT_WEBP) == FLGPU_ACCEPT_WEBP; }
     void accept_avif() { flags_ |= FLGPU_ACCEPT_AVIF; }
     bool avif_accepted() const { return (flags_ & FLGPU_ACCEPT_AVIF) == FLGPU_ACCEPT_AVIF; }
+    // not a content::Format bit: the library finishes image/png bodies for PNG inputs that stay PNG (FLGPU_RESULT_PNG_STREAM)
+    void encode_png() { flags_ |= FLGPU_ENCODE_PNG; }
     uint32_t flags() const { return flags_; }
 
 private:
@@ -95,7 +97,7 @@ struct Decoded {
 };
 
 struct Processed {
-    flgpu_result_kind kind;        // AS_IS: serve the original bytes; JPEG_STREAM: body is final; WEBP_PLANES / PIXELS: host encoder
+    flgpu_result_kind kind;        // AS_IS: serve the original bytes; JPEG_STREAM / PNG_STREAM: body is final; WEBP_PLANES / PIXELS: host encoder
     flgpu_out_format negotiated;   // container chosen at src/handler.rs:256-261
     flgpu_plan plan;               // geometry of what `data` holds
     uint32_t flags;                // FLGPU_IMG_*
@@ -138,7 +140,8 @@ public:
         check(flgpu_process_image_plan(&src, img.orientation, params.text().c_str(), content.flags(), img.format, &out.plan, &kind));
         out.kind = static_cast<flgpu_result_kind>(kind);
         if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
-        out.data.resize(out.plan.out_bytes);
+        // a PNG body is staged at the format's worst case, so that it never comes back too small
+        out.data.resize(out.kind == FLGPU_RESULT_PNG_STREAM ? out.plan.max_out_bytes : out.plan.out_bytes);
         flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
         check(flgpu_process_image(ctx_, &src, img.orientation, params.text().c_str(), content.flags(), img.format, &dst, &out.plan, &kind, &fmt), ctx_);
         out.negotiated = static_cast<flgpu_out_format>(fmt);

@@ -30,15 +30,19 @@ pub const FE_NONE: u8 = 0;
 pub const FE_JFIF444: u8 = 1;
 pub const FE_WEBP420: u8 = 2;
 pub const FE_JPEG: u8 = 3;
+pub const FE_PNG: u8 = 4;
 pub const FILTER_NEAREST: u8 = 1;
 const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
 pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
+// not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
+pub const ENCODE_PNG: u32 = 0x100;
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
 pub const RESULT_WEBP_PLANES: c_int = 2;
 pub const RESULT_PIXELS: c_int = 3;
+pub const RESULT_PNG_STREAM: c_int = 4;
 const ERR_UNSUPPORTED: c_int = 2; // FLGPU_ERR_UNSUPPORTED: a stream the device decoder does not cover
 const CMYK_INPUT_YCCK: u32 = 1;
 
@@ -133,14 +137,14 @@ impl Gpu {
         if let Some((w, h)) = q.dimensions() { p.has_dims = 1; p.w = w; p.h = h; }
         let mut plan = FlPlan::default();
         check(unsafe { flgpu_plan_output(&p, img.width(), img.height(), c, &mut plan) })?;
-        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, where it is the
+        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG and FE_PNG, where it is the
         // worst case of the format: with it the call cannot fail for lack of room, as `encode_image` into a Vec cannot.
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let src = FlImage { data: bytes.as_ptr() as *mut u8, capacity: bytes.len() as u64,
                             width: img.width(), height: img.height(), channels: c, flags: 0, bytes: 0 };
         let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
         check(unsafe { flgpu_transform(self.0, &src, &p, &mut dst) })?;
-        out.truncate(dst.bytes as usize); // pixels / planes: == out_bytes; JPEG: the stream length
+        out.truncate(dst.bytes as usize); // pixels / planes: == out_bytes; JPEG / PNG: the stream length
         Ok(Outcome::Device { plan, bytes: out, has_alpha: dst.flags & IMG_HAS_ALPHA != 0 })
     }
 
@@ -268,6 +272,22 @@ fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(
 //             if params.grayscale() { img = img.grayscale(); } else if params.inverse() { img.invert(); }
 //             /* ... the reference's own resize / overlay / blur, unchanged ... */
 //         }
+//     }
+//
+// PNG sources that stay PNG (the `ImageFormat::Png` arm, lines 264-273): the finished body instead of the pixels.  Through
+// `flgpu_process_image` the caller opts in with ENCODE_PNG next to the content::Format bits and gets RESULT_PNG_STREAM:
+//
+//     let accept = (content.webp_accepted() as u32) * gpu::ACCEPT_WEBP | (content.avif_accepted() as u32) * gpu::ACCEPT_AVIF
+//                  | gpu::ENCODE_PNG;
+//     match kind {
+//         gpu::RESULT_PNG_STREAM => return Ok((ImageFormat::Png.to_mime_type(), bytes)),                     // lines 264-273
+//         /* ... the other kinds as above ... */
+//     }
+//
+// or, through `transform` (quality picks the compression level as the reference's match on params.quality() does):
+//
+//     if let gpu::Outcome::Device { bytes, .. } = self.gpu.transform(&img, params, orientation.to_exif(), gpu::FE_PNG, false)? {
+//         return Ok((ImageFormat::Png.to_mime_type(), bytes));
 //     }
 //
 // and, for JPEG sources that stay JPEG, the whole `ImageFormat::Jpeg` arm (lines 274-278):
