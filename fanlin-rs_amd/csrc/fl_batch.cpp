@@ -75,15 +75,6 @@ bool wtile_resample_wanted(const Work &)
     return true;
 }
 
-// Blurs the window-tile matrix-pipe kernel takes: every one its planner accepts.  (Round 4 left the one-channel shortcut -- a grey
-// picture on a grey frame, config 2 -- to the vector kernel, which filters one byte column in four there: the matrix kernel would have
-// filtered all four.  Round 5: stage 1 leaves the unframed Luma8 picture, the matrix kernel filters ONE channel, reading the frame's
-// rows and columns as the fill value, and expands to Rgba8 in its store -- Work::luma_mid.)
-bool wtile_blur_wanted(const DebugSwitches &, const Work &)
-{
-    return true;
-}
-
 // Row bands per picture for the window-tile kernel: small batches are cut so that the chip still sees a few hundred workgroups
 // (the result does not depend on the cut: every M-tile is computed from the same rows by the same instructions).
 uint32_t wtile_bands(const DebugSwitches &dbg, const WtPlan &p, size_t pictures)
@@ -779,10 +770,13 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
                 w.bwplan = nullptr; w.luma_mid = false; // (a second attempt after an arena reset plans again)
                 if (!get_axis(c, w.plan.out_h, w.plan.out_h, FILTER_GAUSSIAN, w.p->blur_sigma, &kv, &hv) ||
                     !get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &k, &h)) full = true;
-                else if (use_wtile && wtile_blur_wanted(dbg, w)) {
-                    // a grey picture on a grey frame (R == G == B everywhere, alpha 255): one channel is filtered, if that plan is one of
-                    // the single-register-set kind (the kernel's framed source exists in that instantiation only)
-                    const bool one = w.plan.letterboxed && w.plan.out_c == 4u && blur_channels(w) == 1u && w.s1 != S1_NONE && w.s1 != S1_NEAREST;
+                else if (use_wtile) {
+                    // Blurs the window-tile matrix-pipe kernel takes: every one its planner accepts.  A grey picture on a grey frame (R == G == B
+                    // everywhere, alpha 255): ONE channel is filtered, if that plan is one of the single-register-set kind (the kernel's framed
+                    // source exists in that instantiation only) -- stage 1 leaves the unframed Luma8 picture, the kernel reads the frame's rows
+                    // and columns as the fill value and expands to Rgba8 in its store (Work::luma_mid).  no_luma_mid: the Rgba8 blur of the
+                    // framed picture instead (A/B runs and the tests that compare the two routes)
+                    const bool one = !dbg.on(DBG_NO_LUMA_MID) && w.plan.letterboxed && w.plan.out_c == 4u && blur_channels(w) == 1u && w.s1 != S1_NONE && w.s1 != S1_NEAREST;
                     WtPlan *wp = one ? get_wtile_plan(c, kv, *hv, k, *h, 0, 0, w.plan.out_w, w.plan.out_h, 1u) : nullptr;
                     if (wp && !wp->arena_full && wp->ok && wp->nslot == 1u) { w.bwplan = wp; w.luma_mid = true; }
                     else {

@@ -360,7 +360,7 @@ void resolve_pending(flgpu_ctx *c)
 }
 
 const char *const kDebugKeyNames[DBG_COUNT] = {
-    "no_mfma", "force_generic", "no_wtile", "wtile_blur_always", "wtile_first", "mfma_arith", "force_bands", "no_tile", "no_place4",
+    "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first", "mfma_arith", "force_bands", "no_tile", "no_place4",
     "host_huffman", "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh",
 };
 

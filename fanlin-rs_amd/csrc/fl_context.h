@@ -144,7 +144,7 @@ enum DebugKey : uint32_t {
     DBG_NO_MFMA = 0,              // the f32 streaming kernel also where the matrix-pipe kernel would run
     DBG_FORCE_GENERIC,            // the two-pass kernels instead of every fused one
     DBG_NO_WTILE,                 // mild ratios, up-scales and blurs on the f32 vector kernels
-    DBG_WTILE_BLUR_ALWAYS,        // one-channel blurs on the window-tile kernel too
+    DBG_NO_LUMA_MID,              // grey pictures on a grey frame: the Rgba8 window-tile blur of the framed picture, not the one-channel one
     DBG_WTILE_FIRST,              // the window-tile kernel is asked before the streaming matrix-pipe kernel at every ratio
     DBG_MFMA_ARITH,               // 0 = full-width arithmetic, 1 = the packed arithmetic of rounds 2-3
     DBG_FORCE_BANDS,              // row bands per picture (0 = the planner's choice)

@@ -403,10 +403,11 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * multi-threaded server, and a stray variable must not change output bytes.  The environment is read exactly once, in flgpu_create
  * (FLGPU_<KEY IN CAPITALS> seeds the switch `key`); afterwards a switch changes only through this call, atomically, for the
  * context, its queue lanes and its device shards.  Keys (csrc/fl_context.h DebugKey): "no_mfma", "force_generic", "no_wtile",
- * "wtile_blur_always", "wtile_first", "mfma_arith" (0 full width, 1 packed), "force_bands", "no_tile", "no_place4", "host_huffman",
- * "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh"; "reset" restores every default.
- * Only "no_mfma", "force_generic", "no_wtile", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB (they pick
- * another resample kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
+ * "no_luma_mid" (a grey picture on a grey frame is blurred as Rgba8, not as one channel), "wtile_first", "mfma_arith" (0 full width,
+ * 1 packed), "force_bands", "no_tile", "no_place4", "host_huffman", "device_huffman_always", "device_huffman_min_bytes",
+ * "mfma_spin_limit", "debug_mfma", "debug_jh"; "reset" restores every default.
+ * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
+ * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);
 int flgpu_debug_get(flgpu_ctx *ctx, const char *key, int64_t *value);
 

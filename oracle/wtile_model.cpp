@@ -13,11 +13,13 @@
 #include "../fanlin-rs_amd/csrc/fl_tables.h"
 #include "../fanlin-rs_amd/csrc/fl_wtile.h"
 
-extern "C" int wtile_model_run(const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t cs, uint32_t rw, uint32_t rh, float blur_sigma,
-                                       uint8_t *dst, uint32_t info[8])
+// info: m_tiles, n_tiles, strips, hs, nslot, nkmax (the kernel instantiation's K-steps per register set), lds_bytes, table_words,
+// nkv_max, nkh_max (the largest K-step counts of the plan's M-tiles / N-tiles; nkh_max > nkmax: tiles the kernel walks uncached)
+static int run_model(const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t cs, uint32_t rw, uint32_t rh, float blur_sigma, uint8_t *dst,
+                     uint32_t info[10])
 {
     using namespace fl;
-    if (info) for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (info) for (int k = 0; k < 10; ++k) info[k] = 0;
     if (!sw || !sh || !cs || cs > 4) return 0;
     HostAxis v, h;
     if (blur_sigma > 0.0f) {
@@ -40,6 +42,7 @@ extern "C" int wtile_model_run(const uint8_t *src, uint32_t sw, uint32_t sh, uin
     if (info) {
         info[0] = hd.n_mt; info[1] = hd.n_nt; info[2] = hd.n_strips; info[3] = hd.hs; info[4] = p.nslot; info[5] = p.nkmax; info[6] = p.lds_bytes;
         info[7] = (uint32_t)p.blk.size();
+        info[8] = hd.nkv_max; info[9] = hd.nkh_max;
     }
     if (!src || !dst) return 1;
     auto f16 = [](uint32_t hbits) -> double {
@@ -106,4 +109,21 @@ extern "C" int wtile_model_run(const uint8_t *src, uint32_t sw, uint32_t sh, uin
     }
     (void)strips;
     return 1;
+}
+
+// The first eight words of info (the entry point's original layout: callers pass eight-word arrays)
+extern "C" int wtile_model_run(const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t cs, uint32_t rw, uint32_t rh, float blur_sigma,
+                                       uint8_t *dst, uint32_t info[8])
+{
+    uint32_t all[10];
+    const int r = run_model(src, sw, sh, cs, rw, rh, blur_sigma, dst, all);
+    if (info) memcpy(info, all, 8 * sizeof(uint32_t));
+    return r;
+}
+
+// All ten words of info
+extern "C" int wtile_model_run_ext(const uint8_t *src, uint32_t sw, uint32_t sh, uint32_t cs, uint32_t rw, uint32_t rh, float blur_sigma,
+                                   uint8_t *dst, uint32_t info[10])
+{
+    return run_model(src, sw, sh, cs, rw, rh, blur_sigma, dst, info);
 }
