@@ -28,11 +28,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLGPU_LIB") or os.path.join(_HERE, "libfanlin_gpu.so")
 
 FE_NONE, FE_JFIF444, FE_WEBP420, FE_JPEG, FE_PNG = 0, 1, 2, 3, 4
+FE_WEBP_LOSSLESS = 6  # (5 is not a front end)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
+ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
 IN_OTHER, IN_JPEG, IN_PNG, IN_WEBP, IN_GIF_FRAME = 0, 1, 2, 3, 4
-RESULT_AS_IS, RESULT_JPEG_STREAM, RESULT_WEBP_PLANES, RESULT_PIXELS, RESULT_PNG_STREAM = 0, 1, 2, 3, 4
+RESULT_AS_IS, RESULT_JPEG_STREAM, RESULT_WEBP_PLANES, RESULT_PIXELS, RESULT_PNG_STREAM, RESULT_WEBP_STREAM = 0, 1, 2, 3, 4, 5
+_RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG,
+              RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
 IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE = 1, 2, 4, 8, 16
 BATCH_SAME_PARAMS = 1
@@ -485,7 +489,7 @@ def _as_image_array(a: np.ndarray) -> np.ndarray:
 def _split_output(buf: np.ndarray, plan: flgpu_plan, front_end: int, flags: int, nbytes: int = 0):
     if front_end == FE_NONE:
         return buf[: plan.pixel_bytes].reshape(plan.out_h, plan.out_w, plan.out_c)
-    if front_end in (FE_JPEG, FE_PNG):
+    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS):
         return buf[:nbytes].tobytes()
     ny = plan.plane_w * plan.plane_h
     nc = plan.chroma_w * plan.chroma_h
@@ -561,7 +565,8 @@ class State:
                       orientation: int = 1):
         """State::process_image after the decoder (reference src/handler.rs:198-308): returns (mime, kind, payload) where
         payload is None (AS_IS), the JPEG body (bytes), WebP planes (Planes) or the pixels for a host encoder (ndarray);
-        with ENCODE_PNG in the content flags a PNG input that stays PNG gives the PNG body (bytes, RESULT_PNG_STREAM)."""
+        with ENCODE_PNG in the content flags a PNG input that stays PNG gives the PNG body (bytes, RESULT_PNG_STREAM); with
+        ENCODE_WEBP_LOSSLESS the WebP arm at quality 100 gives the lossless WebP body (bytes, RESULT_WEBP_STREAM)."""
         img = _as_image_array(decoded)
         src = flgpu_image(img.ctypes.data, img.nbytes, img.shape[1], img.shape[0], img.shape[2], 0)
         plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
@@ -575,7 +580,7 @@ class State:
         _check(self._lib.flgpu_process_image(self._ctx, C.byref(src), orientation, qs, flags, input_format, C.byref(dst), C.byref(plan),
                                              C.byref(kind), C.byref(fmt)), self._ctx)
         mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else MIME.get(input_format, "application/octet-stream")
-        fe = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG}[kind.value]
+        fe = _RESULT_FE[kind.value]
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
 
     # -- JPEG sources: the decode front end (handler.rs:205-220) --------------------------------------------------
@@ -610,7 +615,7 @@ class State:
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
         _check(self._lib.flgpu_process_jpeg(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
         mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else "image/jpeg"
-        fe = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG}[kind.value]
+        fe = _RESULT_FE[kind.value]
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
 
     def process_batch(self, images: Sequence, params: Sequence[flgpu_params]) -> List:

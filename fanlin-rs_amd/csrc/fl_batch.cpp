@@ -37,6 +37,7 @@ struct Work {
     size_t jpeg_coef_off = 0, jpeg_off_off = 0, jpeg_raw_off = 0; // FE_JPEG scratch (bytes)
     uint32_t jpeg_tab = 0;
     size_t png_filt_off = 0; uint32_t png_row0 = 0, png_seg0 = 0, png_nseg = 0; // FE_PNG scratch: filtered rows (bytes), flat row / segment numbers
+    size_t wll_res_off = 0, wll_tok_off = 0, wll_stream_off = 0; uint32_t wll_tile0 = 0, wll_pic = 0; // FE_WEBP_LOSSLESS scratch (bytes), flat tile / picture numbers
     uint32_t orient = 0, raw_w = 0, raw_h = 0; // EXIF orientation pre-pass (2..8), source size before it
     size_t orient_off = 0;
     uint32_t tile_w = 0;        // S1_TILE: output columns per tile (power of two)
@@ -555,6 +556,8 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     std::vector<Work> work(n);
     size_t tmp_a_bytes = 0, tmp_b_bytes = 0, tmp_o_bytes = 0, tmp_al_bytes = 0, jpeg_coef_bytes = 0, jpeg_off_bytes = 0, jpeg_raw_bytes = 0, png_filt_bytes = 0;
     uint32_t png_rows = 0, png_segs = 0;
+    size_t wll_res_bytes = 0, wll_tok_bytes = 0, wll_stream_bytes = 0;
+    uint32_t wll_tiles = 0, wll_pics = 0;
     for (size_t i = 0; i < n; ++i) {
         Work &w = work[i];
         const flgpu_image &s = srcs[i];
@@ -619,6 +622,16 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
             w.png_row0 = png_rows; png_rows += pl.out_h;
             w.png_seg0 = png_segs; w.png_nseg = (uint32_t)png_segments(fb); png_segs += w.png_nseg;
         }
+        if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) {
+            const uint64_t npix = (uint64_t)pl.out_w * pl.out_h;
+            if ((uint64_t)wll_tiles + webpll_tiles(npix) >= (1ull << 31) || webpll_max_out_bytes(pl.out_w, pl.out_h) / 4u >= (1ull << 32))
+                return FLGPU_ERR_UNSUPPORTED;
+            w.wll_res_off = wll_res_bytes; wll_res_bytes += align_up(npix * 4u, 256);
+            w.wll_tok_off = wll_tok_bytes; wll_tok_bytes += align_up(npix * 2u, 256);
+            w.wll_stream_off = wll_stream_bytes; wll_stream_bytes += align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256);
+            w.wll_tile0 = wll_tiles; wll_tiles += (uint32_t)webpll_tiles(npix);
+            w.wll_pic = wll_pics++;
+        }
     }
     FL_HIP(c, c->d_jpeg_coef.reserve(jpeg_coef_bytes), "JPEG coefficient scratch");
     FL_HIP(c, c->d_jpeg_off.reserve(jpeg_off_bytes), "JPEG offset scratch");
@@ -627,6 +640,11 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     FL_HIP(c, c->d_png_chunks.reserve((size_t)png_segs * kPngSegOutBytes), "PNG chunk scratch");
     FL_HIP(c, c->d_png_syms.reserve((size_t)png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
     FL_HIP(c, c->d_png_recs.reserve((size_t)png_segs * 4u * sizeof(uint32_t)), "PNG segment records");
+    FL_HIP(c, c->d_webpll_res.reserve(wll_res_bytes), "WebP residual scratch");
+    FL_HIP(c, c->d_webpll_tok.reserve(wll_tok_bytes), "WebP token scratch");
+    FL_HIP(c, c->d_webpll_tiles.reserve((size_t)wll_tiles * sizeof(WebpllTile)), "WebP tile records");
+    FL_HIP(c, c->d_webpll_pic.reserve((size_t)wll_pics * kWebpllPicWords * sizeof(uint32_t)), "WebP per-picture scratch");
+    FL_HIP(c, c->d_webpll_stream.reserve(wll_stream_bytes), "WebP bit-stream scratch");
     FL_HIP(c, c->d_tmp_o.reserve(tmp_o_bytes), "orientation scratch");
     for (auto &w : work)
         if (w.orient) { w.raw_src = w.src; w.src = static_cast<uint8_t *>(c->d_tmp_o.p) + w.orient_off; }
@@ -1020,12 +1038,34 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     for (auto &L : s1_launches) has_err_word |= (L.k.kind & 255u) == S1_MFMA;
     // (they live at the end of the batch's descriptor block and arrive zeroed with it: a clear of their own was two fill kernels
     // and two engine switches between one batch's last kernel and the next one's first)
-    std::vector<size_t> jjob_idx, fjob_idx, pjob_idx; // image of every encoder / front-end job: its result words are addressed once the block's place is known
+    std::vector<size_t> jjob_idx, fjob_idx, pjob_idx, wjob_idx; // image of every encoder / front-end job: its result words are addressed once the block's place is known
     const uint32_t mfma_spin_limit = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_MFMA_SPIN_LIMIT)); // tests: 0 = every bounded wait expires
     std::vector<JpegJob> jjobs;
     std::vector<PngJob> pjobs;
+    std::vector<WebpJob> wjobs;
     uint32_t jpeg_max_blocks = 0;
     for (auto &kv : fe_groups) {
+        if (kv.first.kind == FLGPU_FE_WEBP_LOSSLESS) {
+            for (size_t idx : kv.second) {
+                const Work &w = work[idx];
+                const flgpu_plan &pl = w.plan;
+                WebpJob j; memset(&j, 0, sizeof(j));
+                j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
+                j.dst = w.final_dst;
+                j.res = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_res.p) + w.wll_res_off);
+                j.tok = reinterpret_cast<uint16_t *>(static_cast<char *>(c->d_webpll_tok.p) + w.wll_tok_off);
+                j.tiles = static_cast<WebpllTile *>(c->d_webpll_tiles.p) + w.wll_tile0;
+                j.pic = static_cast<uint32_t *>(c->d_webpll_pic.p) + (size_t)w.wll_pic * kWebpllPicWords;
+                j.stream = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_stream.p) + w.wll_stream_off);
+                j.result = nullptr; wjob_idx.push_back(idx);
+                j.w = pl.out_w; j.h = pl.out_h; j.c = pl.out_c;
+                j.tile0 = w.wll_tile0; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
+                j.dst_cap = (uint32_t)std::min<uint64_t>(dsts[idx].capacity, 0xffffffffull);
+                j.stream_words = (uint32_t)(align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256) / 4u);
+                wjobs.push_back(j);
+            }
+            continue;
+        }
         if (kv.first.kind == FLGPU_FE_PNG) {
             for (size_t idx : kv.second) {
                 const Work &w = work[idx];
@@ -1107,9 +1147,9 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     const size_t jobs_b = align_up(jobs.size() * sizeof(Job), 256), items_b = align_up(items.size() * sizeof(StreamItem), 256),
                  fjobs_b = align_up(fjobs.size() * sizeof(FrontendJob), 256), jjobs_b = align_up(jjobs.size() * sizeof(JpegJob), 256),
                  mitems_b = align_up(mitems.size() * sizeof(MfmaItem), 256), mreqs_b = align_up(mreqs.size() * sizeof(MfmaReq), 256), mwg_b = align_up(mwg.size() * sizeof(uint32_t), 256),
-                 pjobs_b = align_up(pjobs.size() * sizeof(PngJob), 256);
-    const size_t pjobs_off = jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b + mwg_b;
-    const size_t stat_off = pjobs_off + pjobs_b, stat_b = (has_results || has_err_word) ? align_up(n * 8 + 8, 256) : 0;
+                 pjobs_b = align_up(pjobs.size() * sizeof(PngJob), 256), wjobs_b = align_up(wjobs.size() * sizeof(WebpJob), 256);
+    const size_t pjobs_off = jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b + mwg_b, wjobs_off = pjobs_off + pjobs_b;
+    const size_t stat_off = wjobs_off + wjobs_b, stat_b = (has_results || has_err_word) ? align_up(n * 8 + 8, 256) : 0;
     const size_t desc_b = stat_off + stat_b;
     uint32_t *status_dev = nullptr;
     const Job *d_jobs = nullptr; const StreamItem *d_items = nullptr; const FrontendJob *d_fjobs = nullptr; const JpegJob *d_jjobs = nullptr;
@@ -1117,6 +1157,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     const MfmaReq *d_mreqs = nullptr;
     const uint32_t *d_mwg = nullptr;
     const PngJob *d_pjobs = nullptr;
+    const WebpJob *d_wjobs = nullptr;
     DescSlot *slot = nullptr;
     if (desc_b) {
         slot = &c->slots[c->next_slot];
@@ -1132,6 +1173,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
             for (size_t k = 0; k < jjobs.size(); ++k) jjobs[k].result = status_dev + 2 * jjob_idx[k];
             for (size_t k = 0; k < fjobs.size(); ++k) fjobs[k].status = status_dev + 2 * fjob_idx[k];
             for (size_t k = 0; k < pjobs.size(); ++k) pjobs[k].result = status_dev + 2 * pjob_idx[k];
+            for (size_t k = 0; k < wjobs.size(); ++k) wjobs[k].result = status_dev + 2 * wjob_idx[k];
         }
         if (!jobs.empty()) memcpy(hp, jobs.data(), jobs.size() * sizeof(Job));
         if (!items.empty()) memcpy(hp + jobs_b, items.data(), items.size() * sizeof(StreamItem));
@@ -1141,6 +1183,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         if (!mreqs.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b, mreqs.data(), mreqs.size() * sizeof(MfmaReq));
         if (!mwg.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b, mwg.data(), mwg.size() * sizeof(uint32_t));
         if (!pjobs.empty()) memcpy(hp + pjobs_off, pjobs.data(), pjobs.size() * sizeof(PngJob));
+        if (!wjobs.empty()) memcpy(hp + wjobs_off, wjobs.data(), wjobs.size() * sizeof(WebpJob));
         // While a previous batch is still running, the block goes up on the context's upload stream: the slot is free (its last
         // batch has ended, see above), so the copy runs under that batch's kernels, and this batch's first kernel follows its
         // last one without a copy engine in between.  A lone request on an idle device sends the block down its own stream (no
@@ -1165,6 +1208,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
         d_mreqs = reinterpret_cast<const MfmaReq *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b);
         d_mwg = reinterpret_cast<const uint32_t *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b);
         d_pjobs = reinterpret_cast<const PngJob *>(dp + pjobs_off);
+        d_wjobs = reinterpret_cast<const WebpJob *>(dp + wjobs_off);
     }
 
     range_plan.reset();
@@ -1270,6 +1314,11 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     if (!pjobs.empty()) {
         ProfileScope ps(c, st, 2);
         FL_HIP(c, launch_png_encode(d_pjobs, (uint32_t)pjobs.size(), png_rows, png_segs, st), "PNG encode");
+        c->stats.frontend_launches++;
+    }
+    if (!wjobs.empty()) {
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_webpll_encode(d_wjobs, (uint32_t)wjobs.size(), wll_tiles, st), "lossless WebP encode");
         c->stats.frontend_launches++;
     }
     // plain copies for requests that change nothing

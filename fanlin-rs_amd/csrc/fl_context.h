@@ -32,6 +32,7 @@
 #include "fl_mfma.h"
 #include "fl_png.h"
 #include "fl_tables.h"
+#include "fl_webpll.h"
 #include "fl_wtile.h"
 
 namespace fl {
@@ -215,6 +216,7 @@ struct flgpu_ctx {
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
     fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
+    fl::DeviceBuf d_webpll_res, d_webpll_tok, d_webpll_tiles, d_webpll_pic, d_webpll_stream; // lossless WebP scratch (fl_webpll.hip): residuals, tokens, tile records, per-picture words, bit streams
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front
     // end, FL_JPEG_RESULT_OVERFLOW), [2i + 1] bytes of an encoded stream
@@ -342,7 +344,7 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
 // room to give an encoded result on the device: the planning bound, or the format's worst case if the caller offers it
 uint64_t staged_out_bytes(const flgpu_params &p, const flgpu_plan &plan, uint64_t dst_capacity);
 // front ends whose output is an encoded stream: its length is a result word, known once the batch has run
-inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG; }
+inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS; }
 // JPEG sources of a batch: dsrc[i].data = DEVICE copy of the coefficient blob whose header (host copy) is hdrs[i], or
 // hdrs[i] == nullptr for ordinary pixel sources.  Runs the decode kernels into scratch and points dsrc[i] at the pixels.
 struct JpegSrc {

@@ -14,6 +14,7 @@
 #include "../../include/fanlin_gpu.h"
 #include "fl_abi.h"
 #include "fl_png.h"
+#include "fl_webpll.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_mfma.h"
@@ -248,9 +249,20 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
     }
     /* a PNG that stays PNG: the finished image/png body (handler.rs:264-273) when the caller opts in */
     if (input_format == FLGPU_IN_PNG && fmt == FLGPU_OUT_KEEP && (accept_flags & FLGPU_ENCODE_PNG)) p->front_end = FLGPU_FE_PNG;
+    /* the WebP arm at quality 100 (negotiated, or a WebP that stays WebP): the finished lossless image/webp body
+       (handler.rs:286-292) when the caller opts in and the VP8L header can hold the size; otherwise pixels, and the host
+       encoder fails on an oversized picture as the reference's does */
+    const bool webp_lossless = input_format != FLGPU_IN_GIF_FRAME && p->front_end == FLGPU_FE_NONE &&
+                               (fmt == FLGPU_OUT_WEBP || (fmt == FLGPU_OUT_KEEP && input_format == FLGPU_IN_WEBP)) &&
+                               (accept_flags & FLGPU_ENCODE_WEBP_LOSSLESS);
     if (out_format) *out_format = fmt;
-    *result_kind = p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
-    return flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
+    rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
+    if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {
+        p->front_end = FLGPU_FE_WEBP_LOSSLESS;
+        rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
+    }
+    *result_kind = p->front_end == FLGPU_FE_WEBP_LOSSLESS ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    return rc;
 }
 
 int flgpu_process_image_plan(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags,
@@ -366,7 +378,9 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    if (p->front_end > FLGPU_FE_PNG || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST) return FLGPU_ERR_INVALID_ARG;
+    /* front ends 0-4 and 6 (5 is not one) */
+    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
+        return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
     if (p->orientation >= 5) { const uint32_t t = sw; sw = sh; sh = t; }
@@ -443,6 +457,13 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         // dst of this capacity is never too small.
         plan->out_bytes = fl::png_filtered_bytes(plan->out_w, plan->out_h, plan->out_c);
         plan->max_out_bytes = fl::png_max_out_bytes(plan->out_bytes);
+        break;
+    case FLGPU_FE_WEBP_LOSSLESS:
+        // the VP8L header holds 14 bits of width - 1 and of height - 1.  out_bytes: a planning bound, the Rgba8 bytes.
+        // max_out_bytes: the format's worst case (fl_webpll.h), so a dst of this capacity is never too small.
+        if (plan->out_w > fl::kWebpllMaxSide || plan->out_h > fl::kWebpllMaxSide) return FLGPU_ERR_UNSUPPORTED;
+        plan->out_bytes = 4ull * plan->out_w * plan->out_h;
+        plan->max_out_bytes = fl::webpll_max_out_bytes(plan->out_w, plan->out_h);
         break;
     case FLGPU_FE_WEBP420:
         plan->plane_w = plan->out_w;

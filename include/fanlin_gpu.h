@@ -29,6 +29,8 @@
  *                                       src/handler.rs:274-278 (FDCT, quantiser, Huffman coder, framing)
  *   front_end = FLGPU_FE_PNG            the whole PngEncoder::new_with_quality(ct, FilterType::Adaptive) +
  *                                       img.write_with_encoder, src/handler.rs:264-273 (row filters, deflate, framing)
+ *   front_end = FLGPU_FE_WEBP_LOSSLESS  image's lossless WebP encoder for q == 100 after img.into_rgba8(),
+ *                                       src/handler.rs:286-292 (transforms, prefix codes, runs, framing)
  *   params.filter = NEAREST             the per-frame pipeline of process_gif, src/handler.rs:327-353
  *   flgpu_process_image                 State::process_image after the decoder as one call, src/handler.rs:198-308
  *   flgpu_ycck_to_cmyk                  the YCCK loop of convert_jpeg_color_if_needed, src/handler.rs:423-438
@@ -94,10 +96,16 @@ typedef enum flgpu_front_end {
                               libwebp's WebPPictureARGBToYUVA makes of the RGBA picture, alpha-weighted chroma included */
     FLGPU_FE_JPEG = 3,     /* dst = the finished JFIF stream of JpegEncoder::new_with_quality(q).encode_image(&img)
                               (src/handler.rs:274-278): baseline, 3 components, 4:4:4; dst->bytes long */
-    FLGPU_FE_PNG = 4       /* dst = the finished PNG file of PngEncoder (src/handler.rs:264-273): signature, IHDR, IDAT...,
+    FLGPU_FE_PNG = 4,      /* dst = the finished PNG file of PngEncoder (src/handler.rs:264-273): signature, IHDR, IDAT...,
                               IEND; 8-bit samples, colour type 0 / 4 / 2 / 6 for out_c 1 / 2 / 3 / 4, no interlace; row
                               filters by the png crate's adaptive rule; compression from quality (< 50 best, < 85 default,
                               otherwise fast); decodes to exactly the FLGPU_FE_NONE pixels; dst->bytes long */
+    /* 5 is not a front end */
+    FLGPU_FE_WEBP_LOSSLESS = 6 /* dst = the finished lossless WebP file (RIFF / VP8L) of image's encoder for q == 100
+                              (src/handler.rs:286-292): the FLGPU_FE_NONE pixels as img.into_rgba8() gives them,
+                              subtract-green, predictor T (L on row 0), one group of prefix codes, runs of the previous pixel;
+                              decodes to exactly into_rgba8() of the FLGPU_FE_NONE pixels; out_w, out_h <= 16384;
+                              dst->bytes long */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
@@ -106,6 +114,10 @@ typedef enum flgpu_front_end {
 /* Not a content::Format bit: the caller wants the library to finish image/png bodies (FLGPU_FE_PNG,
  * FLGPU_RESULT_PNG_STREAM) for PNG inputs that stay PNG.  Without it such requests return pixels, as before. */
 #define FLGPU_ENCODE_PNG 0x100u
+/* Not a content::Format bit: the caller wants the library to finish lossless image/webp bodies (FLGPU_FE_WEBP_LOSSLESS,
+ * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs at quality 100 (src/handler.rs:286-292).  Without it such requests
+ * return pixels, as before. */
+#define FLGPU_ENCODE_WEBP_LOSSLESS 0x200u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -151,12 +163,15 @@ typedef struct flgpu_plan {
     uint64_t pixel_bytes;              /* out_w * out_h * out_c */
     uint64_t out_bytes;                /* bytes the call writes to dst (pixels or planes); for FLGPU_FE_JPEG a planning bound
                                           (about 1 byte per sample) that ordinary pictures stay far below; for FLGPU_FE_PNG
-                                          the filtered rows, out_h * (1 + out_w * out_c) */
+                                          the filtered rows, out_h * (1 + out_w * out_c); for FLGPU_FE_WEBP_LOSSLESS a planning
+                                          bound, the Rgba8 bytes 4 * out_w * out_h */
     uint64_t max_out_bytes;            /* FLGPU_FE_JPEG: the worst case of the format (every 8x8 block of every component at its
                                           longest code, every byte stuffed): a dst of this capacity can never be too small, as
                                           JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).
                                           FLGPU_FE_PNG: the worst case of the format, every 32 KB segment of the filtered rows
                                           as stored blocks: 63 + sum over segments of (L + 5 * ceil(L / 65535) + 5 + 12).
+                                          FLGPU_FE_WEBP_LOSSLESS: the worst case of the format, at most 60 bits per pixel after
+                                          headers under 1 KB: 1024 + ceil(15 * out_w * out_h / 2).
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 
@@ -298,12 +313,16 @@ int flgpu_transform(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *
  *   JPEG_STREAM   input was JPEG and no other container was negotiated: dst holds the finished "image/jpeg" body
  *   PNG_STREAM    input was PNG, no other container was negotiated and accept_flags has FLGPU_ENCODE_PNG: dst holds the
  *                 finished "image/png" body (handler.rs:264-273), dst->bytes long
+ *   WEBP_STREAM   the WebP arm at quality 100 (clamped 1..100, so 255 too; negotiated, or a WebP input that stays WebP) and
+ *                 accept_flags has FLGPU_ENCODE_WEBP_LOSSLESS: dst holds the finished lossless "image/webp" body
+ *                 (handler.rs:286-292), dst->bytes long; an output wider or taller than 16384 stays PIXELS
  *   WEBP_PLANES   lossy WebP was negotiated (handler.rs:286-297): dst holds Y | U | V for WebPEncode
- *   PIXELS        everything else (PNG without FLGPU_ENCODE_PNG, AVIF, lossless WebP, GIF frames, ...): dst holds the DynamicImage pixels for
+ *   PIXELS        everything else (PNG without FLGPU_ENCODE_PNG, AVIF, lossless WebP without FLGPU_ENCODE_WEBP_LOSSLESS, GIF frames, ...): dst holds the DynamicImage pixels for
  *                 the crate's own encoder; *out_format says which container was negotiated
  * Errors: FLGPU_ERR_PARSE where axum answers 400 (bad query, or the size gate of src/main.rs:134-138). */
 typedef enum flgpu_input_format { FLGPU_IN_OTHER = 0, FLGPU_IN_JPEG = 1, FLGPU_IN_PNG = 2, FLGPU_IN_WEBP = 3, FLGPU_IN_GIF_FRAME = 4 } flgpu_input_format;
-typedef enum flgpu_result_kind { FLGPU_RESULT_AS_IS = 0, FLGPU_RESULT_JPEG_STREAM = 1, FLGPU_RESULT_WEBP_PLANES = 2, FLGPU_RESULT_PIXELS = 3, FLGPU_RESULT_PNG_STREAM = 4 } flgpu_result_kind;
+typedef enum flgpu_result_kind { FLGPU_RESULT_AS_IS = 0, FLGPU_RESULT_JPEG_STREAM = 1, FLGPU_RESULT_WEBP_PLANES = 2, FLGPU_RESULT_PIXELS = 3, FLGPU_RESULT_PNG_STREAM = 4,
+                                 FLGPU_RESULT_WEBP_STREAM = 5 } flgpu_result_kind;
 int flgpu_process_image(flgpu_ctx *ctx, const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string,
                         uint32_t accept_flags, int input_format, flgpu_image *dst, flgpu_plan *plan, int *result_kind,
                         int *out_format);
@@ -359,7 +378,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG, FLGPU_FE_PNG: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS

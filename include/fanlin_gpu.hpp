@@ -79,6 +79,9 @@ public:
     bool avif_accepted() const { return (flags_ & FLGPU_ACCEPT_AVIF) == FLGPU_ACCEPT_AVIF; }
     // not a content::Format bit: the library finishes image/png bodies for PNG inputs that stay PNG (FLGPU_RESULT_PNG_STREAM)
     void encode_png() { flags_ |= FLGPU_ENCODE_PNG; }
+    // not a content::Format bit: the library finishes lossless image/webp bodies, the WebP arm at quality 100
+    // (FLGPU_RESULT_WEBP_STREAM)
+    void encode_webp_lossless() { flags_ |= FLGPU_ENCODE_WEBP_LOSSLESS; }
     uint32_t flags() const { return flags_; }
 
 private:
@@ -97,7 +100,7 @@ struct Decoded {
 };
 
 struct Processed {
-    flgpu_result_kind kind;        // AS_IS: serve the original bytes; JPEG_STREAM / PNG_STREAM: body is final; WEBP_PLANES / PIXELS: host encoder
+    flgpu_result_kind kind;        // AS_IS: serve the original bytes; JPEG_STREAM / PNG_STREAM / WEBP_STREAM: body is final; WEBP_PLANES / PIXELS: host encoder
     flgpu_out_format negotiated;   // container chosen at src/handler.rs:256-261
     flgpu_plan plan;               // geometry of what `data` holds
     uint32_t flags;                // FLGPU_IMG_*
@@ -140,8 +143,8 @@ public:
         check(flgpu_process_image_plan(&src, img.orientation, params.text().c_str(), content.flags(), img.format, &out.plan, &kind));
         out.kind = static_cast<flgpu_result_kind>(kind);
         if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
-        // a PNG body is staged at the format's worst case, so that it never comes back too small
-        out.data.resize(out.kind == FLGPU_RESULT_PNG_STREAM ? out.plan.max_out_bytes : out.plan.out_bytes);
+        // a PNG or lossless WebP body is staged at the format's worst case, so that it never comes back too small
+        out.data.resize(out.kind == FLGPU_RESULT_PNG_STREAM || out.kind == FLGPU_RESULT_WEBP_STREAM ? out.plan.max_out_bytes : out.plan.out_bytes);
         flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
         check(flgpu_process_image(ctx_, &src, img.orientation, params.text().c_str(), content.flags(), img.format, &dst, &out.plan, &kind, &fmt), ctx_);
         out.negotiated = static_cast<flgpu_out_format>(fmt);

@@ -31,6 +31,7 @@ pub const FE_JFIF444: u8 = 1;
 pub const FE_WEBP420: u8 = 2;
 pub const FE_JPEG: u8 = 3;
 pub const FE_PNG: u8 = 4;
+pub const FE_WEBP_LOSSLESS: u8 = 6; // (5 is not a front end)
 pub const FILTER_NEAREST: u8 = 1;
 const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
@@ -38,11 +39,14 @@ pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
 // not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
 pub const ENCODE_PNG: u32 = 0x100;
+// not a content::Format bit: finish lossless image/webp bodies on the device, the WebP arm at quality 100 (RESULT_WEBP_STREAM)
+pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
 pub const RESULT_WEBP_PLANES: c_int = 2;
 pub const RESULT_PIXELS: c_int = 3;
 pub const RESULT_PNG_STREAM: c_int = 4;
+pub const RESULT_WEBP_STREAM: c_int = 5;
 const ERR_UNSUPPORTED: c_int = 2; // FLGPU_ERR_UNSUPPORTED: a stream the device decoder does not cover
 const CMYK_INPUT_YCCK: u32 = 1;
 
@@ -137,14 +141,14 @@ impl Gpu {
         if let Some((w, h)) = q.dimensions() { p.has_dims = 1; p.w = w; p.h = h; }
         let mut plan = FlPlan::default();
         check(unsafe { flgpu_plan_output(&p, img.width(), img.height(), c, &mut plan) })?;
-        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG and FE_PNG, where it is the
+        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, FE_PNG and FE_WEBP_LOSSLESS, where it is the
         // worst case of the format: with it the call cannot fail for lack of room, as `encode_image` into a Vec cannot.
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let src = FlImage { data: bytes.as_ptr() as *mut u8, capacity: bytes.len() as u64,
                             width: img.width(), height: img.height(), channels: c, flags: 0, bytes: 0 };
         let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
         check(unsafe { flgpu_transform(self.0, &src, &p, &mut dst) })?;
-        out.truncate(dst.bytes as usize); // pixels / planes: == out_bytes; JPEG / PNG: the stream length
+        out.truncate(dst.bytes as usize); // pixels / planes: == out_bytes; JPEG / PNG / WebP: the stream length
         Ok(Outcome::Device { plan, bytes: out, has_alpha: dst.flags & IMG_HAS_ALPHA != 0 })
     }
 
@@ -288,6 +292,23 @@ fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(
 //
 //     if let gpu::Outcome::Device { bytes, .. } = self.gpu.transform(&img, params, orientation.to_exif(), gpu::FE_PNG, false)? {
 //         return Ok((ImageFormat::Png.to_mime_type(), bytes));
+//     }
+//
+// The WebP arm at quality 100 (lines 286-292: `image`'s lossless encoder after `into_rgba8()`): with ENCODE_WEBP_LOSSLESS the
+// finished lossless body instead of the pixels, for a negotiated `webp=true` and for a WebP source that stays WebP.  Outputs
+// wider or taller than 16384 still come back as RESULT_PIXELS, and the crate's encoder refuses them as before:
+//
+//     let accept = (content.webp_accepted() as u32) * gpu::ACCEPT_WEBP | (content.avif_accepted() as u32) * gpu::ACCEPT_AVIF
+//                  | gpu::ENCODE_PNG | gpu::ENCODE_WEBP_LOSSLESS;
+//     match kind {
+//         gpu::RESULT_WEBP_STREAM => return Ok((ImageFormat::WebP.to_mime_type(), bytes)),                   // lines 286-292
+//         /* ... the other kinds as above ... */
+//     }
+//
+// or, through `transform` where the handler has already taken the q == 100 WebP arm:
+//
+//     if let gpu::Outcome::Device { bytes, .. } = self.gpu.transform(&img, params, orientation.to_exif(), gpu::FE_WEBP_LOSSLESS, false)? {
+//         return Ok((ImageFormat::WebP.to_mime_type(), bytes));
 //     }
 //
 // and, for JPEG sources that stay JPEG, the whole `ImageFormat::Jpeg` arm (lines 274-278):
