@@ -5,7 +5,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cassert>
 #include <memory>
+#include <optional>
 
 #include "fl_context.h"
 
@@ -16,7 +18,7 @@ namespace {
 // ---- batch execution -------------------------------------------------------
 
 enum Stage1Kind { S1_NONE = 0, S1_PLACE = 1, S1_GENERIC = 2, S1_STREAM = 3, S1_NEAREST = 4, S1_MFMA = 5, S1_TILE = 6, S1_WTILE = 7 };
-constexpr uint32_t kBlurWtileKind = 0x1000u; // blur group key: the window-tile kernel instead of blur_tile_kernel (| its register split)
+constexpr size_t kNoScratch = ~(size_t)0; // Work: an output that does not go to scratch
 
 struct Work {
     flgpu_plan plan;
@@ -24,9 +26,10 @@ struct Work {
     uint32_t cs, pre, sw, sh;
     Stage1Kind s1;
     const uint8_t *src;
-    uint8_t *s1_dst;   // output of stage 1 (== src when S1_NONE)
-    uint8_t *blur_dst; // output of the blur stage (or null)
+    uint8_t *s1_dst = nullptr;   // output of stage 1 (== src when S1_NONE)
+    uint8_t *blur_dst = nullptr; // output of the blur stage (or null)
     uint8_t *final_dst;
+    size_t s1_off = kNoScratch, blur_off = kNoScratch; // where stage 1's / the blur's output goes to scratch A / B: its offset there
     AxisKey vk, hk;
     const HostAxis *va = nullptr, *ha = nullptr;
     uint32_t vtab = 0, htab = 0;
@@ -34,26 +37,95 @@ struct Work {
     const MfmaPlan *mplan = nullptr;
     const std::vector<MfmaItem> *mitems = nullptr; // its workgroups for the band count of this batch
     bool unaligned = false;
-    size_t jpeg_coef_off = 0, jpeg_off_off = 0, jpeg_raw_off = 0; // FE_JPEG scratch (bytes)
     uint32_t jpeg_tab = 0;
-    size_t png_filt_off = 0; uint32_t png_row0 = 0, png_seg0 = 0, png_nseg = 0; // FE_PNG scratch: filtered rows (bytes), flat row / segment numbers
-    size_t wll_res_off = 0, wll_tok_off = 0, wll_stream_off = 0; uint32_t wll_tile0 = 0, wll_pic = 0; // FE_WEBP_LOSSLESS scratch (bytes), flat tile / picture numbers
     uint32_t orient = 0, raw_w = 0, raw_h = 0; // EXIF orientation pre-pass (2..8), source size before it
     size_t orient_off = 0;
     uint32_t tile_w = 0;        // S1_TILE: output columns per tile (power of two)
     uint32_t tile_vplan = 0;    // S1_TILE: arena offset of the vertical band tables (build_tile_vplan)
-    size_t align_off = 0;       // misaligned device source of a matrix-pipe geometry: offset of its aligned copy in d_tmp_al
-    bool align_copy = false;
+    size_t align_off = kNoScratch; // misaligned device source of a matrix-pipe geometry: offset of its aligned copy in d_tmp_al
     const uint8_t *raw_src = nullptr;
     const WtPlan *wplan = nullptr;   // S1_WTILE: the window-tile matrix-pipe kernel's tables
     const WtPlan *bwplan = nullptr;  // ... for the blur stage, where that kernel serves it
     bool luma_mid = false;           // grey picture on a grey frame + blur on that kernel: stage 1 leaves the UNFRAMED Luma8 picture, the blur reads it through a virtual frame and writes Rgba8
 };
 
-struct GroupKey {
-    uint32_t kind, cs, pre, lb;
-    bool operator<(const GroupKey &o) const { return std::tie(kind, cs, pre, lb) < std::tie(o.kind, o.cs, o.pre, o.lb); }
+// A stage-1 launch: pictures one kernel instantiation serves together.  S1_WTILE: nslot register sets; S1_MFMA: the plans'
+// layout and arithmetic (ops_in_lds, wide, full, compact); S1_STREAM: nacc accumulator slots, rows that are not dword aligned
+// (unaligned: the funnel-shift variant); lb: a letterboxed destination.
+struct ResampleKey {
+    Stage1Kind s1;
+    uint32_t nslot, nacc, cs, pre;
+    bool ops_in_lds, wide, full, compact, unaligned, lb;
+    // Launches go out in the order they always have: by this word (the stage kind, its flags from bit 8 up), then cs, pre, lb.
+    uint32_t rank() const { return s1 | nslot << 8 | ops_in_lds << 8 | wide << 9 | full << 10 | compact << 11 | nacc << 8 | unaligned << 16; }
+    bool operator<(const ResampleKey &o) const { return std::make_tuple(rank(), cs, pre, lb) < std::make_tuple(o.rank(), o.cs, o.pre, o.lb); }
 };
+
+// A blur launch: the window-tile kernel (nslot register sets; luma_mid: one channel read through a virtual frame) or blur_tile_kernel
+// (lanes per workgroup, channels filtered); c = channels of the blurred picture.  blur_tile_kernel's launches go out first.
+struct BlurKey {
+    bool wtile;
+    uint32_t nslot, lanes, c, filtered;
+    bool luma_mid;
+    bool operator<(const BlurKey &o) const { return std::tie(wtile, nslot, lanes, c, filtered, luma_mid) < std::tie(o.wtile, o.nslot, o.lanes, o.c, o.filtered, o.luma_mid); }
+};
+
+// One launch of stage 1 or of the blur: its jobs and work items in the batch's arrays, and what its kernel needs besides
+// (matrix-pipe kernel: widest strip, persistent workgroups and their item lists; blur_tile_kernel: grid, whether it serves the launch).
+template <class Key> struct Launch {
+    Key k;
+    uint32_t job_base = 0, njobs = 0, item_base = 0, nitems = 0, max_nout = 0, grid = 0, wg_base = 0, blur_grid_x = 0;
+    bool blur_tiled = false;
+    LaunchGeneric g{};
+    size_t lds = 0, mid_floats = 0;
+};
+struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
+
+// Bytes (or records) of every scratch buffer a batch needs; while pictures are added, the running totals are their offsets.
+struct ScratchSizes {
+    size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
+    size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
+    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0;
+};
+
+// What passes between the phases of run_batch_device.
+struct Batch {
+    size_t n;
+    flgpu_image *dsts;
+    const DebugSwitches &dbg; // the context's switches (flgpu_debug_set; tests and A/B runs)
+    std::vector<Work> work;
+    ScratchSizes scratch;
+    // launches, and the arrays their descriptor block holds
+    std::vector<LaunchGeneric> orient_launches; // EXIF orientation pre-pass, one per channel count
+    std::vector<Launch<ResampleKey>> s1_launches;
+    std::vector<Launch<BlurKey>> blur_launches;
+    std::vector<FeLaunch> fe_launches;
+    std::vector<Job> jobs;
+    std::vector<StreamItem> items;
+    std::vector<MfmaItem> mitems;
+    std::vector<MfmaReq> mreqs;
+    std::vector<uint32_t> mwg; // matrix-pipe launches with persistent workgroups: {first item, items} of every workgroup
+    std::vector<FrontendJob> fjobs;
+    std::vector<JpegJob> jjobs;
+    std::vector<PngJob> pjobs;
+    std::vector<WebpJob> wjobs;
+    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img; // image of every front-end / encoder job: addresses its result words
+    uint32_t jpeg_max_blocks = 0;
+    size_t mid_floats_max = 0;
+    bool has_results = false, has_err_word = false;
+    // the staged descriptor block
+    DescSlot *slot = nullptr;
+    uint32_t *status_dev = nullptr;
+    struct {
+        const Job *jobs; const StreamItem *items; const FrontendJob *fjobs; const JpegJob *jjobs; const MfmaItem *mitems;
+        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs;
+    } d{}; // the arrays' device copies
+    Batch(flgpu_ctx *c, size_t n_, flgpu_image *dsts_) : n(n_), dsts(dsts_), dbg(*c->dbg), work(n_) {}
+};
+
+// The window-tile matrix-pipe kernel (fl_wtile.h) for mild ratios, up-scales and blurs: full-width arithmetic only (mfma_arith = 1
+// asks for rounds 2-3's packed arithmetic: A/B runs and the tests that keep the packed kernel's bars); no_wtile keeps the f32 vector kernels.
+bool use_wtile(const DebugSwitches &dbg) { return !dbg.on(DBG_NO_WTILE) && !dbg.on(DBG_NO_MFMA) && !dbg.on(DBG_FORCE_GENERIC) && !dbg.on(DBG_MFMA_ARITH); }
 
 // Channels the blur really has to filter: a letterboxed picture of an opaque source has alpha == 255 everywhere,
 // and a grey one on a grey fill has R == G == B (see blur_tile_kernel).
@@ -65,15 +137,6 @@ uint32_t blur_channels(const Work &w)
         ce = grey ? 1u : 3u;
     }
     return ce;
-}
-
-// Resamples the window-tile matrix-pipe kernel takes from the f32 vector kernels: every one its planner accepts.  (The first version
-// measured equal to the tiled kernel on up-scales and the rule kept those there; after the kernel's tuning it is ahead on them as
-// well -- 1080p -> 2000x1000 1.23 vs 1.48 ms per 128, 720p -> 1600x900 1.64 vs 1.97 per 256, 1080p -> 1600x900 1.02 vs 1.77 per 128,
-// thumbnails 3.4 vs 3.55 per 8,192; profiles/r04_wtile_experiments.txt.)
-bool wtile_resample_wanted(const Work &)
-{
-    return true;
 }
 
 // Row bands per picture for the window-tile kernel: small batches are cut so that the chip still sees a few hundred workgroups
@@ -317,6 +380,786 @@ void xcd_interleave(Item *first, uint32_t nitems, Len len_of)
     }
 }
 
+
+// ---- planning ------------------------------------------------------------------------------------------------------------------
+
+// Encoded-stream front ends: the scratch one picture needs, appended to s, and the format's limits.  The job-building pass calls
+// them again on a running copy of the totals, which gives every picture the offsets it got here.
+int jpeg_scratch(const flgpu_plan &pl, ScratchSizes &s)
+{
+    if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions
+    const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
+    if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
+    s.jpeg_coef += align_up(units * sizeof(uint32_t), 256);
+    s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
+    s.jpeg_raw += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
+    return FLGPU_OK;
+}
+
+int png_scratch(const flgpu_plan &pl, ScratchSizes &s)
+{
+    const uint64_t fb = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
+    if ((uint64_t)s.png_rows + pl.out_h >= (1ull << 31) || (uint64_t)s.png_segs + png_segments(fb) >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
+    s.png_filt += align_up(fb, 256);
+    s.png_rows += pl.out_h;
+    s.png_segs += (uint32_t)png_segments(fb);
+    return FLGPU_OK;
+}
+
+int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
+{
+    const uint64_t npix = (uint64_t)pl.out_w * pl.out_h;
+    if ((uint64_t)s.wll_tiles + webpll_tiles(npix) >= (1ull << 31) || webpll_max_out_bytes(pl.out_w, pl.out_h) / 4u >= (1ull << 32))
+        return FLGPU_ERR_UNSUPPORTED;
+    s.wll_res += align_up(npix * 4u, 256);
+    s.wll_tok += align_up(npix * 2u, 256);
+    s.wll_stream += align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256);
+    s.wll_tiles += (uint32_t)webpll_tiles(npix);
+    s.wll_pics++;
+    return FLGPU_OK;
+}
+
+// Validates and plans every picture of the batch and sizes its scratch.  Nothing is enqueued before all of them have passed.
+int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, bool same_params)
+{
+    for (size_t i = 0; i < B.n; ++i) {
+        Work &w = B.work[i];
+        const flgpu_image &s = srcs[i];
+        w.p = same_params ? &ps[0] : &ps[i];
+        if (!s.data || !B.dsts[i].data) return FLGPU_ERR_INVALID_ARG;
+        int rc = flgpu_plan_output(w.p, s.width, s.height, s.channels, &w.plan);
+        if (rc) return rc;
+        if (s.capacity < (uint64_t)s.width * s.height * s.channels) return FLGPU_ERR_INVALID_ARG;
+        if (B.dsts[i].capacity < w.plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+        w.cs = s.channels; w.sw = w.plan.src_w; w.sh = w.plan.src_h; // size after apply_orientation
+        w.raw_w = s.width; w.raw_h = s.height;
+        w.orient = w.p->orientation >= 2 ? w.p->orientation : 0;
+        if (w.orient) { w.orient_off = B.scratch.o; B.scratch.o += align_up((size_t)s.width * s.height * s.channels, 256); }
+        w.pre = w.p->grayscale ? PRE_GRAY : (w.p->inverse ? PRE_INVERT : PRE_NONE);
+        w.src = s.data;
+        w.final_dst = B.dsts[i].data;
+        const flgpu_plan &pl = w.plan;
+        const bool cropped = pl.crop_x || pl.crop_y || pl.out_w != pl.resized_w || pl.out_h != pl.resized_h;
+        // grayscale of Luma/LumaA and "no-op" pre-ops change nothing
+        const bool pre_changes = (w.pre == PRE_INVERT) || (w.pre == PRE_GRAY && w.cs >= 3);
+        if (!pre_changes) w.pre = PRE_NONE;
+        if (pl.resampled) w.s1 = w.p->filter == FLGPU_FILTER_NEAREST ? S1_NEAREST : S1_GENERIC;
+        else if (pre_changes || pl.letterboxed || cropped) w.s1 = S1_PLACE;
+        else w.s1 = S1_NONE;
+        // Which resample kernel serves a request is a function of the REQUEST (geometry, channels, pre-op), never of where the
+        // caller's buffer happens to start: the matrix-pipe kernel moves 16-byte pieces of a row, so a source whose rows qualify
+        // but whose base is not 16-byte aligned (only possible through the device-batch entry point; staged and decoded sources
+        // are 256-byte aligned) is copied to aligned scratch first.  The two kernels may differ by 1 LSB; an HTTP cache in front of
+        // the service must not see that difference come and go with an address.
+        // (only where that kernel can be the one: its own gate below -- no pre-op, rows of at least 64 bytes, not switched off -- and a
+        // ratio above the window-tile kernel's range, which takes any alignment; everything else is served by kernels that do not care)
+        // (from ratio 2 up whether or not the window-tile kernel is on: that kernel takes any alignment, but where ITS planner refuses
+        // a geometry below ratio 2.5 the request falls through to the matrix-pipe branch -- which must not then depend on the address)
+        const bool mfma_candidate = !B.dbg.on(DBG_NO_MFMA) && !B.dbg.on(DBG_FORCE_GENERIC) && (size_t)w.sw * w.cs >= 64u && (uint64_t)w.sh >= 2u * (uint64_t)pl.resized_h;
+        if (pl.resampled && w.s1 == S1_GENERIC && !pre_changes && !w.orient && mfma_candidate && ((size_t)w.sw * w.cs) % 16u == 0 && (uintptr_t)s.data % 16u != 0) {
+            w.align_off = B.scratch.al;
+            B.scratch.al += align_up((size_t)s.width * s.height * s.channels, 256);
+        }
+        const bool blur = w.p->blur_sigma > 0.0f;
+        const bool fe = w.p->front_end != FLGPU_FE_NONE;
+        // buffer chain: stage 1 -> blur -> front end, each writing the final destination if it is the last stage, else scratch
+        if (w.s1 != S1_NONE && !blur && !fe) w.s1_dst = w.final_dst;
+        else if (w.s1 != S1_NONE) { w.s1_off = B.scratch.a; B.scratch.a += align_up(pl.pixel_bytes, 256); }
+        if (blur && !fe) w.blur_dst = w.final_dst;
+        else if (blur) { w.blur_off = B.scratch.b; B.scratch.b += align_up(pl.pixel_bytes, 256); }
+        if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
+        if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
+        if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
+        if (rc) return rc;
+    }
+    return FLGPU_OK;
+}
+
+// Reserves the batch's scratch, points every picture at its part of it, and enqueues the copies of the sources that the
+// orientation pre-pass and the alignment rule move.
+int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
+{
+    const ScratchSizes &sz = B.scratch;
+    FL_HIP(c, c->d_jpeg_coef.reserve(sz.jpeg_coef), "JPEG coefficient scratch");
+    FL_HIP(c, c->d_jpeg_off.reserve(sz.jpeg_off), "JPEG offset scratch");
+    FL_HIP(c, c->d_jpeg_raw.reserve(sz.jpeg_raw), "JPEG bit-stream scratch");
+    FL_HIP(c, c->d_png_filt.reserve(sz.png_filt), "PNG filtered-row scratch");
+    FL_HIP(c, c->d_png_chunks.reserve((size_t)sz.png_segs * kPngSegOutBytes), "PNG chunk scratch");
+    FL_HIP(c, c->d_png_syms.reserve((size_t)sz.png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
+    FL_HIP(c, c->d_png_recs.reserve((size_t)sz.png_segs * 4u * sizeof(uint32_t)), "PNG segment records");
+    FL_HIP(c, c->d_webpll_res.reserve(sz.wll_res), "WebP residual scratch");
+    FL_HIP(c, c->d_webpll_tok.reserve(sz.wll_tok), "WebP token scratch");
+    FL_HIP(c, c->d_webpll_tiles.reserve((size_t)sz.wll_tiles * sizeof(WebpllTile)), "WebP tile records");
+    FL_HIP(c, c->d_webpll_pic.reserve((size_t)sz.wll_pics * kWebpllPicWords * sizeof(uint32_t)), "WebP per-picture scratch");
+    FL_HIP(c, c->d_webpll_stream.reserve(sz.wll_stream), "WebP bit-stream scratch");
+    FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
+    FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
+    for (auto &w : B.work)
+        if (w.align_off != kNoScratch) {
+            uint8_t *al = static_cast<uint8_t *>(c->d_tmp_al.p) + w.align_off;
+            FL_HIP(c, hipMemcpyAsync(al, w.src, (size_t)w.sw * w.sh * w.cs, hipMemcpyDeviceToDevice, st), "alignment copy");
+            w.src = al;
+        }
+    FL_HIP(c, c->d_tmp_a.reserve(sz.a), "scratch A");
+    FL_HIP(c, c->d_tmp_b.reserve(sz.b), "scratch B");
+    for (auto &w : B.work) {
+        if (w.orient) { w.raw_src = w.src; w.src = static_cast<uint8_t *>(c->d_tmp_o.p) + w.orient_off; }
+        if (w.s1 == S1_NONE) w.s1_dst = const_cast<uint8_t *>(w.src);
+        if (w.s1_off != kNoScratch) w.s1_dst = static_cast<uint8_t *>(c->d_tmp_a.p) + w.s1_off;
+        if (w.blur_off != kNoScratch) w.blur_dst = static_cast<uint8_t *>(c->d_tmp_b.p) + w.blur_off;
+    }
+    return FLGPU_OK;
+}
+
+// ---- tables ----------------------------------------------------------------------------------------------------------------------
+
+// Planning stops short of the arena's last 1024 words: the batch starts over after a reset instead.
+bool arena_nearly_full(const flgpu_ctx *c) { return c->h_arena.size() >= c->arena_cap_words - 1024; }
+
+// The arena offset of the table block `cache` holds under `key`; on a miss build(blk) makes the block and it is appended.
+// 0 = the arena is full.
+template <class Map, class Build> uint32_t cached_block(flgpu_ctx *c, Map &cache, const typename Map::key_type &key, Build &&build)
+{
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    std::vector<uint32_t> blk;
+    build(blk);
+    const uint32_t off = arena_append(c, blk.data(), blk.size());
+    if (off) cache.emplace(key, off);
+    return off;
+}
+
+// One resample kernel asked for picture w (j: its job, for the kept window): w.s1 becomes that kernel's if its planner accepts the
+// geometry.  false = the table arena is full.
+bool try_wtile(flgpu_ctx *c, Work &w, const Job &j)
+{
+    WtPlan *wp = get_wtile_plan(c, w.vk, *w.va, w.hk, *w.ha, j.cx, j.cy, j.cw, j.ch, w.cs);
+    if (wp->arena_full || arena_nearly_full(c)) return false;
+    if (wp->ok) { w.s1 = S1_WTILE; w.wplan = wp; }
+    return true;
+}
+
+bool try_mfma(flgpu_ctx *c, const DebugSwitches &dbg, size_t n_resample, Work &w, const Job &j)
+{
+    MfmaPlan *mp = get_mfma_plan(c, w.vk, *w.va, w.hk, *w.ha, j.cx, j.cy, j.cw, j.ch, w.cs, dbg.on(DBG_MFMA_ARITH) ? MFMA_ARITH_PACKED : MFMA_ARITH_FULL);
+    if (mp->arena_full || arena_nearly_full(c)) return false;
+    if (!mp->ok) return true;
+    uint32_t nbands = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_FORCE_BANDS));
+    if (!nbands && n_resample < 128) {
+        // A small launch: bands of rows so that every CU has an item -- and so that the items come out in whole rounds of the
+        // workgroups.  (Until round 5: ceil(256 / (3 n)) bands; 13 files x 3 strips x 7 bands = 273 items on 256 workgroups,
+        // i.e. two rounds of items a seventh of a strip long where one round of sixths does: 84 us per batch of file requests.)
+        // The cost of a band count: rounds x (the longest item's K-blocks -- the bands' halos are in there -- + a transition's two).
+        const uint64_t G = std::max(1u, c->cu_count);
+        uint64_t best = ~0ull;
+        for (uint32_t b = 1; b <= std::min<uint32_t>(16u, (uint32_t)mp->tiles.size()); ++b) {
+            const std::vector<MfmaItem> &cand = mp->items_for(b);
+            uint32_t longest = 0;
+            for (const MfmaItem &mi : cand) longest = std::max(longest, mi.kb1 - mi.kb0);
+            const uint64_t cost = (((uint64_t)n_resample * cand.size() + G - 1) / G) * (longest + 2u);
+            if (cost < best) { best = cost; nbands = b; }
+        }
+    }
+    w.s1 = S1_MFMA; w.mplan = mp; w.mitems = &mp->items_for(std::max(nbands, 1u));
+    return true;
+}
+
+bool try_stream(flgpu_ctx *c, const DebugSwitches &dbg, size_t n_resample, Work &w, const Job &j)
+{
+    uint32_t nbands = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_FORCE_BANDS));
+    // small batches: split images into row bands so that the chip still gets >= ~1024 workgroups
+    if (!nbands && n_resample < 512) nbands = std::min((uint32_t)((1024 + n_resample * 2 - 1) / (n_resample * 2)), j.ch / 24u);
+    nbands = std::min(std::max(nbands, 1u), std::max(1u, j.ch));
+    const StreamPlan *sp = get_stream_plan(c, w.vk, *w.va, w.hk, *w.ha, j.cx, j.cy, j.cw, j.ch, nbands, w.cs, w.pre);
+    if (arena_nearly_full(c)) return false;
+    if (sp->ok) { w.s1 = S1_STREAM; w.splan = sp; }
+    return true;
+}
+
+bool try_tile(flgpu_ctx *c, Work &w, const Job &j)
+{
+    const uint32_t tw = tile_width_for(*w.ha, *w.va, j.cx, j.cw, j.cy, j.ch, mid_channels(w.cs, w.pre));
+    if (!tw) return true;
+    const uint32_t off = cached_block(c, c->tile_vplans, std::make_tuple(w.vk, j.cy, j.ch), [&](std::vector<uint32_t> &blk) { build_tile_vplan(*w.va, j.cy, j.ch, blk); });
+    if (off) { w.s1 = S1_TILE; w.tile_w = tw; w.tile_vplan = off; }
+    return off != 0;
+}
+
+// Stage 1's resample kernel for picture w: sets w.s1 and its plan, the HBM two-pass kernels (S1_GENERIC) if no other takes it.
+// false = the table arena is full.
+bool route_resample(flgpu_ctx *c, const DebugSwitches &dbg, size_t n_resample, Work &w)
+{
+    w.vtab = get_axis(c, w.sh, w.plan.resized_h, FILTER_LANCZOS3, 0.0f, &w.vk, &w.va);
+    w.htab = get_axis(c, w.sw, w.plan.resized_w, FILTER_LANCZOS3, 0.0f, &w.hk, &w.ha);
+    if (!w.vtab || !w.htab) return false;
+    w.s1 = S1_GENERIC;
+    // rows that are not dword aligned: Rgb8 has a funnel-shift variant of the kernel, others use the generic path
+    w.unaligned = ((w.sw * w.cs) % 4u != 0) || ((uintptr_t)w.src % 4u != 0);
+    const bool force_generic = dbg.on(DBG_FORCE_GENERIC), lb_ok = !w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0;
+    const bool wtile_ok = use_wtile(dbg) && (w.pre == PRE_NONE || w.pre == PRE_INVERT) && lb_ok;
+    Job j; fill_job(w, j);
+    // The matrix-pipe kernel takes down-scales (any channel count, no pre-op) whose rows are 16-byte aligned (it moves 16-byte pieces of a row
+    // straight into LDS).  The choice depends on the request's geometry only, never on the batch around it.
+    // Ratios below 2.5 (up-scales included) go to the window-tile kernel BEFORE the fused ones: measured 1.00 vs 1.03 ms per 256 at ratio 2.4 and -- against the
+    // streaming f32 kernel, which serves what the matrix-pipe planner refuses down there -- 1.16 vs 2.10 at 2.13.  From 2.67 up the
+    // streaming matrix-pipe kernel wins since its wide layout keeps operands in LDS (0.78 vs 0.92 at 2.67, 0.72 vs 0.80 at 3;
+    // profiles/r04_wtile_experiments.txt); where ITS planner refuses a geometry below ratio 3.4, the window-tile kernel is asked again.
+    // (wt_first, experiments: the window-tile kernel before the streaming matrix-pipe kernel)
+    bool ok = true;
+    if ((dbg.on(DBG_WTILE_FIRST) || 2u * w.sh < 5u * w.plan.resized_h) && wtile_ok) ok = try_wtile(c, w, j);
+    if (ok && w.s1 == S1_GENERIC && w.pre == PRE_NONE && !force_generic && !dbg.on(DBG_NO_MFMA) && (w.sw * w.cs) % 16u == 0 && (uintptr_t)w.src % 16u == 0 &&
+        lb_ok && w.sw * w.cs >= 64u)
+        ok = try_mfma(c, dbg, n_resample, w, j);
+    // (ratio 2.5 .. 3.4 and no streaming matrix-pipe plan: unaligned rows, a pre-op, a refused geometry)
+    if (ok && w.s1 == S1_GENERIC && wtile_ok && 2u * w.sh >= 5u * w.plan.resized_h && 10u * w.sh < 34u * w.plan.resized_h) ok = try_wtile(c, w, j);
+    if (ok && w.s1 == S1_GENERIC && stream_supported(w.cs, w.pre) && (!w.unaligned || w.cs == 3) && lb_ok && !force_generic) ok = try_stream(c, dbg, n_resample, w, j);
+    // What neither fused kernel takes and no pre-op precedes: the window-tile matrix-pipe kernel (any pitch and alignment) -- every
+    // resample its planner accepts.  (The first version measured equal to the tiled kernel on up-scales and the rule kept those
+    // there; after the kernel's tuning it is ahead on them as well -- 1080p -> 2000x1000 1.23 vs 1.48 ms per 128, 720p -> 1600x900
+    // 1.64 vs 1.97 per 256, 1080p -> 1600x900 1.02 vs 1.77 per 128, thumbnails 3.4 vs 3.55 per 8,192; profiles/r04_wtile_experiments.txt.)
+    if (ok && w.s1 == S1_GENERIC && wtile_ok) ok = try_wtile(c, w, j);
+    // what neither fused kernel takes (up-scales, mild down-scales, odd pitches, forced generic): the two passes through an
+    // LDS tile instead of an f32 intermediate in HBM, if a tile width fits (FLGPU_NO_TILE=1 keeps the HBM form: tests, A/B)
+    if (ok && w.s1 == S1_GENERIC && !dbg.on(DBG_NO_TILE)) ok = try_tile(c, w, j);
+    return ok;
+}
+
+// The blur stage's tables for picture w: the window-tile kernel's where its planner takes the picture, else blur_tile_kernel's.
+// false = the table arena is full.
+bool plan_blur(flgpu_ctx *c, const DebugSwitches &dbg, Work &w)
+{
+    AxisKey k; const HostAxis *h;
+    AxisKey kv; const HostAxis *hv;
+    w.bwplan = nullptr; w.luma_mid = false; // (a second attempt after an arena reset plans again)
+    if (!get_axis(c, w.plan.out_h, w.plan.out_h, FILTER_GAUSSIAN, w.p->blur_sigma, &kv, &hv) ||
+        !get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &k, &h)) return false;
+    if (use_wtile(dbg)) {
+        // Blurs the window-tile matrix-pipe kernel takes: every one its planner accepts.  A grey picture on a grey frame (R == G == B
+        // everywhere, alpha 255): ONE channel is filtered, if that plan is one of the single-register-set kind (the kernel's framed
+        // source exists in that instantiation only) -- stage 1 leaves the unframed Luma8 picture, the kernel reads the frame's rows
+        // and columns as the fill value and expands to Rgba8 in its store (Work::luma_mid).  no_luma_mid: the Rgba8 blur of the
+        // framed picture instead (A/B runs and the tests that compare the two routes)
+        const bool one = !dbg.on(DBG_NO_LUMA_MID) && w.plan.letterboxed && w.plan.out_c == 4u && blur_channels(w) == 1u && w.s1 != S1_NONE && w.s1 != S1_NEAREST;
+        WtPlan *wp = one ? get_wtile_plan(c, kv, *hv, k, *h, 0, 0, w.plan.out_w, w.plan.out_h, 1u) : nullptr;
+        if (wp && wp->arena_full) return false;
+        if (wp && wp->ok && wp->nslot == 1u) { w.bwplan = wp; w.luma_mid = true; }
+        else {
+            wp = get_wtile_plan(c, kv, *hv, k, *h, 0, 0, w.plan.out_w, w.plan.out_h, w.plan.out_c);
+            if (wp->arena_full || arena_nearly_full(c)) return false;
+            if (wp->ok) w.bwplan = wp;
+        }
+        if (arena_nearly_full(c)) return false;
+    }
+    if (w.bwplan || !blur_tile_supported(h->max_taps) || !blur_tile_supported(hv->max_taps)) return true;
+    const uint32_t ty = blur_band_rows(blur_channels(w));
+    return cached_block(c, c->blur_plans, std::make_tuple(kv, k, ty), [&](std::vector<uint32_t> &blk) { build_blur_plan(*hv, *h, blur_tile_count(w.plan.out_w, h->max_taps), ty, blk); });
+}
+
+// The JPEG encoder's header and quantisation tables for picture w.  false = the table arena is full.
+bool plan_jpeg_tables(flgpu_ctx *c, Work &w)
+{
+    const uint32_t q = std::min<uint32_t>(std::max<uint32_t>(w.p->quality, 1u), 100u); // handler.rs:275 quality().clamp(1, 100)
+    w.jpeg_tab = cached_block(c, c->jpeg_tables, std::make_tuple(w.plan.out_w, w.plan.out_h, q), [&](std::vector<uint32_t> &blk) { build_jpeg_tables(w.plan.out_w, w.plan.out_h, q, blk); });
+    return w.jpeg_tab != 0;
+}
+
+// Every table the batch's kernels read, in the arena; the first pass may overflow it: reset once and retry.
+int plan_tables(flgpu_ctx *c, Batch &B, hipStream_t st)
+{
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        bool ok = true;
+        size_t n_resample = 0;
+        for (auto &w : B.work) n_resample += (w.plan.resampled && w.s1 != S1_NEAREST) ? 1 : 0;
+        for (auto &w : B.work)
+            if (w.plan.resampled && w.s1 != S1_NEAREST && !(ok = route_resample(c, B.dbg, n_resample, w))) break;
+        for (auto &w : B.work)
+            if (ok && w.p->blur_sigma > 0.0f) ok = plan_blur(c, B.dbg, w);
+        for (auto &w : B.work)
+            if (ok && w.p->front_end == FLGPU_FE_JPEG) ok = plan_jpeg_tables(c, w);
+        if (ok) break;
+        if (attempt == 1) return FLGPU_ERR_OOM;
+        FL_HIP(c, hipStreamSynchronize(st), "arena reset sync");
+        FL_HIP(c, hipDeviceSynchronize(), "arena reset sync");
+        arena_reset(c);
+    }
+    return arena_flush(c, st);
+}
+
+// ---- launch groups and job arrays ------------------------------------------------------------------------------------------------
+
+const size_t kMidCapFloats = (size_t)256 << 20; // 1 GiB of f32 intermediate per launch group
+
+// Longest work items first (in a mixed batch a 4K band walks four times the rows of a 1080p one, and the hardware hands out
+// workgroups in index order -- started last, the long ones would be the launch's tail), strips of a picture on one XCD.
+template <class Item, class Len> void order_items(Item *first, uint32_t n, Len len)
+{
+    std::stable_sort(first, first + n, [&](const Item &a, const Item &b) { return len(a) > len(b); });
+    xcd_interleave(first, n, len);
+}
+
+void add_resample_launch(flgpu_ctx *c, Batch &B, const ResampleKey &k, const std::vector<size_t> &pics)
+{
+    auto fresh = [&] {
+        Launch<ResampleKey> L{k, (uint32_t)B.jobs.size(), 0, (uint32_t)(k.s1 == S1_MFMA || k.s1 == S1_WTILE ? B.mitems.size() : B.items.size())};
+        L.g.cs = k.cs; L.g.pre = k.pre; L.g.letterbox = k.lb; L.g.grouped = 1;
+        return L;
+    };
+    Launch<ResampleKey> L = fresh();
+    const MfmaPlan *launch_plan = B.work[pics[0]].mplan; // S1_MFMA: the plan every picture of the launch shares, if they all do
+    for (size_t idx : pics) {
+        const Work &w = B.work[idx];
+        Job j; fill_job(w, j);
+        const size_t mid = k.s1 == S1_GENERIC ? (size_t)w.sw * w.plan.resized_h * mid_channels(w.cs, w.pre) : 0;
+        if (k.s1 == S1_GENERIC && L.njobs && L.mid_floats + mid > kMidCapFloats) {
+            B.s1_launches.push_back(L);
+            L = fresh();
+        }
+        j.mid_off = (uint32_t)L.mid_floats;
+        L.mid_floats += mid;
+        B.mid_floats_max = std::max(B.mid_floats_max, L.mid_floats);
+        L.g.max_sw = std::max(L.g.max_sw, j.sw); L.g.max_rh = std::max(L.g.max_rh, j.rh);
+        L.g.max_cw = std::max(L.g.max_cw, j.cw); L.g.max_ch = std::max(L.g.max_ch, j.ch);
+        L.g.max_dw = std::max(L.g.max_dw, j.dw); L.g.max_dh = std::max(L.g.max_dh, j.dh);
+        const uint32_t job = (uint32_t)B.jobs.size();
+        const size_t mitems_before = B.mitems.size(), items_before = B.items.size();
+        if (k.s1 == S1_TILE) L.g.tile_w_min = L.g.tile_w_min ? std::min(L.g.tile_w_min, w.tile_w) : w.tile_w;
+        if (k.s1 == S1_WTILE) {
+            w.wplan->items_for(wtile_bands(B.dbg, *w.wplan, pics.size()), job, B.mitems);
+            L.lds = std::max(L.lds, (size_t)w.wplan->lds_bytes);
+        }
+        if (k.s1 == S1_MFMA) {
+            if (launch_plan != w.mplan) launch_plan = nullptr;
+            for (MfmaItem it2 : *w.mitems) { it2.job = job; B.mitems.push_back(it2); }
+            L.max_nout = std::max(L.max_nout, w.mplan->max_nout);
+        }
+        if (k.s1 == S1_STREAM) {
+            for (StreamItem it2 : w.splan->items) { it2.job = job; B.items.push_back(it2); }
+            L.lds = std::max(L.lds, w.splan->lds_bytes);
+        }
+        L.nitems += (uint32_t)(B.mitems.size() - mitems_before + B.items.size() - items_before);
+        if (k.s1 == S1_TILE || k.s1 == S1_WTILE || k.s1 == S1_MFMA || k.s1 == S1_STREAM) {
+            c->stats.resample_src_bytes += (uint64_t)j.src_bytes;
+            c->stats.resample_dst_bytes += w.plan.pixel_bytes;
+        }
+        B.jobs.push_back(j);
+        L.njobs++;
+    }
+    if (k.s1 == S1_MFMA && L.nitems > 1) order_items(&B.mitems[L.item_base], L.nitems, [](const MfmaItem &x) { return x.kb1 - x.kb0; });
+    if (k.s1 == S1_MFMA && k.full) {
+        // full-width arithmetic: persistent workgroups, each with its own list of items
+        L.grid = std::max(1u, std::min(L.nitems, c->cu_count));
+        L.wg_base = (uint32_t)B.mwg.size();
+        std::vector<uint32_t> lists;
+        assign_items(B.mitems, L.item_base, L.nitems, L.grid, const_cast<MfmaPlan *>(launch_plan), lists);
+        B.mwg.insert(B.mwg.end(), lists.begin(), lists.end());
+    }
+    // (window-tile items: strips and bands of a picture on one XCD -- their source windows overlap, the halo then comes from that XCD's L2)
+    if (k.s1 == S1_WTILE && L.nitems > 1) xcd_interleave(&B.mitems[L.item_base], L.nitems, [](const MfmaItem &) { return 1u; });
+    if (k.s1 == S1_STREAM && L.nitems > 1) order_items(&B.items[L.item_base], L.nitems, [](const StreamItem &x) { return x.r1 - x.r0; });
+    B.s1_launches.push_back(L);
+}
+
+void add_blur_launch(flgpu_ctx *c, Batch &B, const BlurKey &k, const std::vector<size_t> &pics)
+{
+    auto fresh = [&] {
+        Launch<BlurKey> L{k, (uint32_t)B.jobs.size(), 0, (uint32_t)(k.wtile ? B.mitems.size() : B.items.size())};
+        L.g.cs = k.c;
+        return L;
+    };
+    Launch<BlurKey> L = fresh();
+    for (size_t idx : pics) {
+        const Work &w = B.work[idx];
+        const flgpu_plan &pl = w.plan;
+        Job j; memset(&j, 0, sizeof(j));
+        j.src = w.s1_dst; j.dst = w.blur_dst; j.src_bytes = (uint32_t)pl.pixel_bytes;
+        j.sw = pl.out_w; j.sh = pl.out_h; j.rw = pl.out_w; j.rh = pl.out_h; j.cw = pl.out_w; j.ch = pl.out_h;
+        j.dw = pl.out_w; j.dh = pl.out_h;
+        AxisKey vkey, hkey;
+        j.vtab = get_axis(c, pl.out_h, pl.out_h, FILTER_GAUSSIAN, w.p->blur_sigma, &vkey, nullptr);
+        j.htab = get_axis(c, pl.out_w, pl.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &hkey, nullptr);
+        const uint32_t filtered = k.wtile ? pl.out_c : k.filtered;
+        auto bt = c->blur_plans.find(std::make_tuple(vkey, hkey, blur_band_rows(filtered)));
+        j.pad0 = bt != c->blur_plans.end() ? bt->second : 0u; // table block of the blur kernel
+        if (k.wtile) {
+            if (w.luma_mid) {
+                // the source is stage 1's unframed Luma8 picture (rw x rh) at (cx, cy) of a virtual sw x sh frame of value `fill`
+                j.rw = std::min(pl.resized_w - pl.crop_x, pl.out_w - pl.place_x); j.rh = std::min(pl.resized_h - pl.crop_y, pl.out_h - pl.place_y);
+                j.cx = pl.place_x; j.cy = pl.place_y;
+                j.src_bytes = j.rw * j.rh;
+                j.fill = (uint32_t)w.p->fill_r * 0x01010101u;
+            }
+            const size_t before = B.mitems.size();
+            w.bwplan->items_for(wtile_bands(B.dbg, *w.bwplan, pics.size()), (uint32_t)B.jobs.size(), B.mitems);
+            L.nitems += (uint32_t)(B.mitems.size() - before);
+            L.lds = std::max(L.lds, (size_t)w.bwplan->lds_bytes);
+        } else {
+            const size_t mid = (size_t)pl.out_w * pl.out_h * pl.out_c;
+            if (L.njobs && L.mid_floats + mid > kMidCapFloats) { B.blur_launches.push_back(L); L = fresh(); }
+            const AxisTable *vh = reinterpret_cast<const AxisTable *>(c->h_arena.data() + j.vtab);
+            const AxisTable *hh = reinterpret_cast<const AxisTable *>(c->h_arena.data() + j.htab);
+            const size_t lds = blur_lds_bytes(pl.out_w, filtered, vh->max_taps, hh->max_taps);
+            L.blur_tiled = (L.njobs == 0 || L.blur_tiled) && blur_tile_supported(hh->max_taps) && blur_tile_supported(vh->max_taps) && lds <= 150 * 1024 && j.pad0;
+            L.lds = std::max(L.lds, lds);
+            L.blur_grid_x = std::max(L.blur_grid_x, blur_grid_x(pl.out_w, pl.out_h, hh->max_taps, filtered));
+            j.mid_off = (uint32_t)L.mid_floats;
+            L.mid_floats += mid;
+            B.mid_floats_max = std::max(B.mid_floats_max, L.mid_floats);
+            L.g.max_sw = std::max(L.g.max_sw, j.sw); L.g.max_rh = std::max(L.g.max_rh, j.rh);
+            L.g.max_cw = std::max(L.g.max_cw, j.cw); L.g.max_ch = std::max(L.g.max_ch, j.ch);
+        }
+        B.jobs.push_back(j);
+        L.njobs++;
+    }
+    if (k.wtile && L.nitems > 1) xcd_interleave(&B.mitems[L.item_base], L.nitems, [](const MfmaItem &) { return 1u; });
+    B.blur_launches.push_back(L);
+}
+
+// The header every encoded-stream job starts with: the picture it reads (the blur's output, else stage 1's), where the stream goes
+// and how much of it fits, and the image whose result words it writes (addressed once the descriptor block has its place).
+template <class J> J &encoder_job(Batch &B, std::vector<J> &jobs, std::vector<size_t> &image_of, size_t i)
+{
+    const Work &w = B.work[i];
+    J &j = jobs.emplace_back();
+    memset(&j, 0, sizeof(j));
+    j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
+    j.dst = w.final_dst;
+    j.dst_cap = (uint32_t)std::min<uint64_t>(B.dsts[i].capacity, 0xffffffffull);
+    j.w = w.plan.out_w; j.h = w.plan.out_h; j.c = w.plan.out_c;
+    image_of.push_back(i);
+    return j;
+}
+
+// Each encoder's job.  `at` holds the scratch totals of the pictures before this one, i.e. its offsets; the format's *_scratch
+// moves it past this picture (its limits were checked on the same totals in plan_pictures: it returns FLGPU_OK again).
+int add_jpeg_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
+{
+    JpegJob &j = encoder_job(B, B.jjobs, B.jjob_img, i);
+    const flgpu_plan &pl = B.work[i].plan;
+    j.meta = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_coef.p) + at.jpeg_coef);
+    j.unit_off = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_off.p) + at.jpeg_off);
+    j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_raw.p) + at.jpeg_raw);
+    j.bx = pl.plane_w / 8u; j.by = pl.plane_h / 8u;
+    j.tab_off = B.work[i].jpeg_tab;
+    B.jpeg_max_blocks = std::max(B.jpeg_max_blocks, j.bx * j.by);
+    return jpeg_scratch(pl, at);
+}
+
+int add_png_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
+{
+    PngJob &j = encoder_job(B, B.pjobs, B.pjob_img, i);
+    const flgpu_plan &pl = B.work[i].plan;
+    j.fbytes = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
+    j.filt = static_cast<uint8_t *>(c->d_png_filt.p) + at.png_filt;
+    j.chunks = static_cast<uint8_t *>(c->d_png_chunks.p) + (size_t)at.png_segs * kPngSegOutBytes;
+    j.syms = static_cast<uint16_t *>(c->d_png_syms.p) + (size_t)at.png_segs * kPngSegBytes;
+    j.recs = static_cast<uint32_t *>(c->d_png_recs.p) + (size_t)at.png_segs * 4u;
+    j.row0 = at.png_rows; j.seg0 = at.png_segs; j.nseg = (uint32_t)png_segments(j.fbytes);
+    j.level = png_level(B.work[i].p->quality);
+    return png_scratch(pl, at);
+}
+
+int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
+{
+    WebpJob &j = encoder_job(B, B.wjobs, B.wjob_img, i);
+    const flgpu_plan &pl = B.work[i].plan;
+    j.res = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_res.p) + at.wll_res);
+    j.tok = reinterpret_cast<uint16_t *>(static_cast<char *>(c->d_webpll_tok.p) + at.wll_tok);
+    j.tiles = static_cast<WebpllTile *>(c->d_webpll_tiles.p) + at.wll_tiles;
+    j.pic = static_cast<uint32_t *>(c->d_webpll_pic.p) + (size_t)at.wll_pics * kWebpllPicWords;
+    j.stream = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_stream.p) + at.wll_stream);
+    j.tile0 = at.wll_tiles; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
+    j.stream_words = (uint32_t)(align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256) / 4u);
+    return webpll_scratch(pl, at);
+}
+
+// The planar front ends (JFIF444, WebP420): one launch per kind.
+void add_planes_launch(Batch &B, uint32_t kind, const std::vector<size_t> &pics)
+{
+    FeLaunch F{kind, (uint32_t)B.fjobs.size(), 0, 0, 0, true};
+    for (size_t idx : pics) {
+        const Work &w = B.work[idx];
+        FrontendJob f; memset(&f, 0, sizeof(f));
+        f.src = w.blur_dst ? w.blur_dst : w.s1_dst;
+        f.dst = w.final_dst;
+        f.w = w.plan.out_w; f.h = w.plan.out_h; f.c = w.plan.out_c;
+        f.plane_w = w.plan.plane_w; f.plane_h = w.plan.plane_h; f.chroma_w = w.plan.chroma_w; f.chroma_h = w.plan.chroma_h;
+        if (f.c != 4 || ((uintptr_t)f.src & 3u) || ((uintptr_t)f.dst & 3u)) F.rgba = false;
+        if (F.kind == FLGPU_FE_JFIF444) { F.mw = std::max(F.mw, f.plane_w); F.mh = std::max(F.mh, f.plane_h); }
+        else { F.mw = std::max(F.mw, f.chroma_w); F.mh = std::max(F.mh, f.chroma_h); }
+        B.fjobs.push_back(f);
+        B.fjob_img.push_back(idx);
+        F.n++;
+    }
+    B.fe_launches.push_back(F);
+}
+
+// Groups the pictures into launches (each group in key order) and builds the job and item arrays the kernels read.
+int build_launches(flgpu_ctx *c, Batch &B)
+{
+    std::map<ResampleKey, std::vector<size_t>> s1_groups;
+    std::map<BlurKey, std::vector<size_t>> blur_groups;
+    std::map<uint32_t, std::vector<size_t>> fe_groups; // by front end
+    for (size_t i = 0; i < B.n; ++i) {
+        const Work &w = B.work[i];
+        if (w.s1 != S1_NONE) {
+            ResampleKey k{};
+            k.s1 = w.s1; k.cs = w.cs; k.pre = w.pre; k.lb = w.plan.letterboxed && !w.luma_mid;
+            if (w.s1 == S1_WTILE) k.nslot = w.wplan->nslot;
+            else if (w.s1 == S1_MFMA) { k.ops_in_lds = w.mplan->ops_in_lds; k.wide = w.mplan->wide; k.full = w.mplan->full; k.compact = w.mplan->compact; }
+            else { k.nacc = w.splan ? w.splan->nacc : 0u; k.unaligned = w.s1 == S1_STREAM && w.unaligned; }
+            s1_groups[k].push_back(i);
+        }
+        if (w.p->blur_sigma > 0.0f && w.bwplan) blur_groups[{true, w.bwplan->nslot, 0u, w.luma_mid ? 1u : w.plan.out_c, 0u, w.luma_mid}].push_back(i);
+        else if (w.p->blur_sigma > 0.0f) {
+            // pictures of one launch share the workgroup width the kernel is instantiated for
+            AxisKey hk; const HostAxis *hh = nullptr;
+            const bool tiled = get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &hk, &hh) && hh && blur_tile_supported(hh->max_taps);
+            blur_groups[{false, 0u, tiled ? blur_lanes(w.plan.out_w, hh->max_taps) : 256u, w.plan.out_c, blur_channels(w), false}].push_back(i);
+        }
+        if (w.p->front_end != FLGPU_FE_NONE) fe_groups[w.p->front_end].push_back(i);
+    }
+    // EXIF orientation pre-pass jobs, one launch per channel count
+    for (uint32_t cs = 1; cs <= 4; ++cs) {
+        LaunchGeneric O{};
+        O.cs = cs; O.job_base = (uint32_t)B.jobs.size();
+        for (auto &w : B.work) {
+            if (!w.orient || w.cs != cs) continue;
+            Job j; memset(&j, 0, sizeof(j));
+            j.src = w.raw_src; j.dst = const_cast<uint8_t *>(w.src);
+            j.sw = w.raw_w; j.sh = w.raw_h; j.dw = w.sw; j.dh = w.sh; j.fill = w.orient;
+            O.max_dw = std::max(O.max_dw, j.dw); O.max_dh = std::max(O.max_dh, j.dh);
+            B.jobs.push_back(j);
+            O.njobs++;
+        }
+        if (O.njobs) B.orient_launches.push_back(O);
+    }
+    for (auto &g : s1_groups) add_resample_launch(c, B, g.first, g.second);
+    for (auto &g : blur_groups) add_blur_launch(c, B, g.first, g.second);
+    // result words: two per image of the batch, see flgpu_ctx::last_fe
+    // ... followed by the batch's device error word (fl_mfma.h FLGPU_DEVERR_*): kernels that wait on one another inside a
+    // workgroup bound their waits and report an expired one here instead of delivering pixels that were never synchronised
+    B.has_results = !fe_groups.empty();
+    for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
+    for (auto &g : fe_groups) {
+        ScratchSizes at;
+        for (size_t i : g.second) {
+            int rc = FLGPU_OK;
+            if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
+            if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
+            if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, at);
+            assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
+            (void)rc;
+        }
+        if (g.first == FLGPU_FE_JFIF444 || g.first == FLGPU_FE_WEBP420) add_planes_launch(B, g.first, g.second);
+    }
+    FL_HIP(c, c->d_mid.reserve(B.mid_floats_max * 4), "f32 intermediate");
+    return FLGPU_OK;
+}
+
+// ---- descriptor block ------------------------------------------------------------------------------------------------------------
+
+// The batch's descriptor block, one upload: every array a 256-byte aligned region, then the result words and the device error
+// word.  f(array, pointer) is called for each region in layout order; the pointer receives the array's device address.
+template <class F> void desc_regions(Batch &B, F &&f)
+{
+    f(B.jobs, B.d.jobs);
+    f(B.items, B.d.items);
+    f(B.fjobs, B.d.fjobs);
+    f(B.jjobs, B.d.jjobs);
+    f(B.mitems, B.d.mitems);
+    f(B.mreqs, B.d.mreqs);
+    f(B.mwg, B.d.mwg);
+    f(B.pjobs, B.d.pjobs);
+    f(B.wjobs, B.d.wjobs);
+}
+
+template <class J> void point_results(std::vector<J> &jobs, const std::vector<size_t> &image_of, uint32_t *J::*word, uint32_t *status)
+{
+    for (size_t k = 0; k < jobs.size(); ++k) jobs[k].*word = status + 2 * image_of[k];
+}
+
+// Lays the batch's arrays out in one descriptor block and sends it to the device.
+int stage_descriptors(flgpu_ctx *c, Batch &B, hipStream_t st)
+{
+    // The matrix-pipe kernel's persistent workgroups request the first K-block of their NEXT item in the last pass of the current
+    // one: what that request needs (source, pitch, last row, the strip's first byte, the first K-block), one record per item in item
+    // order, so that it is ONE scalar load at that point and nothing of the next item occupies registers before (fl_mfma.h MfmaReq).
+    for (auto &L : B.s1_launches) {
+        if (L.k.s1 != S1_MFMA) continue;
+        B.mreqs.resize(B.mitems.size());
+        for (uint32_t k = L.item_base; k < L.item_base + L.nitems; ++k) {
+            const MfmaItem &mi = B.mitems[k];
+            const Job &j = B.jobs[mi.job];
+            MfmaReq &r = B.mreqs[k];
+            r.src = j.src; r.pitch = j.sw * L.k.cs; r.last_row = j.sh - 1u; r.kb0 = mi.kb0; r.kb1 = mi.kb1; r.job = mi.job;
+            r.strip_off = mi.strip_off; r.vplan_off = mi.vplan_off; r.pad[0] = r.pad[1] = 0;
+            r.byte0 = reinterpret_cast<const MfmaStrip *>(c->h_arena.data() + mi.strip_off)->byte0;
+        }
+    }
+    size_t bytes = 0;
+    desc_regions(B, [&](const auto &v, auto &) { bytes += align_up(v.size() * sizeof(v[0]), 256); });
+    // (the result words arrive zeroed with the block: a clear of their own was two fill kernels and two engine switches between
+    // one batch's last kernel and the next one's first)
+    const size_t words_off = bytes, words_b = (B.has_results || B.has_err_word) ? align_up(B.n * 8 + 8, 256) : 0;
+    bytes += words_b;
+    if (!bytes) return FLGPU_OK;
+    DescSlot *slot = B.slot = &c->slots[c->next_slot];
+    c->next_slot = (c->next_slot + 1) % 4;
+    if (slot->busy) { FL_HIP(c, hipEventSynchronize(slot->done), "descriptor slot wait"); slot->busy = false; }
+    if (!slot->done) FL_HIP(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming), "event");
+    FL_HIP(c, slot->host.reserve(bytes), "pinned descriptors");
+    FL_HIP(c, slot->dev.reserve(bytes), "device descriptors");
+    char *hp = static_cast<char *>(slot->host.p), *dp = static_cast<char *>(slot->dev.p);
+    if (words_b) {
+        B.status_dev = reinterpret_cast<uint32_t *>(dp + words_off);
+        memset(hp + words_off, 0, words_b);
+        point_results(B.jjobs, B.jjob_img, &JpegJob::result, B.status_dev);
+        point_results(B.fjobs, B.fjob_img, &FrontendJob::status, B.status_dev);
+        point_results(B.pjobs, B.pjob_img, &PngJob::result, B.status_dev);
+        point_results(B.wjobs, B.wjob_img, &WebpJob::result, B.status_dev);
+    }
+    size_t off = 0;
+    desc_regions(B, [&](const auto &v, auto &dev) {
+        dev = reinterpret_cast<std::remove_reference_t<decltype(dev)>>(dp + off);
+        if (!v.empty()) memcpy(hp + off, v.data(), v.size() * sizeof(v[0]));
+        off += align_up(v.size() * sizeof(v[0]), 256);
+    });
+    // While a previous batch is still running, the block goes up on the context's upload stream: the slot is free (its last
+    // batch has ended, see above), so the copy runs under that batch's kernels, and this batch's first kernel follows its
+    // last one without a copy engine in between.  A lone request on an idle device sends the block down its own stream (no
+    // second stream, no wait: the 15 us would be 3 % of its latency).
+    if (c->last_done && hipEventQuery(c->last_done) == hipErrorNotReady) {
+        if (!c->up_stream) FL_HIP(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking), "upload stream");
+        if (!slot->uploaded) FL_HIP(c, hipEventCreateWithFlags(&slot->uploaded, hipEventDisableTiming), "event");
+        FL_HIP(c, hipMemcpyAsync(slot->dev.p, hp, bytes, hipMemcpyHostToDevice, c->up_stream), "descriptor upload");
+        FL_HIP(c, hipEventRecord(slot->uploaded, c->up_stream), "event record");
+        // (the HOST waits the ~15 us the 130 KB take: a device-side wait on the event is a barrier packet between the previous
+        // batch's last kernel and this one's first, 7 us of idle chip per batch; the host has the previous batch's 2 ms to spare)
+        FL_HIP(c, hipEventSynchronize(slot->uploaded), "descriptor upload wait");
+    } else {
+        FL_HIP(c, hipMemcpyAsync(slot->dev.p, hp, bytes, hipMemcpyHostToDevice, st), "descriptor upload");
+    }
+    return FLGPU_OK;
+}
+
+// ---- launches --------------------------------------------------------------------------------------------------------------------
+
+// Enqueues the batch's kernels in their order -- orientation, stage 1, blur, planar front ends, JPEG, PNG, lossless WebP --, then the
+// plain copies of the requests that change nothing, and records the batch's events.
+int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
+{
+    for (auto &g : B.orient_launches) {
+        g.jobs = B.d.jobs;
+        FL_HIP(c, launch_orient(g, st), "orientation kernel");
+    }
+    for (auto &L : B.s1_launches) {
+        const ResampleKey &k = L.k;
+        L.g.jobs = B.d.jobs; L.g.arena = c->d_arena; L.g.mid = static_cast<float *>(c->d_mid.p);
+        L.g.job_base = L.job_base; L.g.njobs = L.njobs;
+        L.g.no_place4 = B.dbg.on(DBG_NO_PLACE4) ? 1u : 0u;
+        L.g.nearest = k.s1 == S1_NEAREST ? 1u : 0u;
+        // (the matrix-pipe and streaming kernels paint the letterbox frame themselves)
+        if (k.lb && (k.s1 == S1_TILE || k.s1 == S1_WTILE || k.s1 == S1_GENERIC)) FL_HIP(c, launch_place(L.g, true, st), "border fill");
+        // the resample kernels proper are timed (ProfileScope kind 0), the placements and border fills are not
+        const bool resample = k.s1 == S1_TILE || k.s1 == S1_WTILE || k.s1 == S1_MFMA || k.s1 == S1_STREAM;
+        std::optional<ProfileScope> ps;
+        if (resample) ps.emplace(c, st, 0);
+        LaunchWtile wt{};
+        LaunchMfma m{};
+        LaunchStream s{};
+        switch (k.s1) {
+        case S1_NEAREST:
+            FL_HIP(c, launch_place(L.g, false, st), "nearest kernel");
+            break;
+        case S1_PLACE:
+            FL_HIP(c, launch_place(L.g, false, st), "place kernel");
+            break;
+        case S1_TILE:
+            FL_HIP(c, launch_tile_resample(L.g, st), "tiled two-pass resample kernel");
+            break;
+        case S1_WTILE:
+            wt.jobs = B.d.jobs; wt.items = reinterpret_cast<const WtItem *>(B.d.mitems + L.item_base); wt.arena = c->d_arena; wt.nitems = L.nitems;
+            wt.nslot = k.nslot; wt.nkmax = kWtOperandRegs / wt.nslot; wt.letterbox = k.lb; wt.lds_bytes = (uint32_t)L.lds; wt.invert = k.pre == PRE_INVERT;
+            FL_HIP(c, launch_wtile(wt, st), "window-tile matrix-pipe kernel");
+            break;
+        case S1_GENERIC:
+            FL_HIP(c, launch_vpass_generic(L.g, st), "generic vertical pass");
+            FL_HIP(c, launch_hpass_generic(L.g, st), "generic horizontal pass");
+            break;
+        case S1_MFMA:
+            m.jobs = B.d.jobs; m.items = B.d.mitems + L.item_base; m.reqs = B.d.mreqs + L.item_base; m.arena = c->d_arena; m.nitems = L.nitems;
+            m.grid = L.grid; m.wg_lists = L.grid ? B.d.mwg + L.wg_base : nullptr;
+            m.cs = k.cs; m.letterbox = k.lb; m.ops_in_lds = k.ops_in_lds; m.wide = k.wide; m.full = k.full; m.compact = k.compact; m.max_nout = L.max_nout;
+            m.spin_limit = (uint32_t)std::max<int64_t>(0, B.dbg.get(DBG_MFMA_SPIN_LIMIT)); // tests: 0 = every bounded wait expires
+            m.err_word = B.status_dev + 2 * B.n;
+            FL_HIP(c, launch_mfma(m, st), "matrix-pipe resample kernel");
+            break;
+        case S1_STREAM:
+            s.jobs = B.d.jobs; s.items = B.d.items + L.item_base; s.arena = c->d_arena; s.nitems = L.nitems;
+            s.cs = k.cs; s.pre = k.pre; s.letterbox = k.lb; s.lds_bytes = L.lds; s.nacc = k.nacc; s.unaligned = k.unaligned;
+            FL_HIP(c, launch_stream(s, st), "streaming resample kernel");
+            break;
+        case S1_NONE:
+            break;
+        }
+        c->stats.resample_launches += resample;
+        c->stats.generic_launches += k.s1 == S1_TILE || k.s1 == S1_GENERIC; // (S1_TILE: the two-pass generic resample, LDS form)
+        c->stats.mfma_launches += k.s1 == S1_WTILE || k.s1 == S1_MFMA;
+        c->stats.wtile_launches += k.s1 == S1_WTILE;
+    }
+    for (auto &L : B.blur_launches) {
+        L.g.jobs = B.d.jobs; L.g.arena = c->d_arena; L.g.mid = static_cast<float *>(c->d_mid.p);
+        L.g.job_base = L.job_base; L.g.njobs = L.njobs;
+        ProfileScope ps(c, st, 1);
+        if (L.k.wtile) {
+            LaunchWtile m{};
+            m.jobs = B.d.jobs; m.items = reinterpret_cast<const WtItem *>(B.d.mitems + L.item_base); m.arena = c->d_arena; m.nitems = L.nitems;
+            m.nslot = L.k.nslot; m.nkmax = kWtOperandRegs / m.nslot; m.letterbox = L.k.luma_mid; m.framed = L.k.luma_mid; m.lds_bytes = (uint32_t)L.lds; m.half_waves = L.k.c == 1u; // (one-channel pictures: little work per step, two 4-wave workgroups per CU hide each other's barriers; Rgba8 blurs measured 2 % slower that way)
+            FL_HIP(c, launch_wtile(m, st), "window-tile matrix-pipe kernel (blur)");
+            c->stats.mfma_launches++;
+            c->stats.wtile_launches++;
+        } else if (L.blur_tiled && !B.dbg.on(DBG_FORCE_GENERIC)) {
+            L.g.pre = L.k.filtered; // channels to filter, see blur_tile_kernel
+            L.g.blur_lanes = L.k.lanes;
+            FL_HIP(c, launch_blur_tile(L.g, L.blur_grid_x, L.lds, st), "blur kernel");
+        } else {
+            FL_HIP(c, launch_vpass_generic(L.g, st), "blur vertical pass");
+            FL_HIP(c, launch_hpass_generic(L.g, st), "blur horizontal pass");
+        }
+        c->stats.blur_launches++;
+    }
+    for (auto &F : B.fe_launches) {
+        ProfileScope ps(c, st, 2);
+        if (F.kind == FLGPU_FE_JFIF444) FL_HIP(c, launch_jfif444(B.d.fjobs, F.base, F.n, F.mw, F.mh, F.rgba, st), "jfif front end");
+        else FL_HIP(c, launch_webp420(B.d.fjobs, c->d_arena, c->gamma_off, F.base, F.n, F.mw, F.mh, F.rgba, st), "webp front end");
+        c->stats.frontend_launches++;
+    }
+    if (!B.jjobs.empty()) {
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_jpeg_encode(B.d.jjobs, c->d_arena, 0, (uint32_t)B.jjobs.size(), B.jpeg_max_blocks, st), "JPEG encode");
+        c->stats.frontend_launches++;
+    }
+    if (!B.pjobs.empty()) {
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_png_encode(B.d.pjobs, (uint32_t)B.pjobs.size(), B.scratch.png_rows, B.scratch.png_segs, st), "PNG encode");
+        c->stats.frontend_launches++;
+    }
+    if (!B.wjobs.empty()) {
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_webpll_encode(B.d.wjobs, (uint32_t)B.wjobs.size(), B.scratch.wll_tiles, st), "lossless WebP encode");
+        c->stats.frontend_launches++;
+    }
+    // plain copies for requests that change nothing
+    for (const Work &w : B.work)
+        if (w.s1 == S1_NONE && !(w.p->blur_sigma > 0.0f) && w.p->front_end == FLGPU_FE_NONE)
+            FL_HIP(c, hipMemcpyAsync(w.final_dst, w.src, w.plan.pixel_bytes, hipMemcpyDeviceToDevice, st), "copy");
+    if (B.slot) { FL_HIP(c, hipEventRecord(B.slot->done, st), "event record"); B.slot->busy = true; }
+    if (!c->last_done) FL_HIP(c, hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming), "event");
+    FL_HIP(c, hipEventRecord(c->last_done, st), "event record");
+    c->last_stream = st;
+    return FLGPU_OK;
+}
+
 } // namespace
 
 namespace fl {
@@ -536,11 +1379,6 @@ int entropy_failures(flgpu_ctx *c, size_t n, std::vector<uint8_t> &bad, hipStrea
     return nbad;
 }
 
-uint64_t staged_out_bytes(const flgpu_params &p, const flgpu_plan &plan, uint64_t)
-{
-    return fe_encoded(p.front_end) ? plan.max_out_bytes : plan.out_bytes;
-}
-
 int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, bool same_params,
                      flgpu_image *dsts, hipStream_t st)
 {
@@ -551,800 +1389,31 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     if (c->last_stream && c->last_stream != st && c->last_done) FL_HIP(c, hipStreamWaitEvent(st, c->last_done, 0), "stream handoff");
 
     RoctxRange range_batch("flgpu batch");
-    // ---- plan every image ------------------------------------------------
-    std::unique_ptr<RoctxRange> range_plan(new RoctxRange("flgpu plan + tables"));
-    std::vector<Work> work(n);
-    size_t tmp_a_bytes = 0, tmp_b_bytes = 0, tmp_o_bytes = 0, tmp_al_bytes = 0, jpeg_coef_bytes = 0, jpeg_off_bytes = 0, jpeg_raw_bytes = 0, png_filt_bytes = 0;
-    uint32_t png_rows = 0, png_segs = 0;
-    size_t wll_res_bytes = 0, wll_tok_bytes = 0, wll_stream_bytes = 0;
-    uint32_t wll_tiles = 0, wll_pics = 0;
-    for (size_t i = 0; i < n; ++i) {
-        Work &w = work[i];
-        const flgpu_image &s = srcs[i];
-        w.p = same_params ? &ps[0] : &ps[i];
-        if (!s.data || !dsts[i].data) return FLGPU_ERR_INVALID_ARG;
-        int rc = flgpu_plan_output(w.p, s.width, s.height, s.channels, &w.plan);
-        if (rc) return rc;
-        if (s.capacity < (uint64_t)s.width * s.height * s.channels) return FLGPU_ERR_INVALID_ARG;
-        if (dsts[i].capacity < w.plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
-        w.cs = s.channels; w.sw = w.plan.src_w; w.sh = w.plan.src_h; // size after apply_orientation
-        w.raw_w = s.width; w.raw_h = s.height;
-        w.orient = w.p->orientation >= 2 ? w.p->orientation : 0;
-        if (w.orient) { w.orient_off = tmp_o_bytes; tmp_o_bytes += align_up((size_t)s.width * s.height * s.channels, 256); }
-        w.pre = w.p->grayscale ? PRE_GRAY : (w.p->inverse ? PRE_INVERT : PRE_NONE);
-        w.src = s.data;
-        w.final_dst = dsts[i].data;
-        const flgpu_plan &pl = w.plan;
-        const bool cropped = pl.crop_x || pl.crop_y || pl.out_w != pl.resized_w || pl.out_h != pl.resized_h;
-        // grayscale of Luma/LumaA and "no-op" pre-ops change nothing
-        const bool pre_changes = (w.pre == PRE_INVERT) || (w.pre == PRE_GRAY && w.cs >= 3);
-        if (!pre_changes) w.pre = PRE_NONE;
-        if (pl.resampled) w.s1 = w.p->filter == FLGPU_FILTER_NEAREST ? S1_NEAREST : S1_GENERIC;
-        else if (pre_changes || pl.letterboxed || cropped) w.s1 = S1_PLACE;
-        else w.s1 = S1_NONE;
-        // Which resample kernel serves a request is a function of the REQUEST (geometry, channels, pre-op), never of where the
-        // caller's buffer happens to start: the matrix-pipe kernel moves 16-byte pieces of a row, so a source whose rows qualify
-        // but whose base is not 16-byte aligned (only possible through the device-batch entry point; staged and decoded sources
-        // are 256-byte aligned) is copied to aligned scratch first.  The two kernels may differ by 1 LSB; an HTTP cache in front of
-        // the service must not see that difference come and go with an address.
-        // (only where that kernel can be the one: its own gate below -- no pre-op, rows of at least 64 bytes, not switched off -- and a
-        // ratio above the window-tile kernel's range, which takes any alignment; everything else is served by kernels that do not care)
-        // (from ratio 2 up whether or not the window-tile kernel is on: that kernel takes any alignment, but where ITS planner refuses
-        // a geometry below ratio 2.5 the request falls through to the matrix-pipe branch -- which must not then depend on the address)
-        const bool mfma_candidate = !c->dbg->on(DBG_NO_MFMA) && !c->dbg->on(DBG_FORCE_GENERIC) && (size_t)w.sw * w.cs >= 64u &&
-                                    (uint64_t)w.sh >= 2u * (uint64_t)pl.resized_h;
-        if (pl.resampled && w.s1 == S1_GENERIC && !pre_changes && !w.orient && mfma_candidate && ((size_t)w.sw * w.cs) % 16u == 0 && (uintptr_t)s.data % 16u != 0) {
-            w.align_off = tmp_al_bytes; w.align_copy = true;
-            tmp_al_bytes += align_up((size_t)s.width * s.height * s.channels, 256);
-        }
-        const bool blur = w.p->blur_sigma > 0.0f;
-        const bool fe = w.p->front_end != FLGPU_FE_NONE;
-        // buffer chain
-        if (w.s1 == S1_NONE) w.s1_dst = const_cast<uint8_t *>(w.src);
-        else if (!blur && !fe) w.s1_dst = w.final_dst;
-        else { w.s1_dst = reinterpret_cast<uint8_t *>(tmp_a_bytes); tmp_a_bytes += align_up(pl.pixel_bytes, 256); }
-        if (blur) {
-            if (!fe) w.blur_dst = w.final_dst;
-            else { w.blur_dst = reinterpret_cast<uint8_t *>(tmp_b_bytes); tmp_b_bytes += align_up(pl.pixel_bytes, 256); }
-        } else w.blur_dst = nullptr;
-        if (w.p->front_end == FLGPU_FE_JPEG) {
-            if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions
-            const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
-            if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
-            w.jpeg_coef_off = jpeg_coef_bytes; jpeg_coef_bytes += align_up(units * sizeof(uint32_t), 256);
-            w.jpeg_off_off = jpeg_off_bytes; jpeg_off_bytes += align_up((units + 1) * sizeof(uint32_t), 256);
-            w.jpeg_raw_off = jpeg_raw_bytes; jpeg_raw_bytes += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
-        }
-        if (w.p->front_end == FLGPU_FE_PNG) {
-            const uint64_t fb = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
-            if ((uint64_t)png_rows + pl.out_h >= (1ull << 31) || (uint64_t)png_segs + png_segments(fb) >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-            w.png_filt_off = png_filt_bytes; png_filt_bytes += align_up(fb, 256);
-            w.png_row0 = png_rows; png_rows += pl.out_h;
-            w.png_seg0 = png_segs; w.png_nseg = (uint32_t)png_segments(fb); png_segs += w.png_nseg;
-        }
-        if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) {
-            const uint64_t npix = (uint64_t)pl.out_w * pl.out_h;
-            if ((uint64_t)wll_tiles + webpll_tiles(npix) >= (1ull << 31) || webpll_max_out_bytes(pl.out_w, pl.out_h) / 4u >= (1ull << 32))
-                return FLGPU_ERR_UNSUPPORTED;
-            w.wll_res_off = wll_res_bytes; wll_res_bytes += align_up(npix * 4u, 256);
-            w.wll_tok_off = wll_tok_bytes; wll_tok_bytes += align_up(npix * 2u, 256);
-            w.wll_stream_off = wll_stream_bytes; wll_stream_bytes += align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256);
-            w.wll_tile0 = wll_tiles; wll_tiles += (uint32_t)webpll_tiles(npix);
-            w.wll_pic = wll_pics++;
-        }
+    Batch B(c, n, dsts);
+    {
+        RoctxRange range_plan("flgpu plan + tables");
+        if (int rc = plan_pictures(B, srcs, ps, same_params)) return rc;
+        if (int rc = reserve_scratch(c, B, st)) return rc;
+        if (int rc = plan_tables(c, B, st)) return rc;
+        if (int rc = build_launches(c, B)) return rc;
+        if (int rc = stage_descriptors(c, B, st)) return rc;
     }
-    FL_HIP(c, c->d_jpeg_coef.reserve(jpeg_coef_bytes), "JPEG coefficient scratch");
-    FL_HIP(c, c->d_jpeg_off.reserve(jpeg_off_bytes), "JPEG offset scratch");
-    FL_HIP(c, c->d_jpeg_raw.reserve(jpeg_raw_bytes), "JPEG bit-stream scratch");
-    FL_HIP(c, c->d_png_filt.reserve(png_filt_bytes), "PNG filtered-row scratch");
-    FL_HIP(c, c->d_png_chunks.reserve((size_t)png_segs * kPngSegOutBytes), "PNG chunk scratch");
-    FL_HIP(c, c->d_png_syms.reserve((size_t)png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
-    FL_HIP(c, c->d_png_recs.reserve((size_t)png_segs * 4u * sizeof(uint32_t)), "PNG segment records");
-    FL_HIP(c, c->d_webpll_res.reserve(wll_res_bytes), "WebP residual scratch");
-    FL_HIP(c, c->d_webpll_tok.reserve(wll_tok_bytes), "WebP token scratch");
-    FL_HIP(c, c->d_webpll_tiles.reserve((size_t)wll_tiles * sizeof(WebpllTile)), "WebP tile records");
-    FL_HIP(c, c->d_webpll_pic.reserve((size_t)wll_pics * kWebpllPicWords * sizeof(uint32_t)), "WebP per-picture scratch");
-    FL_HIP(c, c->d_webpll_stream.reserve(wll_stream_bytes), "WebP bit-stream scratch");
-    FL_HIP(c, c->d_tmp_o.reserve(tmp_o_bytes), "orientation scratch");
-    for (auto &w : work)
-        if (w.orient) { w.raw_src = w.src; w.src = static_cast<uint8_t *>(c->d_tmp_o.p) + w.orient_off; }
-    FL_HIP(c, c->d_tmp_al.reserve(tmp_al_bytes), "alignment scratch");
-    for (auto &w : work)
-        if (w.align_copy) {
-            uint8_t *al = static_cast<uint8_t *>(c->d_tmp_al.p) + w.align_off;
-            FL_HIP(c, hipMemcpyAsync(al, w.src, (size_t)w.sw * w.sh * w.cs, hipMemcpyDeviceToDevice, st), "alignment copy");
-            w.src = al;
-        }
-    FL_HIP(c, c->d_tmp_a.reserve(tmp_a_bytes), "scratch A");
-    FL_HIP(c, c->d_tmp_b.reserve(tmp_b_bytes), "scratch B");
-    for (auto &w : work) {
-        const bool blur = w.p->blur_sigma > 0.0f, fe = w.p->front_end != FLGPU_FE_NONE;
-        if (w.s1 == S1_NONE) w.s1_dst = const_cast<uint8_t *>(w.src);
-        if (w.s1 != S1_NONE && (blur || fe)) w.s1_dst = static_cast<uint8_t *>(c->d_tmp_a.p) + reinterpret_cast<size_t>(w.s1_dst);
-        if (blur && fe) w.blur_dst = static_cast<uint8_t *>(c->d_tmp_b.p) + reinterpret_cast<size_t>(w.blur_dst);
-    }
-
-    // ---- tables ------------------------------------------------------------
-    // first pass may overflow the arena: reset once and retry
-    // the context's switches (flgpu_debug_set; tests and A/B runs), read once per batch
-    const DebugSwitches &dbg = *c->dbg;
-    const bool force_generic = dbg.on(DBG_FORCE_GENERIC);
-    const uint32_t forced_bands = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_FORCE_BANDS));
-    const bool no_mfma = dbg.on(DBG_NO_MFMA); // keep the streaming kernel
-    // which arithmetic the matrix-pipe kernel computes in (fl_mfma.h): the full-width one unless mfma_arith = 1 asks for
-    // rounds 2-3's (A/B runs and the tests that keep the packed kernel's bars)
-    const MfmaArith mfma_arith = dbg.on(DBG_MFMA_ARITH) ? MFMA_ARITH_PACKED : MFMA_ARITH_FULL;
-    const bool no_tile = dbg.on(DBG_NO_TILE);
-    // the window-tile matrix-pipe kernel (fl_wtile.h) for mild ratios, up-scales and blurs: full-width arithmetic only; no_wtile
-    // keeps the f32 vector kernels
-    const bool use_wtile = !dbg.on(DBG_NO_WTILE) && !no_mfma && !force_generic && mfma_arith == MFMA_ARITH_FULL;
-    const bool wt_first = dbg.on(DBG_WTILE_FIRST); // experiments: the window-tile kernel before the streaming matrix-pipe kernel
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        bool full = false;
-        size_t n_resample = 0;
-        for (auto &w : work) n_resample += (w.plan.resampled && w.s1 != S1_NEAREST) ? 1 : 0;
-        for (auto &w : work) {
-            if (!w.plan.resampled || w.s1 == S1_NEAREST) continue;
-            w.vtab = get_axis(c, w.sh, w.plan.resized_h, FILTER_LANCZOS3, 0.0f, &w.vk, &w.va);
-            w.htab = get_axis(c, w.sw, w.plan.resized_w, FILTER_LANCZOS3, 0.0f, &w.hk, &w.ha);
-            if (!w.vtab || !w.htab) { full = true; break; }
-            // fused streaming kernel if the geometry allows it
-            w.s1 = S1_GENERIC;
-            // rows that are not dword aligned: Rgb8 has a funnel-shift variant of the kernel, others use the generic path
-            w.unaligned = ((w.sw * w.cs) % 4u != 0) || ((uintptr_t)w.src % 4u != 0);
-            const bool aligned = (!w.unaligned || w.cs == 3) && (!w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0);
-            // The matrix-pipe kernel takes down-scales (any channel count, no pre-op) whose rows are 16-byte aligned (it moves 16-byte pieces of a row
-            // straight into LDS).  The choice depends on the request's geometry only, never on the batch around it.
-            // Ratios below 2.5 (up-scales included) go to the window-tile kernel BEFORE the fused ones: measured 1.00 vs 1.03 ms per 256 at ratio 2.4 and -- against the
-            // streaming f32 kernel, which serves what the matrix-pipe planner refuses down there -- 1.16 vs 2.10 at 2.13.  From 2.67 up the
-            // streaming matrix-pipe kernel wins since its wide layout keeps operands in LDS (0.78 vs 0.92 at 2.67, 0.72 vs 0.80 at 3;
-            // profiles/r04_wtile_experiments.txt); where ITS planner refuses a geometry below ratio 3.4, the window-tile kernel is asked again.
-            const bool wt_range = 2u * w.sh < 5u * w.plan.resized_h;
-            if ((wt_first || wt_range) && use_wtile && (w.pre == PRE_NONE || w.pre == PRE_INVERT) && (!w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0)) {
-                Job jtmp; fill_job(w, jtmp);
-                WtPlan *wp = get_wtile_plan(c, w.vk, *w.va, w.hk, *w.ha, jtmp.cx, jtmp.cy, jtmp.cw, jtmp.ch, w.cs);
-                if (wp->arena_full || c->h_arena.size() >= c->arena_cap_words - 1024) { full = true; break; }
-                if (wp->ok) { w.s1 = S1_WTILE; w.wplan = wp; continue; }
-            }
-            if (w.pre == PRE_NONE && !force_generic && !no_mfma && (w.sw * w.cs) % 16u == 0 && (uintptr_t)w.src % 16u == 0 &&
-                (!w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0) && w.sw * w.cs >= 64u) {
-                Job jtmp; fill_job(w, jtmp);
-                MfmaPlan *mp = get_mfma_plan(c, w.vk, *w.va, w.hk, *w.ha, jtmp.cx, jtmp.cy, jtmp.cw, jtmp.ch, w.cs, mfma_arith);
-                if (mp->arena_full || c->h_arena.size() >= c->arena_cap_words - 1024) { full = true; break; }
-                if (mp->ok) {
-                    uint32_t nbands = 1;
-                    if (forced_bands) nbands = forced_bands;
-                    else if (n_resample < 128) {
-                        // A small launch: bands of rows so that every CU has an item -- and so that the items come out in whole rounds of the
-                        // workgroups.  (Until round 5: ceil(256 / (3 n)) bands; 13 files x 3 strips x 7 bands = 273 items on 256 workgroups,
-                        // i.e. two rounds of items a seventh of a strip long where one round of sixths does: 84 us per batch of file requests.)
-                        // The cost of a band count: rounds x (the longest item's K-blocks -- the bands' halos are in there -- + a transition's two).
-                        const uint64_t G = std::max(1u, c->cu_count);
-                        uint64_t best = ~0ull;
-                        for (uint32_t b = 1; b <= std::min<uint32_t>(16u, (uint32_t)mp->tiles.size()); ++b) {
-                            const std::vector<MfmaItem> &cand = mp->items_for(b);
-                            uint32_t longest = 0;
-                            for (const MfmaItem &mi : cand) longest = std::max(longest, mi.kb1 - mi.kb0);
-                            const uint64_t cost = (((uint64_t)n_resample * cand.size() + G - 1) / G) * (longest + 2u);
-                            if (cost < best) { best = cost; nbands = b; }
-                        }
-                    }
-                    w.s1 = S1_MFMA; w.mplan = mp; w.mitems = &mp->items_for(nbands);
-                    continue;
-                }
-            }
-            if (use_wtile && (w.pre == PRE_NONE || w.pre == PRE_INVERT) && 2u * w.sh >= 5u * w.plan.resized_h && 10u * w.sh < 34u * w.plan.resized_h &&
-                (!w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0)) { // (ratio 2.5 .. 3.4 and no streaming matrix-pipe plan: unaligned rows, a pre-op, a refused geometry)
-                Job jtmp; fill_job(w, jtmp);
-                WtPlan *wp = get_wtile_plan(c, w.vk, *w.va, w.hk, *w.ha, jtmp.cx, jtmp.cy, jtmp.cw, jtmp.ch, w.cs);
-                if (wp->arena_full || c->h_arena.size() >= c->arena_cap_words - 1024) { full = true; break; }
-                if (wp->ok) { w.s1 = S1_WTILE; w.wplan = wp; continue; }
-            }
-            if (stream_supported(w.cs, w.pre) && aligned && !force_generic) {
-                Job jtmp; fill_job(w, jtmp);
-                uint32_t nbands = 1;
-                if (forced_bands) nbands = forced_bands;
-                else if (n_resample < 512) {
-                    // small batches: split images into row bands so that the chip still gets >= ~1024 workgroups
-                    const uint32_t want = (uint32_t)((1024 + n_resample * 2 - 1) / (n_resample * 2));
-                    nbands = std::max(1u, std::min(want, jtmp.ch / 24u));
-                }
-                nbands = std::min(nbands, std::max(1u, jtmp.ch));
-                const StreamPlan *sp = get_stream_plan(c, w.vk, *w.va, w.hk, *w.ha, jtmp.cx, jtmp.cy, jtmp.cw, jtmp.ch, nbands, w.cs, w.pre);
-                if (c->h_arena.size() >= c->arena_cap_words - 1024) { full = true; break; }
-                if (sp->ok) { w.s1 = S1_STREAM; w.splan = sp; }
-            }
-            // what neither fused kernel takes and no pre-op precedes: the window-tile matrix-pipe kernel (any pitch and alignment)
-            if (w.s1 == S1_GENERIC && use_wtile && (w.pre == PRE_NONE || w.pre == PRE_INVERT) && wtile_resample_wanted(w) && (!w.plan.letterboxed || (uintptr_t)w.s1_dst % 4u == 0)) {
-                Job jtmp; fill_job(w, jtmp);
-                WtPlan *wp = get_wtile_plan(c, w.vk, *w.va, w.hk, *w.ha, jtmp.cx, jtmp.cy, jtmp.cw, jtmp.ch, w.cs);
-                if (wp->arena_full || c->h_arena.size() >= c->arena_cap_words - 1024) { full = true; break; }
-                if (wp->ok) { w.s1 = S1_WTILE; w.wplan = wp; }
-            }
-            // what neither fused kernel takes (up-scales, mild down-scales, odd pitches, forced generic): the two passes through an
-            // LDS tile instead of an f32 intermediate in HBM, if a tile width fits (FLGPU_NO_TILE=1 keeps the HBM form: tests, A/B)
-            if (w.s1 == S1_GENERIC && !no_tile) {
-                Job jtmp; fill_job(w, jtmp);
-                const uint32_t tw = tile_width_for(*w.ha, *w.va, jtmp.cx, jtmp.cw, jtmp.cy, jtmp.ch, mid_channels(w.cs, w.pre));
-                if (tw) {
-                    const auto key = std::make_tuple(w.vk, jtmp.cy, jtmp.ch);
-                    auto it = c->tile_vplans.find(key);
-                    if (it == c->tile_vplans.end()) {
-                        std::vector<uint32_t> blk;
-                        build_tile_vplan(*w.va, jtmp.cy, jtmp.ch, blk);
-                        const uint32_t off = arena_append(c, blk.data(), blk.size());
-                        if (!off) { full = true; break; }
-                        it = c->tile_vplans.emplace(key, off).first;
-                    }
-                    w.s1 = S1_TILE; w.tile_w = tw; w.tile_vplan = it->second;
-                }
-            }
-        }
-        for (auto &w : work) {
-            if (full) break;
-            if (w.p->blur_sigma > 0.0f) {
-                AxisKey k; const HostAxis *h;
-                AxisKey kv; const HostAxis *hv;
-                w.bwplan = nullptr; w.luma_mid = false; // (a second attempt after an arena reset plans again)
-                if (!get_axis(c, w.plan.out_h, w.plan.out_h, FILTER_GAUSSIAN, w.p->blur_sigma, &kv, &hv) ||
-                    !get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &k, &h)) full = true;
-                else if (use_wtile) {
-                    // Blurs the window-tile matrix-pipe kernel takes: every one its planner accepts.  A grey picture on a grey frame (R == G == B
-                    // everywhere, alpha 255): ONE channel is filtered, if that plan is one of the single-register-set kind (the kernel's framed
-                    // source exists in that instantiation only) -- stage 1 leaves the unframed Luma8 picture, the kernel reads the frame's rows
-                    // and columns as the fill value and expands to Rgba8 in its store (Work::luma_mid).  no_luma_mid: the Rgba8 blur of the
-                    // framed picture instead (A/B runs and the tests that compare the two routes)
-                    const bool one = !dbg.on(DBG_NO_LUMA_MID) && w.plan.letterboxed && w.plan.out_c == 4u && blur_channels(w) == 1u && w.s1 != S1_NONE && w.s1 != S1_NEAREST;
-                    WtPlan *wp = one ? get_wtile_plan(c, kv, *hv, k, *h, 0, 0, w.plan.out_w, w.plan.out_h, 1u) : nullptr;
-                    if (wp && !wp->arena_full && wp->ok && wp->nslot == 1u) { w.bwplan = wp; w.luma_mid = true; }
-                    else {
-                        if (wp && wp->arena_full) full = true;
-                        wp = full ? nullptr : get_wtile_plan(c, kv, *hv, k, *h, 0, 0, w.plan.out_w, w.plan.out_h, w.plan.out_c);
-                        if (wp && (wp->arena_full || c->h_arena.size() >= c->arena_cap_words - 1024)) full = true;
-                        else if (wp && wp->ok) w.bwplan = wp;
-                    }
-                    if (c->h_arena.size() >= c->arena_cap_words - 1024) full = true;
-                }
-                if (!full && !w.bwplan) {
-                    const uint32_t ty = blur_band_rows(blur_channels(w));
-                    if (blur_tile_supported(h->max_taps) && blur_tile_supported(hv->max_taps) && !c->blur_plans.count(std::make_tuple(kv, k, ty))) {
-                        std::vector<uint32_t> blk;
-                        build_blur_plan(*hv, *h, blur_tile_count(w.plan.out_w, h->max_taps), ty, blk);
-                        const uint32_t off = arena_append(c, blk.data(), blk.size());
-                        if (!off) full = true; else c->blur_plans[std::make_tuple(kv, k, ty)] = off;
-                    }
-                }
-            }
-        }
-        for (auto &w : work) {
-            if (full) break;
-            if (w.p->front_end != FLGPU_FE_JPEG) continue;
-            const uint32_t q = std::min<uint32_t>(std::max<uint32_t>(w.p->quality, 1u), 100u); // handler.rs:275 quality().clamp(1, 100)
-            const auto key = std::make_tuple(w.plan.out_w, w.plan.out_h, q);
-            auto it = c->jpeg_tables.find(key);
-            if (it == c->jpeg_tables.end()) {
-                std::vector<uint32_t> blk;
-                build_jpeg_tables(w.plan.out_w, w.plan.out_h, q, blk);
-                const uint32_t off = arena_append(c, blk.data(), blk.size());
-                if (!off) { full = true; break; }
-                it = c->jpeg_tables.emplace(key, off).first;
-            }
-            w.jpeg_tab = it->second;
-        }
-        if (!full) break;
-        if (attempt == 1) return FLGPU_ERR_OOM;
-        FL_HIP(c, hipStreamSynchronize(st), "arena reset sync");
-        FL_HIP(c, hipDeviceSynchronize(), "arena reset sync");
-        arena_reset(c);
-    }
-    { int rc = arena_flush(c, st); if (rc) return rc; }
-
-    // ---- descriptors ---------------------------------------------------------
-    std::map<GroupKey, std::vector<size_t>> s1_groups, blur_groups, fe_groups;
-    for (size_t i = 0; i < n; ++i) {
-        const Work &w = work[i];
-        if (w.s1 == S1_WTILE) s1_groups[{(uint32_t)S1_WTILE | (w.wplan->nslot << 8), w.cs, w.pre, w.plan.letterboxed && !w.luma_mid}].push_back(i);
-        else if (w.s1 == S1_MFMA) s1_groups[{(uint32_t)S1_MFMA | (w.mplan->ops_in_lds ? 1u << 8 : 0u) | (w.mplan->wide ? 1u << 9 : 0u) | (w.mplan->full ? 1u << 10 : 0u) | (w.mplan->compact ? 1u << 11 : 0u), w.cs, w.pre, w.plan.letterboxed && !w.luma_mid}].push_back(i);
-        else if (w.s1 != S1_NONE) s1_groups[{(uint32_t)w.s1 | (w.splan ? w.splan->nacc << 8 : 0u) | (w.s1 == S1_STREAM && w.unaligned ? 1u << 16 : 0u), w.cs, w.pre, w.plan.letterboxed && !w.luma_mid}].push_back(i);
-        if (w.p->blur_sigma > 0.0f && w.bwplan) blur_groups[{kBlurWtileKind | w.bwplan->nslot, w.luma_mid ? 1u : w.plan.out_c, 0, w.luma_mid ? 1u : 0u}].push_back(i);
-        else if (w.p->blur_sigma > 0.0f) {
-            const uint32_t ce = blur_channels(w);
-            // pictures of one launch share the workgroup width the kernel is instantiated for
-            AxisKey hk2; const HostAxis *hh2 = nullptr;
-            const uint32_t lanes = (get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &hk2, &hh2) && hh2 &&
-                                    blur_tile_supported(hh2->max_taps)) ? blur_lanes(w.plan.out_w, hh2->max_taps) : 256u;
-            blur_groups[{lanes, w.plan.out_c, ce, 0}].push_back(i);
-        }
-        if (w.p->front_end != FLGPU_FE_NONE) fe_groups[{w.p->front_end, 0, 0, 0}].push_back(i);
-    }
-    std::vector<Job> jobs;
-    std::vector<StreamItem> items;
-    std::vector<MfmaItem> mitems;
-    std::vector<uint32_t> mwg; // matrix-pipe launches with persistent workgroups: {first item, items} of every workgroup
-    std::vector<FrontendJob> fjobs;
-    // EXIF orientation pre-pass jobs, grouped by channel count
-    struct OrientLaunch { uint32_t cs, base, n, mw, mh; };
-    std::vector<OrientLaunch> orient_launches;
-    for (uint32_t cs = 1; cs <= 4; ++cs) {
-        OrientLaunch O{cs, (uint32_t)jobs.size(), 0, 0, 0};
-        for (auto &w : work) {
-            if (!w.orient || w.cs != cs) continue;
-            Job j; memset(&j, 0, sizeof(j));
-            j.src = w.raw_src; j.dst = const_cast<uint8_t *>(w.src);
-            j.sw = w.raw_w; j.sh = w.raw_h; j.dw = w.sw; j.dh = w.sh; j.fill = w.orient;
-            O.mw = std::max(O.mw, j.dw); O.mh = std::max(O.mh, j.dh);
-            jobs.push_back(j);
-            O.n++;
-        }
-        if (O.n) orient_launches.push_back(O);
-    }
-    struct S1Launch { GroupKey k; uint32_t job_base, njobs, item_base, nitems, nacc, max_nout, grid = 0, wg_base = 0; LaunchGeneric g; size_t lds; size_t mid_floats; uint32_t blur_grid_x; bool blur_tiled; };
-    std::vector<S1Launch> s1_launches, blur_launches;
-    struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
-    std::vector<FeLaunch> fe_launches;
-    size_t mid_floats_max = 0;
-    const size_t kMidCapFloats = (size_t)256 << 20; // 1 GiB of f32 intermediate per launch group
-
-    auto new_launch = [&](const GroupKey &k) {
-        S1Launch L{};
-        L.k = k; L.job_base = (uint32_t)jobs.size(); L.item_base = (uint32_t)(((k.kind & 255u) == S1_MFMA || (k.kind & 255u) == S1_WTILE || (k.kind & kBlurWtileKind)) ? mitems.size() : items.size());
-        L.g.cs = k.cs; L.g.pre = k.pre; L.g.letterbox = k.lb; L.g.grouped = 1;
-        return L;
-    };
-    for (auto &kv : s1_groups) {
-        const GroupKey &k = kv.first;
-        S1Launch L = new_launch(k);
-        MfmaPlan *launch_plan = nullptr; // the matrix-pipe plan every picture of the launch shares, if they all do
-        bool launch_plan_set = false;
-        for (size_t idx : kv.second) {
-            const Work &w = work[idx];
-            Job j; fill_job(w, j);
-            const size_t mid = ((k.kind & 255u) == S1_GENERIC) ? (size_t)w.sw * w.plan.resized_h * mid_channels(w.cs, w.pre) : 0;
-            if ((k.kind & 255u) == S1_GENERIC && L.njobs && L.mid_floats + mid > kMidCapFloats) {
-                s1_launches.push_back(L);
-                L = new_launch(k);
-            }
-            j.mid_off = (uint32_t)L.mid_floats;
-            L.mid_floats += mid;
-            mid_floats_max = std::max(mid_floats_max, L.mid_floats);
-            L.g.max_sw = std::max(L.g.max_sw, j.sw); L.g.max_rh = std::max(L.g.max_rh, j.rh);
-            L.g.max_cw = std::max(L.g.max_cw, j.cw); L.g.max_ch = std::max(L.g.max_ch, j.ch);
-            L.g.max_dw = std::max(L.g.max_dw, j.dw); L.g.max_dh = std::max(L.g.max_dh, j.dh);
-            if ((k.kind & 255u) == S1_TILE) {
-                L.g.tile_w_min = L.g.tile_w_min ? std::min(L.g.tile_w_min, w.tile_w) : w.tile_w;
-                c->stats.resample_src_bytes += (uint64_t)j.src_bytes;
-                c->stats.resample_dst_bytes += w.plan.pixel_bytes;
-            }
-            if ((k.kind & 255u) == S1_WTILE) {
-                const size_t before = mitems.size();
-                w.wplan->items_for(wtile_bands(dbg, *w.wplan, kv.second.size()), (uint32_t)jobs.size(), mitems);
-                L.nitems += (uint32_t)(mitems.size() - before);
-                L.lds = std::max(L.lds, (size_t)w.wplan->lds_bytes);
-                c->stats.resample_src_bytes += (uint64_t)j.src_bytes;
-                c->stats.resample_dst_bytes += w.plan.pixel_bytes;
-            }
-            if ((k.kind & 255u) == S1_MFMA) {
-                launch_plan = (!launch_plan_set || launch_plan == w.mplan) ? const_cast<MfmaPlan *>(w.mplan) : nullptr; launch_plan_set = true; // (one plan for the whole launch, or none)
-                for (MfmaItem it2 : *w.mitems) { it2.job = (uint32_t)jobs.size(); mitems.push_back(it2); }
-                L.nitems += (uint32_t)w.mitems->size();
-                L.max_nout = std::max(L.max_nout, w.mplan->max_nout);
-                c->stats.resample_src_bytes += (uint64_t)j.src_bytes;
-                c->stats.resample_dst_bytes += w.plan.pixel_bytes;
-            }
-            if ((k.kind & 255u) == S1_STREAM) {
-                for (StreamItem it2 : w.splan->items) { it2.job = (uint32_t)jobs.size(); items.push_back(it2); }
-                L.nitems += (uint32_t)w.splan->items.size();
-                L.lds = std::max(L.lds, w.splan->lds_bytes);
-                L.nacc = w.splan->nacc;
-                c->stats.resample_src_bytes += (uint64_t)j.src_bytes;
-                c->stats.resample_dst_bytes += w.plan.pixel_bytes;
-            }
-            jobs.push_back(j);
-            L.njobs++;
-        }
-        if ((k.kind & 255u) == S1_MFMA) {
-            if (L.nitems > 1) {
-                // longest workgroups first and strips of a picture on one XCD, as for the streaming kernel below
-                auto first = mitems.begin() + L.item_base;
-                std::stable_sort(first, first + L.nitems, [](const MfmaItem &a, const MfmaItem &b) { return a.kb1 - a.kb0 > b.kb1 - b.kb0; });
-                xcd_interleave(&*first, L.nitems, [](const MfmaItem &x) { return x.kb1 - x.kb0; });
-            }
-            if ((k.kind >> 10) & 1u) {
-                // full-width arithmetic: persistent workgroups, each with its own list of items
-                L.grid = std::max(1u, std::min(L.nitems, c->cu_count));
-                L.wg_base = (uint32_t)mwg.size();
-                std::vector<uint32_t> lists;
-                assign_items(mitems, L.item_base, L.nitems, L.grid, launch_plan, lists);
-                mwg.insert(mwg.end(), lists.begin(), lists.end());
-            }
-        }
-        if ((k.kind & 255u) == S1_WTILE && L.nitems > 1) {
-            // strips and bands of a picture on one XCD (their source windows overlap: the halo then comes from that XCD's L2)
-            auto first = mitems.begin() + L.item_base;
-            xcd_interleave(&*first, L.nitems, [](const MfmaItem &) { return 1u; });
-        }
-        if ((k.kind & 255u) == S1_STREAM && L.nitems > 1) {
-            // longest workgroups first: in a mixed batch a 4K band walks four times the rows of a 1080p one, and the
-            // hardware hands out workgroups in index order -- started last, the long ones would be the launch's tail
-            auto first = items.begin() + L.item_base;
-            std::stable_sort(first, first + L.nitems, [](const StreamItem &a, const StreamItem &b) { return a.r1 - a.r0 > b.r1 - b.r0; });
-            xcd_interleave(&*first, L.nitems, [](const StreamItem &x) { return x.r1 - x.r0; });
-        }
-        s1_launches.push_back(L);
-    }
-    for (auto &kv : blur_groups) {
-        const GroupKey &k = kv.first; // cs = channel count of the blurred image
-        S1Launch L = new_launch(k);
-        for (size_t idx : kv.second) {
-            const Work &w = work[idx];
-            const flgpu_plan &pl = w.plan;
-            Job j; memset(&j, 0, sizeof(j));
-            j.src = w.s1_dst; j.dst = w.blur_dst; j.src_bytes = (uint32_t)pl.pixel_bytes;
-            j.sw = pl.out_w; j.sh = pl.out_h; j.rw = pl.out_w; j.rh = pl.out_h; j.cw = pl.out_w; j.ch = pl.out_h;
-            j.dw = pl.out_w; j.dh = pl.out_h;
-            AxisKey vkey, hkey;
-            j.vtab = get_axis(c, pl.out_h, pl.out_h, FILTER_GAUSSIAN, w.p->blur_sigma, &vkey, nullptr);
-            j.htab = get_axis(c, pl.out_w, pl.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &hkey, nullptr);
-            {
-                auto bt = c->blur_plans.find(std::make_tuple(vkey, hkey, blur_band_rows(k.pre ? k.pre : pl.out_c)));
-                j.pad0 = bt != c->blur_plans.end() ? bt->second : 0u; // table block of the blur kernel
-            }
-            if (k.kind & kBlurWtileKind) {
-                if (w.luma_mid) {
-                    // the source is stage 1's unframed Luma8 picture (rw x rh) at (cx, cy) of a virtual sw x sh frame of value `fill`
-                    j.rw = std::min(pl.resized_w - pl.crop_x, pl.out_w - pl.place_x); j.rh = std::min(pl.resized_h - pl.crop_y, pl.out_h - pl.place_y);
-                    j.cx = pl.place_x; j.cy = pl.place_y;
-                    j.src_bytes = j.rw * j.rh;
-                    j.fill = (uint32_t)w.p->fill_r * 0x01010101u;
-                }
-                const size_t before = mitems.size();
-                w.bwplan->items_for(wtile_bands(dbg, *w.bwplan, kv.second.size()), (uint32_t)jobs.size(), mitems);
-                L.nitems += (uint32_t)(mitems.size() - before);
-                L.lds = std::max(L.lds, (size_t)w.bwplan->lds_bytes);
-                jobs.push_back(j);
-                L.njobs++;
-                continue;
-            }
-            const size_t mid = (size_t)pl.out_w * pl.out_h * pl.out_c;
-            if (L.njobs && L.mid_floats + mid > kMidCapFloats) { blur_launches.push_back(L); L = new_launch(k); }
-            {
-                const AxisTable *vh = reinterpret_cast<const AxisTable *>(c->h_arena.data() + j.vtab);
-                const AxisTable *hh = reinterpret_cast<const AxisTable *>(c->h_arena.data() + j.htab);
-                if (L.njobs == 0) L.blur_tiled = true;
-                const size_t lds = blur_lds_bytes(pl.out_w, k.pre ? k.pre : pl.out_c, vh->max_taps, hh->max_taps); // k.pre = channels filtered
-                if (!blur_tile_supported(hh->max_taps) || !blur_tile_supported(vh->max_taps) || lds > 150 * 1024 || !j.pad0) L.blur_tiled = false;
-                L.lds = std::max(L.lds, lds);
-                L.blur_grid_x = std::max(L.blur_grid_x, blur_grid_x(pl.out_w, pl.out_h, hh->max_taps, k.pre ? k.pre : pl.out_c));
-            }
-            j.mid_off = (uint32_t)L.mid_floats;
-            L.mid_floats += mid;
-            mid_floats_max = std::max(mid_floats_max, L.mid_floats);
-            L.g.max_sw = std::max(L.g.max_sw, j.sw); L.g.max_rh = std::max(L.g.max_rh, j.rh);
-            L.g.max_cw = std::max(L.g.max_cw, j.cw); L.g.max_ch = std::max(L.g.max_ch, j.ch);
-            jobs.push_back(j);
-            L.njobs++;
-        }
-        if ((k.kind & kBlurWtileKind) && L.nitems > 1) {
-            auto first = mitems.begin() + L.item_base;
-            xcd_interleave(&*first, L.nitems, [](const MfmaItem &) { return 1u; });
-        }
-        blur_launches.push_back(L);
-    }
-    // result words: two per image of the batch, see flgpu_ctx::last_fe
-    // ... followed by the batch's device error word (fl_mfma.h FLGPU_DEVERR_*): kernels that wait on one another inside a
-    // workgroup bound their waits and report an expired one here instead of delivering pixels that were never synchronised
-    const bool has_results = !fe_groups.empty();
-    bool has_err_word = false;
-    for (auto &L : s1_launches) has_err_word |= (L.k.kind & 255u) == S1_MFMA;
-    // (they live at the end of the batch's descriptor block and arrive zeroed with it: a clear of their own was two fill kernels
-    // and two engine switches between one batch's last kernel and the next one's first)
-    std::vector<size_t> jjob_idx, fjob_idx, pjob_idx, wjob_idx; // image of every encoder / front-end job: its result words are addressed once the block's place is known
-    const uint32_t mfma_spin_limit = (uint32_t)std::max<int64_t>(0, dbg.get(DBG_MFMA_SPIN_LIMIT)); // tests: 0 = every bounded wait expires
-    std::vector<JpegJob> jjobs;
-    std::vector<PngJob> pjobs;
-    std::vector<WebpJob> wjobs;
-    uint32_t jpeg_max_blocks = 0;
-    for (auto &kv : fe_groups) {
-        if (kv.first.kind == FLGPU_FE_WEBP_LOSSLESS) {
-            for (size_t idx : kv.second) {
-                const Work &w = work[idx];
-                const flgpu_plan &pl = w.plan;
-                WebpJob j; memset(&j, 0, sizeof(j));
-                j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-                j.dst = w.final_dst;
-                j.res = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_res.p) + w.wll_res_off);
-                j.tok = reinterpret_cast<uint16_t *>(static_cast<char *>(c->d_webpll_tok.p) + w.wll_tok_off);
-                j.tiles = static_cast<WebpllTile *>(c->d_webpll_tiles.p) + w.wll_tile0;
-                j.pic = static_cast<uint32_t *>(c->d_webpll_pic.p) + (size_t)w.wll_pic * kWebpllPicWords;
-                j.stream = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_stream.p) + w.wll_stream_off);
-                j.result = nullptr; wjob_idx.push_back(idx);
-                j.w = pl.out_w; j.h = pl.out_h; j.c = pl.out_c;
-                j.tile0 = w.wll_tile0; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
-                j.dst_cap = (uint32_t)std::min<uint64_t>(dsts[idx].capacity, 0xffffffffull);
-                j.stream_words = (uint32_t)(align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256) / 4u);
-                wjobs.push_back(j);
-            }
-            continue;
-        }
-        if (kv.first.kind == FLGPU_FE_PNG) {
-            for (size_t idx : kv.second) {
-                const Work &w = work[idx];
-                const flgpu_plan &pl = w.plan;
-                PngJob j; memset(&j, 0, sizeof(j));
-                j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-                j.dst = w.final_dst;
-                j.filt = static_cast<uint8_t *>(c->d_png_filt.p) + w.png_filt_off;
-                j.chunks = static_cast<uint8_t *>(c->d_png_chunks.p) + (size_t)w.png_seg0 * kPngSegOutBytes;
-                j.syms = static_cast<uint16_t *>(c->d_png_syms.p) + (size_t)w.png_seg0 * kPngSegBytes;
-                j.recs = static_cast<uint32_t *>(c->d_png_recs.p) + (size_t)w.png_seg0 * 4u;
-                j.result = nullptr; pjob_idx.push_back(idx);
-                j.w = pl.out_w; j.h = pl.out_h; j.c = pl.out_c;
-                j.row0 = w.png_row0; j.seg0 = w.png_seg0; j.nseg = w.png_nseg;
-                j.level = png_level(w.p->quality);
-                j.dst_cap = (uint32_t)std::min<uint64_t>(dsts[idx].capacity, 0xffffffffull);
-                j.fbytes = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
-                pjobs.push_back(j);
-            }
-            continue;
-        }
-        if (kv.first.kind == FLGPU_FE_JPEG) {
-            for (size_t idx : kv.second) {
-                const Work &w = work[idx];
-                const flgpu_plan &pl = w.plan;
-                JpegJob j; memset(&j, 0, sizeof(j));
-                j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-                j.dst = w.final_dst;
-                j.meta = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_coef.p) + w.jpeg_coef_off);
-                j.unit_off = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_off.p) + w.jpeg_off_off);
-                j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_raw.p) + w.jpeg_raw_off);
-                j.result = nullptr; jjob_idx.push_back(idx);
-                j.w = pl.out_w; j.h = pl.out_h; j.c = pl.out_c;
-                j.bx = pl.plane_w / 8u; j.by = pl.plane_h / 8u;
-                j.tab_off = w.jpeg_tab;
-                j.dst_cap = (uint32_t)std::min<uint64_t>(dsts[idx].capacity, 0xffffffffull);
-                jpeg_max_blocks = std::max(jpeg_max_blocks, j.bx * j.by);
-                jjobs.push_back(j);
-            }
-            continue;
-        }
-        FeLaunch F{kv.first.kind, (uint32_t)fjobs.size(), 0, 0, 0, true};
-        for (size_t idx : kv.second) {
-            const Work &w = work[idx];
-            const flgpu_plan &pl = w.plan;
-            FrontendJob f; memset(&f, 0, sizeof(f));
-            f.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-            f.dst = w.final_dst;
-            f.status = nullptr; fjob_idx.push_back(idx);
-            f.w = pl.out_w; f.h = pl.out_h; f.c = pl.out_c;
-            f.plane_w = pl.plane_w; f.plane_h = pl.plane_h; f.chroma_w = pl.chroma_w; f.chroma_h = pl.chroma_h;
-            if (f.c != 4 || ((uintptr_t)f.src & 3u) || ((uintptr_t)f.dst & 3u)) F.rgba = false;
-            if (F.kind == FLGPU_FE_JFIF444) { F.mw = std::max(F.mw, f.plane_w); F.mh = std::max(F.mh, f.plane_h); }
-            else { F.mw = std::max(F.mw, f.chroma_w); F.mh = std::max(F.mh, f.chroma_h); }
-            fjobs.push_back(f);
-            F.n++;
-        }
-        fe_launches.push_back(F);
-    }
-    FL_HIP(c, c->d_mid.reserve(mid_floats_max * 4), "f32 intermediate");
-
-    // The matrix-pipe kernel's persistent workgroups request the first K-block of their NEXT item in the last pass of the current
-    // one: what that request needs (source, pitch, last row, the strip's first byte, the first K-block), one record per item in item
-    // order, so that it is ONE scalar load at that point and nothing of the next item occupies registers before (fl_mfma.h MfmaReq).
-    std::vector<MfmaReq> mreqs;
-    for (auto &L : s1_launches) {
-        if ((L.k.kind & 255u) != S1_MFMA) continue;
-        mreqs.resize(mitems.size());
-        for (uint32_t k = L.item_base; k < L.item_base + L.nitems; ++k) {
-            const MfmaItem &mi = mitems[k];
-            const Job &j = jobs[mi.job];
-            MfmaReq &r = mreqs[k];
-            r.src = j.src; r.pitch = j.sw * L.k.cs; r.last_row = j.sh - 1u; r.kb0 = mi.kb0; r.kb1 = mi.kb1; r.job = mi.job;
-            r.strip_off = mi.strip_off; r.vplan_off = mi.vplan_off; r.pad[0] = r.pad[1] = 0;
-            r.byte0 = reinterpret_cast<const MfmaStrip *>(c->h_arena.data() + mi.strip_off)->byte0;
-        }
-    }
-    // one staging slot: [jobs][items][fjobs][jjobs][mitems][mreqs][mwg]
-    const size_t jobs_b = align_up(jobs.size() * sizeof(Job), 256), items_b = align_up(items.size() * sizeof(StreamItem), 256),
-                 fjobs_b = align_up(fjobs.size() * sizeof(FrontendJob), 256), jjobs_b = align_up(jjobs.size() * sizeof(JpegJob), 256),
-                 mitems_b = align_up(mitems.size() * sizeof(MfmaItem), 256), mreqs_b = align_up(mreqs.size() * sizeof(MfmaReq), 256), mwg_b = align_up(mwg.size() * sizeof(uint32_t), 256),
-                 pjobs_b = align_up(pjobs.size() * sizeof(PngJob), 256), wjobs_b = align_up(wjobs.size() * sizeof(WebpJob), 256);
-    const size_t pjobs_off = jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b + mwg_b, wjobs_off = pjobs_off + pjobs_b;
-    const size_t stat_off = wjobs_off + wjobs_b, stat_b = (has_results || has_err_word) ? align_up(n * 8 + 8, 256) : 0;
-    const size_t desc_b = stat_off + stat_b;
-    uint32_t *status_dev = nullptr;
-    const Job *d_jobs = nullptr; const StreamItem *d_items = nullptr; const FrontendJob *d_fjobs = nullptr; const JpegJob *d_jjobs = nullptr;
-    const MfmaItem *d_mitems = nullptr;
-    const MfmaReq *d_mreqs = nullptr;
-    const uint32_t *d_mwg = nullptr;
-    const PngJob *d_pjobs = nullptr;
-    const WebpJob *d_wjobs = nullptr;
-    DescSlot *slot = nullptr;
-    if (desc_b) {
-        slot = &c->slots[c->next_slot];
-        c->next_slot = (c->next_slot + 1) % 4;
-        if (slot->busy) { FL_HIP(c, hipEventSynchronize(slot->done), "descriptor slot wait"); slot->busy = false; }
-        if (!slot->done) FL_HIP(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming), "event");
-        FL_HIP(c, slot->host.reserve(desc_b), "pinned descriptors");
-        FL_HIP(c, slot->dev.reserve(desc_b), "device descriptors");
-        char *hp = static_cast<char *>(slot->host.p);
-        if (stat_b) {
-            status_dev = reinterpret_cast<uint32_t *>(static_cast<char *>(slot->dev.p) + stat_off);
-            memset(hp + stat_off, 0, stat_b);
-            for (size_t k = 0; k < jjobs.size(); ++k) jjobs[k].result = status_dev + 2 * jjob_idx[k];
-            for (size_t k = 0; k < fjobs.size(); ++k) fjobs[k].status = status_dev + 2 * fjob_idx[k];
-            for (size_t k = 0; k < pjobs.size(); ++k) pjobs[k].result = status_dev + 2 * pjob_idx[k];
-            for (size_t k = 0; k < wjobs.size(); ++k) wjobs[k].result = status_dev + 2 * wjob_idx[k];
-        }
-        if (!jobs.empty()) memcpy(hp, jobs.data(), jobs.size() * sizeof(Job));
-        if (!items.empty()) memcpy(hp + jobs_b, items.data(), items.size() * sizeof(StreamItem));
-        if (!fjobs.empty()) memcpy(hp + jobs_b + items_b, fjobs.data(), fjobs.size() * sizeof(FrontendJob));
-        if (!jjobs.empty()) memcpy(hp + jobs_b + items_b + fjobs_b, jjobs.data(), jjobs.size() * sizeof(JpegJob));
-        if (!mitems.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b, mitems.data(), mitems.size() * sizeof(MfmaItem));
-        if (!mreqs.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b, mreqs.data(), mreqs.size() * sizeof(MfmaReq));
-        if (!mwg.empty()) memcpy(hp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b, mwg.data(), mwg.size() * sizeof(uint32_t));
-        if (!pjobs.empty()) memcpy(hp + pjobs_off, pjobs.data(), pjobs.size() * sizeof(PngJob));
-        if (!wjobs.empty()) memcpy(hp + wjobs_off, wjobs.data(), wjobs.size() * sizeof(WebpJob));
-        // While a previous batch is still running, the block goes up on the context's upload stream: the slot is free (its last
-        // batch has ended, see above), so the copy runs under that batch's kernels, and this batch's first kernel follows its
-        // last one without a copy engine in between.  A lone request on an idle device sends the block down its own stream (no
-        // second stream, no wait: the 15 us would be 3 % of its latency).
-        if (c->last_done && hipEventQuery(c->last_done) == hipErrorNotReady) {
-            if (!c->up_stream) FL_HIP(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking), "upload stream");
-            if (!slot->uploaded) FL_HIP(c, hipEventCreateWithFlags(&slot->uploaded, hipEventDisableTiming), "event");
-            FL_HIP(c, hipMemcpyAsync(slot->dev.p, hp, desc_b, hipMemcpyHostToDevice, c->up_stream), "descriptor upload");
-            FL_HIP(c, hipEventRecord(slot->uploaded, c->up_stream), "event record");
-            // (the HOST waits the ~15 us the 130 KB take: a device-side wait on the event is a barrier packet between the previous
-            // batch's last kernel and this one's first, 7 us of idle chip per batch; the host has the previous batch's 2 ms to spare)
-            FL_HIP(c, hipEventSynchronize(slot->uploaded), "descriptor upload wait");
-        } else {
-            FL_HIP(c, hipMemcpyAsync(slot->dev.p, hp, desc_b, hipMemcpyHostToDevice, st), "descriptor upload");
-        }
-        char *dp = static_cast<char *>(slot->dev.p);
-        d_jobs = reinterpret_cast<const Job *>(dp);
-        d_items = reinterpret_cast<const StreamItem *>(dp + jobs_b);
-        d_fjobs = reinterpret_cast<const FrontendJob *>(dp + jobs_b + items_b);
-        d_jjobs = reinterpret_cast<const JpegJob *>(dp + jobs_b + items_b + fjobs_b);
-        d_mitems = reinterpret_cast<const MfmaItem *>(dp + jobs_b + items_b + fjobs_b + jjobs_b);
-        d_mreqs = reinterpret_cast<const MfmaReq *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b);
-        d_mwg = reinterpret_cast<const uint32_t *>(dp + jobs_b + items_b + fjobs_b + jjobs_b + mitems_b + mreqs_b);
-        d_pjobs = reinterpret_cast<const PngJob *>(dp + pjobs_off);
-        d_wjobs = reinterpret_cast<const WebpJob *>(dp + wjobs_off);
-    }
-
-    range_plan.reset();
-    // ---- launches --------------------------------------------------------------
     RoctxRange range_launch("flgpu launches");
-    for (auto &O : orient_launches) {
-        LaunchGeneric g{};
-        g.jobs = d_jobs; g.job_base = O.base; g.njobs = O.n; g.cs = O.cs; g.max_dw = O.mw; g.max_dh = O.mh;
-        FL_HIP(c, launch_orient(g, st), "orientation kernel");
-    }
-    for (auto &L : s1_launches) {
-        L.g.jobs = d_jobs; L.g.arena = c->d_arena; L.g.mid = static_cast<float *>(c->d_mid.p);
-        L.g.job_base = L.job_base; L.g.njobs = L.njobs;
-        L.g.no_place4 = dbg.on(DBG_NO_PLACE4) ? 1u : 0u;
-        if ((L.k.kind & 255u) == S1_NEAREST) {
-            L.g.nearest = 1;
-            FL_HIP(c, launch_place(L.g, false, st), "nearest kernel");
-        } else if ((L.k.kind & 255u) == S1_PLACE) {
-            FL_HIP(c, launch_place(L.g, false, st), "place kernel");
-        } else if ((L.k.kind & 255u) == S1_TILE) {
-            if (L.k.lb) FL_HIP(c, launch_place(L.g, true, st), "border fill");
-            L.g.grouped = 1;
-            {
-                ProfileScope ps(c, st, 0);
-                FL_HIP(c, launch_tile_resample(L.g, st), "tiled two-pass resample kernel");
-            }
-            c->stats.resample_launches++;
-            c->stats.generic_launches++; // (the two-pass generic resample, LDS form)
-        } else if ((L.k.kind & 255u) == S1_WTILE) {
-            if (L.k.lb) FL_HIP(c, launch_place(L.g, true, st), "border fill");
-            LaunchWtile m{};
-            m.jobs = d_jobs; m.items = reinterpret_cast<const WtItem *>(d_mitems + L.item_base); m.arena = c->d_arena; m.nitems = L.nitems;
-            m.nslot = (L.k.kind >> 8) & 255u; m.nkmax = kWtOperandRegs / m.nslot; m.letterbox = L.k.lb; m.lds_bytes = (uint32_t)L.lds; m.invert = L.k.pre == PRE_INVERT;
-            {
-                ProfileScope ps(c, st, 0);
-                FL_HIP(c, launch_wtile(m, st), "window-tile matrix-pipe kernel");
-            }
-            c->stats.resample_launches++;
-            c->stats.mfma_launches++;
-            c->stats.wtile_launches++;
-        } else if ((L.k.kind & 255u) == S1_GENERIC) {
-            if (L.k.lb) FL_HIP(c, launch_place(L.g, true, st), "border fill");
-            FL_HIP(c, launch_vpass_generic(L.g, st), "generic vertical pass");
-            FL_HIP(c, launch_hpass_generic(L.g, st), "generic horizontal pass");
-            c->stats.generic_launches++;
-        } else if ((L.k.kind & 255u) == S1_MFMA) {
-            LaunchMfma m{}; // (paints the letterbox frame itself, like the streaming kernel)
-            m.jobs = d_jobs; m.items = d_mitems + L.item_base; m.reqs = d_mreqs + L.item_base; m.arena = c->d_arena; m.nitems = L.nitems;
-            m.grid = L.grid; m.wg_lists = L.grid ? d_mwg + L.wg_base : nullptr;
-            m.cs = L.k.cs; m.letterbox = L.k.lb; m.ops_in_lds = (L.k.kind >> 8) & 1u; m.wide = (L.k.kind >> 9) & 1u; m.full = (L.k.kind >> 10) & 1u; m.compact = (L.k.kind >> 11) & 1u; m.max_nout = L.max_nout;
-            m.spin_limit = mfma_spin_limit; m.err_word = status_dev + 2 * n;
-            {
-                ProfileScope ps(c, st, 0);
-                FL_HIP(c, launch_mfma(m, st), "matrix-pipe resample kernel");
-            }
-            c->stats.resample_launches++;
-            c->stats.mfma_launches++;
-        } else {
-            LaunchStream s{}; // (the streaming kernel paints the letterbox frame itself)
-            s.jobs = d_jobs; s.items = d_items + L.item_base; s.arena = c->d_arena; s.nitems = L.nitems;
-            s.cs = L.k.cs; s.pre = L.k.pre; s.letterbox = L.k.lb; s.lds_bytes = L.lds; s.nacc = L.nacc; s.unaligned = (L.k.kind >> 16) & 1u;
-            {
-                ProfileScope ps(c, st, 0);
-                FL_HIP(c, launch_stream(s, st), "streaming resample kernel");
-            }
-            c->stats.resample_launches++;
-        }
-    }
-    for (auto &L : blur_launches) {
-        L.g.jobs = d_jobs; L.g.arena = c->d_arena; L.g.mid = static_cast<float *>(c->d_mid.p);
-        L.g.job_base = L.job_base; L.g.njobs = L.njobs; L.g.letterbox = 0;
-        L.g.grouped = 0;
-        ProfileScope ps(c, st, 1);
-        if (L.k.kind & kBlurWtileKind) {
-            LaunchWtile m{};
-            m.jobs = d_jobs; m.items = reinterpret_cast<const WtItem *>(d_mitems + L.item_base); m.arena = c->d_arena; m.nitems = L.nitems;
-            m.nslot = L.k.kind & 255u; m.nkmax = kWtOperandRegs / m.nslot; m.letterbox = L.k.lb; m.framed = L.k.lb; m.lds_bytes = (uint32_t)L.lds; m.half_waves = L.k.cs == 1u; // (one-channel pictures: little work per step, two 4-wave workgroups per CU hide each other's barriers; Rgba8 blurs measured 2 % slower that way)
-            FL_HIP(c, launch_wtile(m, st), "window-tile matrix-pipe kernel (blur)");
-            c->stats.mfma_launches++;
-            c->stats.wtile_launches++;
-        } else if (L.blur_tiled && !force_generic) {
-            L.g.pre = L.k.pre; // channels to filter (group key), see blur_tile_kernel
-            L.g.blur_lanes = L.k.kind;
-            FL_HIP(c, launch_blur_tile(L.g, L.blur_grid_x, L.lds, st), "blur kernel");
-        } else {
-            L.g.pre = PRE_NONE;
-            FL_HIP(c, launch_vpass_generic(L.g, st), "blur vertical pass");
-            FL_HIP(c, launch_hpass_generic(L.g, st), "blur horizontal pass");
-        }
-        c->stats.blur_launches++;
-    }
-    for (auto &F : fe_launches) {
-        ProfileScope ps(c, st, 2);
-        if (F.kind == FLGPU_FE_JFIF444) FL_HIP(c, launch_jfif444(d_fjobs, F.base, F.n, F.mw, F.mh, F.rgba, st), "jfif front end");
-        else FL_HIP(c, launch_webp420(d_fjobs, c->d_arena, c->gamma_off, F.base, F.n, F.mw, F.mh, F.rgba, st), "webp front end");
-        c->stats.frontend_launches++;
-    }
-    if (!jjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_jpeg_encode(d_jjobs, c->d_arena, 0, (uint32_t)jjobs.size(), jpeg_max_blocks, st), "JPEG encode");
-        c->stats.frontend_launches++;
-    }
-    if (!pjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_png_encode(d_pjobs, (uint32_t)pjobs.size(), png_rows, png_segs, st), "PNG encode");
-        c->stats.frontend_launches++;
-    }
-    if (!wjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_webpll_encode(d_wjobs, (uint32_t)wjobs.size(), wll_tiles, st), "lossless WebP encode");
-        c->stats.frontend_launches++;
-    }
-    // plain copies for requests that change nothing
+    if (int rc = enqueue_launches(c, B, st)) return rc;
+    // what the caller gets back at once, and what collect_results reads later
     for (size_t i = 0; i < n; ++i) {
-        const Work &w = work[i];
-        if (w.s1 == S1_NONE && !(w.p->blur_sigma > 0.0f) && w.p->front_end == FLGPU_FE_NONE)
-            FL_HIP(c, hipMemcpyAsync(w.final_dst, w.src, w.plan.pixel_bytes, hipMemcpyDeviceToDevice, st), "copy");
-    }
-    if (slot) { FL_HIP(c, hipEventRecord(slot->done, st), "event record"); slot->busy = true; }
-    if (!c->last_done) FL_HIP(c, hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming), "event");
-    FL_HIP(c, hipEventRecord(c->last_done, st), "event record");
-    c->last_stream = st;
-
-    for (size_t i = 0; i < n; ++i) {
-        const flgpu_plan &pl = work[i].plan;
+        const flgpu_plan &pl = B.work[i].plan;
         dsts[i].width = pl.out_w; dsts[i].height = pl.out_h; dsts[i].channels = pl.out_c;
-        const uint32_t fe = work[i].p->front_end;
+        const uint32_t fe = B.work[i].p->front_end;
         dsts[i].flags = fe_encoded(fe) ? FLGPU_IMG_ENCODED : (fe != FLGPU_FE_NONE ? FLGPU_IMG_FRONTEND_PLANES : 0u);
         dsts[i].bytes = fe_encoded(fe) ? 0 : pl.out_bytes; // an encoded stream's length is a result word: flgpu_batch_results
     }
     c->last_n = n;
-    c->last_status_dev = status_dev;
-    c->last_has_results = has_results;
-    c->last_has_err_word = has_err_word;
+    c->last_status_dev = B.status_dev;
+    c->last_has_results = B.has_results;
+    c->last_has_err_word = B.has_err_word;
     c->last_fe.resize(n);
-    for (size_t i = 0; i < n; ++i) c->last_fe[i] = work[i].p->front_end;
+    for (size_t i = 0; i < n; ++i) c->last_fe[i] = B.work[i].p->front_end;
     c->stats.images += n;
     c->stats.batches++;
     return FLGPU_OK;
@@ -1477,8 +1546,7 @@ extern "C" int flgpu_debug_assign_items(uint32_t pictures, uint32_t strips, uint
     for (uint32_t p = 0; p < pictures; ++p)
         for (MfmaItem m : plan.items_for(1)) { m.job = p; v.push_back(m); }
     uint32_t n = (uint32_t)v.size();
-    std::stable_sort(v.begin(), v.end(), [](const MfmaItem &a, const MfmaItem &b) { return a.kb1 - a.kb0 > b.kb1 - b.kb0; });
-    xcd_interleave(v.data(), n, [](const MfmaItem &x) { return x.kb1 - x.kb0; });
+    order_items(v.data(), n, [](const MfmaItem &x) { return x.kb1 - x.kb0; });
     const uint32_t G = std::max(1u, std::min(n, workgroups));
     std::vector<uint32_t> l;
     assign_items(v, 0, n, G, &plan, l);

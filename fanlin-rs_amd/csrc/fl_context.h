@@ -341,8 +341,6 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
                      flgpu_image *dsts, hipStream_t st);
 int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
-// room to give an encoded result on the device: the planning bound, or the format's worst case if the caller offers it
-uint64_t staged_out_bytes(const flgpu_params &p, const flgpu_plan &plan, uint64_t dst_capacity);
 // front ends whose output is an encoded stream: its length is a result word, known once the batch has run
 inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS; }
 // JPEG sources of a batch: dsrc[i].data = DEVICE copy of the coefficient blob whose header (host copy) is hdrs[i], or

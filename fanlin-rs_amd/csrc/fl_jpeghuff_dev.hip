@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "fl_jpegdec.h"
+#include "fl_types.h"
 
 namespace fl {
 
@@ -587,15 +588,11 @@ hipError_t launch_jpeg_huff(const JhJob *d_jobs, const JhJob *h_jobs, uint32_t n
     if (!njobs || !nitems) return hipSuccess;
     jh_init_kernel<<<dim3((max_blocks + 255u) / 256u, njobs), 256, 0, st>>>(d_jobs, max_blocks);
     constexpr uint32_t lds = kLdsWords * 4u;
-    static bool attr_done[16] = {};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16 || !attr_done[dev]) { // (more than the 64 KB a kernel gets without asking; idempotent, so a race between two lanes only repeats it)
-        const void *fns[3] = {reinterpret_cast<const void *>(&jh_sync_kernel<true>), reinterpret_cast<const void *>(&jh_sync_kernel<false>), reinterpret_cast<const void *>(&jh_write_kernel)};
-        for (const void *f : fns)
-            if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
-        if (dev >= 0 && dev < 16) attr_done[dev] = true;
-    }
+    static std::atomic<uint64_t> attr_set{0};
+    if (hipError_t e = set_max_lds_once(attr_set, (int)lds, {reinterpret_cast<const void *>(&jh_sync_kernel<true>), reinterpret_cast<const void *>(&jh_sync_kernel<false>),
+                                                              reinterpret_cast<const void *>(&jh_write_kernel)});
+        e != hipSuccess)
+        return e;
     jh_sync_kernel<true><<<nitems, 256, lds, st>>>(d_jobs, d_items);
     for (uint32_t r = 0; r < kJhSyncRounds; ++r) jh_sync_kernel<false><<<nitems, 256, lds, st>>>(d_jobs, d_items); // (each moves the chain across one more workgroup boundary)
     jh_scan_kernel<<<njobs, 256, 0, st>>>(d_jobs);

@@ -824,15 +824,7 @@ static hipError_t launch_mfma_t(const LaunchMfma &m, hipStream_t st)
     const size_t lds = FW ? mfma_lds_bytes_full(LAYOUT) : mfma_lds_bytes(m.max_nout, HLDS, WIDE);
     // the attribute is per function and device (the size is a constant of the instantiation): set once per (instantiation, device)
     static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&resample_mfma_kernel<CS, LB, HLDS, LAYOUT, FW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = set_max_lds_once(attr_set, (int)lds, {reinterpret_cast<const void *>(&resample_mfma_kernel<CS, LB, HLDS, LAYOUT, FW>)}); e != hipSuccess) return e;
     // full-width arithmetic: persistent workgroups, one per CU, each walking items blockIdx.x, blockIdx.x + gridDim.x, ... (the
     // kernel's header says why); the packed arithmetic keeps one item per workgroup
     uint32_t grid = m.nitems;

@@ -27,6 +27,7 @@
 
 #include "fl_huff_build.h"
 #include "fl_png.h"
+#include "fl_types.h"
 
 namespace fl {
 
@@ -607,11 +608,8 @@ __global__ __launch_bounds__(kPngThreads) void png_frame_kernel(const PngJob *__
 hipError_t launch_png_encode(const PngJob *jobs, uint32_t njobs, uint32_t total_rows, uint32_t total_segs, hipStream_t st)
 {
     if (!njobs || !total_rows || !total_segs) return hipSuccess;
-    static bool lds_set = false; // (idempotent; a race between two contexts sets the same value twice)
-    if (!lds_set) {
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&png_deflate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDeflateLds); e != hipSuccess) return e;
-        lds_set = true;
-    }
+    static std::atomic<uint64_t> attr_set{0};
+    if (hipError_t e = set_max_lds_once(attr_set, (int)kDeflateLds, {reinterpret_cast<const void *>(&png_deflate_kernel)}); e != hipSuccess) return e;
     const uint32_t rows_per_wg = kPngThreads / 64u;
     hipLaunchKernelGGL(png_filter_kernel, dim3((total_rows + rows_per_wg - 1u) / rows_per_wg), dim3(kPngThreads), 0, st, jobs, njobs, total_rows);
     FL_LAUNCH_CHECK();

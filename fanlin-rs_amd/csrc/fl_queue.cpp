@@ -130,7 +130,7 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
         flgpu_plan plan;
         int prc = flgpu_plan_output(&ps[i], dsrc[i].width, dsrc[i].height, dsrc[i].channels, &plan);
         if (prc) return prc; // validated by the caller already
-        dev_out[i] = staged_out_bytes(ps[i], plan, 0); // an encoded stream gets the format's worst case on the device
+        dev_out[i] = plan.max_out_bytes; // an encoded stream gets the format's worst case on the device
         dsrc[i].data = reinterpret_cast<uint8_t *>(in_b); dsrc[i].capacity = batch[i]->src_bytes; in_b += align_up(batch[i]->src_bytes, 256);
         ddst[i].data = reinterpret_cast<uint8_t *>(out_b); ddst[i].capacity = dev_out[i]; out_b += align_up(dev_out[i], 256);
     }

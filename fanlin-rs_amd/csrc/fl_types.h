@@ -6,7 +6,25 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <initializer_list>
+
 namespace fl {
+
+// Lets the kernels `fns` use `bytes` of dynamic LDS (more than the 64 KB a kernel gets without asking) on the current device.
+// The attribute is per function and device: `done` is the caller's mask of devices that have it, one mask per set of kernels.
+inline hipError_t set_max_lds_once(std::atomic<uint64_t> &done, int bytes, std::initializer_list<const void *> fns)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    for (const void *f : fns)
+        if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) != hipSuccess) return e;
+    done.fetch_or(bit, std::memory_order_release);
+    return hipSuccess;
+}
 
 // Pointwise operation applied to the SOURCE-resolution image before
 // resampling (reference src/handler.rs:224-228: grayscale wins over inverse).

@@ -422,15 +422,7 @@ hipError_t launch_wtile_t(const LaunchWtile &m, hipStream_t st)
 {
     // the attribute is per function and device: set once per (instantiation, device), not with every launch
     static std::atomic<uint64_t> attr_set{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&resample_wtile_kernel<NSLOT, NKMAX, WAVES>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
+    if (hipError_t e = set_max_lds_once(attr_set, 160 * 1024, {reinterpret_cast<const void *>(&resample_wtile_kernel<NSLOT, NKMAX, WAVES>)}); e != hipSuccess) return e;
     resample_wtile_kernel<NSLOT, NKMAX, WAVES><<<m.nitems, 64 * WAVES, m.lds_bytes, st>>>(m.jobs, m.items, m.arena, m.letterbox, m.invert, m.framed);
     return hipGetLastError();
 }
