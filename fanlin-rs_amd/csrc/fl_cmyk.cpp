@@ -5,7 +5,7 @@
 // (src/handler.rs:446-458).  Little CMS turns such a transform into a 17^4-node device-link table and then
 // interpolates it per pixel; here the table is baked once on the host -- by asking the system's liblcms2 for the
 // value of the un-optimised transform at every node, exactly what cmsopt.c does -- and the per-pixel half runs
-// in cmyk_clut_kernel (fl_kernels.hip).  liblcms2 is loaded with dlopen so that the library itself has no
+// in cmyk_clut_kernel (fl_color.hip).  liblcms2 is loaded with dlopen so that the library itself has no
 // link-time dependency on it; without it flgpu_set_cmyk_profile reports FLGPU_ERR_UNSUPPORTED and callers can
 // still hand over a table of their own with flgpu_set_cmyk_clut.
 #include "fl_cmyk.h"

@@ -26,6 +26,7 @@
 #include "../../include/fanlin_gpu.h"
 #include "fl_abi.h"
 #include "fl_cmyk.h"
+#include "fl_jpeg.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_kernels.h"

@@ -25,9 +25,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fl_jpeg.h"
 #include "fl_jpeg_tables.h"
-#include "fl_kernels.h"
 #include "fl_pixel.h"
+#include "fl_types.h"
 
 namespace fl {
 
@@ -595,8 +596,6 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
 }
 
 } // namespace
-
-#define FL_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
 
 hipError_t launch_jpeg_encode(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
                               hipStream_t st)

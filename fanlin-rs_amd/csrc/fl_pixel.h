@@ -1,4 +1,4 @@
-// fl_pixel.h -- small device helpers shared by the encoder front ends (fl_kernels.hip) and the JPEG back half (fl_jpeg.hip)
+// fl_pixel.h -- small device helpers shared by the encoder front ends (fl_color.hip), the resample kernels and the JPEG back half (fl_jpeg.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 

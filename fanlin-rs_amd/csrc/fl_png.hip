@@ -28,6 +28,7 @@
 #include "fl_huff_build.h"
 #include "fl_png.h"
 #include "fl_types.h"
+#include "fl_wave.h"
 
 namespace fl {
 
@@ -94,40 +95,6 @@ __device__ __forceinline__ void put_be32(uint8_t *p, uint32_t v)
 
 // ---------------------------------------------------------------- wave / workgroup helpers (256 threads) --
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v ^= __shfl_xor(v, o, 64);
-    return v;
-}
-
-// exclusive scan over the workgroup; *total = the sum of all
-__device__ __forceinline__ uint32_t wg_scan(uint32_t v, uint32_t *s_w, uint32_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kPngThreads / 64u; ++i) { const uint32_t t = s_w[i]; if (i < wave) base += t; sum += t; }
-    *total = sum;
-    return base + inc - v;
-}
-
 __device__ __forceinline__ uint64_t wg_sum64(uint64_t v, uint64_t *s)
 {
     v = wave_sum(v);
@@ -138,17 +105,6 @@ __device__ __forceinline__ uint64_t wg_sum64(uint64_t v, uint64_t *s)
 #pragma unroll
     for (uint32_t i = 0; i < kPngThreads / 64u; ++i) t += s[i];
     return t;
-}
-
-// the job a flat row / segment index belongs to: the last one whose first index is <= x
-template <bool SEG> __device__ __forceinline__ uint32_t find_job(const PngJob *__restrict__ jobs, uint32_t njobs, uint32_t x)
-{
-    uint32_t lo = 0, hi = njobs - 1u;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if ((SEG ? jobs[mid].seg0 : jobs[mid].row0) <= x) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
 }
 
 // ---------------------------------------------------------------- kernel 1: row filters --
@@ -170,7 +126,7 @@ __global__ __launch_bounds__(kPngThreads) void png_filter_kernel(const PngJob *_
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t r = blockIdx.x * (kPngThreads / 64u) + (threadIdx.x >> 6);
     if (r >= total_rows) return;
-    const PngJob &jb = jobs[find_job<false>(jobs, njobs, r)];
+    const PngJob &jb = jobs[find_first_le(jobs, njobs, r, &PngJob::row0)];
     const uint32_t y = r - jb.row0, bpp = jb.c;
     const size_t rb = (size_t)jb.w * jb.c;
     const uint8_t *cur = jb.src + (size_t)y * rb;
@@ -284,7 +240,7 @@ __global__ __launch_bounds__(kPngThreads) void png_deflate_kernel(const PngJob *
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t png_lds[];
     const uint32_t tid = threadIdx.x, g = blockIdx.x;
-    const PngJob &jb = jobs[find_job<true>(jobs, njobs, g)];
+    const PngJob &jb = jobs[find_first_le(jobs, njobs, g, &PngJob::seg0)];
     const uint32_t s = g - jb.seg0;
     const uint64_t seg_start = (uint64_t)s * kPngSegBytes;
     const uint32_t L = (uint32_t)min<uint64_t>(kPngSegBytes, jb.fbytes - seg_start);
@@ -462,7 +418,7 @@ __global__ __launch_bounds__(kPngThreads) void png_deflate_kernel(const PngJob *
     }
     uint32_t data_bits;
     const uint32_t hdr_bits = misc[kMiscHdrBits];
-    const uint32_t my_off = hdr_bits + wg_scan(mybits, misc + kMiscScan, &data_bits);
+    const uint32_t my_off = hdr_bits + wg_scan<kPngThreads>(mybits, misc + kMiscScan, &data_bits);
     const uint32_t end_bits = hdr_bits + data_bits + (cl[256] >> 16);
     // non-final: an empty stored block (3 bits, pad, 00 00 FF FF) ends the segment on a byte boundary
     const uint32_t dyn_bytes = final ? (end_bits + 7u) / 8u : (end_bits + 3u + 7u) / 8u + 4u;
@@ -602,8 +558,6 @@ __global__ __launch_bounds__(kPngThreads) void png_frame_kernel(const PngJob *__
 }
 
 } // namespace
-
-#define FL_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
 
 hipError_t launch_png_encode(const PngJob *jobs, uint32_t njobs, uint32_t total_rows, uint32_t total_segs, hipStream_t st)
 {

@@ -11,6 +11,9 @@
 
 namespace fl {
 
+// In a launch wrapper, after a kernel launch: returns the launch's error, if any.
+#define FL_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
+
 // Lets the kernels `fns` use `bytes` of dynamic LDS (more than the 64 KB a kernel gets without asking) on the current device.
 // The attribute is per function and device: `done` is the caller's mask of devices that have it, one mask per set of kernels.
 inline hipError_t set_max_lds_once(std::atomic<uint64_t> &done, int bytes, std::initializer_list<const void *> fns)

@@ -29,6 +29,8 @@
 #include <stdint.h>
 
 #include "fl_huff_build.h"
+#include "fl_types.h"
+#include "fl_wave.h"
 #include "fl_webpll.h"
 
 namespace fl {
@@ -53,44 +55,7 @@ __constant__ uint8_t kClOrder[19] = {17, 18, 0, 1, 2, 3, 4, 5, 16, 6, 7, 8, 9, 1
 
 // ---------------------------------------------------------------- helpers --
 
-// the job a flat tile index belongs to: the last one whose first tile is <= t
-__device__ __forceinline__ uint32_t find_job(const WebpJob *__restrict__ jobs, uint32_t njobs, uint32_t t)
-{
-    uint32_t lo = 0, hi = njobs - 1u;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1u) >> 1;
-        if (jobs[mid].tile0 <= t) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
-    return v;
-}
-
-// exclusive scans over the workgroup (sum / max); *total = the sum of all
-__device__ __forceinline__ uint32_t wg_scan(uint32_t v, uint32_t *s_w, uint32_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= (uint32_t)o) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < kWebpllThreads / 64u; ++i) { const uint32_t t = s_w[i]; if (i < wave) base += t; sum += t; }
-    *total = sum;
-    return base + inc - v;
-}
-
+// exclusive scan (maximum) over the workgroup, the counterpart of fl_wave.h wg_scan; *all = the maximum of all
 __device__ __forceinline__ uint32_t wg_excl_max(uint32_t v, uint32_t *s_w, uint32_t *all)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -208,7 +173,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_resid_kernel(const Webp
     __shared__ uint32_t s_res[kWebpllTile + 1u]; // [k] = residual of pixel base + k - 1
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
-    const WebpJob &jb = jobs[find_job(jobs, njobs, t)];
+    const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t k = tid; k <= kWebpllTile; k += kWebpllThreads) {
         const uint32_t i = base + k - 1u;
@@ -257,7 +222,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_token_kernel(const Webp
     __shared__ uint32_t s_edge[2];
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
-    const WebpJob &jb = jobs[find_job(jobs, njobs, t)];
+    const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) s_hist[i] = 0u;
     const uint32_t p0 = base + tid * kPx;
@@ -404,7 +369,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_bits_kernel(const WebpJ
     __shared__ uint32_t s_code[kAlph];
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
-    const WebpJob &jb = jobs[find_job(jobs, njobs, t)];
+    const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) s_code[i] = jb.pic[kPicCodes + i];
     __syncthreads();
@@ -418,7 +383,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_bits_kernel(const WebpJ
             if (p0 + k < npix) bits += token_bits(tk[k], r[k], s_code);
     }
     uint32_t total;
-    (void)wg_scan(bits, s_w, &total);
+    (void)wg_scan<kWebpllThreads>(bits, s_w, &total);
     if (tid == 0u) jb.tiles[lt].bits = total;
 }
 
@@ -434,7 +399,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_scan_kernel(const WebpJ
     for (uint32_t b0 = 0; b0 < jb.ntiles; b0 += kWebpllThreads) {
         const uint32_t t = b0 + tid;
         uint32_t total;
-        const uint32_t ex = wg_scan(t < jb.ntiles ? jb.tiles[t].bits : 0u, s_w, &total);
+        const uint32_t ex = wg_scan<kWebpllThreads>(t < jb.ntiles ? jb.tiles[t].bits : 0u, s_w, &total);
         if (t < jb.ntiles) jb.tiles[t].off = run + ex;
         run += total;
     }
@@ -451,7 +416,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_place_kernel(const Webp
     __shared__ uint32_t s_buf[kTileWords];
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
-    const WebpJob &jb = jobs[find_job(jobs, njobs, t)];
+    const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     const uint64_t off = jb.tiles[lt].off;
     const uint32_t tbits = jb.tiles[lt].bits;
@@ -473,7 +438,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_place_kernel(const Webp
         }
     }
     uint32_t total;
-    const uint32_t my = wg_scan(bits, s_w, &total);
+    const uint32_t my = wg_scan<kWebpllThreads>(bits, s_w, &total);
     if (act && bits) {
         BitSink o(s_buf, (uint32_t)(off & 31u) + my, true);
 #pragma unroll
@@ -535,8 +500,6 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_frame_kernel(const Webp
 }
 
 } // namespace
-
-#define FL_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return e__; } while (0)
 
 hipError_t launch_webpll_encode(const WebpJob *jobs, uint32_t njobs, uint32_t total_tiles, hipStream_t st)
 {
