@@ -1214,6 +1214,15 @@ int device_huffman_policy(const flgpu_ctx *c, uint64_t file_bytes)
     return dbg.on(DBG_DEVICE_HUFFMAN_ALWAYS) ? 2 : 1;
 }
 
+// The buffer of a JPEG source holds the coefficient blob (sized by the picture's blocks) or, for the device entropy decoder, the staged file:
+// four code tables and the segment itself -- more than the blob of a small picture or of a dense one.  Sized by the blob alone, whether the
+// device decoded such a file depended on how far the allocator happened to round the buffer up (tests/test_jpeg_layouts.py).
+size_t jpeg_source_capacity(const flgpu_ctx *c, const flgpu_image *src, const JpegInfo &info)
+{
+    const size_t blob = jpeg_blob_bound(info);
+    return device_huffman_policy(c, src->capacity) != 0 ? std::max(blob, jpeg_stage_bound((size_t)src->capacity)) : blob;
+}
+
 int jpeg_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, JpegBlobHeader *hdr, size_t *used, bool host_huffman)
 {
     int rc = -2;
@@ -1471,7 +1480,7 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
             if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
             rc = jpeg_source_precheck(c, &srcs[i], info);
             if (rc) return rc;
-            blobs[i].resize(jpeg_blob_bound(info));
+            blobs[i].resize(jpeg_source_capacity(c, &srcs[i], info));
             size_t used = 0;
             rc = jpeg_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &jh[i], &used);
             if (rc) return rc;

@@ -362,6 +362,8 @@ int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st);
 constexpr int FL_STATUS_RETRY_HOST_HUFFMAN = 1000;
 // Host half for one source: parses + Huffman-decodes `src` (a JPEG file) into `blob`; validates the declared size.
 int jpeg_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, JpegBlobHeader *hdr, size_t *used, bool host_huffman = false);
+// capacity of the buffer jpeg_source_to_blob fills: the coefficient blob's bound and, where the device may decode the file, the staging step's
+size_t jpeg_source_capacity(const flgpu_ctx *c, const flgpu_image *src, const JpegInfo &info);
 // set while a request is run again after the device entropy decoder gave up on its file (this thread's JPEG sources are then decoded on the host)
 extern thread_local bool tl_force_host_huffman;
 int device_huffman_policy(const flgpu_ctx *c, uint64_t file_bytes); // fl_batch.cpp

@@ -487,7 +487,7 @@ try {
     c->staging.fetch_add(1, std::memory_order_acq_rel);
     // buffers from flgpu_host_alloc are page-locked already: the DMA engine reads / writes them directly, no staging copy
     const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
-    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_blob_bound(jinfo) : r.src_bytes);
+    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : r.src_bytes);
     if (dst_pinned) r.out = PinBlock{dst->data, 0}; else r.out = pin_acquire(c, r.out_bytes);
     auto give_back = [&] { if (!src_pinned) pin_release(c, r.in); if (!dst_pinned) pin_release(c, r.out); };
     if (!r.in.p || !r.out.p) {

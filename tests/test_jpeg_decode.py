@@ -8,8 +8,10 @@ Three layers, three bars:
     zune-jpeg itself (no Rust here); what is pinned is the distance to the other production decoder on the reference's own
     images/lenna.jpg and on synthetic streams: <= 4 LSB per channel, mean < 1 (two integer IDCTs differ by <= 1, zune's
     5/6-bit colour constants by <= 2-3 from libjpeg's 16-bit ones, its two-step chroma interpolation by <= 1);
-  * device half (-m gpu): bit-identical to the oracle decoder, for every sampling layout, odd sizes and restart intervals,
-    alone and inside the whole request (decode + resize + letterbox + encode in one pass)."""
+  * device half (-m gpu): bit-identical to the oracle decoder, for the sampling layouts Pillow writes (4:4:4, 4:2:2, 4:2:0), odd
+    sizes and restart intervals, alone and inside the whole request (decode + resize + letterbox + encode in one pass).
+The layouts, tables and sizes Pillow's defaults do not reach -- 4:4:0, RGB files, optimised Huffman tables, 16-bit quantiser tables,
+every width 1 .. 64, saturating pictures -- are in test_jpeg_layouts.py, under the same three bars."""
 import io
 import os
 
@@ -230,7 +232,8 @@ def test_exif_orientation_and_unsupported_streams(fl):
 def test_host_decoder_survives_mutated_streams_under_address_sanitizer(tmp_path):
     """The entropy decoder reads bytes fetched from an origin server (src/handler.rs:192-220): tests/tools/fuzz_jpeg_huff.cpp
     is built here with g++ -fsanitize=address,undefined over csrc/fl_jpeghuff.cpp itself (host-only code, no GPU) and fed
-    the reference picture plus five sequential and three progressive layouts, each under 400 truncations / byte flips / stray markers / splices:
+    the reference picture plus five sequential, three progressive and four rewritten layouts (4:4:0, RGB, 16-bit quantiser tables,
+    optimised Huffman tables), each under 400 truncations / byte flips / stray markers / splices:
     every stream must end in a blob or an error code; any out-of-bounds access or signed overflow aborts the harness."""
     import shutil
     import subprocess
@@ -260,6 +263,13 @@ def test_host_decoder_survives_mutated_streams_under_address_sanitizer(tmp_path)
             kw["restart_marker_blocks"] = rst
         (tmp_path / f"prog{i}.jpg").write_bytes(_save(synth.photo(h, w, c, index=20 + i), **kw))
         seeds.append(str(tmp_path / f"prog{i}.jpg"))
+    import jpeg_surgery                                           # layouts and tables Pillow's defaults never show (test_jpeg_layouts.py)
+    surgery = {"s440": jpeg_surgery.to_440(make_jpeg(40, 56, 3, 85, 1, 0, index=30)), "rgb": jpeg_surgery.to_rgb(make_jpeg(37, 53, 3, 85, 2, 0, index=31)),
+               "dqt16": jpeg_surgery.dqt16(make_jpeg(40, 56, 3, 85, 2, 0, index=32)),
+               "optimised": _save(synth.uniform(48, 64, 3, index=33), quality=98, subsampling=2, optimize=True)}
+    for name, data in surgery.items():
+        (tmp_path / f"{name}.jpg").write_bytes(data)
+        seeds.append(str(tmp_path / f"{name}.jpg"))
     r = subprocess.run([exe] + seeds, capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, r.stderr[-3000:]
