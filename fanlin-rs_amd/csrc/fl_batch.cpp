@@ -1240,7 +1240,7 @@ int jpeg_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, siz
     return FLGPU_OK;
 }
 
-int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const JpegSrc *srcs, hipStream_t st)
+int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
 {
     size_t nj = 0, scratch = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -1362,6 +1362,82 @@ int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const JpegSrc
     return FLGPU_OK;
 }
 
+// ---- PNG sources -----------------------------------------------------------------------------------------------------------------
+
+// The container walk has bounded what the file may make the library reserve (png_parse_info: below 2^31 bytes, and no more than
+// 1032 x its IDAT payload); here the file is held against what the caller announced.
+int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info)
+{
+    // (layout only: png_source_to_blob verifies the CRCs, so the file is summed once per request)
+    if (png_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)"); return FLGPU_ERR_PARSE; }
+    if (!info.supported) { c->set_error("PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)"); return FLGPU_ERR_UNSUPPORTED; }
+    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
+        c->set_error("FLGPU_IMG_PNG_SOURCE: width / height / channels do not match the file (see flgpu_png_info_of)");
+        return FLGPU_ERR_INVALID_ARG;
+    }
+    return FLGPU_OK;
+}
+
+int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used)
+{
+    if (cap < sizeof(PngBlobHeader)) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const int rc = png_decode_scanlines(src->data, (size_t)src->capacity, blob + sizeof(PngBlobHeader), cap - sizeof(PngBlobHeader), hdr);
+    if (rc == kPngParse) c->set_error("malformed PNG file (chunk CRC, Huffman code, distance, length, Adler-32 or filter byte)");
+    if (rc == kPngUnsupported) c->set_error("PNG stream holds more scanline data than its IHDR implies");
+    if (rc) return png_status(rc);
+    memcpy(blob, hdr, sizeof(*hdr));
+    *used = hdr->total_bytes;
+    return FLGPU_OK;
+}
+
+int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
+{
+    size_t np = 0, scratch = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const PngBlobHeader *H = srcs[i].png;
+        if (!H) continue;
+        ++np;
+        scratch += align_up((size_t)H->width * H->height * H->channels + 64, 256);
+        if (!H->direct) scratch += align_up((size_t)H->height * H->row_bytes + 64, 256);
+    }
+    if (!np) return FLGPU_OK;
+    FL_HIP(c, c->d_pngdec.reserve(scratch), "PNG decode scratch");
+    FL_HIP(c, c->h_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
+    FL_HIP(c, c->d_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
+    // jobs ordered by bpp (one launch per pixel size), behind them once more the ones the expand kernel takes
+    PngDecJob *jobs = static_cast<PngDecJob *>(c->h_pngjobs.p), *xjobs = jobs + np;
+    uint32_t per_bpp[4] = {0, 0, 0, 0}, nx = 0, max_px = 0;
+    size_t off = 0, k = 0;
+    for (uint32_t bpp = 1; bpp <= 4; ++bpp)
+        for (size_t i = 0; i < n; ++i) {
+            if (!srcs[i].png || srcs[i].png->bpp != bpp) continue;
+            const PngBlobHeader &H = *srcs[i].png;
+            PngDecJob &j = jobs[k++];
+            memset(&j, 0, sizeof(j));
+            j.blob = dsrc[i].data;
+            j.width = H.width; j.height = H.height; j.row_bytes = H.row_bytes; j.bpp = H.bpp;
+            j.pixels = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
+            j.rows = j.pixels;
+            if (!H.direct) {
+                j.rows = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.height * H.row_bytes + 64, 256);
+                xjobs[nx++] = j;
+                max_px = std::max(max_px, H.width * H.height);
+            }
+            per_bpp[bpp - 1]++;
+            if (!tl_force_host_huffman) { c->png_sources++; c->png_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
+            dsrc[i].data = j.pixels;
+            dsrc[i].channels = H.channels;
+            dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
+            dsrc[i].flags &= ~FLGPU_IMG_PNG_SOURCE;
+        }
+    if (k != np) { c->set_error("PNG source: pixel size outside 1..4 bytes"); return FLGPU_ERR_INVALID_ARG; }
+    FL_HIP(c, hipMemcpyAsync(c->d_pngjobs.p, jobs, (np + nx) * sizeof(PngDecJob), hipMemcpyHostToDevice, st), "PNG decode descriptors");
+    const PngDecJob *d_jobs = static_cast<const PngDecJob *>(c->d_pngjobs.p);
+    FL_HIP(c, launch_png_unfilter(d_jobs, per_bpp, st), "PNG unfilter kernel");
+    if (nx) FL_HIP(c, launch_png_expand(d_jobs + np, nx, max_px, st), "PNG expand kernel");
+    return FLGPU_OK;
+}
+
 // Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway
 // asks for them in front of that wait and passes fetched = true below.
 int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st)
@@ -1466,8 +1542,9 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     // JPEG sources: the serial half (parsing + Huffman decoding) runs here, on the host; what is staged is the blob
     std::vector<std::vector<uint8_t>> blobs(n);
     std::vector<JpegBlobHeader> jh(n);
-    std::vector<JpegSrc> jhp(n);
+    std::vector<FileSrc> fsrc(n);
     std::vector<std::vector<uint8_t>> iccs(n);
+    std::vector<PngBlobHeader> ph;
     size_t in_b = 0, out_b = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!srcs[i].data || !dsts[i].data) return FLGPU_ERR_INVALID_ARG;
@@ -1484,11 +1561,24 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
             size_t used = 0;
             rc = jpeg_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &jh[i], &used);
             if (rc) return rc;
-            stage_of(blobs[i].data(), jh[i], jhp[i].stage);
+            stage_of(blobs[i].data(), jh[i], fsrc[i].stage);
             blobs[i].resize(used);
-            jhp[i].hdr = &jh[i];
-            if (jh[i].nc == 4 && c->cfg.use_embedded_profile && !info.icc.empty()) { iccs[i].swap(info.icc); jhp[i].icc = iccs[i].data(); jhp[i].icc_len = iccs[i].size(); }
+            fsrc[i].hdr = &jh[i];
+            if (jh[i].nc == 4 && c->cfg.use_embedded_profile && !info.icc.empty()) { iccs[i].swap(info.icc); fsrc[i].icc = iccs[i].data(); fsrc[i].icc_len = iccs[i].size(); }
             c->stats.jpeg_file_bytes += srcs[i].capacity;
+            sb = used;
+        } else if (srcs[i].flags & FLGPU_IMG_PNG_SOURCE) {
+            // PNG sources: container + inflate here, on the host; what is staged is the header and the filtered scanlines
+            PngInfo info;
+            rc = png_source_info(c, &srcs[i], info);
+            if (rc) return rc;
+            if (ph.empty()) ph.resize(n);
+            blobs[i].resize(png_blob_bytes(info));
+            size_t used = 0;
+            rc = png_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &ph[i], &used);
+            if (rc) return rc;
+            fsrc[i].png = &ph[i];
+            if (!tl_force_host_huffman) c->png_file_bytes += srcs[i].capacity;
             sb = used;
         } else
         if (srcs[i].capacity < sb) return FLGPU_ERR_INVALID_ARG;
@@ -1505,12 +1595,13 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     hipStream_t st = c->stream;
     for (size_t i = 0; i < n; ++i) {
         const size_t off = reinterpret_cast<size_t>(dsrc[i].data);
-        memcpy(static_cast<char *>(c->h_stage_in.p) + off, jhp[i].hdr ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
+        memcpy(static_cast<char *>(c->h_stage_in.p) + off, (fsrc[i].hdr || fsrc[i].png) ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
         dsrc[i].data = static_cast<uint8_t *>(c->d_in.p) + off;
         ddst[i].data = static_cast<uint8_t *>(c->d_out.p) + reinterpret_cast<size_t>(ddst[i].data);
     }
     FL_HIP(c, hipMemcpyAsync(c->d_in.p, c->h_stage_in.p, in_b, hipMemcpyHostToDevice, st), "H2D");
-    { int drc = decode_jpeg_sources(c, n, dsrc.data(), jhp.data(), st); if (drc) return drc; }
+    { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps, false, ddst.data(), st);
     if (rc) return rc;
     FL_HIP(c, hipMemcpyAsync(c->h_stage_out.p, c->d_out.p, out_b, hipMemcpyDeviceToHost, st), "D2H");

@@ -512,6 +512,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_png_filt.release(); c->d_png_chunks.release(); c->d_png_syms.release(); c->d_png_recs.release();
     c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
+    c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
     release_cmyk(c);
     c->h_results.release();
     c->h_stage_in.release(); c->h_stage_out.release();
@@ -623,6 +624,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         (void)hipSetDevice(c->device);
         resolve_pending(c);
         c->stats = flgpu_stats{};
+        c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
     }
     const size_t nl = c->n_lanes.load(std::memory_order_acquire);
     for (size_t i = 0; i < nl; ++i) (void)flgpu_reset_stats(c->lanes[i]);
@@ -646,6 +648,19 @@ int flgpu_debug_set(flgpu_ctx *c, const char *key, int64_t value)
 int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value || !c->dbg) return FLGPU_ERR_INVALID_ARG;
+    // read-only counters of the PNG decode front end (flgpu_stats keeps its size): this context's and its lanes' / shards'
+    static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
+        {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes}};
+    for (const auto &k : counters) {
+        if (strcmp(key, k.name)) continue;
+        uint64_t sum;
+        { std::lock_guard<std::mutex> g(c->mu); sum = c->*k.field; }
+        const size_t nl = c->n_lanes.load(std::memory_order_acquire);
+        for (size_t i = 0; i < nl; ++i) { std::lock_guard<std::mutex> g(c->lanes[i]->mu); sum += c->lanes[i]->*k.field; }
+        for (flgpu_ctx *s : c->shard_ctx) { std::lock_guard<std::mutex> g(s->mu); sum += s->*k.field; }
+        *value = (int64_t)sum;
+        return FLGPU_OK;
+    }
     for (uint32_t k = 0; k < fl::DBG_COUNT; ++k)
         if (!strcmp(key, fl::kDebugKeyNames[k])) { *value = c->dbg->get((fl::DebugKey)k); return FLGPU_OK; }
     return FLGPU_ERR_INVALID_ARG;

@@ -32,6 +32,7 @@
 #include "fl_kernels.h"
 #include "fl_mfma.h"
 #include "fl_png.h"
+#include "fl_pngdec.h"
 #include "fl_tables.h"
 #include "fl_webpll.h"
 #include "fl_wtile.h"
@@ -132,6 +133,8 @@ struct Request {
     JpegHuffStage jstage{}; // jhdr.magic == kJhMagic: `in` holds the staged entropy-coded segment, decoded on the device
     std::vector<uint8_t> icc; // four-component source + use_embedded_profile: the file's own ICC profile
     uint64_t file_bytes = 0;
+    bool png = false;      // FLGPU_IMG_PNG_SOURCE: `in` holds header + filtered scanlines the caller's thread inflated, phdr the header
+    PngBlobHeader phdr;
     int status = 0;
     bool done = false;
     std::condition_variable cv; // the caller waits here (qmu): a lane wakes the callers of ITS batch, not every waiting caller
@@ -213,6 +216,9 @@ struct flgpu_ctx {
     // entropy decoding on the device (fl_jpeghuff_dev.hip): blobs + per-subsequence scratch of a batch, descriptors, per-picture error words
     fl::DeviceBuf d_jh, d_jhjobs, d_jherr;
     fl::PinnedBuf h_jhjobs, h_jherr;
+    fl::DeviceBuf d_pngdec, d_pngjobs;                 // PNG decode (fl_pngdec.hip): unfiltered rows + pixels of a batch, job descriptors
+    fl::PinnedBuf h_pngjobs;
+    uint64_t png_sources = 0, png_file_bytes = 0, png_upload_bytes = 0; // counters behind flgpu_debug_get (guarded by mu)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
@@ -346,13 +352,15 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
 inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS; }
 // JPEG sources of a batch: dsrc[i].data = DEVICE copy of the coefficient blob whose header (host copy) is hdrs[i], or
 // hdrs[i] == nullptr for ordinary pixel sources.  Runs the decode kernels into scratch and points dsrc[i] at the pixels.
-struct JpegSrc {
+// (one entry per image of a batch: a JPEG file's blob header, a PNG file's, or neither for pixel sources)
+struct FileSrc {
     const JpegBlobHeader *hdr = nullptr;
     const uint8_t *icc = nullptr;
     size_t icc_len = 0;
     JpegHuffStage stage{}; // hdr->magic == kJhMagic: the staged segment's description (a host copy: the blob itself is on its way to the device)
+    const PngBlobHeader *png = nullptr; // a PNG source instead: dsrc[i].data = DEVICE copy of header + filtered scanlines
 };
-int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const JpegSrc *srcs, hipStream_t st);
+int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
 // After the batch decode_jpeg_sources fed has completed on `st`: bad[i] = 1 where the device entropy decoder gave up on picture i
 // (its states did not settle, or the stream holds an invalid code word): the caller decodes that file on the host instead.
 // Returns the number of such pictures, or a negative FLGPU_ERR_* .
@@ -376,6 +384,13 @@ inline void stage_of(const uint8_t *staged_blob, const JpegBlobHeader &hdr, Jpeg
 int select_clut(flgpu_ctx *c, const uint8_t *icc, uint64_t icc_len, const void **dev);
 int clut_batch_begin(flgpu_ctx *c);
 int jpeg_source_precheck(flgpu_ctx *c, const flgpu_image *src, const fl::JpegInfo &info);
+// PNG sources of a batch (srcs[i].png set): runs the unfilter / expand kernels into scratch and points dsrc[i] at the pixels.
+int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
+// Host half for one PNG source.  png_source_info: container walk + what the caller announced against the file (FLGPU_ERR_PARSE /
+// _UNSUPPORTED / _INVALID_ARG).  png_source_to_blob: inflates into blob[0 .. png_blob_bytes(info)), header in front.
+int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info);
+int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used);
+inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FLGPU_ERR_PARSE : rc == kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------
 // contiguous split of n weighted items into n_shards shards of about equal weight: shard_of[i] is non-decreasing

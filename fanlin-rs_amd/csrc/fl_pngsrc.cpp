@@ -1,0 +1,478 @@
+// fl_pngsrc.cpp -- host half of the PNG decode front end: container, CRC-32, inflate, Adler-32 (see fl_pngsrc.h).
+// Plain C++: no HIP, no zlib.  Every read is bounds-checked against the file, every write against the size IHDR implies.
+#include "fl_pngsrc.h"
+
+#include <string.h>
+
+namespace fl {
+namespace {
+
+inline uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+constexpr uint32_t fourcc(char a, char b, char c, char d) { return (uint32_t)(uint8_t)a << 24 | (uint32_t)(uint8_t)b << 16 | (uint32_t)(uint8_t)c << 8 | (uint8_t)d; }
+constexpr uint32_t kIHDR = fourcc('I', 'H', 'D', 'R'), kPLTE = fourcc('P', 'L', 'T', 'E'), kTRNS = fourcc('t', 'R', 'N', 'S'),
+                   kIDAT = fourcc('I', 'D', 'A', 'T'), kIEND = fourcc('I', 'E', 'N', 'D');
+const uint8_t kSignature[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+
+// CRC-32 (ISO 3309, as PNG uses it), eight bytes per step
+struct CrcTables {
+    uint32_t t[8][256];
+    CrcTables()
+    {
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+            t[0][i] = c;
+        }
+        for (uint32_t i = 0; i < 256; ++i)
+            for (int s = 1; s < 8; ++s) t[s][i] = t[0][t[s - 1][i] & 255u] ^ (t[s - 1][i] >> 8);
+    }
+};
+
+uint32_t crc32(const uint8_t *p, size_t n)
+{
+    static const CrcTables T;
+    uint32_t c = 0xffffffffu;
+    while (n >= 8) {
+        uint32_t a, b;
+        memcpy(&a, p, 4);
+        memcpy(&b, p + 4, 4);
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_BIG_ENDIAN__
+        a = __builtin_bswap32(a); b = __builtin_bswap32(b);
+#endif
+        a ^= c;
+        c = T.t[7][a & 255u] ^ T.t[6][(a >> 8) & 255u] ^ T.t[5][(a >> 16) & 255u] ^ T.t[4][a >> 24] ^
+            T.t[3][b & 255u] ^ T.t[2][(b >> 8) & 255u] ^ T.t[1][(b >> 16) & 255u] ^ T.t[0][b >> 24];
+        p += 8; n -= 8;
+    }
+    while (n--) c = T.t[0][(c ^ *p++) & 255u] ^ (c >> 8);
+    return c ^ 0xffffffffu;
+}
+
+uint32_t adler32(const uint8_t *p, size_t n)
+{
+    uint32_t a = 1, b = 0;
+    while (n) {
+        size_t k = n < 5552 ? n : 5552; // the longest run for which b cannot overflow 32 bits
+        n -= k;
+        while (k >= 8) {
+            a += p[0]; b += a; a += p[1]; b += a; a += p[2]; b += a; a += p[3]; b += a;
+            a += p[4]; b += a; a += p[5]; b += a; a += p[6]; b += a; a += p[7]; b += a;
+            p += 8; k -= 8;
+        }
+        while (k--) { a += *p++; b += a; }
+        a %= 65521u; b %= 65521u;
+    }
+    return b << 16 | a;
+}
+
+// One chunk at data[pos]: 0 = ok (pos advanced behind its CRC), kPngParse = it does not fit the file.
+struct Chunk { uint32_t type; const uint8_t *p; uint32_t len; };
+int next_chunk(const uint8_t *data, size_t n, size_t &pos, Chunk &c)
+{
+    if (pos > n || n - pos < 12) return kPngParse;
+    const uint32_t len = be32(data + pos);
+    if (len > 0x7fffffffu || (size_t)len > n - pos - 12) return kPngParse;
+    c.type = be32(data + pos + 4);
+    c.p = data + pos + 8;
+    c.len = len;
+    pos += 12 + (size_t)len;
+    return 0;
+}
+bool chunk_crc_ok(const Chunk &c) { return crc32(c.p - 4, (size_t)c.len + 4) == be32(c.p + c.len); }
+
+// What the walk over the chunks collects besides PngInfo.
+struct Container {
+    PngInfo info;
+    const uint8_t *plte = nullptr;
+    const uint8_t *trns = nullptr;
+    uint32_t trns_len = 0;
+    size_t first_idat = 0; // file offset of the first IDAT chunk
+};
+
+// verify = false: lengths and layout only (a caller that sizes its buffers first and lets png_decode_scanlines check the CRCs, once)
+int walk(const uint8_t *data, size_t n, Container &C, bool verify)
+{
+    auto crc_ok = [verify](const Chunk &c) { return !verify || chunk_crc_ok(c); };
+    PngInfo &I = C.info;
+    I = PngInfo();
+    if (!data || n < 8 || memcmp(data, kSignature, 8) != 0) return kPngParse;
+    size_t pos = 8;
+    Chunk c;
+    if (next_chunk(data, n, pos, c) || c.type != kIHDR || c.len != 13 || !crc_ok(c)) return kPngParse;
+    I.width = be32(c.p); I.height = be32(c.p + 4);
+    I.bit_depth = c.p[8]; I.color_type = c.p[9];
+    if (I.width == 0 || I.height == 0 || I.width > 0x7fffffffu || I.height > 0x7fffffffu) return kPngParse;
+    if (c.p[10] != 0 || c.p[11] != 0 || c.p[12] > 1) return kPngParse; // compression, filter method, interlace
+    I.interlaced = c.p[12];
+    uint32_t samples = 0;
+    const uint32_t d = I.bit_depth;
+    switch (I.color_type) {
+    case 0: samples = 1; if (d != 1 && d != 2 && d != 4 && d != 8 && d != 16) return kPngParse; break;
+    case 2: samples = 3; if (d != 8 && d != 16) return kPngParse; break;
+    case 3: samples = 1; if (d != 1 && d != 2 && d != 4 && d != 8) return kPngParse; break;
+    case 4: samples = 2; if (d != 8 && d != 16) return kPngParse; break;
+    case 6: samples = 4; if (d != 8 && d != 16) return kPngParse; break;
+    default: return kPngParse;
+    }
+    bool seen_idat = false, seen_iend = false, idat_ended = false;
+    while (!seen_iend) {
+        const size_t at = pos;
+        if (next_chunk(data, n, pos, c)) return kPngParse; // truncated: no IEND
+        if (seen_idat && c.type != kIDAT) idat_ended = true;
+        switch (c.type) {
+        case kIHDR:
+            return kPngParse;
+        case kPLTE:
+            if (!crc_ok(c) || c.len == 0 || c.len % 3u != 0 || c.len > 768u || seen_idat) return kPngParse;
+            if (!C.plte) { C.plte = c.p; I.plte_entries = c.len / 3u; }
+            break;
+        case kTRNS:
+            if (!crc_ok(c) || seen_idat) return kPngParse;
+            if (I.color_type == 0 && c.len != 2) return kPngParse;
+            if (I.color_type == 2 && c.len != 6) return kPngParse;
+            if (I.color_type == 3 && (c.len > 256u || !C.plte)) return kPngParse; // (tRNS in front of PLTE: the png crate refuses it too)
+            // (grey-alpha and RGBA pictures carry their own alpha: a tRNS there means nothing)
+            if (I.color_type == 0 || I.color_type == 2 || I.color_type == 3) { C.trns = c.p; C.trns_len = c.len; I.has_trns = 1; }
+            break;
+        case kIDAT:
+            if (!crc_ok(c) || idat_ended) return kPngParse; // IDAT chunks are consecutive (the png crate refuses others)
+            if (!seen_idat) C.first_idat = at;
+            seen_idat = true;
+            I.idat_bytes += c.len;
+            break;
+        case kIEND:
+            if (!crc_ok(c)) return kPngParse;
+            seen_iend = true;
+            break;
+        default:
+            // ancillary chunks (gAMA, sRGB, iCCP, eXIf, text, ...) are skipped uninterpreted; an unknown CRITICAL chunk
+            // (upper-case first letter) is something a decoder must not ignore
+            if (!(c.type & 0x20000000u)) return kPngParse;
+            break;
+        }
+    }
+    if (!seen_idat) return kPngParse;
+    if (I.color_type == 3 && !C.plte) return kPngParse;
+    const uint64_t row_bits = (uint64_t)I.width * samples * d;
+    const uint64_t row_bytes = (row_bits + 7u) / 8u;
+    I.bpp = samples * d >= 8u ? samples * d / 8u : 1u;
+    uint32_t channels = 0;
+    switch (I.color_type) {
+    case 0: channels = I.has_trns ? 2u : 1u; break;
+    case 2: channels = I.has_trns ? 4u : 3u; break;
+    case 3: channels = I.has_trns ? 4u : 3u; break;
+    case 4: channels = 2u; break;
+    case 6: channels = 4u; break;
+    }
+    I.supported = d <= 8 && !I.interlaced;
+    const uint64_t scan = (uint64_t)I.height * (1u + row_bytes), decoded = (uint64_t)I.width * I.height * channels;
+    if (scan >= kPngMaxDecoded || decoded >= kPngMaxDecoded) I.supported = 0;
+    I.row_bytes = row_bytes <= 0xffffffffu ? (uint32_t)row_bytes : 0u;
+    I.channels = I.supported ? channels : 0u;
+    // A deflate stream expands by at most 1032 : 1 (a length-258 match costs two bits at best), so a file whose IDAT
+    // payload is shorter than that has too few bytes for the picture its header announces: nothing is reserved on the
+    // say-so of a few hostile bytes.
+    if (I.supported && scan > (I.idat_bytes + 1u) * 1032u) return kPngParse;
+    return 0;
+}
+
+// ---- inflate ---------------------------------------------------------------------------------------------------------------------
+
+// The compressed stream is the concatenation of the IDAT payloads: bytes are pulled from the file chunk by chunk (the
+// walk above has verified lengths and CRCs), so nothing is copied and nothing allocated.
+struct BitReader {
+    const uint8_t *data; size_t n, pos; // pos: file offset of the next chunk header
+    const uint8_t *cur = nullptr, *end = nullptr;
+    uint64_t buf = 0;
+    uint32_t cnt = 0;
+    bool next_segment()
+    {
+        Chunk c;
+        while (pos < n) {
+            if (next_chunk(data, n, pos, c)) return false;
+            if (c.type == kIEND) { pos = n; return false; }
+            if (c.type == kIDAT && c.len) { cur = c.p; end = c.p + c.len; return true; }
+        }
+        return false;
+    }
+    inline void refill()
+    {
+        while (cnt <= 56) {
+            if (cur == end && !next_segment()) return;
+            if (end - cur >= 8) { // the common case in one load; the bits above cnt are those of the bytes that follow, so a later refill ORs the same bits again
+                uint64_t v;
+                memcpy(&v, cur, 8);
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_BIG_ENDIAN__
+                v = __builtin_bswap64(v);
+#endif
+                buf |= v << cnt;
+                const uint32_t k = (63u - cnt) >> 3;
+                cur += k; cnt += 8u * k;
+                return;
+            }
+            buf |= (uint64_t)*cur++ << cnt;
+            cnt += 8;
+        }
+    }
+    // true if `k` (<= 32) bits are available
+    inline bool need(uint32_t k) { if (cnt < k) refill(); return cnt >= k; }
+    inline uint32_t peek(uint32_t k) const { return (uint32_t)(buf & ((1ull << k) - 1u)); }
+    inline void drop(uint32_t k) { buf >>= k; cnt -= k; }
+    inline uint32_t take(uint32_t k) { const uint32_t v = peek(k); drop(k); return v; }
+};
+
+constexpr uint32_t kFastBits = 10;
+struct Huffman {
+    uint16_t fast[1u << kFastBits]; // (symbol << 4) | length, 0 = a longer code (or none)
+    uint16_t count[16];
+    uint16_t symbol[288];
+    uint32_t max_len;
+};
+
+// Canonical code from lengths (RFC 1951 3.2.2).  false: over-subscribed, or incomplete with more than one code.
+bool build(Huffman &h, const uint8_t *len, uint32_t nsym)
+{
+    memset(h.count, 0, sizeof(h.count));
+    for (uint32_t s = 0; s < nsym; ++s) h.count[len[s]]++;
+    memset(h.fast, 0, sizeof(h.fast));
+    h.max_len = 0;
+    if (h.count[0] == nsym) return true; // no codes at all: decoding any symbol fails
+    int left = 1;
+    for (uint32_t l = 1; l < 16; ++l) {
+        left <<= 1;
+        left -= h.count[l];
+        if (left < 0) return false;
+        if (h.count[l]) h.max_len = l;
+    }
+    if (left > 0 && nsym - h.count[0] != 1) return false;
+    uint16_t offs[16];
+    offs[1] = 0;
+    for (uint32_t l = 1; l < 15; ++l) offs[l + 1] = offs[l] + h.count[l];
+    for (uint32_t s = 0; s < nsym; ++s) if (len[s]) h.symbol[offs[len[s]]++] = (uint16_t)s;
+    // fast table: every code of up to kFastBits bits, bit-reversed (codes are packed starting from their top bit)
+    uint32_t code = 0, idx = 0;
+    for (uint32_t l = 1; l <= kFastBits; ++l) {
+        for (uint32_t k = 0; k < h.count[l]; ++k, ++code, ++idx) {
+            uint32_t rev = 0;
+            for (uint32_t b = 0; b < l; ++b) rev |= ((code >> b) & 1u) << (l - 1 - b);
+            const uint16_t e = (uint16_t)(h.symbol[idx] << 4 | l);
+            for (uint32_t v = rev; v < (1u << kFastBits); v += 1u << l) h.fast[v] = e;
+        }
+        code <<= 1;
+    }
+    return true;
+}
+
+// One symbol: >= 0, or -1 (invalid code / out of input).
+inline int decode(BitReader &br, const Huffman &h)
+{
+    if (br.cnt < 15) br.refill();
+    const uint16_t e = h.fast[br.peek(kFastBits)];
+    if (e) {
+        const uint32_t l = e & 15u;
+        if (l > br.cnt) return -1;
+        br.drop(l);
+        return e >> 4;
+    }
+    // longer codes, bit by bit
+    int code = 0, first = 0, index = 0;
+    uint64_t bits = br.buf;
+    for (uint32_t l = 1; l <= h.max_len; ++l) {
+        if (l > br.cnt) return -1;
+        code |= (int)(bits & 1u);
+        bits >>= 1;
+        const int count = h.count[l];
+        if (code - count < first) { br.drop(l); return h.symbol[index + (code - first)]; }
+        index += count;
+        first += count;
+        first <<= 1;
+        code <<= 1;
+    }
+    return -1;
+}
+
+const uint16_t kLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+const uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+const uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+const uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+
+struct FixedTables {
+    Huffman lit, dist;
+    FixedTables()
+    {
+        uint8_t l[288];
+        for (int s = 0; s < 144; ++s) l[s] = 8;
+        for (int s = 144; s < 256; ++s) l[s] = 9;
+        for (int s = 256; s < 280; ++s) l[s] = 7;
+        for (int s = 280; s < 288; ++s) l[s] = 8;
+        build(lit, l, 288);
+        for (int s = 0; s < 32; ++s) l[s] = 5; // (codes 30 and 31 exist in the fixed code and are invalid in a stream)
+        build(dist, l, 32);
+    }
+};
+
+int codes(BitReader &br, const Huffman &lit, const Huffman &dist, uint8_t *out, size_t cap, size_t &pos)
+{
+    for (;;) {
+        int sym = decode(br, lit);
+        if (sym < 0) return kPngParse;
+        if (sym < 256) {
+            if (pos >= cap) return kPngUnsupported; // more scanline data than IHDR implies
+            out[pos++] = (uint8_t)sym;
+            continue;
+        }
+        if (sym == 256) return 0;
+        sym -= 257;
+        if (sym >= 29) return kPngParse;
+        if (!br.need(kLenExtra[sym])) return kPngParse;
+        const uint32_t len = kLenBase[sym] + br.take(kLenExtra[sym]);
+        const int ds = decode(br, dist);
+        if (ds < 0 || ds >= 30) return kPngParse;
+        if (!br.need(kDistExtra[ds])) return kPngParse;
+        const size_t d = (size_t)kDistBase[ds] + br.take(kDistExtra[ds]);
+        if (d > pos) return kPngParse; // before the start of the stream
+        if (len > cap - pos) return kPngUnsupported;
+        const uint8_t *from = out + pos - d;
+        uint8_t *to = out + pos;
+        if (d >= len) memcpy(to, from, len);
+        else for (uint32_t k = 0; k < len; ++k) to[k] = from[k]; // overlapping: the run repeats
+        pos += len;
+    }
+}
+
+int inflate(BitReader &br, uint8_t *out, size_t cap, size_t *produced)
+{
+    static const FixedTables fixed;
+    size_t pos = 0;
+    *produced = 0;
+    // zlib header (RFC 1950): deflate, window <= 32 KB, check bits, no preset dictionary
+    if (!br.need(16)) return kPngParse;
+    const uint32_t cmf = br.take(8), flg = br.take(8);
+    if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) return kPngParse;
+    Huffman lit, dist;
+    for (bool last = false; !last;) {
+        if (!br.need(3)) return kPngParse;
+        last = br.take(1) != 0;
+        const uint32_t type = br.take(2);
+        if (type == 0) {
+            br.drop(br.cnt & 7u);
+            if (!br.need(32)) return kPngParse;
+            const uint32_t len = br.take(16), nlen = br.take(16);
+            if ((len ^ nlen) != 0xffffu) return kPngParse;
+            if (len > cap - pos) return kPngUnsupported;
+            uint32_t left = len;
+            while (left && br.cnt >= 8) { out[pos++] = (uint8_t)br.take(8); --left; } // bytes already in the bit buffer
+            br.buf = br.cnt ? br.buf & ((1ull << br.cnt) - 1u) : 0; // (what refill() read ahead is skipped below)
+            while (left) {
+                if (br.cur == br.end && !br.next_segment()) return kPngParse;
+                const size_t k = (size_t)(br.end - br.cur) < left ? (size_t)(br.end - br.cur) : left;
+                memcpy(out + pos, br.cur, k);
+                br.cur += k; pos += k; left -= (uint32_t)k;
+            }
+        } else if (type == 1) {
+            const int rc = codes(br, fixed.lit, fixed.dist, out, cap, pos);
+            if (rc) return rc;
+        } else if (type == 2) {
+            if (!br.need(14)) return kPngParse;
+            const uint32_t nlen = br.take(5) + 257, ndist = br.take(5) + 1, ncode = br.take(4) + 4;
+            if (nlen > 286 || ndist > 30) return kPngParse;
+            static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+            uint8_t lengths[320];
+            memset(lengths, 0, sizeof(lengths));
+            for (uint32_t k = 0; k < ncode; ++k) {
+                if (!br.need(3)) return kPngParse;
+                lengths[order[k]] = (uint8_t)br.take(3);
+            }
+            if (!build(lit, lengths, 19)) return kPngParse; // (lit doubles as the code-length code)
+            uint32_t idx = 0;
+            while (idx < nlen + ndist) {
+                const int sym = decode(br, lit);
+                if (sym < 0) return kPngParse;
+                if (sym < 16) { lengths[idx++] = (uint8_t)sym; continue; }
+                uint32_t rep, val = 0;
+                if (sym == 16) {
+                    if (idx == 0 || !br.need(2)) return kPngParse;
+                    val = lengths[idx - 1];
+                    rep = 3 + br.take(2);
+                } else if (sym == 17) {
+                    if (!br.need(3)) return kPngParse;
+                    rep = 3 + br.take(3);
+                } else {
+                    if (!br.need(7)) return kPngParse;
+                    rep = 11 + br.take(7);
+                }
+                if (idx + rep > nlen + ndist) return kPngParse;
+                while (rep--) lengths[idx++] = (uint8_t)val;
+            }
+            if (lengths[256] == 0) return kPngParse; // no end-of-block code
+            uint8_t dl[32];
+            memcpy(dl, lengths + nlen, ndist);
+            if (!build(lit, lengths, nlen) || !build(dist, dl, ndist)) return kPngParse;
+            const int rc = codes(br, lit, dist, out, cap, pos);
+            if (rc) return rc;
+        } else {
+            return kPngParse;
+        }
+    }
+    *produced = pos;
+    br.drop(br.cnt & 7u);
+    if (!br.need(32)) return kPngParse; // the check value is missing
+    uint32_t want = 0;
+    for (int k = 0; k < 4; ++k) want = want << 8 | br.take(8);
+    if (want != adler32(out, pos)) return kPngParse;
+    return 0;
+}
+
+} // namespace
+
+int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc)
+{
+    Container C;
+    const int rc = walk(data, n, C, verify_crc);
+    info = C.info;
+    return rc;
+}
+
+int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr)
+{
+    Container C;
+    int rc = walk(data, n, C, true);
+    if (rc) return rc;
+    const PngInfo &I = C.info;
+    if (!I.supported) return kPngUnsupported;
+    const size_t want = png_scan_bytes(I);
+    if (!scan || cap < want) return kPngSmall;
+    BitReader br{data, n, C.first_idat};
+    size_t produced = 0;
+    rc = inflate(br, scan, want, &produced);
+    if (rc) return rc;
+    if (produced != want) return kPngParse; // too few bytes for the picture
+    const size_t stride = 1u + (size_t)I.row_bytes;
+    for (uint32_t y = 0; y < I.height; ++y)
+        if (scan[(size_t)y * stride] > 4u) return kPngParse; // the kernel never sees another filter type
+    if (hdr) {
+        memset(hdr, 0, sizeof(*hdr));
+        hdr->magic = kPngMagic;
+        hdr->width = I.width; hdr->height = I.height;
+        hdr->color_type = I.color_type; hdr->bit_depth = I.bit_depth;
+        hdr->channels = I.channels; hdr->bpp = I.bpp; hdr->row_bytes = I.row_bytes;
+        hdr->has_trns = I.has_trns;
+        hdr->direct = (I.bit_depth == 8 && I.color_type != 3 && !I.has_trns) ? 1u : 0u;
+        hdr->scan_off = (uint32_t)sizeof(PngBlobHeader);
+        hdr->total_bytes = (uint32_t)(sizeof(PngBlobHeader) + want);
+        // the key is compared on the raw sample (its low byte: samples have at most 8 bits here)
+        if (I.has_trns && I.color_type == 0) hdr->key[0] = C.trns[1];
+        if (I.has_trns && I.color_type == 2) { hdr->key[0] = C.trns[1]; hdr->key[1] = C.trns[3]; hdr->key[2] = C.trns[5]; }
+        for (uint32_t k = 0; k < 256; ++k) {
+            uint32_t e = 0xff000000u; // beyond PLTE: opaque black
+            if (I.color_type == 3) {
+                if (k < I.plte_entries) e |= (uint32_t)C.plte[3 * k] | (uint32_t)C.plte[3 * k + 1] << 8 | (uint32_t)C.plte[3 * k + 2] << 16;
+                if (I.has_trns && k < C.trns_len) e = (e & 0x00ffffffu) | (uint32_t)C.trns[k] << 24;
+            }
+            hdr->palette[k] = e;
+        }
+    }
+    return 0;
+}
+
+} // namespace fl

@@ -14,6 +14,7 @@
 #include "../../include/fanlin_gpu.h"
 #include "fl_abi.h"
 #include "fl_png.h"
+#include "fl_pngsrc.h"
 #include "fl_webpll.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
@@ -373,6 +374,100 @@ try {
     return flgpu_transform(ctx, &src, &p, dst);
 } FL_ABI_CATCH
 
+/* ---- PNG sources ---------------------------------------------------------------------------------------------------- */
+
+int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info)
+try {
+    if (!png || !info) return FLGPU_ERR_INVALID_ARG;
+    fl::PngInfo I;
+    if (fl::png_parse_info(png, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    memset(info, 0, sizeof(*info));
+    info->width = I.width; info->height = I.height; info->color_type = I.color_type; info->bit_depth = I.bit_depth;
+    info->channels = I.channels; info->interlaced = I.interlaced; info->has_trns = I.has_trns; info->supported = I.supported;
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
+static int plan_png(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
+                    flgpu_plan *plan, int *kind, int *out_format)
+{
+    // (layout only here: flgpu_transform verifies the CRCs once, under the decode bound; as_is serves the file unread, as the reference does)
+    if (!png) return FLGPU_ERR_INVALID_ARG;
+    fl::PngInfo info;
+    if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    int rc;
+    memset(src, 0, sizeof(*src));
+    src->data = const_cast<uint8_t *>(png);
+    src->capacity = n;
+    /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
+    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
+    src->flags = FLGPU_IMG_PNG_SOURCE;
+    if (!info.supported) {
+        /* geometry the planner cannot take (2^31 bytes and more) must not hide the query's own verdict: parse it first */
+        flgpu_query q;
+        rc = flgpu_query_parse(query_string ? query_string : "", &q);
+        if (rc) return rc;
+        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
+        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
+        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
+        memset(plan, 0, sizeof(*plan));
+        *kind = FLGPU_RESULT_AS_IS;
+        if (out_format) *out_format = FLGPU_OUT_KEEP;
+        return FLGPU_OK;
+    }
+    /* the PNG decoder reports no orientation (handler.rs:206 sees none): 1 */
+    return plan_request(src, 1, query_string, accept_flags, FLGPU_IN_PNG, p, plan, kind, out_format);
+}
+
+int flgpu_process_png_plan(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, int *result_kind)
+try {
+    flgpu_image src;
+    flgpu_params p;
+    return plan_png(png, n, query_string, accept_flags, &src, &p, plan, result_kind, nullptr);
+} FL_ABI_CATCH
+
+int flgpu_process_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags,
+                      flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format)
+try {
+    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
+    flgpu_image src;
+    flgpu_params p;
+    flgpu_plan local;
+    int kind = 0;
+    int rc = plan_png(png, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
+    if (result_kind) *result_kind = kind;
+    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
+    return flgpu_transform(ctx, &src, &p, dst);
+} FL_ABI_CATCH
+
+int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst)
+try {
+    if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
+    if (!png) return FLGPU_ERR_INVALID_ARG;
+    fl::PngInfo info;
+    if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE; // (CRCs: once, in flgpu_transform)
+    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
+    flgpu_image src;
+    memset(&src, 0, sizeof(src));
+    src.data = const_cast<uint8_t *>(png); src.capacity = n;
+    src.width = info.width; src.height = info.height; src.channels = info.channels; src.flags = FLGPU_IMG_PNG_SOURCE;
+    flgpu_params p;
+    memset(&p, 0, sizeof(p)); /* the pipeline is the identity, the result the decoded picture */
+    return flgpu_transform(ctx, &src, &p, dst);
+} FL_ABI_CATCH
+
+int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!png || !used) return FLGPU_ERR_INVALID_ARG;
+    fl::PngInfo I;
+    if (fl::png_parse_info(png, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
+    *used = fl::png_scan_bytes(I);
+    if (!out) return FLGPU_OK;
+    if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const int rc = fl::png_decode_scanlines(png, (size_t)n, out, (size_t)capacity, nullptr);
+    return rc == 0 ? FLGPU_OK : rc == fl::kPngParse ? FLGPU_ERR_PARSE : rc == fl::kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL;
+} FL_ABI_CATCH
+
 int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t sc, flgpu_plan *plan)
 {
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
@@ -528,7 +623,7 @@ const char *flgpu_strerror(int status)
     case FLGPU_ERR_NO_DEVICE: return "no usable HIP device (there is no CPU fallback)";
     case FLGPU_ERR_OOM: return "out of memory";
     case FLGPU_ERR_DEVICE: return "HIP runtime error";
-    case FLGPU_ERR_PARSE: return "malformed query string";
+    case FLGPU_ERR_PARSE: return "malformed query string or damaged PNG source";
     case FLGPU_ERR_BUFFER_TOO_SMALL: return "destination buffer too small";
     case FLGPU_ERR_SHUTDOWN: return "context is shutting down";
     }

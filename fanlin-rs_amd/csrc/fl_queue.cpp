@@ -123,7 +123,7 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
     std::vector<flgpu_image> dsrc(n), ddst(n);
     std::vector<flgpu_params> ps(n);
     std::vector<uint64_t> dev_out(n);
-    std::vector<JpegSrc> jhp(n);
+    std::vector<FileSrc> fsrc(n);
     size_t in_b = 0, out_b = 0;
     for (size_t i = 0; i < n; ++i) {
         dsrc[i] = *batch[i]->src; ddst[i] = *batch[i]->dst; ps[i] = *batch[i]->p;
@@ -141,11 +141,13 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
         ddst[i].data = static_cast<uint8_t *>(c->d_out.p) + reinterpret_cast<size_t>(ddst[i].data);
         FL_HIP(c, hipMemcpyAsync(dsrc[i].data, batch[i]->in.p, batch[i]->src_bytes, hipMemcpyHostToDevice, st), "H2D");
         if (batch[i]->jpeg) {
-            jhp[i].hdr = &batch[i]->jhdr; jhp[i].stage = batch[i]->jstage; jhp[i].icc = batch[i]->icc.empty() ? nullptr : batch[i]->icc.data(); jhp[i].icc_len = batch[i]->icc.size();
+            fsrc[i].hdr = &batch[i]->jhdr; fsrc[i].stage = batch[i]->jstage; fsrc[i].icc = batch[i]->icc.empty() ? nullptr : batch[i]->icc.data(); fsrc[i].icc_len = batch[i]->icc.size();
             c->stats.jpeg_file_bytes += batch[i]->file_bytes;
         }
+        if (batch[i]->png) { fsrc[i].png = &batch[i]->phdr; c->png_file_bytes += batch[i]->file_bytes; }
     }
-    { int drc = decode_jpeg_sources(c, n, dsrc.data(), jhp.data(), st); if (drc) return drc; }
+    { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps.data(), false, ddst.data(), st);
     if (rc) return rc;
     // Encoded streams: their lengths are known only on the device (a 300x200 JPEG is ~16 KB of a 183 KB bound).  The first kSpecBytes of every stream
@@ -463,7 +465,14 @@ try {
         if (!jinfo.supported) { c->set_error("JPEG stream not covered by the device decoder"); return FLGPU_ERR_UNSUPPORTED; }
         const int prc = jpeg_source_precheck(c, src, jinfo); // before any block is reserved on the file's say-so
         if (prc) return prc;
-    } else if (src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
+    }
+    const bool psrc = !jsrc && (src->flags & FLGPU_IMG_PNG_SOURCE) != 0;
+    PngInfo pinfo;
+    if (psrc) {
+        const int prc = png_source_info(c, src, pinfo); // before any block is reserved on the file's say-so
+        if (prc) return prc;
+    }
+    if (!jsrc && !psrc && src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
     const bool enc = fe_encoded(p->front_end);
     if (!enc && dst->capacity < plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
     Request r{};
@@ -486,8 +495,8 @@ try {
     } admission{c};
     c->staging.fetch_add(1, std::memory_order_acq_rel);
     // buffers from flgpu_host_alloc are page-locked already: the DMA engine reads / writes them directly, no staging copy
-    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
-    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : r.src_bytes);
+    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc && !psrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
+    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : psrc ? png_blob_bytes(pinfo) : r.src_bytes);
     if (dst_pinned) r.out = PinBlock{dst->data, 0}; else r.out = pin_acquire(c, r.out_bytes);
     auto give_back = [&] { if (!src_pinned) pin_release(c, r.in); if (!dst_pinned) pin_release(c, r.out); };
     if (!r.in.p || !r.out.p) {
@@ -529,6 +538,25 @@ try {
         if (jrc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return jrc; }
         r.jpeg = true;
         if (r.jhdr.nc == 4 && c->cfg.use_embedded_profile) r.icc.swap(jinfo.icc);
+        r.file_bytes = src->capacity;
+        r.src_bytes = used;
+    } else if (psrc) {
+        // the serial half of the PNG decoder (chunk CRCs, inflate, Adler-32) on the caller's thread, straight into pinned memory, under the
+        // same bound as the host Huffman decoders: no more of them at once than the process has CPUs
+        size_t used = 0;
+        int prc;
+        {
+            {
+                std::unique_lock<std::mutex> lk(c->dec_mu);
+                if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
+                (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
+                c->decoding++;
+            }
+            struct Turn { flgpu_ctx *c; ~Turn() { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } } turn{c};
+            prc = png_source_to_blob(c, src, static_cast<uint8_t *>(r.in.p), r.in.cap, &r.phdr, &used);
+        }
+        if (prc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return prc; }
+        r.png = true;
         r.file_bytes = src->capacity;
         r.src_bytes = used;
     } else

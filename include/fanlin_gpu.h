@@ -38,6 +38,7 @@
  *                                       src/main.rs:74-76, src/handler.rs:469-488
  *   flgpu_cmyk_to_rgb[_device]          CMYK2RGB::convert = lcms2 transform_pixels, src/handler.rs:446-462,490-492
  *   FLGPU_IMG_JPEG_SOURCE / flgpu_process_jpeg   JpegDecoder::new + DynamicImage::from_decoder, src/handler.rs:205-220
+ *   FLGPU_IMG_PNG_SOURCE / flgpu_process_png     PngDecoder + DynamicImage::from_decoder, src/handler.rs:218-220
  *   flgpu_create / flgpu_destroy        lifetime of handler::State, src/handler.rs:14-21,36-52
  *   flgpu_config.devices / flgpu_plan_shards   the one shared Arc<State> behind all tokio workers, src/main.rs:108-112
  */
@@ -60,7 +61,7 @@ typedef enum flgpu_status {
     FLGPU_ERR_NO_DEVICE = 3,     /* no usable HIP device: the library never falls back to the CPU */
     FLGPU_ERR_OOM = 4,           /* host or device allocation failed */
     FLGPU_ERR_DEVICE = 5,        /* a HIP call failed; see flgpu_last_error() */
-    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400) */
+    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400); a PNG source that is damaged */
     FLGPU_ERR_BUFFER_TOO_SMALL = 7,
     FLGPU_ERR_SHUTDOWN = 8       /* context is being destroyed */
 } flgpu_status;
@@ -85,6 +86,13 @@ typedef struct flgpu_image {
                                          chroma up-sampling and YCbCr -> RGB on the device -- replacing JpegDecoder::new +
                                          DynamicImage::from_decoder (src/handler.rs:205-220).  ~1 MB crosses PCIe instead of 6.2 MB
                                          for a 1080p picture.  Streams it does not cover: FLGPU_ERR_UNSUPPORTED (decode on the host). */
+#define FLGPU_IMG_PNG_SOURCE      32u /* in (src of flgpu_transform / flgpu_transform_batch): data holds a PNG FILE of `capacity` bytes instead of
+                                         pixels, width / height / channels say what it decodes to (flgpu_png_info_of): the library decodes it itself --
+                                         chunk CRCs and inflate on the calling thread, the row filters and the expansion of palette / sub-byte /
+                                         tRNS pictures on the device -- replacing DynamicImage::from_decoder for PNG inputs (src/handler.rs:218-220).
+                                         The filtered scanlines cross PCIe: the pixel bytes + height for 8-bit RGB, 3-24 x less for palette and
+                                         sub-byte pictures.  Files it does not cover (16-bit samples, Adam7): FLGPU_ERR_UNSUPPORTED (decode on the
+                                         host); damaged files: FLGPU_ERR_PARSE. */
 #define FLGPU_IMG_HAS_ALPHA       2u  /* WEBP420: some pixel is not opaque: the picture is WEBP_YUV420A for libwebp, i.e. the A
                                          plane behind V must be handed to WebPEncode too (for opaque pictures it is all 255) */
 
@@ -360,6 +368,32 @@ int flgpu_process_jpeg(flgpu_ctx *ctx, const uint8_t *jpeg, uint64_t n, const ch
 int flgpu_process_jpeg_plan(const uint8_t *jpeg, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
                             int *result_kind);
 
+/* ---- PNG sources (src/handler.rs:218-220: the png crate through the image crate, Transformations::EXPAND) --------------- */
+typedef struct flgpu_png_info {
+    uint32_t width, height;
+    uint32_t color_type;        /* as stored: 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA */
+    uint32_t bit_depth;         /* as stored: 1, 2, 4, 8 or 16 */
+    uint32_t channels;          /* of the picture the pipeline sees (0 if unsupported): colour type 0 -> 1 (Luma8, samples scaled x255 / x85 /
+                                   x17), 0 + tRNS -> 2 (LumaA8), 2 -> 3, 2 + tRNS -> 4, 3 -> 3, 3 + tRNS -> 4, 4 -> 2, 6 -> 4 */
+    uint32_t interlaced;        /* Adam7 */
+    uint32_t has_trns;
+    uint32_t supported;         /* 1 = FLGPU_IMG_PNG_SOURCE decodes it; 0: 16-bit samples, Adam7 interlace, 2^31 bytes or more */
+} flgpu_png_info;
+/* Header and chunk inspection only (no device needed): signature, IHDR, PLTE, tRNS, IDAT..., IEND with their CRCs; other ancillary
+ * chunks are skipped.  FLGPU_ERR_PARSE if the bytes are not an intact PNG container.  PNG has no orientation (the image crate
+ * reports none): the pipeline runs with orientation 1. */
+int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info);
+/* Decodes a supported PNG to interleaved pixels in HOST memory at dst->data (capacity >= width*height*channels). */
+int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst);
+/* State::process_image for a PNG input from the file bytes on, input_format FLGPU_IN_PNG: query parsing, size gate, as_is, container
+ * negotiation, then inflate + unfilter + pixel pipeline (+ PNG encode with FLGPU_ENCODE_PNG) in one pass.  Same outcomes as
+ * flgpu_process_image; additionally FLGPU_ERR_UNSUPPORTED for files the decoder does not cover (the host then decodes with its own
+ * decoder and calls flgpu_process_image) and FLGPU_ERR_PARSE for damaged ones. */
+int flgpu_process_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags,
+                      flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format);
+int flgpu_process_png_plan(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
+                           int *result_kind);
+
 /* Page-locked host memory for sources / results of flgpu_transform (flag them FLGPU_IMG_PINNED): a decoder that
  * writes straight into such a buffer (zune-jpeg's decode_into) saves the 6 MB staging copy of a 1080p request. */
 void *flgpu_host_alloc(flgpu_ctx *ctx, uint64_t bytes);
@@ -425,6 +459,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "no_luma_mid" (a grey picture on a grey frame is blurred as Rgba8, not as one channel), "wtile_first", "mfma_arith" (0 full width,
  * 1 packed), "force_bands", "no_tile", "no_place4", "host_huffman", "device_huffman_always", "device_huffman_min_bytes",
  * "mfma_spin_limit", "debug_mfma", "debug_jh"; "reset" restores every default.
+ * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
+ * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
+ * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines).
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
  * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);
@@ -447,6 +484,11 @@ int flgpu_debug_axis_table(uint32_t in_size, uint32_t out_size, int filter, floa
  * FLGPU_IMG_JPEG_SOURCE (csrc/fl_jpegdec.h: header, one u32 word per block = first coefficient << 7 | count, i16
  * coefficients in zig-zag order up to the last non-zero one).  blob == NULL: *used = capacity to provide. */
 int flgpu_debug_jpeg_blob(const uint8_t *jpeg, uint64_t n, uint8_t *blob, uint64_t capacity, uint64_t *used);
+
+/* The host half of the PNG decode front end alone (csrc/fl_pngsrc.h): the filtered scanlines flgpu_transform uploads for a
+ * FLGPU_IMG_PNG_SOURCE, height x (1 + row bytes) -- the inflated IDAT stream, Adler-32 and filter bytes checked.
+ * out == NULL: *used = capacity to provide. */
+int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
 
 int flgpu_debug_stream_schedulable(uint32_t in_size, uint32_t out_size, uint32_t y0, uint32_t y1, uint32_t *max_live);
 /* Builds the matrix-pipe kernel's tables (csrc/fl_mfma.h) for a source of sw x sh pixels with `channels` interleaved bytes,

@@ -153,6 +153,28 @@ public:
         return out;
     }
 
+    // PngDecoder::new's view of a file (src/handler.rs:218-220): false if the bytes are no intact PNG container
+    static bool png_info(const std::vector<uint8_t> &file, flgpu_png_info &info) { return flgpu_png_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
+
+    // State::process_image for a PNG input from the file bytes on: inflate on this thread, row filters, expansion, pixel pipeline and
+    // (with FLGPU_ENCODE_PNG in the content flags) the PNG encoder on the device.  Throws on files the decoder does not cover
+    // (FLGPU_ERR_UNSUPPORTED: 16-bit samples, Adam7) and on damaged ones (FLGPU_ERR_PARSE): the host then uses its own decoder.
+    Processed process_png(const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
+    {
+        Processed out{};
+        int kind = 0, fmt = 0;
+        check(flgpu_process_png_plan(file.data(), file.size(), params.text().c_str(), content.flags(), &out.plan, &kind));
+        out.kind = static_cast<flgpu_result_kind>(kind);
+        if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
+        out.data.resize(out.plan.max_out_bytes);
+        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
+        check(flgpu_process_png(ctx_, file.data(), file.size(), params.text().c_str(), content.flags(), &dst, &out.plan, &kind, &fmt), ctx_);
+        out.negotiated = static_cast<flgpu_out_format>(fmt);
+        out.flags = dst.flags;
+        out.data.resize(dst.bytes);
+        return out;
+    }
+
     flgpu_ctx *raw() { return ctx_; }
 
 private:

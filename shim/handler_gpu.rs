@@ -26,6 +26,12 @@ pub struct FlConfig { device: i32, max_batch: u32, flush_timeout_us: u32, profil
 pub struct FlJpegInfo { width: u32, height: u32, components: u32, channels: u32, progressive: u32, restart_interval: u32,
                         h_max: u32, v_max: u32, exif_orientation: u32, supported: u32, adobe_transform: u32, has_icc_profile: u32 }
 
+#[repr(C)] #[derive(Default, Clone, Copy)]
+/// flgpu_png_info: what `PngDecoder::new` learns from IHDR / PLTE / tRNS (src/handler.rs:218-220), for the decision "file bytes to
+/// the device, or the reference's own decoder".  `channels`: 1 Luma8, 2 LumaA8, 3 Rgb8, 4 Rgba8 -- the DynamicImage
+/// Transformations::EXPAND gives; `supported` = 0 for 16-bit samples and Adam7 (tests/test_png_source_host.py checks this mirror).
+pub struct FlPngInfo { width: u32, height: u32, color_type: u32, bit_depth: u32, channels: u32, interlaced: u32, has_trns: u32, supported: u32 }
+
 pub const FE_NONE: u8 = 0;
 pub const FE_JFIF444: u8 = 1;
 pub const FE_WEBP420: u8 = 2;
@@ -35,6 +41,8 @@ pub const FE_WEBP_LOSSLESS: u8 = 6; // (5 is not a front end)
 pub const FILTER_NEAREST: u8 = 1;
 const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
+#[allow(dead_code)]
+const IMG_PNG_SOURCE: u32 = 32;  // ... `data` holds the PNG FILE (flgpu_process_png sets it itself)
 pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
 // not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
@@ -48,6 +56,7 @@ pub const RESULT_PIXELS: c_int = 3;
 pub const RESULT_PNG_STREAM: c_int = 4;
 pub const RESULT_WEBP_STREAM: c_int = 5;
 const ERR_UNSUPPORTED: c_int = 2; // FLGPU_ERR_UNSUPPORTED: a stream the device decoder does not cover
+const ERR_PARSE: c_int = 6;       // FLGPU_ERR_PARSE: a rejected query, or a damaged PNG source
 const CMYK_INPUT_YCCK: u32 = 1;
 
 extern "C" {
@@ -62,6 +71,10 @@ extern "C" {
     fn flgpu_process_jpeg_plan(jpeg: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
     fn flgpu_process_jpeg(ctx: *mut c_void, jpeg: *const u8, n: u64, query: *const c_char, accept: u32,
                           dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
+    fn flgpu_png_info_of(png: *const u8, n: u64, info: *mut FlPngInfo) -> c_int;
+    fn flgpu_process_png_plan(png: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
+    fn flgpu_process_png(ctx: *mut c_void, png: *const u8, n: u64, query: *const c_char, accept: u32,
+                         dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
     fn flgpu_transform_batch(ctx: *mut c_void, n: usize, srcs: *const FlImage, ps: *const FlParams, dsts: *mut FlImage) -> c_int;
     fn flgpu_strerror(status: c_int) -> *const c_char;
     fn flgpu_abi_version() -> u32;
@@ -184,6 +197,34 @@ impl Gpu {
         Ok(Some((kind, fmt, plan, out)))
     }
 
+    /// Header of a PNG file, or None if the bytes are no intact PNG container (then `with_guessed_format` decides as before).
+    pub fn png_info(original: &[u8]) -> Option<FlPngInfo> {
+        let mut info = FlPngInfo::default();
+        if unsafe { flgpu_png_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
+    }
+
+    /// `process_image` for a PNG input FROM THE FILE BYTES ON (src/handler.rs:198-308 in one call, input format PNG, orientation 1):
+    /// chunk CRCs + inflate on this thread, row filters + palette / tRNS expansion + pixel pipeline (+ the PNG encoder with ENCODE_PNG
+    /// in `accept`) in one device pass.  Ok(None): a file the decoder does not cover (16-bit samples, Adam7) or cannot read --
+    /// decode with the reference's own decoder, which also words the error, and use `transform`.  Otherwise as `process_jpeg`:
+    /// RESULT_AS_IS, RESULT_PNG_STREAM (the finished image/png body), RESULT_WEBP_PLANES, RESULT_WEBP_STREAM or RESULT_PIXELS.
+    pub fn process_png(&self, original: &[u8], query: &str, accept: u32)
+        -> Result<Option<(c_int, c_int, FlPlan, Vec<u8>)>, Box<dyn std::error::Error>>
+    {
+        let q = std::ffi::CString::new(query)?;
+        let (mut plan, mut kind, mut fmt) = (FlPlan::default(), 0 as c_int, 0 as c_int);
+        if Self::png_info(original).map_or(true, |i| i.supported == 0) { return Ok(None); }
+        check(unsafe { flgpu_process_png_plan(original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut plan, &mut kind) })?;
+        if kind == RESULT_AS_IS { return Ok(Some((kind, 0, plan, Vec::new()))); }
+        let mut out = vec![0u8; plan.max_out_bytes as usize];
+        let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
+        let rc = unsafe { flgpu_process_png(self.0, original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut dst, &mut plan, &mut kind, &mut fmt) };
+        if rc == ERR_UNSUPPORTED || rc == ERR_PARSE { return Ok(None); } // a damaged stream: the crate's decoder reports it in its own words
+        check(rc)?;
+        out.truncate(dst.bytes as usize);
+        Ok(Some((kind, fmt, plan, out)))
+    }
+
     /// The same decode + pipeline with parameters already taken from a `Query` (no query string at hand): the SOURCE of `transform`
     /// is the file -- `FlImage.flags = IMG_JPEG_SOURCE`, `width / height / channels` from `jpeg_info`.  The EXIF orientation is
     /// read from the file by the library when `orientation` is 0.
@@ -262,6 +303,17 @@ fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(
 //                     _ => { let img = gpu::Gpu::into_dynamic(&plan, bytes); /* PNG / AVIF / lossless WebP arm for `out_format` */ }
 //                 }
 //             }                                                                       // None: fall through to the decoder below
+//         }
+//     }
+//
+// PNG inputs the same way (src/handler.rs:218-220 + everything below them; `accept | gpu::ENCODE_PNG` to get finished image/png bodies):
+//     if gpu::Gpu::png_info(original).map_or(false, |i| i.supported != 0) {
+//         if let Some((kind, out_format, plan, bytes)) = self.gpu.process_png(original, raw_query, accept | gpu::ENCODE_PNG)? {
+//             match kind {
+//                 gpu::RESULT_AS_IS => return Ok((ImageFormat::Png.to_mime_type(), original.to_vec())),
+//                 gpu::RESULT_PNG_STREAM => return Ok((ImageFormat::Png.to_mime_type(), bytes)),                // lines 264-273
+//                 _ => { /* WebP planes / pixels for the negotiated container: as for JPEG inputs above */ }
+//             }
 //         }
 //     }
 //
