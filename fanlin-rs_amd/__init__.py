@@ -38,7 +38,7 @@ RESULT_AS_IS, RESULT_JPEG_STREAM, RESULT_WEBP_PLANES, RESULT_PIXELS, RESULT_PNG_
 _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG,
               RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
-IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE = 1, 2, 4, 8, 16, 32
+IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE, IMG_WEBP_SOURCE = 1, 2, 4, 8, 16, 32, 64
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 BATCH_SAME_PARAMS = 1
 (OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_OOM, ERR_DEVICE, ERR_PARSE, ERR_BUFFER_TOO_SMALL,
@@ -109,6 +109,11 @@ class flgpu_png_info(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "color_type", "bit_depth", "channels", "interlaced", "has_trns", "supported")]
 
 
+class flgpu_webp_info(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "channels", "has_alpha", "extended", "animated", "lossless", "exif_orientation",
+                                           "transforms", "color_cache_bits", "prefix_groups", "supported")]
+
+
 # every symbol include/fanlin_gpu.h declares
 EXPORTED_SYMBOLS = (
     "flgpu_query_parse", "flgpu_query_dimensions", "flgpu_query_fill_color", "flgpu_query_quality",
@@ -117,7 +122,8 @@ EXPORTED_SYMBOLS = (
     "flgpu_params_from_query", "flgpu_plan_output", "flgpu_process_image", "flgpu_process_image_plan", "flgpu_create", "flgpu_destroy", "flgpu_transform",
     "flgpu_transform_batch", "flgpu_transform_batch_device", "flgpu_batch_results", "flgpu_plan_shards", "flgpu_devices",
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
-    "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
+    "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
+    "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
     "flgpu_import_tables", "flgpu_get_stats",
@@ -190,6 +196,13 @@ def load_library() -> C.CDLL:
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.flgpu_process_png_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_int)]
         lib.flgpu_debug_png_scanlines.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_webp_info_of"):  # (the same for lossless WebP sources)
+        lib.flgpu_webp_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_webp_info)]
+        lib.flgpu_decode_webp.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image)]
+        lib.flgpu_process_webp.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_image), C.POINTER(flgpu_plan),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.flgpu_process_webp_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_int)]
+        lib.flgpu_debug_webp_residuals.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.flgpu_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]
     lib.flgpu_devices.restype = C.c_uint32
     lib.flgpu_cmyk_distribution.argtypes = [C.c_void_p]
@@ -408,10 +421,30 @@ def debug_png_scanlines(data: bytes) -> bytes:
     return out[: used.value].tobytes()
 
 
+def webp_info(data: bytes) -> dict:
+    """flgpu_webp_info_of: container, VP8L header, transforms and code groups of a WebP file (pure host function); raises
+    FanlinError(ERR_PARSE) if the container or the headers are damaged."""
+    info = flgpu_webp_info()
+    _check(load_library().flgpu_webp_info_of(data, len(data), C.byref(info)))
+    return {n: getattr(info, n) for n, _ in flgpu_webp_info._fields_}
+
+
+def debug_webp_residuals(data: bytes) -> bytes:
+    """Host half of the lossless WebP decode front end alone: the blob that is uploaded (header, sub-images, residual picture)."""
+    lib = load_library()
+    used = C.c_uint64()
+    _check(lib.flgpu_debug_webp_residuals(data, len(data), None, 0, C.byref(used)))
+    out = np.zeros(max(used.value, 1), np.uint8)
+    _check(lib.flgpu_debug_webp_residuals(data, len(data), out.ctypes.data, used.value, C.byref(used)))
+    return out[: used.value].tobytes()
+
+
 def _source_info(data):
-    """(header dict, source flag) of a file handed over as a source: PNG by its signature, else JPEG."""
+    """(header dict, source flag) of a file handed over as a source: PNG and WebP by their signatures, else JPEG."""
     if bytes(data[:8]) == PNG_SIGNATURE:
         return png_info(bytes(data)), IMG_PNG_SOURCE
+    if bytes(data[:4]) == b"RIFF" and bytes(data[8:12]) == b"WEBP":
+        return webp_info(bytes(data)), IMG_WEBP_SOURCE
     return jpeg_info(bytes(data)), IMG_JPEG_SOURCE
 
 
@@ -694,12 +727,55 @@ class State:
         fe = _RESULT_FE[kind.value]
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
 
+    # -- lossless WebP sources: the decode front end (handler.rs:205-220) ------------------------------------------
+    def decode_webp(self, data: bytes) -> np.ndarray:
+        """DynamicImage::from_decoder(WebPDecoder::new(..)) on the device: (h, w, 3 or 4) uint8; the EXIF orientation is not applied."""
+        info = webp_info(data)
+        out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_decode_webp(self._ctx, data, len(data), C.byref(dst)), self._ctx)
+        return out
+
+    def process_webp_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None):
+        """process_pixels with a lossless WebP FILE as the source (FLGPU_IMG_WEBP_SOURCE): entropy decode on this thread, the rest in
+        one device pass.  ``shape`` = (height, width, channels) to announce instead of what flgpu_webp_info_of says."""
+        if shape is None:
+            info = webp_info(data)
+            shape = (info["height"], info["width"], max(info["channels"], 1))
+        plan = plan_output(params, shape[1], shape[0], shape[2])
+        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
+        buf = C.create_string_buffer(data, len(data))
+        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_WEBP_SOURCE)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
+        return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
+
+    def process_webp(self, data: bytes, query_string: str, content: "Format" = None):
+        """State::process_image for a WebP input from the file bytes on: (mime, kind, payload) as process_image; AS_IS hands the
+        file itself back."""
+        plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
+        flags = content.flags if content else 0
+        qs = query_string.encode()
+        _check(self._lib.flgpu_process_webp_plan(data, len(data), qs, flags, C.byref(plan), C.byref(kind)))
+        if kind.value == RESULT_AS_IS:
+            return "image/webp", RESULT_AS_IS, data
+        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_process_webp(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
+        mime = "image/avif" if fmt.value == OUT_AVIF else "image/webp"
+        fe = _RESULT_FE[kind.value]
+        return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+
+    def webp_counters(self) -> dict:
+        """The lossless WebP decode front end's counters (flgpu_debug_get)."""
+        return {k: self.debug_get(k) for k in ("webp_sources", "webp_file_bytes", "webp_upload_bytes")}
+
     def png_counters(self) -> dict:
         """The PNG decode front end's counters (flgpu_debug_get): pictures decoded, their file bytes, what crossed PCIe for them."""
         return {k: self.debug_get(k) for k in ("png_sources", "png_file_bytes", "png_upload_bytes")}
 
     def process_batch(self, images: Sequence, params: Sequence[flgpu_params]) -> List:
-        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG or a PNG file (decoded by the library)."""
+        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file (decoded by the library)."""
         n = len(images)
         srcinfo = [_source_info(a) if isinstance(a, (bytes, bytearray)) else (None, 0) for a in images]
         infos = [s[0] for s in srcinfo]

@@ -1438,6 +1438,106 @@ int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc 
     return FLGPU_OK;
 }
 
+// ---- lossless WebP sources ---------------------------------------------------------------------------------------------------------
+
+int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info)
+{
+    // (container and VP8L header only: webp_source_to_blob reads the stream itself, once per request)
+    if (webp_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed WebP file (RIFF size, chunk layout, VP8L signature or version)"); return FLGPU_ERR_PARSE; }
+    if (!info.supported) { c->set_error("WebP file not covered by the device decoder (lossy VP8, ALPH, animation)"); return FLGPU_ERR_UNSUPPORTED; }
+    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
+        c->set_error("FLGPU_IMG_WEBP_SOURCE: width / height / channels do not match the file (see flgpu_webp_info_of)");
+        return FLGPU_ERR_INVALID_ARG;
+    }
+    return FLGPU_OK;
+}
+
+int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used)
+{
+    const int rc = webp_decode_residuals(src->data, (size_t)src->capacity, blob, cap, hdr);
+    if (rc == kWebpParse) c->set_error("malformed lossless WebP stream (prefix code, transform, backward reference, colour cache index or too few bytes)");
+    if (rc == kWebpUnsupported) c->set_error("lossless WebP stream with more code tables than the decoder's work area holds");
+    if (rc) return webp_status(rc);
+    *used = hdr->total_bytes;
+    return FLGPU_OK;
+}
+
+int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
+{
+    size_t np = 0, scratch = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const WebpBlobHeader *H = srcs[i].webp;
+        if (!H) continue;
+        ++np;
+        // the pixels, and at most two intermediate pictures of dwords (in front of and behind the predictor transform)
+        scratch += align_up((size_t)H->width * H->height * H->channels + 64, 256) + 2 * align_up((size_t)H->width * H->height * 4u + 64, 256);
+    }
+    if (!np) return FLGPU_OK;
+    const size_t run_bytes = 2 * np * sizeof(WebpRunJob), job_bytes = run_bytes + np * sizeof(WebpPredictJob);
+    FL_HIP(c, c->d_webpdec.reserve(scratch), "WebP decode scratch");
+    FL_HIP(c, c->h_webpjobs.reserve(job_bytes), "WebP decode descriptors");
+    FL_HIP(c, c->d_webpjobs.reserve(job_bytes), "WebP decode descriptors");
+    // descriptors: the runs in front of a predictor transform, the runs that end in pixels, the predictor transforms
+    WebpRunJob *ra = static_cast<WebpRunJob *>(c->h_webpjobs.p), *rb = ra + np;
+    WebpPredictJob *pj = reinterpret_cast<WebpPredictJob *>(static_cast<uint8_t *>(c->h_webpjobs.p) + run_bytes);
+    uint32_t na = 0, nb = 0, npred = 0, max_a = 0, max_b = 0;
+    size_t off = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!srcs[i].webp) continue;
+        const WebpBlobHeader &H = *srcs[i].webp;
+        const uint8_t *blob = dsrc[i].data;
+        uint8_t *base = static_cast<uint8_t *>(c->d_webpdec.p);
+        uint8_t *pixels = base + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
+        const uint32_t *cur = reinterpret_cast<const uint32_t *>(blob + H.res_off);
+        uint32_t cw = H.xsize;
+        WebpRunJob run;
+        auto begin_run = [&] { memset(&run, 0, sizeof(run)); run.src = cur; run.src_w = cw; run.height = H.height; };
+        begin_run();
+        if (H.ntransforms > 4) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+        for (uint32_t k = H.ntransforms; k-- > 0;) { // the inverse transforms, last to first
+            if (H.ttype[k] == kWtPredictor) {
+                if (run.nops) { // what is pointwise in front of it goes into a picture of dwords first
+                    uint32_t *mid = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
+                    run.dst = mid; run.dst_w = cw; run.out_c = 0;
+                    ra[na++] = run;
+                    max_a = std::max(max_a, cw * H.height);
+                    cur = mid;
+                }
+                uint32_t *out = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
+                WebpPredictJob &p = pj[npred++];
+                memset(&p, 0, sizeof(p));
+                p.res = cur; p.modes = reinterpret_cast<const uint32_t *>(blob + H.toff[k]); p.out = out;
+                p.width = cw; p.height = H.height; p.bits = H.tbits[k];
+                if (H.twidth[k] != cw || p.bits < 2u || p.bits > 9u) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+                cur = out;
+                begin_run();
+                continue;
+            }
+            WebpOp &op = run.ops[run.nops++];
+            op.type = H.ttype[k];
+            op.data = reinterpret_cast<const uint32_t *>(blob + H.toff[k]);
+            if (op.type == kWtCrossColor) { op.bits = H.tbits[k]; op.width = H.twidth[k]; }
+            if (op.type == kWtColorIndexing) { op.bits = run.shift = webp_index_shift(H.tbits[k]); cw = H.twidth[k]; }
+        }
+        if (cw != H.width) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+        run.dst = pixels; run.dst_w = cw; run.out_c = H.channels;
+        rb[nb++] = run;
+        max_b = std::max(max_b, cw * H.height);
+        if (!tl_force_host_huffman) { c->webp_sources++; c->webp_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
+        dsrc[i].data = pixels;
+        dsrc[i].channels = H.channels;
+        dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
+        dsrc[i].flags &= ~FLGPU_IMG_WEBP_SOURCE;
+    }
+    FL_HIP(c, hipMemcpyAsync(c->d_webpjobs.p, c->h_webpjobs.p, job_bytes, hipMemcpyHostToDevice, st), "WebP decode descriptors");
+    const WebpRunJob *d_ra = static_cast<const WebpRunJob *>(c->d_webpjobs.p);
+    const WebpPredictJob *d_pj = reinterpret_cast<const WebpPredictJob *>(static_cast<const uint8_t *>(c->d_webpjobs.p) + run_bytes);
+    if (na) { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra, na, max_a, st), "WebP pointwise transform kernel"); }
+    if (npred) { ProfileScope ps(c, st, 3); FL_HIP(c, launch_webp_predict(d_pj, npred, st), "WebP predictor kernel"); }
+    { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra + np, nb, max_b, st), "WebP pointwise transform kernel"); }
+    return FLGPU_OK;
+}
+
 // Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway
 // asks for them in front of that wait and passes fetched = true below.
 int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st)
@@ -1545,6 +1645,7 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     std::vector<FileSrc> fsrc(n);
     std::vector<std::vector<uint8_t>> iccs(n);
     std::vector<PngBlobHeader> ph;
+    std::vector<WebpBlobHeader> wh;
     size_t in_b = 0, out_b = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!srcs[i].data || !dsts[i].data) return FLGPU_ERR_INVALID_ARG;
@@ -1580,6 +1681,19 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
             fsrc[i].png = &ph[i];
             if (!tl_force_host_huffman) c->png_file_bytes += srcs[i].capacity;
             sb = used;
+        } else if (srcs[i].flags & FLGPU_IMG_WEBP_SOURCE) {
+            // lossless WebP sources: container + entropy decoding here, on the host; what is staged is header, sub-images and residuals
+            WebpInfo info;
+            rc = webp_source_info(c, &srcs[i], info);
+            if (rc) return rc;
+            if (wh.empty()) wh.resize(n);
+            blobs[i].resize(webp_blob_capacity(info, (size_t)srcs[i].capacity));
+            size_t used = 0;
+            rc = webp_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &wh[i], &used);
+            if (rc) return rc;
+            fsrc[i].webp = &wh[i];
+            if (!tl_force_host_huffman) c->webp_file_bytes += srcs[i].capacity;
+            sb = used;
         } else
         if (srcs[i].capacity < sb) return FLGPU_ERR_INVALID_ARG;
         if (dsts[i].capacity < plans[i].out_bytes && !fe_encoded(ps[i].front_end)) return FLGPU_ERR_BUFFER_TOO_SMALL;
@@ -1595,13 +1709,14 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     hipStream_t st = c->stream;
     for (size_t i = 0; i < n; ++i) {
         const size_t off = reinterpret_cast<size_t>(dsrc[i].data);
-        memcpy(static_cast<char *>(c->h_stage_in.p) + off, (fsrc[i].hdr || fsrc[i].png) ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
+        memcpy(static_cast<char *>(c->h_stage_in.p) + off, (fsrc[i].hdr || fsrc[i].png || fsrc[i].webp) ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
         dsrc[i].data = static_cast<uint8_t *>(c->d_in.p) + off;
         ddst[i].data = static_cast<uint8_t *>(c->d_out.p) + reinterpret_cast<size_t>(ddst[i].data);
     }
     FL_HIP(c, hipMemcpyAsync(c->d_in.p, c->h_stage_in.p, in_b, hipMemcpyHostToDevice, st), "H2D");
     { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_webp_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps, false, ddst.data(), st);
     if (rc) return rc;
     FL_HIP(c, hipMemcpyAsync(c->h_stage_out.p, c->d_out.p, out_b, hipMemcpyDeviceToHost, st), "D2H");

@@ -351,6 +351,8 @@ void resolve_pending(flgpu_ctx *c)
         if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
             if (p.kind == 0) c->stats.resample_ms += ms;
             else if (p.kind == 1) c->stats.blur_ms += ms;
+            else if (p.kind == 3) c->webp_predict_ns += (uint64_t)((double)ms * 1e6);
+            else if (p.kind == 4) c->webp_pointwise_ns += (uint64_t)((double)ms * 1e6);
             else c->stats.frontend_ms += ms;
         }
         c->event_pool.push_back(p.a);
@@ -513,6 +515,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
+    c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();
     release_cmyk(c);
     c->h_results.release();
     c->h_stage_in.release(); c->h_stage_out.release();
@@ -625,6 +628,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         resolve_pending(c);
         c->stats = flgpu_stats{};
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
+        c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = 0;
     }
     const size_t nl = c->n_lanes.load(std::memory_order_acquire);
     for (size_t i = 0; i < nl; ++i) (void)flgpu_reset_stats(c->lanes[i]);
@@ -648,9 +652,11 @@ int flgpu_debug_set(flgpu_ctx *c, const char *key, int64_t value)
 int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value || !c->dbg) return FLGPU_ERR_INVALID_ARG;
-    // read-only counters of the PNG decode front end (flgpu_stats keeps its size): this context's and its lanes' / shards'
+    // read-only counters of the PNG and lossless WebP decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
-        {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes}};
+        {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
+        {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
+        {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}};
     for (const auto &k : counters) {
         if (strcmp(key, k.name)) continue;
         uint64_t sum;

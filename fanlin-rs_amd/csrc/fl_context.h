@@ -34,6 +34,7 @@
 #include "fl_png.h"
 #include "fl_pngdec.h"
 #include "fl_tables.h"
+#include "fl_webpdec.h"
 #include "fl_webpll.h"
 #include "fl_wtile.h"
 
@@ -135,6 +136,8 @@ struct Request {
     uint64_t file_bytes = 0;
     bool png = false;      // FLGPU_IMG_PNG_SOURCE: `in` holds header + filtered scanlines the caller's thread inflated, phdr the header
     PngBlobHeader phdr;
+    bool webp = false;     // FLGPU_IMG_WEBP_SOURCE: `in` holds header + sub-images + residuals the caller's thread entropy-decoded, whdr the header
+    WebpBlobHeader whdr;
     int status = 0;
     bool done = false;
     std::condition_variable cv; // the caller waits here (qmu): a lane wakes the callers of ITS batch, not every waiting caller
@@ -219,6 +222,10 @@ struct flgpu_ctx {
     fl::DeviceBuf d_pngdec, d_pngjobs;                 // PNG decode (fl_pngdec.hip): unfiltered rows + pixels of a batch, job descriptors
     fl::PinnedBuf h_pngjobs;
     uint64_t png_sources = 0, png_file_bytes = 0, png_upload_bytes = 0; // counters behind flgpu_debug_get (guarded by mu)
+    fl::DeviceBuf d_webpdec, d_webpjobs;               // lossless WebP decode (fl_webpdec.hip): intermediate pictures + pixels of a batch, job descriptors
+    fl::PinnedBuf h_webpjobs;
+    uint64_t webp_sources = 0, webp_file_bytes = 0, webp_upload_bytes = 0;
+    uint64_t webp_predict_ns = 0, webp_pointwise_ns = 0; // HIP-event time of the two kernels' launches (profile = 1; resolved by flgpu_get_stats)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
@@ -359,6 +366,7 @@ struct FileSrc {
     size_t icc_len = 0;
     JpegHuffStage stage{}; // hdr->magic == kJhMagic: the staged segment's description (a host copy: the blob itself is on its way to the device)
     const PngBlobHeader *png = nullptr; // a PNG source instead: dsrc[i].data = DEVICE copy of header + filtered scanlines
+    const WebpBlobHeader *webp = nullptr; // a lossless WebP source instead: dsrc[i].data = DEVICE copy of header + sub-images + residuals
 };
 int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
 // After the batch decode_jpeg_sources fed has completed on `st`: bad[i] = 1 where the device entropy decoder gave up on picture i
@@ -390,6 +398,14 @@ int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc 
 // _UNSUPPORTED / _INVALID_ARG).  png_source_to_blob: inflates into blob[0 .. png_blob_bytes(info)), header in front.
 int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info);
 int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used);
+// Lossless WebP sources of a batch (srcs[i].webp set): runs the inverse transforms into scratch and points dsrc[i] at the pixels.
+int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
+// Host half for one WebP source.  webp_source_info: container walk + what the caller announced against the file (FLGPU_ERR_PARSE /
+// _UNSUPPORTED / _INVALID_ARG).  webp_source_to_blob: entropy-decodes into blob[0 .. webp_blob_capacity(info, file bytes)), header in
+// front; *used = the bytes to upload (the decoder's work area behind them stays on the host).
+int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info);
+int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used);
+inline int webp_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kWebpParse ? FLGPU_ERR_PARSE : rc == kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FLGPU_ERR_PARSE : rc == kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------

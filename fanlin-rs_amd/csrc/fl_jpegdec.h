@@ -56,6 +56,9 @@ struct JpegInfo {
 
 // 0 = ok, -1 = not a JPEG / malformed header
 int jpeg_parse_info(const uint8_t *data, size_t n, JpegInfo &info);
+// The EXIF Orientation tag (1..8, 0 = none) of a TIFF structure that starts at its "II" / "MM" header: what a JPEG APP1 segment
+// holds behind "Exif\0\0", and what a WebP EXIF chunk usually holds bare.
+int tiff_orientation(const uint8_t *tiff, size_t n);
 
 // Size bound of the blob for `info` (worst case: every coefficient present).
 size_t jpeg_blob_bound(const JpegInfo &info);

@@ -146,11 +146,10 @@ inline int receive_extend(BitReader &br, int s)
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-int exif_orientation(const uint8_t *p, size_t len)
+// the Orientation tag of IFD 0; t = the TIFF header ("II" / "MM")
+int tiff_orientation_of(const uint8_t *t, size_t n)
 {
-    if (len < 14 || memcmp(p, "Exif\0\0", 6)) return 0;
-    const uint8_t *t = p + 6;
-    const size_t n = len - 6;
+    if (n < 8) return 0;
     bool le;
     if (t[0] == 'I' && t[1] == 'I') le = true; else if (t[0] == 'M' && t[1] == 'M') le = false; else return 0;
     auto rd16 = [&](size_t o) -> uint32_t { return le ? (uint32_t)(t[o] | (t[o + 1] << 8)) : (uint32_t)((t[o] << 8) | t[o + 1]); };
@@ -170,6 +169,12 @@ int exif_orientation(const uint8_t *p, size_t len)
         if (rd16(e) == 0x0112 && rd16(e + 2) == 3 && rd32(e + 4) == 1) { const uint32_t v = rd16(e + 8); return v >= 1 && v <= 8 ? (int)v : 0; }
     }
     return 0;
+}
+
+int exif_orientation(const uint8_t *p, size_t len)
+{
+    if (len < 14 || memcmp(p, "Exif\0\0", 6)) return 0;
+    return tiff_orientation_of(p + 6, len - 6);
 }
 
 struct Parsed {
@@ -594,6 +599,9 @@ int decode_scans(const uint8_t *d, size_t n, Parsed &P, const JpegBlobHeader &H,
 }
 
 } // namespace
+
+// (a WebP EXIF chunk usually starts at the TIFF header, without the "Exif\0\0" of a JPEG APP1 segment: fl_context.h webp_orientation)
+int tiff_orientation(const uint8_t *t, size_t n) { return tiff_orientation_of(t, n); }
 
 int jpeg_parse_info(const uint8_t *data, size_t n, JpegInfo &info)
 {

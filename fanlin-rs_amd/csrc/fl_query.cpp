@@ -9,12 +9,14 @@
 
 #include <algorithm>
 #include <string>
+#include <memory>
 #include <vector>
 
 #include "../../include/fanlin_gpu.h"
 #include "fl_abi.h"
 #include "fl_png.h"
 #include "fl_pngsrc.h"
+#include "fl_webpsrc.h"
 #include "fl_webpll.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
@@ -468,6 +470,121 @@ try {
     return rc == 0 ? FLGPU_OK : rc == fl::kPngParse ? FLGPU_ERR_PARSE : rc == fl::kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL;
 } FL_ABI_CATCH
 
+/* ---- lossless WebP sources -------------------------------------------------------------------------------------------- */
+
+// the orientation ImageDecoder::orientation() reports for a WebP: from the EXIF chunk, whose payload usually starts at the TIFF
+// header, without the "Exif\0\0" a JPEG APP1 segment has; both forms are taken.  0 = no tag.
+static uint32_t webp_orientation(const uint8_t *file, const fl::WebpInfo &I)
+{
+    if (!I.exif_len) return 0;
+    const uint8_t *p = file + I.exif_off;
+    size_t n = I.exif_len;
+    if (n >= 6 && !memcmp(p, "Exif\0\0", 6)) { p += 6; n -= 6; }
+    return (uint32_t)fl::tiff_orientation(p, n);
+}
+
+int flgpu_webp_info_of(const uint8_t *webp, uint64_t n, flgpu_webp_info *info)
+try {
+    if (!webp || !info) return FLGPU_ERR_INVALID_ARG;
+    fl::WebpInfo I;
+    if (fl::webp_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE;
+    memset(info, 0, sizeof(*info));
+    info->width = I.width; info->height = I.height; info->channels = I.channels; info->has_alpha = I.has_alpha;
+    info->extended = I.extended; info->animated = I.animated; info->lossless = I.lossless;
+    info->exif_orientation = webp_orientation(webp, I);
+    info->transforms = I.transforms; info->color_cache_bits = I.color_cache_bits; info->prefix_groups = I.prefix_groups;
+    info->supported = I.supported;
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
+static int plan_webp(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
+                     flgpu_plan *plan, int *kind, int *out_format)
+{
+    // (container and VP8L header only here: flgpu_transform reads the stream once; as_is serves the file unread, as the reference does)
+    if (!webp) return FLGPU_ERR_INVALID_ARG;
+    fl::WebpInfo info;
+    if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    int rc;
+    memset(src, 0, sizeof(*src));
+    src->data = const_cast<uint8_t *>(webp);
+    src->capacity = n;
+    /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
+    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
+    src->flags = FLGPU_IMG_WEBP_SOURCE;
+    if (!info.supported) {
+        flgpu_query q;
+        rc = flgpu_query_parse(query_string ? query_string : "", &q);
+        if (rc) return rc;
+        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
+        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
+        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
+        memset(plan, 0, sizeof(*plan));
+        *kind = FLGPU_RESULT_AS_IS;
+        if (out_format) *out_format = FLGPU_OUT_KEEP;
+        return FLGPU_OK;
+    }
+    /* ImageDecoder::orientation() falls back to exif_metadata(), which the WebP decoder implements (handler.rs:206) */
+    const uint32_t o = webp_orientation(webp, info);
+    return plan_request(src, (uint8_t)(o ? o : 1u), query_string, accept_flags, FLGPU_IN_WEBP, p, plan, kind, out_format);
+}
+
+int flgpu_process_webp_plan(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, int *result_kind)
+try {
+    flgpu_image src;
+    flgpu_params p;
+    return plan_webp(webp, n, query_string, accept_flags, &src, &p, plan, result_kind, nullptr);
+} FL_ABI_CATCH
+
+int flgpu_process_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags,
+                       flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format)
+try {
+    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
+    flgpu_image src;
+    flgpu_params p;
+    flgpu_plan local;
+    int kind = 0;
+    int rc = plan_webp(webp, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
+    if (result_kind) *result_kind = kind;
+    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
+    return flgpu_transform(ctx, &src, &p, dst);
+} FL_ABI_CATCH
+
+int flgpu_decode_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst)
+try {
+    if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
+    if (!webp) return FLGPU_ERR_INVALID_ARG;
+    fl::WebpInfo info;
+    if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
+    flgpu_image src;
+    memset(&src, 0, sizeof(src));
+    src.data = const_cast<uint8_t *>(webp); src.capacity = n;
+    src.width = info.width; src.height = info.height; src.channels = info.channels; src.flags = FLGPU_IMG_WEBP_SOURCE;
+    flgpu_params p;
+    memset(&p, 0, sizeof(p)); /* the pipeline is the identity, the result the decoded picture (no orientation applied) */
+    return flgpu_transform(ctx, &src, &p, dst);
+} FL_ABI_CATCH
+
+int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!webp || !used) return FLGPU_ERR_INVALID_ARG;
+    fl::WebpInfo I;
+    if (fl::webp_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE; // (the blob's size follows from the transform headers)
+    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
+    *used = I.blob_bytes;
+    if (!out) return FLGPU_OK;
+    if (capacity < I.blob_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    // the blob in front, the decoder's work area behind it: one buffer, as flgpu_transform has it in its staging
+    const size_t cap = fl::webp_blob_capacity(I, (size_t)n);
+    std::unique_ptr<uint8_t[]> work(new uint8_t[cap + 16u]);
+    uint8_t *blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
+    fl::WebpBlobHeader H;
+    const int rc = fl::webp_decode_residuals(webp, (size_t)n, blob, cap, &H);
+    if (rc) return rc == fl::kWebpParse ? FLGPU_ERR_PARSE : rc == fl::kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL;
+    memcpy(out, blob, H.total_bytes);
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
 int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t sc, flgpu_plan *plan)
 {
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
@@ -623,7 +740,7 @@ const char *flgpu_strerror(int status)
     case FLGPU_ERR_NO_DEVICE: return "no usable HIP device (there is no CPU fallback)";
     case FLGPU_ERR_OOM: return "out of memory";
     case FLGPU_ERR_DEVICE: return "HIP runtime error";
-    case FLGPU_ERR_PARSE: return "malformed query string or damaged PNG source";
+    case FLGPU_ERR_PARSE: return "malformed query string or damaged PNG / WebP source";
     case FLGPU_ERR_BUFFER_TOO_SMALL: return "destination buffer too small";
     case FLGPU_ERR_SHUTDOWN: return "context is shutting down";
     }

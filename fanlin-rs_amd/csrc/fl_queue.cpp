@@ -145,9 +145,11 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
             c->stats.jpeg_file_bytes += batch[i]->file_bytes;
         }
         if (batch[i]->png) { fsrc[i].png = &batch[i]->phdr; c->png_file_bytes += batch[i]->file_bytes; }
+        if (batch[i]->webp) { fsrc[i].webp = &batch[i]->whdr; c->webp_file_bytes += batch[i]->file_bytes; }
     }
     { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_webp_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps.data(), false, ddst.data(), st);
     if (rc) return rc;
     // Encoded streams: their lengths are known only on the device (a 300x200 JPEG is ~16 KB of a 183 KB bound).  The first kSpecBytes of every stream
@@ -472,7 +474,13 @@ try {
         const int prc = png_source_info(c, src, pinfo); // before any block is reserved on the file's say-so
         if (prc) return prc;
     }
-    if (!jsrc && !psrc && src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
+    const bool wsrc = !jsrc && !psrc && (src->flags & FLGPU_IMG_WEBP_SOURCE) != 0;
+    WebpInfo winfo;
+    if (wsrc) {
+        const int wrc = webp_source_info(c, src, winfo); // before any block is reserved on the file's say-so
+        if (wrc) return wrc;
+    }
+    if (!jsrc && !psrc && !wsrc && src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
     const bool enc = fe_encoded(p->front_end);
     if (!enc && dst->capacity < plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
     Request r{};
@@ -495,8 +503,8 @@ try {
     } admission{c};
     c->staging.fetch_add(1, std::memory_order_acq_rel);
     // buffers from flgpu_host_alloc are page-locked already: the DMA engine reads / writes them directly, no staging copy
-    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc && !psrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
-    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : psrc ? png_blob_bytes(pinfo) : r.src_bytes);
+    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc && !psrc && !wsrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
+    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : psrc ? png_blob_bytes(pinfo) : wsrc ? webp_blob_capacity(winfo, (size_t)src->capacity) : r.src_bytes);
     if (dst_pinned) r.out = PinBlock{dst->data, 0}; else r.out = pin_acquire(c, r.out_bytes);
     auto give_back = [&] { if (!src_pinned) pin_release(c, r.in); if (!dst_pinned) pin_release(c, r.out); };
     if (!r.in.p || !r.out.p) {
@@ -557,6 +565,25 @@ try {
         }
         if (prc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return prc; }
         r.png = true;
+        r.file_bytes = src->capacity;
+        r.src_bytes = used;
+    } else if (wsrc) {
+        // the serial half of the lossless WebP decoder (prefix codes, LZ77, colour cache) on the caller's thread, straight into pinned
+        // memory, under the same bound as the other host decoders
+        size_t used = 0;
+        int wrc;
+        {
+            {
+                std::unique_lock<std::mutex> lk(c->dec_mu);
+                if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
+                (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
+                c->decoding++;
+            }
+            struct Turn { flgpu_ctx *c; ~Turn() { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } } turn{c};
+            wrc = webp_source_to_blob(c, src, static_cast<uint8_t *>(r.in.p), r.in.cap, &r.whdr, &used);
+        }
+        if (wrc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return wrc; }
+        r.webp = true;
         r.file_bytes = src->capacity;
         r.src_bytes = used;
     } else

@@ -39,6 +39,8 @@
  *   flgpu_cmyk_to_rgb[_device]          CMYK2RGB::convert = lcms2 transform_pixels, src/handler.rs:446-462,490-492
  *   FLGPU_IMG_JPEG_SOURCE / flgpu_process_jpeg   JpegDecoder::new + DynamicImage::from_decoder, src/handler.rs:205-220
  *   FLGPU_IMG_PNG_SOURCE / flgpu_process_png     PngDecoder + DynamicImage::from_decoder, src/handler.rs:218-220
+ *   FLGPU_IMG_WEBP_SOURCE / flgpu_process_webp   WebPDecoder (lossless VP8L) + DynamicImage::from_decoder and its EXIF orientation,
+ *                                                src/handler.rs:205-220
  *   flgpu_create / flgpu_destroy        lifetime of handler::State, src/handler.rs:14-21,36-52
  *   flgpu_config.devices / flgpu_plan_shards   the one shared Arc<State> behind all tokio workers, src/main.rs:108-112
  */
@@ -61,7 +63,7 @@ typedef enum flgpu_status {
     FLGPU_ERR_NO_DEVICE = 3,     /* no usable HIP device: the library never falls back to the CPU */
     FLGPU_ERR_OOM = 4,           /* host or device allocation failed */
     FLGPU_ERR_DEVICE = 5,        /* a HIP call failed; see flgpu_last_error() */
-    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400); a PNG source that is damaged */
+    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400); a PNG or WebP source that is damaged */
     FLGPU_ERR_BUFFER_TOO_SMALL = 7,
     FLGPU_ERR_SHUTDOWN = 8       /* context is being destroyed */
 } flgpu_status;
@@ -93,6 +95,13 @@ typedef struct flgpu_image {
                                          The filtered scanlines cross PCIe: the pixel bytes + height for 8-bit RGB, 3-24 x less for palette and
                                          sub-byte pictures.  Files it does not cover (16-bit samples, Adam7): FLGPU_ERR_UNSUPPORTED (decode on the
                                          host); damaged files: FLGPU_ERR_PARSE. */
+#define FLGPU_IMG_WEBP_SOURCE     64u /* in (src of flgpu_transform / flgpu_transform_batch): data holds a lossless WebP FILE of `capacity` bytes instead
+                                         of pixels, width / height / channels say what it decodes to (flgpu_webp_info_of): the library decodes it
+                                         itself -- container, prefix codes, LZ77 and colour cache on the calling thread, the predictor, cross-colour,
+                                         add-green and colour-indexing transforms on the device -- replacing DynamicImage::from_decoder for WebP
+                                         inputs (src/handler.rs:205-220).  The residual picture crosses PCIe: 4 bytes per pixel, 1 / 2 / 4 / 8 x
+                                         less for palette pictures.  Lossy and animated files: FLGPU_ERR_UNSUPPORTED (decode on the host);
+                                         damaged files: FLGPU_ERR_PARSE. */
 #define FLGPU_IMG_HAS_ALPHA       2u  /* WEBP420: some pixel is not opaque: the picture is WEBP_YUV420A for libwebp, i.e. the A
                                          plane behind V must be handed to WebPEncode too (for opaque pictures it is all 255) */
 
@@ -394,6 +403,37 @@ int flgpu_process_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, const char
 int flgpu_process_png_plan(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
                            int *result_kind);
 
+/* ---- lossless WebP sources (src/handler.rs:205-220: image-webp through the image crate) ----------------------------------- */
+typedef struct flgpu_webp_info {
+    uint32_t width, height;
+    uint32_t channels;          /* of the picture the pipeline sees (0 if unsupported): 4 (Rgba8) if the file announces alpha, else 3 (Rgb8, the
+                                   decoded alpha dropped) -- as image 0.25.6 / image-webp report it as far as is known; unpinned */
+    uint32_t has_alpha;         /* the VP8L header's alpha bit (simple form), the VP8X alpha flag (extended form) */
+    uint32_t extended;          /* the file starts with a VP8X chunk */
+    uint32_t animated;          /* VP8X animation flag, ANIM or ANMF */
+    uint32_t lossless;          /* the picture is a VP8L chunk */
+    uint32_t exif_orientation;  /* 1..8 from the EXIF chunk, 0 = none (the pipeline then runs with 1) */
+    uint32_t transforms;        /* bit k = transform type k present: 0 predictor, 1 cross-colour, 2 subtract-green, 3 colour indexing */
+    uint32_t color_cache_bits;  /* of the main image, 0 = none */
+    uint32_t prefix_groups;     /* code groups of the main image (1 without an entropy image) */
+    uint32_t supported;         /* 1 = FLGPU_IMG_WEBP_SOURCE decodes it; 0: lossy VP8 (with or without ALPH), animation */
+} flgpu_webp_info;
+/* Container, VP8L header, transform headers and the main image's code groups (no device needed).  FLGPU_ERR_PARSE if the bytes are
+ * not an intact WebP container or the headers are damaged. */
+int flgpu_webp_info_of(const uint8_t *webp, uint64_t n, flgpu_webp_info *info);
+/* Decodes a supported WebP to interleaved pixels in HOST memory at dst->data (capacity >= width*height*channels); the EXIF
+ * orientation is not applied. */
+int flgpu_decode_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst);
+/* State::process_image for a WebP input from the file bytes on, input_format FLGPU_IN_WEBP (so an empty query is as_is), with the
+ * file's EXIF orientation: query parsing, size gate, as_is, container negotiation, then entropy decode + inverse transforms + pixel
+ * pipeline in one pass; with FLGPU_ENCODE_WEBP_LOSSLESS and quality=100 the result is the finished lossless WebP file.  Same
+ * outcomes as flgpu_process_image; additionally FLGPU_ERR_UNSUPPORTED for files the decoder does not cover (the host then decodes
+ * with its own decoder and calls flgpu_process_image) and FLGPU_ERR_PARSE for damaged ones. */
+int flgpu_process_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags,
+                       flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format);
+int flgpu_process_webp_plan(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
+                            int *result_kind);
+
 /* Page-locked host memory for sources / results of flgpu_transform (flag them FLGPU_IMG_PINNED): a decoder that
  * writes straight into such a buffer (zune-jpeg's decode_into) saves the 6 MB staging copy of a 1080p request. */
 void *flgpu_host_alloc(flgpu_ctx *ctx, uint64_t bytes);
@@ -461,7 +501,10 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "mfma_spin_limit", "debug_mfma", "debug_jh"; "reset" restores every default.
  * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
  * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
- * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines).
+ * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines);
+ * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
+ * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
+ * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats).
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
  * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);
@@ -489,6 +532,11 @@ int flgpu_debug_jpeg_blob(const uint8_t *jpeg, uint64_t n, uint8_t *blob, uint64
  * FLGPU_IMG_PNG_SOURCE, height x (1 + row bytes) -- the inflated IDAT stream, Adler-32 and filter bytes checked.
  * out == NULL: *used = capacity to provide. */
 int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
+
+/* The host half of the lossless WebP decode front end alone (csrc/fl_webpsrc.h): the blob flgpu_transform uploads for a
+ * FLGPU_IMG_WEBP_SOURCE -- WebpBlobHeader, the mode / cross-colour images, the palette, the entropy-decoded residual picture.
+ * out == NULL: *used = capacity to provide. */
+int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
 
 int flgpu_debug_stream_schedulable(uint32_t in_size, uint32_t out_size, uint32_t y0, uint32_t y1, uint32_t *max_live);
 /* Builds the matrix-pipe kernel's tables (csrc/fl_mfma.h) for a source of sw x sh pixels with `channels` interleaved bytes,

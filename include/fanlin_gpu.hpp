@@ -175,6 +175,29 @@ public:
         return out;
     }
 
+    // WebPDecoder::new's view of a file (src/handler.rs:205-220): false if the bytes are no intact WebP container
+    static bool webp_info(const std::vector<uint8_t> &file, flgpu_webp_info &info) { return flgpu_webp_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
+
+    // State::process_image for a lossless WebP input from the file bytes on, with the file's EXIF orientation: entropy decode on this
+    // thread, inverse transforms, pixel pipeline and (with FLGPU_ENCODE_WEBP_LOSSLESS in the content flags, quality=100) the lossless
+    // WebP encoder on the device.  Throws on files the decoder does not cover (FLGPU_ERR_UNSUPPORTED: lossy, animated) and on damaged
+    // ones (FLGPU_ERR_PARSE): the host then uses its own decoder.
+    Processed process_webp(const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
+    {
+        Processed out{};
+        int kind = 0, fmt = 0;
+        check(flgpu_process_webp_plan(file.data(), file.size(), params.text().c_str(), content.flags(), &out.plan, &kind));
+        out.kind = static_cast<flgpu_result_kind>(kind);
+        if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
+        out.data.resize(out.plan.max_out_bytes);
+        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
+        check(flgpu_process_webp(ctx_, file.data(), file.size(), params.text().c_str(), content.flags(), &dst, &out.plan, &kind, &fmt), ctx_);
+        out.negotiated = static_cast<flgpu_out_format>(fmt);
+        out.flags = dst.flags;
+        out.data.resize(dst.bytes);
+        return out;
+    }
+
     flgpu_ctx *raw() { return ctx_; }
 
 private:

@@ -32,6 +32,13 @@ pub struct FlJpegInfo { width: u32, height: u32, components: u32, channels: u32,
 /// Transformations::EXPAND gives; `supported` = 0 for 16-bit samples and Adam7 (tests/test_png_source_host.py checks this mirror).
 pub struct FlPngInfo { width: u32, height: u32, color_type: u32, bit_depth: u32, channels: u32, interlaced: u32, has_trns: u32, supported: u32 }
 
+#[repr(C)] #[derive(Default, Clone, Copy)]
+/// flgpu_webp_info: what `WebPDecoder::new` learns from the container and the VP8L headers (src/handler.rs:205-220), for the decision
+/// "file bytes to the device, or the reference's own decoder".  `channels`: 3 Rgb8, 4 Rgba8 (the file announces alpha); `supported`
+/// = 0 for lossy VP8 and animated files (tests/test_webp_source_host.py checks this mirror).
+pub struct FlWebpInfo { width: u32, height: u32, channels: u32, has_alpha: u32, extended: u32, animated: u32, lossless: u32, exif_orientation: u32,
+                        transforms: u32, color_cache_bits: u32, prefix_groups: u32, supported: u32 }
+
 pub const FE_NONE: u8 = 0;
 pub const FE_JFIF444: u8 = 1;
 pub const FE_WEBP420: u8 = 2;
@@ -43,6 +50,8 @@ const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
 #[allow(dead_code)]
 const IMG_PNG_SOURCE: u32 = 32;  // ... `data` holds the PNG FILE (flgpu_process_png sets it itself)
+#[allow(dead_code)]
+const IMG_WEBP_SOURCE: u32 = 64; // ... `data` holds the lossless WebP FILE (flgpu_process_webp sets it itself)
 pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
 // not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
@@ -75,6 +84,10 @@ extern "C" {
     fn flgpu_process_png_plan(png: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
     fn flgpu_process_png(ctx: *mut c_void, png: *const u8, n: u64, query: *const c_char, accept: u32,
                          dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
+    fn flgpu_webp_info_of(webp: *const u8, n: u64, info: *mut FlWebpInfo) -> c_int;
+    fn flgpu_process_webp_plan(webp: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
+    fn flgpu_process_webp(ctx: *mut c_void, webp: *const u8, n: u64, query: *const c_char, accept: u32,
+                          dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
     fn flgpu_transform_batch(ctx: *mut c_void, n: usize, srcs: *const FlImage, ps: *const FlParams, dsts: *mut FlImage) -> c_int;
     fn flgpu_strerror(status: c_int) -> *const c_char;
     fn flgpu_abi_version() -> u32;
@@ -219,6 +232,34 @@ impl Gpu {
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
         let rc = unsafe { flgpu_process_png(self.0, original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut dst, &mut plan, &mut kind, &mut fmt) };
+        if rc == ERR_UNSUPPORTED || rc == ERR_PARSE { return Ok(None); } // a damaged stream: the crate's decoder reports it in its own words
+        check(rc)?;
+        out.truncate(dst.bytes as usize);
+        Ok(Some((kind, fmt, plan, out)))
+    }
+
+    /// Header of a WebP file, or None if the bytes are no intact WebP container (then `with_guessed_format` decides as before).
+    pub fn webp_info(original: &[u8]) -> Option<FlWebpInfo> {
+        let mut info = FlWebpInfo::default();
+        if unsafe { flgpu_webp_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
+    }
+
+    /// `process_image` for a lossless WebP input FROM THE FILE BYTES ON (src/handler.rs:198-308 in one call, input format WebP, the
+    /// file's EXIF orientation): prefix codes + LZ77 + colour cache on this thread, inverse transforms + pixel pipeline (+ the lossless
+    /// WebP encoder with ENCODE_WEBP_LOSSLESS in `accept` and quality=100) in one device pass.  Ok(None): a file the decoder does not
+    /// cover (lossy, animated) or cannot read -- decode with the reference's own decoder, which also words the error, and use
+    /// `transform`.  Otherwise as `process_png`: RESULT_AS_IS, RESULT_WEBP_STREAM, RESULT_WEBP_PLANES or RESULT_PIXELS.
+    pub fn process_webp(&self, original: &[u8], query: &str, accept: u32)
+        -> Result<Option<(c_int, c_int, FlPlan, Vec<u8>)>, Box<dyn std::error::Error>>
+    {
+        let q = std::ffi::CString::new(query)?;
+        let (mut plan, mut kind, mut fmt) = (FlPlan::default(), 0 as c_int, 0 as c_int);
+        if Self::webp_info(original).map_or(true, |i| i.supported == 0) { return Ok(None); }
+        check(unsafe { flgpu_process_webp_plan(original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut plan, &mut kind) })?;
+        if kind == RESULT_AS_IS { return Ok(Some((kind, 0, plan, Vec::new()))); }
+        let mut out = vec![0u8; plan.max_out_bytes as usize];
+        let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
+        let rc = unsafe { flgpu_process_webp(self.0, original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut dst, &mut plan, &mut kind, &mut fmt) };
         if rc == ERR_UNSUPPORTED || rc == ERR_PARSE { return Ok(None); } // a damaged stream: the crate's decoder reports it in its own words
         check(rc)?;
         out.truncate(dst.bytes as usize);
