@@ -114,6 +114,12 @@ class flgpu_webp_info(C.Structure):
                                            "transforms", "color_cache_bits", "prefix_groups", "supported")]
 
 
+class flgpu_gif_info(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames", "has_global_table", "interlaced_frames", "transparent_frames",
+                                           "disposal_mask", "max_code_size")] + [("decoded_bytes", C.c_uint64), ("supported", C.c_uint32),
+                                                                                 ("reserved", C.c_uint32)]
+
+
 # every symbol include/fanlin_gpu.h declares
 EXPORTED_SYMBOLS = (
     "flgpu_query_parse", "flgpu_query_dimensions", "flgpu_query_fill_color", "flgpu_query_quality",
@@ -123,7 +129,8 @@ EXPORTED_SYMBOLS = (
     "flgpu_transform_batch", "flgpu_transform_batch_device", "flgpu_batch_results", "flgpu_plan_shards", "flgpu_devices",
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
-    "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
+    "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
+    "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
     "flgpu_import_tables", "flgpu_get_stats",
@@ -203,6 +210,13 @@ def load_library() -> C.CDLL:
                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.flgpu_process_webp_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_int)]
         lib.flgpu_debug_webp_residuals.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_gif_info_of"):  # (the same for GIF files)
+        lib.flgpu_gif_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_gif_info)]
+        lib.flgpu_decode_gif.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image), C.POINTER(C.c_uint32)]
+        lib.flgpu_process_gif.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_image), C.POINTER(flgpu_plan),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.flgpu_process_gif_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        lib.flgpu_debug_gif_blob.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.flgpu_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]
     lib.flgpu_devices.restype = C.c_uint32
     lib.flgpu_cmyk_distribution.argtypes = [C.c_void_p]
@@ -436,6 +450,24 @@ def debug_webp_residuals(data: bytes) -> bytes:
     _check(lib.flgpu_debug_webp_residuals(data, len(data), None, 0, C.byref(used)))
     out = np.zeros(max(used.value, 1), np.uint8)
     _check(lib.flgpu_debug_webp_residuals(data, len(data), out.ctypes.data, used.value, C.byref(used)))
+    return out[: used.value].tobytes()
+
+
+def gif_info(data: bytes) -> dict:
+    """flgpu_gif_info_of: canvas, frames and what the frames use, from the container and the LZW stage of a GIF file (pure host
+    function); raises FanlinError(ERR_PARSE) if the file is damaged."""
+    info = flgpu_gif_info()
+    _check(load_library().flgpu_gif_info_of(data, len(data), C.byref(info)))
+    return {n: getattr(info, n) for n, _ in flgpu_gif_info._fields_ if n != "reserved"}
+
+
+def debug_gif_blob(data: bytes) -> bytes:
+    """Host half of the GIF decode front end alone: the blob that is uploaded (header, frame records, index bytes, palettes)."""
+    lib = load_library()
+    used = C.c_uint64()
+    _check(lib.flgpu_debug_gif_blob(data, len(data), None, 0, C.byref(used)))
+    out = np.zeros(max(used.value, 1), np.uint8)
+    _check(lib.flgpu_debug_gif_blob(data, len(data), out.ctypes.data, out.nbytes, C.byref(used)))
     return out[: used.value].tobytes()
 
 
@@ -765,6 +797,36 @@ class State:
         mime = "image/avif" if fmt.value == OUT_AVIF else "image/webp"
         fe = _RESULT_FE[kind.value]
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+
+    # -- GIF files: decode, compositing and the per-frame pipeline (handler.rs:311-353) -------------------------------
+    def decode_gif(self, data: bytes) -> np.ndarray:
+        """GifDecoder::new(..).into_frames().collect_frames() on the device: (frames, h, w, 4) uint8, every frame the composited canvas."""
+        info = gif_info(data)
+        out = np.empty((max(info["frames"], 1), info["height"], info["width"], 4), np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        frames = C.c_uint32()
+        _check(self._lib.flgpu_decode_gif(self._ctx, data, len(data), C.byref(dst), C.byref(frames)), self._ctx)
+        return out[: frames.value]
+
+    def process_gif(self, data: bytes, query_string: str, content: "Format" = None):
+        """process_gif from the file bytes on: (mime, kind, payload); payload is the file itself for AS_IS, else the list of the
+        frames' pixels (out_h, out_w, out_c), in frame order, for the host's GIF encoder."""
+        plan, kind, fmt, frames = flgpu_plan(), C.c_int(), C.c_int(), C.c_uint32()
+        flags = content.flags if content else 0
+        qs = query_string.encode()
+        _check(self._lib.flgpu_process_gif_plan(data, len(data), qs, flags, C.byref(plan), C.byref(frames), C.byref(kind)))
+        if kind.value == RESULT_AS_IS:
+            return "image/gif", RESULT_AS_IS, data
+        out = np.empty(max(int(plan.out_bytes) * frames.value, 1), dtype=np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_process_gif(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(frames), C.byref(kind),
+                                           C.byref(fmt)), self._ctx)
+        px = out[: int(plan.out_bytes) * frames.value].reshape(frames.value, plan.out_h, plan.out_w, plan.out_c)
+        return "image/gif", kind.value, [px[f] for f in range(frames.value)]
+
+    def gif_counters(self) -> dict:
+        """The GIF decode front end's counters (flgpu_debug_get)."""
+        return {k: self.debug_get(k) for k in ("gif_sources", "gif_frames", "gif_file_bytes", "gif_upload_bytes")}
 
     def webp_counters(self) -> dict:
         """The lossless WebP decode front end's counters (flgpu_debug_get)."""

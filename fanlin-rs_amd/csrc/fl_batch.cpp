@@ -1538,6 +1538,90 @@ int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc
     return FLGPU_OK;
 }
 
+// ---- GIF files ---------------------------------------------------------------------------------------------------------------------
+
+// The compose phase: `blob` is the DEVICE copy of what gif_decode_blob left, H its header.  Runs gif_compose_kernel into scratch
+// and describes the H.frames composited canvases as device-resident Rgba8 sources in dsrc[0 .. H.frames).
+int decode_gif_sources(flgpu_ctx *c, const GifBlobHeader &H, const uint8_t *blob, flgpu_image *dsrc, hipStream_t st)
+{
+    const size_t plane = (size_t)H.width * H.height * 4u;
+    FL_HIP(c, c->d_gifdec.reserve((size_t)H.frames * plane + 256), "GIF decode scratch");
+    uint8_t *frames = static_cast<uint8_t *>(c->d_gifdec.p);
+    { ProfileScope ps(c, st, 5); FL_HIP(c, launch_gif_compose(blob, H.width, H.height, H.frames, frames, st), "GIF compose kernel"); }
+    for (uint32_t f = 0; f < H.frames; ++f) {
+        memset(&dsrc[f], 0, sizeof(dsrc[f]));
+        dsrc[f].data = frames + (size_t)f * plane;
+        dsrc[f].capacity = plane;
+        dsrc[f].width = H.width; dsrc[f].height = H.height; dsrc[f].channels = 4;
+    }
+    c->gif_sources++; c->gif_frames += H.frames; c->gif_upload_bytes += H.total_bytes;
+    return FLGPU_OK;
+}
+
+int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames)
+{
+    if (!gif || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
+    // the serial half on the calling thread, before any device work and outside the context's lock: callers decode side by side
+    GifInfo info;
+    if (gif_parse_info(gif, n, info) != 0) { c->set_error("malformed GIF file (signature, logical screen, block layout, colour table or too few bytes)"); return FLGPU_ERR_PARSE; }
+    if (!info.supported) { c->set_error("GIF file not covered by the device decoder (no frames, a frame outside the canvas or without area, code size, frame count, decoded size)"); return FLGPU_ERR_UNSUPPORTED; }
+    flgpu_plan plan;
+    memset(&plan, 0, sizeof(plan));
+    const size_t canvas = (size_t)info.width * info.height * 4u;
+    if (params) {
+        if (fe_encoded(params->front_end)) return FLGPU_ERR_INVALID_ARG; // (GIF frames leave as pixels: the GIF encoder is the host's)
+        if (int rc = flgpu_plan_output(params, info.width, info.height, 4, &plan)) return rc;
+    }
+    const size_t each = params ? (size_t)plan.out_bytes : canvas;
+    if (dst->capacity < (uint64_t)each * info.frames) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    std::vector<uint8_t> blob(gif_blob_capacity(info));
+    GifBlobHeader H;
+    const int drc = gif_decode_blob(gif, n, blob.data(), blob.size(), &H);
+    if (drc == kGifParse) c->set_error("malformed GIF stream (an LZW code beyond the table, or fewer indices than the frame has pixels)");
+    if (drc == kGifUnsupported) c->set_error("GIF frame with an index beyond its colour table");
+    if (drc) return gif_status(drc);
+
+    flgpu_ctx *s = c->shard_ctx.empty() ? c : c->shard_ctx[0]; // one file, one device
+    std::lock_guard<std::mutex> g(s->mu);
+    FL_HIP(s, hipSetDevice(s->device), "hipSetDevice");
+    hipStream_t st = s->stream;
+    if (s->last_stream && s->last_stream != st && s->last_done) FL_HIP(s, hipStreamWaitEvent(st, s->last_done, 0), "stream handoff");
+    FL_HIP(s, s->d_in.reserve(H.total_bytes), "device input staging");
+    FL_HIP(s, s->h_stage_in.reserve(H.total_bytes), "pinned input staging");
+    memcpy(s->h_stage_in.p, blob.data(), H.total_bytes);
+    FL_HIP(s, hipMemcpyAsync(s->d_in.p, s->h_stage_in.p, H.total_bytes, hipMemcpyHostToDevice, st), "H2D");
+    std::vector<flgpu_image> dsrc(H.frames);
+    if (int rc = decode_gif_sources(s, H, static_cast<const uint8_t *>(s->d_in.p), dsrc.data(), st)) return rc;
+    s->gif_file_bytes += n;
+    if (frames) *frames = H.frames;
+    dst->width = info.width; dst->height = info.height; dst->channels = 4; dst->flags = 0;
+    if (!params) { // the composited frames themselves
+        FL_HIP(s, hipMemcpyAsync(dst->data, s->d_gifdec.p, canvas * H.frames, hipMemcpyDeviceToHost, st), "D2H");
+        FL_HIP(s, hipStreamSynchronize(st), "GIF decode sync");
+        dst->bytes = (uint64_t)canvas * H.frames;
+        return FLGPU_OK;
+    }
+    // the per-frame pipeline: every frame the same request, one device batch
+    const size_t pitch = align_up(plan.max_out_bytes, 256);
+    FL_HIP(s, s->d_out.reserve(pitch * H.frames), "device output staging");
+    FL_HIP(s, s->h_stage_out.reserve(pitch * H.frames), "pinned output staging");
+    std::vector<flgpu_image> ddst(H.frames);
+    for (uint32_t f = 0; f < H.frames; ++f) {
+        memset(&ddst[f], 0, sizeof(ddst[f]));
+        ddst[f].data = static_cast<uint8_t *>(s->d_out.p) + pitch * f;
+        ddst[f].capacity = plan.max_out_bytes;
+    }
+    int rc = run_batch_device(s, H.frames, dsrc.data(), params, true, ddst.data(), st);
+    if (rc) return rc;
+    FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, s->d_out.p, pitch * H.frames, hipMemcpyDeviceToHost, st), "D2H");
+    rc = collect_results(s, H.frames, ddst.data(), st);
+    if (rc) return rc;
+    for (uint32_t f = 0; f < H.frames; ++f) memcpy(dst->data + each * f, static_cast<const uint8_t *>(s->h_stage_out.p) + pitch * f, each);
+    dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = ddst[0].flags;
+    dst->bytes = (uint64_t)each * H.frames;
+    return FLGPU_OK;
+}
+
 // Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway
 // asks for them in front of that wait and passes fetched = true below.
 int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st)

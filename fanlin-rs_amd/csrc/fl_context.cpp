@@ -353,6 +353,7 @@ void resolve_pending(flgpu_ctx *c)
             else if (p.kind == 1) c->stats.blur_ms += ms;
             else if (p.kind == 3) c->webp_predict_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 4) c->webp_pointwise_ns += (uint64_t)((double)ms * 1e6);
+            else if (p.kind == 5) c->gif_compose_ns += (uint64_t)((double)ms * 1e6);
             else c->stats.frontend_ms += ms;
         }
         c->event_pool.push_back(p.a);
@@ -516,6 +517,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
     c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();
+    c->d_gifdec.release();
     release_cmyk(c);
     c->h_results.release();
     c->h_stage_in.release(); c->h_stage_out.release();
@@ -629,6 +631,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         c->stats = flgpu_stats{};
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = 0;
+        c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
     }
     const size_t nl = c->n_lanes.load(std::memory_order_acquire);
     for (size_t i = 0; i < nl; ++i) (void)flgpu_reset_stats(c->lanes[i]);
@@ -652,11 +655,13 @@ int flgpu_debug_set(flgpu_ctx *c, const char *key, int64_t value)
 int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value || !c->dbg) return FLGPU_ERR_INVALID_ARG;
-    // read-only counters of the PNG and lossless WebP decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
+    // read-only counters of the PNG, lossless WebP and GIF decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
-        {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}};
+        {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns},
+        {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
+        {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns}};
     for (const auto &k : counters) {
         if (strcmp(key, k.name)) continue;
         uint64_t sum;

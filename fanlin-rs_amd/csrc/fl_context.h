@@ -28,6 +28,7 @@
 #include "fl_cmyk.h"
 #include "fl_jpeg.h"
 #include "fl_jpeg_tables.h"
+#include "fl_gifdec.h"
 #include "fl_jpegdec.h"
 #include "fl_kernels.h"
 #include "fl_mfma.h"
@@ -226,6 +227,9 @@ struct flgpu_ctx {
     fl::PinnedBuf h_webpjobs;
     uint64_t webp_sources = 0, webp_file_bytes = 0, webp_upload_bytes = 0;
     uint64_t webp_predict_ns = 0, webp_pointwise_ns = 0; // HIP-event time of the two kernels' launches (profile = 1; resolved by flgpu_get_stats)
+    fl::DeviceBuf d_gifdec;                            // GIF decode (fl_gifdec.hip): the composited frames of one animation
+    uint64_t gif_sources = 0, gif_frames = 0, gif_file_bytes = 0, gif_upload_bytes = 0;
+    uint64_t gif_compose_ns = 0;                       // HIP-event time of the compose kernel's launches (profile = 1; resolved by flgpu_get_stats)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
@@ -405,6 +409,12 @@ int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc
 // front; *used = the bytes to upload (the decoder's work area behind them stays on the host).
 int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info);
 int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used);
+// A GIF file (not a source of a batch: it IS one).  The LZW stage runs on the calling thread, outside the context's lock; then blob
+// upload, gif_compose_kernel into scratch, and -- with params -- the frames as one device-resident Rgba8 batch with the same
+// params through run_batch_device: dst->data receives *frames results plan.out_bytes apart.  params == nullptr: the composited
+// frames themselves.
+int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames);
+inline int gif_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kGifParse ? FLGPU_ERR_PARSE : rc == kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 inline int webp_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kWebpParse ? FLGPU_ERR_PARSE : rc == kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FLGPU_ERR_PARSE : rc == kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 

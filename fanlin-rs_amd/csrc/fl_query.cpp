@@ -17,6 +17,7 @@
 #include "fl_png.h"
 #include "fl_pngsrc.h"
 #include "fl_webpsrc.h"
+#include "fl_gifsrc.h"
 #include "fl_webpll.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
@@ -585,6 +586,113 @@ try {
     return FLGPU_OK;
 } FL_ABI_CATCH
 
+/* ---- GIF files -------------------------------------------------------------------------------------------------------- */
+
+extern "C++" { namespace fl { int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames); } } // fl_batch.cpp
+
+static int gif_rc(int rc) { return rc == 0 ? FLGPU_OK : rc == fl::kGifParse ? FLGPU_ERR_PARSE : rc == fl::kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
+
+// the host half into a buffer of this call's own: the blob in `work`, its header in H
+static int gif_blob(const uint8_t *gif, uint64_t n, const fl::GifInfo &I, std::unique_ptr<uint8_t[]> &work, uint8_t *&blob, fl::GifBlobHeader &H)
+{
+    const size_t cap = fl::gif_blob_capacity(I);
+    work.reset(new uint8_t[cap + 16u]);
+    blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
+    return gif_rc(fl::gif_decode_blob(gif, (size_t)n, blob, cap, &H));
+}
+
+int flgpu_gif_info_of(const uint8_t *gif, uint64_t n, flgpu_gif_info *info)
+try {
+    if (!gif || !info) return FLGPU_ERR_INVALID_ARG;
+    fl::GifInfo I;
+    if (fl::gif_parse_info(gif, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    memset(info, 0, sizeof(*info));
+    info->width = I.width; info->height = I.height; info->frames = I.frames; info->has_global_table = I.has_global_table;
+    info->interlaced_frames = I.interlaced_frames; info->transparent_frames = I.transparent_frames;
+    info->disposal_mask = I.disposal_mask; info->max_code_size = I.max_code_size; info->decoded_bytes = I.decoded_bytes;
+    info->supported = I.supported;
+    if (I.supported) { // whether the file is supported is known only behind the LZW stage (an index beyond its colour table)
+        std::unique_ptr<uint8_t[]> work;
+        uint8_t *blob = nullptr;
+        fl::GifBlobHeader H;
+        const int rc = gif_blob(gif, n, I, work, blob, H);
+        if (rc == FLGPU_ERR_UNSUPPORTED) info->supported = 0;
+        else if (rc) return rc;
+    }
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
+static int plan_gif(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_params *p, flgpu_plan *plan,
+                    uint32_t *frames, int *kind, int *out_format)
+{
+    /* (the container only: flgpu_process_gif runs the LZW stage once; as_is serves the file unread, as the reference does) */
+    if (!gif) return FLGPU_ERR_INVALID_ARG;
+    fl::GifInfo info;
+    if (fl::gif_parse_info(gif, (size_t)n, info) != 0) return FLGPU_ERR_PARSE;
+    flgpu_image canvas;
+    memset(&canvas, 0, sizeof(canvas));
+    canvas.width = info.width; canvas.height = info.height; canvas.channels = 4; /* every frame is the Rgba8 canvas (handler.rs:327-333) */
+    if (frames) *frames = info.frames;
+    if (!info.supported) { /* only as_is, which never decodes, gets past this (the canvas may be beyond what a plan can describe) */
+        flgpu_query q;
+        const int rc = flgpu_query_parse(query_string ? query_string : "", &q);
+        if (rc) return rc;
+        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
+        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
+        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
+        memset(plan, 0, sizeof(*plan));
+        *kind = FLGPU_RESULT_AS_IS;
+        if (out_format) *out_format = FLGPU_OUT_KEEP;
+        return FLGPU_OK;
+    }
+    return plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
+}
+
+int flgpu_process_gif_plan(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, uint32_t *frames,
+                           int *result_kind)
+try {
+    flgpu_params p;
+    return plan_gif(gif, n, query_string, accept_flags, &p, plan, frames, result_kind, nullptr);
+} FL_ABI_CATCH
+
+int flgpu_process_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *dst,
+                      flgpu_plan *plan, uint32_t *frames, int *result_kind, int *out_format)
+try {
+    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
+    flgpu_params p;
+    flgpu_plan local;
+    int kind = 0;
+    int rc = plan_gif(gif, n, query_string, accept_flags, &p, plan ? plan : &local, frames, &kind, out_format);
+    if (result_kind) *result_kind = kind;
+    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
+    return fl::run_gif_host(ctx, gif, (size_t)n, &p, dst, frames);
+} FL_ABI_CATCH
+
+int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image *dst, uint32_t *frames)
+try {
+    if (!ctx || !dst || !dst->data || !gif) return FLGPU_ERR_INVALID_ARG;
+    return fl::run_gif_host(ctx, gif, (size_t)n, nullptr, dst, frames);
+} FL_ABI_CATCH
+
+int flgpu_debug_gif_blob(const uint8_t *gif, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!gif || !used) return FLGPU_ERR_INVALID_ARG;
+    fl::GifInfo I;
+    if (fl::gif_parse_info(gif, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
+    *used = fl::gif_blob_capacity(I); // (a bound: the palettes the frames share are known only behind the decode)
+    if (!out) return FLGPU_OK;
+    std::unique_ptr<uint8_t[]> work;
+    uint8_t *blob = nullptr;
+    fl::GifBlobHeader H;
+    const int rc = gif_blob(gif, n, I, work, blob, H);
+    if (rc) return rc;
+    *used = H.total_bytes;
+    if (capacity < H.total_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    memcpy(out, blob, H.total_bytes);
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
 int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t sc, flgpu_plan *plan)
 {
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
@@ -740,7 +848,7 @@ const char *flgpu_strerror(int status)
     case FLGPU_ERR_NO_DEVICE: return "no usable HIP device (there is no CPU fallback)";
     case FLGPU_ERR_OOM: return "out of memory";
     case FLGPU_ERR_DEVICE: return "HIP runtime error";
-    case FLGPU_ERR_PARSE: return "malformed query string or damaged PNG / WebP source";
+    case FLGPU_ERR_PARSE: return "malformed query string or damaged PNG / WebP / GIF source";
     case FLGPU_ERR_BUFFER_TOO_SMALL: return "destination buffer too small";
     case FLGPU_ERR_SHUTDOWN: return "context is shutting down";
     }

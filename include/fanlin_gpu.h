@@ -41,6 +41,8 @@
  *   FLGPU_IMG_PNG_SOURCE / flgpu_process_png     PngDecoder + DynamicImage::from_decoder, src/handler.rs:218-220
  *   FLGPU_IMG_WEBP_SOURCE / flgpu_process_webp   WebPDecoder (lossless VP8L) + DynamicImage::from_decoder and its EXIF orientation,
  *                                                src/handler.rs:205-220
+ *   flgpu_process_gif / flgpu_decode_gif         GifDecoder::new + into_frames().collect_frames() and the per-frame pipeline of
+ *                                                process_gif, src/handler.rs:311-353
  *   flgpu_create / flgpu_destroy        lifetime of handler::State, src/handler.rs:14-21,36-52
  *   flgpu_config.devices / flgpu_plan_shards   the one shared Arc<State> behind all tokio workers, src/main.rs:108-112
  */
@@ -63,7 +65,7 @@ typedef enum flgpu_status {
     FLGPU_ERR_NO_DEVICE = 3,     /* no usable HIP device: the library never falls back to the CPU */
     FLGPU_ERR_OOM = 4,           /* host or device allocation failed */
     FLGPU_ERR_DEVICE = 5,        /* a HIP call failed; see flgpu_last_error() */
-    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400); a PNG or WebP source that is damaged */
+    FLGPU_ERR_PARSE = 6,         /* query string rejected (axum would answer 400); a PNG, WebP or GIF source that is damaged */
     FLGPU_ERR_BUFFER_TOO_SMALL = 7,
     FLGPU_ERR_SHUTDOWN = 8       /* context is being destroyed */
 } flgpu_status;
@@ -434,6 +436,44 @@ int flgpu_process_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, const ch
 int flgpu_process_webp_plan(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
                             int *result_kind);
 
+/* ---- GIF files (src/handler.rs:311-366, process_gif: the gif crate through the image crate) ------------------------------- */
+typedef struct flgpu_gif_info {
+    uint32_t width, height;     /* the logical screen: the canvas every frame is composited onto (handler.rs:327-333 sees Rgba8 frames of this size) */
+    uint32_t frames;
+    uint32_t has_global_table;
+    uint32_t interlaced_frames;
+    uint32_t transparent_frames; /* frames whose graphic control extension names a transparent index */
+    uint32_t disposal_mask;     /* bit k = disposal method k occurs */
+    uint32_t max_code_size;     /* the largest LZW minimum code size of a frame */
+    uint64_t decoded_bytes;     /* frames x width x height x 4: what flgpu_decode_gif writes, and what crosses PCIe on the transform_gif_frames path */
+    uint32_t supported;         /* 1 = flgpu_process_gif / flgpu_decode_gif take it; 0: no frames, a frame without area or reaching outside the
+                                   canvas, an LZW minimum code size outside 2..8, an index at or beyond its colour table's size, more than 4,096
+                                   frames, decoded_bytes above 512 MiB */
+    uint32_t reserved;
+} flgpu_gif_info;
+/* Container and LZW stage of a GIF file (no device needed; the whole file is decoded, since only the indices say whether it is
+ * supported).  FLGPU_ERR_PARSE if the file is damaged: bad signature, truncated before the trailer, a zero canvas side, an LZW
+ * code beyond the next free entry, fewer indices than a frame has pixels, a frame with neither a local nor a global colour table,
+ * an unknown block introducer. */
+int flgpu_gif_info_of(const uint8_t *gif, uint64_t n, flgpu_gif_info *info);
+/* Decodes a supported GIF to its composited Rgba8 frames -- what GifDecoder::into_frames() yields, handler.rs:315-321 -- one after
+ * the other in HOST memory at dst->data (capacity >= decoded_bytes); *frames = their number.  LZW on the calling thread, palette
+ * lookup, de-interlacing and the disposal chain on the device.  Delays are not returned (Frame::new at handler.rs:350 drops them
+ * too). */
+int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image *dst, uint32_t *frames);
+/* process_gif from the file bytes on (handler.rs:311-353), input_format FLGPU_IN_GIF_FRAME (so an empty query is as_is, and the
+ * per-frame pipeline is Nearest, no blur, no orientation, FE_NONE): query parsing, size gate, as_is, then LZW, compositing and
+ * the pipeline of every frame in one pass.  dst->data holds *frames results plan->out_bytes apart (capacity >= frames x
+ * out_bytes, see flgpu_process_gif_plan), *result_kind is FLGPU_RESULT_PIXELS, and the host's GifEncoder follows (handler.rs:
+ * 355-363).  FLGPU_ERR_UNSUPPORTED / FLGPU_ERR_PARSE as above, both before any device work: the host then decodes with its own
+ * decoder (which also substitutes the reference's 1 x 1 grey frames for damaged files; the library does not imitate that) and
+ * hands the frames to flgpu_transform_batch.  A GIF is a batch already: it does not travel through flgpu_transform's queue. */
+int flgpu_process_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags,
+                      flgpu_image *dst, flgpu_plan *plan, uint32_t *frames, int *result_kind, int *out_format);
+/* The same decisions without a device (container walk only, no LZW): plan and *frames, for sizing dst. */
+int flgpu_process_gif_plan(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
+                           uint32_t *frames, int *result_kind);
+
 /* Page-locked host memory for sources / results of flgpu_transform (flag them FLGPU_IMG_PINNED): a decoder that
  * writes straight into such a buffer (zune-jpeg's decode_into) saves the 6 MB staging copy of a 1080p request. */
 void *flgpu_host_alloc(flgpu_ctx *ctx, uint64_t bytes);
@@ -504,7 +544,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines);
  * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
- * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats).
+ * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
+ * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
+ * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
  * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);
@@ -537,6 +579,20 @@ int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint
  * FLGPU_IMG_WEBP_SOURCE -- WebpBlobHeader, the mode / cross-colour images, the palette, the entropy-decoded residual picture.
  * out == NULL: *used = capacity to provide. */
 int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
+
+/* The host half of the GIF decode front end alone (csrc/fl_gifsrc.h): the blob flgpu_process_gif uploads, all fields little-endian
+ * dwords, offsets in bytes from the blob's start:
+ *   header, 32 bytes:       magic "GIF1", canvas width, height, frames, palettes stored, offset of the first palette, offset of the
+ *                           first frame's indices, total bytes
+ *   one record per frame, 32 bytes each, behind the header: x, y, w, h of the frame's rectangle, disposal method (0..7), interlaced
+ *                           flag, palette offset, index offset
+ *   the index bytes of every frame, w x h each, rows in the order the file stores them (an interlaced frame's four passes one
+ *                           after the other: the device undoes the interlace)
+ *   the palettes, 256 dwords each, R | G << 8 | B << 16 | 255 << 24, entries beyond the colour table's size 0; a frame with a
+ *                           transparent index has a copy of its table with that entry 0, 0, 0, 0; a frame whose palette equals the
+ *                           frame before's, or the global table's plain copy, shares it
+ * out == NULL: *used = a capacity that suffices; with out, *used = the blob's bytes. */
+int flgpu_debug_gif_blob(const uint8_t *gif, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
 
 int flgpu_debug_stream_schedulable(uint32_t in_size, uint32_t out_size, uint32_t y0, uint32_t y1, uint32_t *max_live);
 /* Builds the matrix-pipe kernel's tables (csrc/fl_mfma.h) for a source of sw x sh pixels with `channels` interleaved bytes,

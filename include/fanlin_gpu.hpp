@@ -198,6 +198,29 @@ public:
         return out;
     }
 
+    // GifDecoder::new's view of a file (src/handler.rs:311-321), LZW stage included: false if the file is damaged
+    static bool gif_info(const std::vector<uint8_t> &file, flgpu_gif_info &info) { return flgpu_gif_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
+
+    // process_gif from the file bytes on (src/handler.rs:311-353): LZW on this thread, compositing and the per-frame pipeline on the
+    // device.  `data` holds `frames` results plan.out_bytes apart, for the GIF encoder (handler.rs:355-363).  Throws on files the
+    // decoder does not vouch for (FLGPU_ERR_UNSUPPORTED) and on damaged ones (FLGPU_ERR_PARSE): the host then decodes the frames
+    // itself and hands them to flgpu_transform_batch.
+    Processed process_gif(const std::vector<uint8_t> &file, const query::Query &params, uint32_t &frames)
+    {
+        Processed out{};
+        int kind = 0, fmt = 0;
+        check(flgpu_process_gif_plan(file.data(), file.size(), params.text().c_str(), 0, &out.plan, &frames, &kind));
+        out.kind = static_cast<flgpu_result_kind>(kind);
+        out.negotiated = FLGPU_OUT_KEEP;
+        if (out.kind == FLGPU_RESULT_AS_IS) return out;
+        out.data.resize(out.plan.out_bytes * frames);
+        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
+        check(flgpu_process_gif(ctx_, file.data(), file.size(), params.text().c_str(), 0, &dst, &out.plan, &frames, &kind, &fmt), ctx_);
+        out.flags = dst.flags;
+        out.data.resize(dst.bytes);
+        return out;
+    }
+
     flgpu_ctx *raw() { return ctx_; }
 
 private:

@@ -39,6 +39,13 @@ pub struct FlPngInfo { width: u32, height: u32, color_type: u32, bit_depth: u32,
 pub struct FlWebpInfo { width: u32, height: u32, channels: u32, has_alpha: u32, extended: u32, animated: u32, lossless: u32, exif_orientation: u32,
                         transforms: u32, color_cache_bits: u32, prefix_groups: u32, supported: u32 }
 
+#[repr(C)] #[derive(Default, Clone, Copy)]
+/// flgpu_gif_info: what `GifDecoder::new(..).into_frames()` would meet in the file (src/handler.rs:311-321), for the decision "file
+/// bytes to the device, or the reference's own decoder".  `supported` = 0 for files the device decoder does not vouch for
+/// (tests/test_gif_source_host.py checks this mirror).
+pub struct FlGifInfo { width: u32, height: u32, frames: u32, has_global_table: u32, interlaced_frames: u32, transparent_frames: u32,
+                       disposal_mask: u32, max_code_size: u32, decoded_bytes: u64, supported: u32, reserved: u32 }
+
 pub const FE_NONE: u8 = 0;
 pub const FE_JFIF444: u8 = 1;
 pub const FE_WEBP420: u8 = 2;
@@ -88,6 +95,10 @@ extern "C" {
     fn flgpu_process_webp_plan(webp: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
     fn flgpu_process_webp(ctx: *mut c_void, webp: *const u8, n: u64, query: *const c_char, accept: u32,
                           dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
+    fn flgpu_gif_info_of(gif: *const u8, n: u64, info: *mut FlGifInfo) -> c_int;
+    fn flgpu_process_gif_plan(gif: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, frames: *mut u32, kind: *mut c_int) -> c_int;
+    fn flgpu_process_gif(ctx: *mut c_void, gif: *const u8, n: u64, query: *const c_char, accept: u32,
+                         dst: *mut FlImage, plan: *mut FlPlan, frames: *mut u32, kind: *mut c_int, out_format: *mut c_int) -> c_int;
     fn flgpu_transform_batch(ctx: *mut c_void, n: usize, srcs: *const FlImage, ps: *const FlParams, dsts: *mut FlImage) -> c_int;
     fn flgpu_strerror(status: c_int) -> *const c_char;
     fn flgpu_abi_version() -> u32;
@@ -307,6 +318,36 @@ impl Gpu {
         let ps: Vec<FlParams> = frames.iter().map(|_| FlParams { ..p_clone(&p) }).collect();
         check(unsafe { flgpu_transform_batch(self.0, frames.len(), srcs.as_ptr(), ps.as_ptr(), dsts.as_mut_ptr()) })?;
         Ok((plan, outs))
+    }
+
+    /// Container and LZW stage of a GIF file, or None if it is damaged (then the reference's decoder words the error).
+    pub fn gif_info(original: &[u8]) -> Option<FlGifInfo> {
+        let mut info = FlGifInfo::default();
+        if unsafe { flgpu_gif_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
+    }
+
+    /// `process_gif` FROM THE FILE BYTES ON (src/handler.rs:311-353 in one call): LZW on this thread, palette lookup, de-interlacing,
+    /// the disposal chain and the per-frame pipeline in one device pass; what crosses PCIe is one index byte per pixel of each
+    /// frame's rectangle, not `frames x w x h x 4`.  Ok(None): RESULT_AS_IS (serve the file).  Otherwise the plan and one Rgba8 / La8
+    /// buffer per frame, in frame order, for the GIF encoder (lines 355-363; delays are dropped there too).  A file the decoder
+    /// does not vouch for or cannot read (ERR_UNSUPPORTED / ERR_PARSE) goes the old way: `decode_frames` is the reference's own
+    /// `GifDecoder::new(..).into_frames().collect_frames()` with its 1 x 1 grey substitute, and `transform_gif_frames` follows.
+    pub fn process_gif(&self, original: &[u8], query: &str, q: &crate::query::Query,
+                       decode_frames: impl FnOnce(&[u8]) -> Vec<image::RgbaImage>)
+        -> Result<Option<(FlPlan, Vec<Vec<u8>>)>, Box<dyn std::error::Error>>
+    {
+        let qs = std::ffi::CString::new(query)?;
+        let (mut plan, mut kind, mut fmt, mut frames) = (FlPlan::default(), 0 as c_int, 0 as c_int, 0u32);
+        let rc = unsafe { flgpu_process_gif_plan(original.as_ptr(), original.len() as u64, qs.as_ptr(), 0, &mut plan, &mut frames, &mut kind) };
+        if rc == 0 && kind == RESULT_AS_IS { return Ok(None); }
+        if rc == 0 {
+            let mut out = vec![0u8; plan.out_bytes as usize * frames as usize];
+            let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
+            let rc = unsafe { flgpu_process_gif(self.0, original.as_ptr(), original.len() as u64, qs.as_ptr(), 0, &mut dst, &mut plan, &mut frames, &mut kind, &mut fmt) };
+            if rc == 0 { return Ok(Some((plan, out.chunks(plan.out_bytes as usize).map(|c| c.to_vec()).collect()))); }
+            if rc != ERR_UNSUPPORTED && rc != ERR_PARSE { check(rc)?; }
+        } else if rc != ERR_UNSUPPORTED && rc != ERR_PARSE { check(rc)?; }
+        self.transform_gif_frames(&decode_frames(original), q).map(Some)
     }
 
     /// The pixels of `Outcome::Device` (front_end 0) as the `DynamicImage` the rest of process_image expects.
