@@ -33,8 +33,18 @@ ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
+ENCODE_GIF = 0x400  # accept_flags bit: State.process_gif finishes the image/gif body on the device where every frame has at most 256 colours
 IN_OTHER, IN_JPEG, IN_PNG, IN_WEBP, IN_GIF_FRAME = 0, 1, 2, 3, 4
 RESULT_AS_IS, RESULT_JPEG_STREAM, RESULT_WEBP_PLANES, RESULT_PIXELS, RESULT_PNG_STREAM, RESULT_WEBP_STREAM = 0, 1, 2, 3, 4, 5
+RESULT_GIF_STREAM = 6  # process_gif with ENCODE_GIF only: one file from all the frames, not a per-picture front end
+GIF_SEG_INDICES = 2048  # csrc/fl_gif.h kGifSegIndices: indices per independently coded LZW segment
+
+
+def gif_max_frame_bytes(pixels: int) -> int:
+    """csrc/fl_gif.h gif_max_frame_bytes: control extension 8 + descriptor 10 + table 768 + code size 1 + the data (a clear code,
+    one code per index, every segment's closing code, all at 12 bits) in sub-blocks of 255 + the terminator."""
+    d = (12 * (pixels + 1 + (pixels + GIF_SEG_INDICES - 1) // GIF_SEG_INDICES) + 7) // 8
+    return 8 + 10 + 768 + 1 + d + (d + 254) // 255 + 1
 _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG,
               RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
@@ -810,23 +820,33 @@ class State:
 
     def process_gif(self, data: bytes, query_string: str, content: "Format" = None):
         """process_gif from the file bytes on: (mime, kind, payload); payload is the file itself for AS_IS, else the list of the
-        frames' pixels (out_h, out_w, out_c), in frame order, for the host's GIF encoder."""
+        frames' pixels (out_h, out_w, out_c), in frame order, for the host's GIF encoder.  With ENCODE_GIF in the content flags
+        and no frame above 256 colours the payload is the finished file (bytes, RESULT_GIF_STREAM)."""
         plan, kind, fmt, frames = flgpu_plan(), C.c_int(), C.c_int(), C.c_uint32()
         flags = content.flags if content else 0
         qs = query_string.encode()
         _check(self._lib.flgpu_process_gif_plan(data, len(data), qs, flags, C.byref(plan), C.byref(frames), C.byref(kind)))
         if kind.value == RESULT_AS_IS:
             return "image/gif", RESULT_AS_IS, data
-        out = np.empty(max(int(plan.out_bytes) * frames.value, 1), dtype=np.uint8)
+        size = int(plan.out_bytes) * frames.value
+        if kind.value == RESULT_GIF_STREAM:  # either outcome fits
+            size = 64 + frames.value * int(plan.max_out_bytes)
+        out = np.empty(max(size, 1), dtype=np.uint8)
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
         _check(self._lib.flgpu_process_gif(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(frames), C.byref(kind),
                                            C.byref(fmt)), self._ctx)
+        if kind.value == RESULT_GIF_STREAM:
+            return "image/gif", kind.value, out[: int(dst.bytes)].tobytes()
         px = out[: int(plan.out_bytes) * frames.value].reshape(frames.value, plan.out_h, plan.out_w, plan.out_c)
         return "image/gif", kind.value, [px[f] for f in range(frames.value)]
 
     def gif_counters(self) -> dict:
         """The GIF decode front end's counters (flgpu_debug_get)."""
         return {k: self.debug_get(k) for k in ("gif_sources", "gif_frames", "gif_file_bytes", "gif_upload_bytes")}
+
+    def gif_encode_counters(self) -> dict:
+        """The GIF encoder's counters (flgpu_debug_get): files finished on the device, their bytes, files handed back as pixels."""
+        return {k: self.debug_get(k) for k in ("gif_encoded", "gif_encode_fallbacks", "gif_encoded_bytes")}
 
     def webp_counters(self) -> dict:
         """The lossless WebP decode front end's counters (flgpu_debug_get)."""

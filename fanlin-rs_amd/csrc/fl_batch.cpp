@@ -1558,7 +1558,39 @@ int decode_gif_sources(flgpu_ctx *c, const GifBlobHeader &H, const uint8_t *blob
     return FLGPU_OK;
 }
 
-int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames)
+// The encode phase behind run_batch_device: the frames lie in d_out at `pitch`; the six kernels of fl_gif.hip leave the file and
+// its status record in scratch.  Enqueues only.
+static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t frames, size_t pitch, uint64_t frame_max, const uint8_t **file, hipStream_t st)
+{
+    GifEncJob J;
+    memset(&J, 0, sizeof(J));
+    J.w = plan.out_w; J.h = plan.out_h; J.c = plan.out_c; J.frames = frames;
+    J.px = plan.out_w * plan.out_h; J.nseg = (uint32_t)gif_segments(J.px);
+    J.pixels = static_cast<const uint8_t *>(c->d_out.p); J.pix_pitch = pitch;
+    J.idx_pitch = align_up((size_t)J.px, 16) + 16; J.body_pitch = align_up((size_t)frame_max, 16);
+    const size_t segs = (size_t)frames * J.nseg;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
+    const size_t o_status = carve(16), o_frec = carve((size_t)frames * kGifFrameRec * 4), o_ckeys = carve((size_t)frames * kGifColourSlots * 4),
+                 o_cvals = carve((size_t)frames * kGifColourSlots * 4), o_idx = carve((size_t)frames * J.idx_pitch),
+                 o_segs = carve(segs * kGifSegDwords * 4), o_bits = carve(segs * 4), o_off = carve(segs * 4),
+                 o_bodies = carve((size_t)frames * J.body_pitch), o_file = carve((size_t)gif_max_file_bytes(frames, frame_max));
+    FL_HIP(c, c->d_gifenc.reserve(off), "GIF encode scratch");
+    FL_HIP(c, c->h_gifstat.reserve(16), "pinned GIF encode status");
+    uint8_t *base = static_cast<uint8_t *>(c->d_gifenc.p);
+    J.status = reinterpret_cast<uint32_t *>(base + o_status); J.frec = reinterpret_cast<uint32_t *>(base + o_frec);
+    J.ckeys = reinterpret_cast<uint32_t *>(base + o_ckeys); J.cvals = reinterpret_cast<uint32_t *>(base + o_cvals);
+    J.indices = base + o_idx; J.segs = reinterpret_cast<uint32_t *>(base + o_segs);
+    J.seg_bits = reinterpret_cast<uint32_t *>(base + o_bits); J.seg_off = reinterpret_cast<uint32_t *>(base + o_off);
+    J.bodies = base + o_bodies; J.file = base + o_file;
+    *file = J.file;
+    FL_HIP(c, hipMemsetAsync(J.status, 0, 16, st), "GIF encode status");
+    { ProfileScope ps(c, st, 6); FL_HIP(c, launch_gif_encode(J, st), "GIF encode kernels"); }
+    FL_HIP(c, hipMemcpyAsync(c->h_gifstat.p, J.status, 16, hipMemcpyDeviceToHost, st), "GIF encode status D2H");
+    return FLGPU_OK;
+}
+
+int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind)
 {
     if (!gif || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
     // the serial half on the calling thread, before any device work and outside the context's lock: callers decode side by side
@@ -1569,10 +1601,15 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
     memset(&plan, 0, sizeof(plan));
     const size_t canvas = (size_t)info.width * info.height * 4u;
     if (params) {
-        if (fe_encoded(params->front_end)) return FLGPU_ERR_INVALID_ARG; // (GIF frames leave as pixels: the GIF encoder is the host's)
+        if (fe_encoded(params->front_end)) return FLGPU_ERR_INVALID_ARG; // (GIF encode is not a per-picture front end: one file comes from all the frames, FLGPU_ENCODE_GIF below)
         if (int rc = flgpu_plan_output(params, info.width, info.height, 4, &plan)) return rc;
     }
     const size_t each = params ? (size_t)plan.out_bytes : canvas;
+    // FLGPU_ENCODE_GIF: the file is attempted; the destination holds either outcome
+    const bool encode = params && (accept_flags & FLGPU_ENCODE_GIF) && gif_encodable(plan.out_w, plan.out_h, plan.out_c, info.frames, plan.out_bytes);
+    const uint64_t frame_max = encode ? gif_max_frame_bytes((uint64_t)plan.out_w * plan.out_h) : 0;
+    if (result_kind) *result_kind = FLGPU_RESULT_PIXELS;
+    if (encode && dst->capacity < gif_max_file_bytes(info.frames, std::max<uint64_t>(frame_max, plan.out_bytes))) return FLGPU_ERR_BUFFER_TOO_SMALL;
     if (dst->capacity < (uint64_t)each * info.frames) return FLGPU_ERR_BUFFER_TOO_SMALL;
     std::vector<uint8_t> blob(gif_blob_capacity(info));
     GifBlobHeader H;
@@ -1604,7 +1641,7 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
     // the per-frame pipeline: every frame the same request, one device batch
     const size_t pitch = align_up(plan.max_out_bytes, 256);
     FL_HIP(s, s->d_out.reserve(pitch * H.frames), "device output staging");
-    FL_HIP(s, s->h_stage_out.reserve(pitch * H.frames), "pinned output staging");
+    FL_HIP(s, s->h_stage_out.reserve(std::max<size_t>(pitch * H.frames, encode ? (size_t)gif_max_file_bytes(H.frames, frame_max) : 0)), "pinned output staging");
     std::vector<flgpu_image> ddst(H.frames);
     for (uint32_t f = 0; f < H.frames; ++f) {
         memset(&ddst[f], 0, sizeof(ddst[f]));
@@ -1613,6 +1650,34 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
     }
     int rc = run_batch_device(s, H.frames, dsrc.data(), params, true, ddst.data(), st);
     if (rc) return rc;
+    if (encode) {
+        // the device decides: one small status record comes back, then the file or -- a frame above 256 colours -- the pixels
+        const uint8_t *file = nullptr;
+        rc = encode_gif_frames(s, plan, H.frames, pitch, frame_max, &file, st);
+        if (rc) return rc;
+        rc = collect_results(s, H.frames, ddst.data(), st);
+        if (rc) return rc;
+        const uint32_t *status = static_cast<const uint32_t *>(s->h_gifstat.p);
+        if (!status[0]) {
+            const uint64_t bytes = status[1];
+            if (bytes <= kGifFileHead || bytes > gif_max_file_bytes(H.frames, frame_max)) { s->set_error("GIF encode: file length outside its bounds"); return FLGPU_ERR_DEVICE; }
+            FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, file, bytes, hipMemcpyDeviceToHost, st), "D2H");
+            FL_HIP(s, hipStreamSynchronize(st), "GIF encode sync");
+            memcpy(dst->data, s->h_stage_out.p, bytes);
+            dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = FLGPU_IMG_ENCODED;
+            dst->bytes = bytes;
+            s->gif_encoded++; s->gif_encoded_bytes += bytes;
+            if (result_kind) *result_kind = FLGPU_RESULT_GIF_STREAM;
+            return FLGPU_OK;
+        }
+        s->gif_encode_fallbacks++;
+        FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, s->d_out.p, pitch * H.frames, hipMemcpyDeviceToHost, st), "D2H");
+        FL_HIP(s, hipStreamSynchronize(st), "GIF frames sync");
+        for (uint32_t f = 0; f < H.frames; ++f) memcpy(dst->data + each * f, static_cast<const uint8_t *>(s->h_stage_out.p) + pitch * f, each);
+        dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = ddst[0].flags;
+        dst->bytes = (uint64_t)each * H.frames;
+        return FLGPU_OK;
+    }
     FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, s->d_out.p, pitch * H.frames, hipMemcpyDeviceToHost, st), "D2H");
     rc = collect_results(s, H.frames, ddst.data(), st);
     if (rc) return rc;

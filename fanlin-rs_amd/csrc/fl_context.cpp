@@ -354,6 +354,7 @@ void resolve_pending(flgpu_ctx *c)
             else if (p.kind == 3) c->webp_predict_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 4) c->webp_pointwise_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 5) c->gif_compose_ns += (uint64_t)((double)ms * 1e6);
+            else if (p.kind == 6) c->gif_encode_ns += (uint64_t)((double)ms * 1e6);
             else c->stats.frontend_ms += ms;
         }
         c->event_pool.push_back(p.a);
@@ -518,6 +519,8 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
     c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();
     c->d_gifdec.release();
+    c->d_gifenc.release();
+    c->h_gifstat.release();
     release_cmyk(c);
     c->h_results.release();
     c->h_stage_in.release(); c->h_stage_out.release();
@@ -632,6 +635,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = 0;
         c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
+        c->gif_encoded = c->gif_encode_fallbacks = c->gif_encoded_bytes = c->gif_encode_ns = 0;
     }
     const size_t nl = c->n_lanes.load(std::memory_order_acquire);
     for (size_t i = 0; i < nl; ++i) (void)flgpu_reset_stats(c->lanes[i]);
@@ -661,7 +665,9 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
-        {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns}};
+        {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns},
+        {"gif_encoded", &flgpu_ctx::gif_encoded}, {"gif_encode_fallbacks", &flgpu_ctx::gif_encode_fallbacks}, {"gif_encoded_bytes", &flgpu_ctx::gif_encoded_bytes},
+        {"gif_encode_ns", &flgpu_ctx::gif_encode_ns}};
     for (const auto &k : counters) {
         if (strcmp(key, k.name)) continue;
         uint64_t sum;

@@ -28,6 +28,7 @@
 #include "fl_cmyk.h"
 #include "fl_jpeg.h"
 #include "fl_jpeg_tables.h"
+#include "fl_gif.h"
 #include "fl_gifdec.h"
 #include "fl_jpegdec.h"
 #include "fl_kernels.h"
@@ -230,6 +231,10 @@ struct flgpu_ctx {
     fl::DeviceBuf d_gifdec;                            // GIF decode (fl_gifdec.hip): the composited frames of one animation
     uint64_t gif_sources = 0, gif_frames = 0, gif_file_bytes = 0, gif_upload_bytes = 0;
     uint64_t gif_compose_ns = 0;                       // HIP-event time of the compose kernel's launches (profile = 1; resolved by flgpu_get_stats)
+    fl::DeviceBuf d_gifenc;                            // GIF encode (fl_gif.hip): status, frame records, colour tables, indices, segments, frame bodies, the file
+    fl::PinnedBuf h_gifstat;                           // its status record {a frame above 256 colours, file bytes}
+    uint64_t gif_encoded = 0, gif_encode_fallbacks = 0, gif_encoded_bytes = 0; // files finished on the device, files handed back as pixels, bytes of the former
+    uint64_t gif_encode_ns = 0;                        // HIP-event time of the encode kernels' launches (profile = 1)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
@@ -412,8 +417,9 @@ int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, siz
 // A GIF file (not a source of a batch: it IS one).  The LZW stage runs on the calling thread, outside the context's lock; then blob
 // upload, gif_compose_kernel into scratch, and -- with params -- the frames as one device-resident Rgba8 batch with the same
 // params through run_batch_device: dst->data receives *frames results plan.out_bytes apart.  params == nullptr: the composited
-// frames themselves.
-int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames);
+// frames themselves.  With FLGPU_ENCODE_GIF in accept_flags the encoder (fl_gif.hip) runs behind the batch and dst receives the
+// finished file, or -- a frame above 256 colours -- the same pixels; *result_kind says which.
+int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind);
 inline int gif_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kGifParse ? FLGPU_ERR_PARSE : rc == kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 inline int webp_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kWebpParse ? FLGPU_ERR_PARSE : rc == kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FLGPU_ERR_PARSE : rc == kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }

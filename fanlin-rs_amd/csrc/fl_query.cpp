@@ -18,6 +18,7 @@
 #include "fl_pngsrc.h"
 #include "fl_webpsrc.h"
 #include "fl_gifsrc.h"
+#include "fl_gif.h"
 #include "fl_webpll.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
@@ -588,7 +589,7 @@ try {
 
 /* ---- GIF files -------------------------------------------------------------------------------------------------------- */
 
-extern "C++" { namespace fl { int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, flgpu_image *dst, uint32_t *frames); } } // fl_batch.cpp
+extern "C++" { namespace fl { int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind); } } // fl_batch.cpp
 
 static int gif_rc(int rc) { return rc == 0 ? FLGPU_OK : rc == fl::kGifParse ? FLGPU_ERR_PARSE : rc == fl::kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 
@@ -645,7 +646,15 @@ static int plan_gif(const uint8_t *gif, uint64_t n, const char *query_string, ui
         if (out_format) *out_format = FLGPU_OUT_KEEP;
         return FLGPU_OK;
     }
-    return plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
+    const int rc = plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
+    /* FLGPU_ENCODE_GIF: the finished file is what will be attempted (a frame above 256 colours turns it back into pixels); the
+       per-frame parameters stay as they are, one file comes from all the frames */
+    if (rc == FLGPU_OK && *kind == FLGPU_RESULT_PIXELS && (accept_flags & FLGPU_ENCODE_GIF) &&
+        fl::gif_encodable(plan->out_w, plan->out_h, plan->out_c, info.frames, plan->out_bytes)) {
+        *kind = FLGPU_RESULT_GIF_STREAM;
+        plan->max_out_bytes = std::max<uint64_t>(plan->out_bytes, fl::gif_max_frame_bytes((uint64_t)plan->out_w * plan->out_h));
+    }
+    return rc;
 }
 
 int flgpu_process_gif_plan(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, uint32_t *frames,
@@ -665,13 +674,15 @@ try {
     int rc = plan_gif(gif, n, query_string, accept_flags, &p, plan ? plan : &local, frames, &kind, out_format);
     if (result_kind) *result_kind = kind;
     if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    return fl::run_gif_host(ctx, gif, (size_t)n, &p, dst, frames);
+    rc = fl::run_gif_host(ctx, gif, (size_t)n, &p, accept_flags, dst, frames, &kind);
+    if (result_kind) *result_kind = kind; /* what happened: the file, or the pixels */
+    return rc;
 } FL_ABI_CATCH
 
 int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image *dst, uint32_t *frames)
 try {
     if (!ctx || !dst || !dst->data || !gif) return FLGPU_ERR_INVALID_ARG;
-    return fl::run_gif_host(ctx, gif, (size_t)n, nullptr, dst, frames);
+    return fl::run_gif_host(ctx, gif, (size_t)n, nullptr, 0, dst, frames, nullptr);
 } FL_ABI_CATCH
 
 int flgpu_debug_gif_blob(const uint8_t *gif, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)

@@ -137,6 +137,10 @@ typedef enum flgpu_front_end {
  * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs at quality 100 (src/handler.rs:286-292).  Without it such requests
  * return pixels, as before. */
 #define FLGPU_ENCODE_WEBP_LOSSLESS 0x200u
+/* Not a content::Format bit: the caller wants flgpu_process_gif to finish the image/gif body (FLGPU_RESULT_GIF_STREAM) where
+ * every frame has at most 256 colours -- the exact-palette branch of the reference's GifEncoder (src/handler.rs:355-364).
+ * Without it, and for files with a frame above 256 colours, the frames return as pixels, as before. */
+#define FLGPU_ENCODE_GIF 0x400u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -341,7 +345,7 @@ int flgpu_transform(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *
  * Errors: FLGPU_ERR_PARSE where axum answers 400 (bad query, or the size gate of src/main.rs:134-138). */
 typedef enum flgpu_input_format { FLGPU_IN_OTHER = 0, FLGPU_IN_JPEG = 1, FLGPU_IN_PNG = 2, FLGPU_IN_WEBP = 3, FLGPU_IN_GIF_FRAME = 4 } flgpu_input_format;
 typedef enum flgpu_result_kind { FLGPU_RESULT_AS_IS = 0, FLGPU_RESULT_JPEG_STREAM = 1, FLGPU_RESULT_WEBP_PLANES = 2, FLGPU_RESULT_PIXELS = 3, FLGPU_RESULT_PNG_STREAM = 4,
-                                 FLGPU_RESULT_WEBP_STREAM = 5 } flgpu_result_kind;
+                                 FLGPU_RESULT_WEBP_STREAM = 5, FLGPU_RESULT_GIF_STREAM = 6 /* flgpu_process_gif with FLGPU_ENCODE_GIF only */ } flgpu_result_kind;
 int flgpu_process_image(flgpu_ctx *ctx, const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string,
                         uint32_t accept_flags, int input_format, flgpu_image *dst, flgpu_plan *plan, int *result_kind,
                         int *out_format);
@@ -467,7 +471,23 @@ int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image
  * out_bytes, see flgpu_process_gif_plan), *result_kind is FLGPU_RESULT_PIXELS, and the host's GifEncoder follows (handler.rs:
  * 355-363).  FLGPU_ERR_UNSUPPORTED / FLGPU_ERR_PARSE as above, both before any device work: the host then decodes with its own
  * decoder (which also substitutes the reference's 1 x 1 grey frames for damaged files; the library does not imitate that) and
- * hands the frames to flgpu_transform_batch.  A GIF is a batch already: it does not travel through flgpu_transform's queue. */
+ * hands the frames to flgpu_transform_batch.  A GIF is a batch already: it does not travel through flgpu_transform's queue.
+ *
+ * With FLGPU_ENCODE_GIF in accept_flags the device also writes what GifEncoder::encode_frames writes for frames of at most 256
+ * colours (image 0.25.6 over gif 0.13.1, Frame::from_rgba_speed: alpha != 0 becomes 255, the palette is the distinct r, g, b, a
+ * tuples in ascending order padded with zeros to 2 .. 256 entries, the transparent index that of the last pixel with alpha 0;
+ * GIF89a, no global table, NETSCAPE2.0 loop count 0, every frame a full-canvas image with a local table, disposal 1, delay 0).
+ * The per-frame parameters are the same; flgpu_process_gif_plan reports FLGPU_RESULT_GIF_STREAM (what will be attempted),
+ * plan->out_bytes stays the pixel bytes of a frame and plan->max_out_bytes = max(out_bytes, worst case of one encoded frame).
+ * dst->capacity must be >= 64 + frames x max_out_bytes (FLGPU_ERR_BUFFER_TOO_SMALL otherwise, before any device work), which
+ * holds either outcome.  *result_kind says what happened:
+ *   GIF_STREAM  dst->data holds the finished file, dst->bytes long, dst->flags has FLGPU_IMG_ENCODED
+ *   PIXELS      a frame has more than 256 colours (the reference runs NeuQuant there; the library does not restate it): bytes,
+ *               flags and layout exactly as without the bit
+ * The device decides; the host reads a status record of two words and downloads the file or the pixels, never both.  The LZW
+ * stream is not the gif crate's byte for byte (every 2,048 indices it restarts from a clear code, so that segments are coded
+ * side by side); it decodes to exactly the frames' indices.  Outputs that are not LumaA8 / Rgba8, sides above 65,535 and
+ * files whose worst case reaches 2 GiB are planned and returned as PIXELS. */
 int flgpu_process_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags,
                       flgpu_image *dst, flgpu_plan *plan, uint32_t *frames, int *result_kind, int *out_format);
 /* The same decisions without a device (container walk only, no LZW): plan and *frames, for sizing dst. */
@@ -546,7 +566,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
  * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
- * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time.
+ * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
+ * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files
+ * it handed back as pixels (a frame above 256 colours), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
  * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);

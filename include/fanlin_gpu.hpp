@@ -82,6 +82,9 @@ public:
     // not a content::Format bit: the library finishes lossless image/webp bodies, the WebP arm at quality 100
     // (FLGPU_RESULT_WEBP_STREAM)
     void encode_webp_lossless() { flags_ |= FLGPU_ENCODE_WEBP_LOSSLESS; }
+    // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours
+    // (FLGPU_RESULT_GIF_STREAM)
+    void encode_gif() { flags_ |= FLGPU_ENCODE_GIF; }
     uint32_t flags() const { return flags_; }
 
 private:
@@ -202,20 +205,23 @@ public:
     static bool gif_info(const std::vector<uint8_t> &file, flgpu_gif_info &info) { return flgpu_gif_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
 
     // process_gif from the file bytes on (src/handler.rs:311-353): LZW on this thread, compositing and the per-frame pipeline on the
-    // device.  `data` holds `frames` results plan.out_bytes apart, for the GIF encoder (handler.rs:355-363).  Throws on files the
-    // decoder does not vouch for (FLGPU_ERR_UNSUPPORTED) and on damaged ones (FLGPU_ERR_PARSE): the host then decodes the frames
-    // itself and hands them to flgpu_transform_batch.
-    Processed process_gif(const std::vector<uint8_t> &file, const query::Query &params, uint32_t &frames)
+    // device.  `data` holds `frames` results plan.out_bytes apart, for the GIF encoder (handler.rs:355-363); with encode_gif() in
+    // `accepted` and no frame above 256 colours it holds the finished file instead (kind FLGPU_RESULT_GIF_STREAM; handler.rs:355-364
+    // on the device too).  Throws on files the decoder does not vouch for (FLGPU_ERR_UNSUPPORTED) and on damaged ones
+    // (FLGPU_ERR_PARSE): the host then decodes the frames itself and hands them to flgpu_transform_batch.
+    Processed process_gif(const std::vector<uint8_t> &file, const query::Query &params, uint32_t &frames, const content::Format &accepted = content::Format())
     {
         Processed out{};
         int kind = 0, fmt = 0;
-        check(flgpu_process_gif_plan(file.data(), file.size(), params.text().c_str(), 0, &out.plan, &frames, &kind));
+        check(flgpu_process_gif_plan(file.data(), file.size(), params.text().c_str(), accepted.flags(), &out.plan, &frames, &kind));
         out.kind = static_cast<flgpu_result_kind>(kind);
         out.negotiated = FLGPU_OUT_KEEP;
         if (out.kind == FLGPU_RESULT_AS_IS) return out;
-        out.data.resize(out.plan.out_bytes * frames);
+        // (a planned stream may still come back as pixels: 64 + frames x max_out_bytes holds either)
+        out.data.resize(out.kind == FLGPU_RESULT_GIF_STREAM ? 64 + out.plan.max_out_bytes * frames : out.plan.out_bytes * frames);
         flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
-        check(flgpu_process_gif(ctx_, file.data(), file.size(), params.text().c_str(), 0, &dst, &out.plan, &frames, &kind, &fmt), ctx_);
+        check(flgpu_process_gif(ctx_, file.data(), file.size(), params.text().c_str(), accepted.flags(), &dst, &out.plan, &frames, &kind, &fmt), ctx_);
+        out.kind = static_cast<flgpu_result_kind>(kind); // what happened
         out.flags = dst.flags;
         out.data.resize(dst.bytes);
         return out;

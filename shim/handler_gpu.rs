@@ -65,12 +65,15 @@ pub const ACCEPT_AVIF: u32 = 2;
 pub const ENCODE_PNG: u32 = 0x100;
 // not a content::Format bit: finish lossless image/webp bodies on the device, the WebP arm at quality 100 (RESULT_WEBP_STREAM)
 pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
+// not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours (RESULT_GIF_STREAM)
+pub const ENCODE_GIF: u32 = 0x400;
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
 pub const RESULT_WEBP_PLANES: c_int = 2;
 pub const RESULT_PIXELS: c_int = 3;
 pub const RESULT_PNG_STREAM: c_int = 4;
 pub const RESULT_WEBP_STREAM: c_int = 5;
+pub const RESULT_GIF_STREAM: c_int = 6;
 const ERR_UNSUPPORTED: c_int = 2; // FLGPU_ERR_UNSUPPORTED: a stream the device decoder does not cover
 const ERR_PARSE: c_int = 6;       // FLGPU_ERR_PARSE: a rejected query, or a damaged PNG source
 const CMYK_INPUT_YCCK: u32 = 1;
@@ -119,6 +122,14 @@ pub enum Outcome {
     /// a pixel layout the device path does not take (16-bit / float `DynamicImage`s from 16-bit PNGs,
     /// src/handler.rs:219): the caller keeps the reference's own CPU code for THIS request, exactly as before
     KeepCpuPath,
+}
+
+/// What `Gpu::process_gif` hands back.
+pub enum GifOutcome {
+    /// the finished image/gif body: `GifEncoder::encode_frames` (src/handler.rs:355-364) ran on the device too
+    Body(Vec<u8>),
+    /// the plan and one pixel buffer per frame, for the host's `GifEncoder`
+    Frames(FlPlan, Vec<Vec<u8>>),
 }
 
 impl Gpu {
@@ -326,28 +337,33 @@ impl Gpu {
         if unsafe { flgpu_gif_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
     }
 
-    /// `process_gif` FROM THE FILE BYTES ON (src/handler.rs:311-353 in one call): LZW on this thread, palette lookup, de-interlacing,
-    /// the disposal chain and the per-frame pipeline in one device pass; what crosses PCIe is one index byte per pixel of each
-    /// frame's rectangle, not `frames x w x h x 4`.  Ok(None): RESULT_AS_IS (serve the file).  Otherwise the plan and one Rgba8 / La8
-    /// buffer per frame, in frame order, for the GIF encoder (lines 355-363; delays are dropped there too).  A file the decoder
-    /// does not vouch for or cannot read (ERR_UNSUPPORTED / ERR_PARSE) goes the old way: `decode_frames` is the reference's own
+    /// `process_gif` FROM THE FILE BYTES ON (src/handler.rs:311-364 in one call): LZW on this thread, palette lookup, de-interlacing,
+    /// the disposal chain, the per-frame pipeline and -- ENCODE_GIF -- the GIF encoder in one device pass; what crosses PCIe is one
+    /// index byte per pixel of each frame's rectangle on the way in and the finished file on the way out.  Ok(None): RESULT_AS_IS
+    /// (serve the file).  GifOutcome::Body: the finished image/gif body (no frame above 256 colours).  GifOutcome::Frames: the plan
+    /// and one Rgba8 / La8 buffer per frame, in frame order, for the GIF encoder (lines 355-363; delays are dropped there too): a
+    /// frame above 256 colours, where the encoder runs NeuQuant.  A file the decoder does not vouch for or cannot read
+    /// (ERR_UNSUPPORTED / ERR_PARSE) goes the old way: `decode_frames` is the reference's own
     /// `GifDecoder::new(..).into_frames().collect_frames()` with its 1 x 1 grey substitute, and `transform_gif_frames` follows.
     pub fn process_gif(&self, original: &[u8], query: &str, q: &crate::query::Query,
                        decode_frames: impl FnOnce(&[u8]) -> Vec<image::RgbaImage>)
-        -> Result<Option<(FlPlan, Vec<Vec<u8>>)>, Box<dyn std::error::Error>>
+        -> Result<Option<GifOutcome>, Box<dyn std::error::Error>>
     {
         let qs = std::ffi::CString::new(query)?;
         let (mut plan, mut kind, mut fmt, mut frames) = (FlPlan::default(), 0 as c_int, 0 as c_int, 0u32);
-        let rc = unsafe { flgpu_process_gif_plan(original.as_ptr(), original.len() as u64, qs.as_ptr(), 0, &mut plan, &mut frames, &mut kind) };
+        let rc = unsafe { flgpu_process_gif_plan(original.as_ptr(), original.len() as u64, qs.as_ptr(), ENCODE_GIF, &mut plan, &mut frames, &mut kind) };
         if rc == 0 && kind == RESULT_AS_IS { return Ok(None); }
         if rc == 0 {
-            let mut out = vec![0u8; plan.out_bytes as usize * frames as usize];
+            // (a planned stream may still come back as pixels: 64 + frames x max_out_bytes holds either)
+            let cap = if kind == RESULT_GIF_STREAM { 64 + plan.max_out_bytes as usize * frames as usize } else { plan.out_bytes as usize * frames as usize };
+            let mut out = vec![0u8; cap];
             let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
-            let rc = unsafe { flgpu_process_gif(self.0, original.as_ptr(), original.len() as u64, qs.as_ptr(), 0, &mut dst, &mut plan, &mut frames, &mut kind, &mut fmt) };
-            if rc == 0 { return Ok(Some((plan, out.chunks(plan.out_bytes as usize).map(|c| c.to_vec()).collect()))); }
+            let rc = unsafe { flgpu_process_gif(self.0, original.as_ptr(), original.len() as u64, qs.as_ptr(), ENCODE_GIF, &mut dst, &mut plan, &mut frames, &mut kind, &mut fmt) };
+            if rc == 0 && kind == RESULT_GIF_STREAM { out.truncate(dst.bytes as usize); return Ok(Some(GifOutcome::Body(out))); }
+            if rc == 0 { return Ok(Some(GifOutcome::Frames(plan, out[..dst.bytes as usize].chunks(plan.out_bytes as usize).map(|c| c.to_vec()).collect()))); }
             if rc != ERR_UNSUPPORTED && rc != ERR_PARSE { check(rc)?; }
         } else if rc != ERR_UNSUPPORTED && rc != ERR_PARSE { check(rc)?; }
-        self.transform_gif_frames(&decode_frames(original), q).map(Some)
+        self.transform_gif_frames(&decode_frames(original), q).map(|(plan, frames)| Some(GifOutcome::Frames(plan, frames)))
     }
 
     /// The pixels of `Outcome::Device` (front_end 0) as the `DynamicImage` the rest of process_image expects.
