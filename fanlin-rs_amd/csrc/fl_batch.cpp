@@ -1164,555 +1164,6 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
 
 namespace fl {
 
-// What a JPEG file's own header may make this library allocate is decided here, before anything is allocated: the header
-// must describe the picture the caller announced, the decoded picture must respect the limit the reference's decoder runs
-// under (image::Limits::default(): max_alloc 512 MiB -- ImageReader rejects larger pictures, handler.rs:205-220), and the file
-// must be long enough to hold that many blocks at all (a block costs at least a DC and an end-of-block code, two bits), so a
-// few hundred hostile bytes cannot reserve gigabytes of pinned or host memory.
-int jpeg_source_precheck(flgpu_ctx *c, const flgpu_image *src, const JpegInfo &info)
-{
-    if (info.width != src->width || info.height != src->height) {
-        c->set_error("FLGPU_IMG_JPEG_SOURCE: width / height do not match the file (see flgpu_jpeg_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    const uint64_t decoded = (uint64_t)info.width * info.height * std::max<uint32_t>(info.components, 1u);
-    if (decoded > (512ull << 20)) {
-        c->set_error("JPEG source: the decoded picture exceeds the 512 MiB the reference's decoder allows (image::Limits)");
-        return FLGPU_ERR_UNSUPPORTED;
-    }
-    const uint64_t blocks = ((uint64_t)(info.width + 7u) / 8u) * ((info.height + 7u) / 8u) * std::max<uint32_t>(info.components, 1u);
-    // How short can a file be for that many blocks?  Sequential coding spends at least a DC and an end-of-block code on a block
-    // (two bits); a progressive file needs only its first DC scan (one bit per block), every later scan may end 32767 blocks
-    // with one end-of-band run.  Below that the header lies about the picture.  (Chroma sub-sampling only lowers the count:
-    // the test is repeated on the smallest count the frame could mean.)
-    const uint64_t bits_per_block = info.progressive ? 1u : 2u;
-    const uint64_t fewest = ((uint64_t)(info.width + 15u) / 16u) * ((info.height + 15u) / 16u) * 3u;
-    if (std::min(blocks, std::max<uint64_t>(fewest, 1u)) * bits_per_block > 8ull * src->capacity + 512ull) {
-        c->set_error("malformed JPEG stream: shorter than its header's picture needs");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    // multi-scan files are assembled in a full coefficient array first (128 bytes per block, fl_jpeghuff.cpp): it counts
-    // against the same 512 MiB
-    if (info.progressive && blocks * 128ull > (512ull << 20)) {
-        c->set_error("JPEG source: the coefficient array of this progressive picture exceeds 512 MiB");
-        return FLGPU_ERR_UNSUPPORTED;
-    }
-    return FLGPU_OK;
-}
-
-thread_local bool tl_force_host_huffman = false;
-
-// Whether JPEG sources are entropy-decoded on the device where the file allows it.
-// 0 = this file is Huffman-decoded on the host, 1 = on the device if the caller has no idle CPU for it, 2 = on the device in any case.
-// Switches (flgpu_debug_set; tests and A/B runs): host_huffman = never on the device, device_huffman_always = always,
-// device_huffman_min_bytes = files below it are decoded faster by the thread that holds them than by six kernel launches.
-int device_huffman_policy(const flgpu_ctx *c, uint64_t file_bytes)
-{
-    const DebugSwitches &dbg = *c->dbg;
-    if (tl_force_host_huffman || dbg.on(DBG_HOST_HUFFMAN)) return 0;
-    if (file_bytes < (uint64_t)std::max<int64_t>(0, dbg.get(DBG_DEVICE_HUFFMAN_MIN_BYTES))) return 0;
-    return dbg.on(DBG_DEVICE_HUFFMAN_ALWAYS) ? 2 : 1;
-}
-
-// The buffer of a JPEG source holds the coefficient blob (sized by the picture's blocks) or, for the device entropy decoder, the staged file:
-// four code tables and the segment itself -- more than the blob of a small picture or of a dense one.  Sized by the blob alone, whether the
-// device decoded such a file depended on how far the allocator happened to round the buffer up (tests/test_jpeg_layouts.py).
-size_t jpeg_source_capacity(const flgpu_ctx *c, const flgpu_image *src, const JpegInfo &info)
-{
-    const size_t blob = jpeg_blob_bound(info);
-    return device_huffman_policy(c, src->capacity) != 0 ? std::max(blob, jpeg_stage_bound((size_t)src->capacity)) : blob;
-}
-
-int jpeg_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, JpegBlobHeader *hdr, size_t *used, bool host_huffman)
-{
-    int rc = -2;
-    // files the device entropy decoder takes (sequential, one interleaved scan) are only STAGED here: header,
-    // code tables, the segment without its stuffing -- tens of microseconds instead of ~2 ms of Huffman decoding on this thread
-    if (!host_huffman && device_huffman_policy(c, src->capacity) != 0) rc = jpeg_entropy_stage(src->data, (size_t)src->capacity, blob, cap, used);
-    if (rc == -2) rc = jpeg_entropy_decode(src->data, (size_t)src->capacity, blob, cap, used);
-    if (rc == -2) { c->set_error("JPEG stream not covered by the device decoder (arithmetic coding, 12-bit samples, lossless or hierarchical processes)"); return FLGPU_ERR_UNSUPPORTED; }
-    if (rc) { c->set_error("malformed JPEG stream"); return FLGPU_ERR_INVALID_ARG; }
-    memcpy(hdr, blob, sizeof(*hdr));
-    if (hdr->width != src->width || hdr->height != src->height || (hdr->nc == 4 ? 3u : hdr->nc) != src->channels) {
-        c->set_error("FLGPU_IMG_JPEG_SOURCE: width / height / channels do not match the file (see flgpu_jpeg_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    return FLGPU_OK;
-}
-
-int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
-{
-    size_t nj = 0, scratch = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const JpegBlobHeader *H = srcs[i].hdr;
-        if (!H) continue;
-        ++nj;
-        const size_t px = (size_t)H->width * H->height;
-        scratch += align_up(H->plane_bytes, 256) + align_up(px * H->nc + 64, 256);
-        if (H->nc == 4) scratch += align_up((px + 3) / 4 * 12, 256); // the Rgb8 picture after the CMYK table
-    }
-    c->last_jh_slot.assign(n, -1);
-    c->last_jh_n = 0;
-    if (!nj) return FLGPU_OK;
-    { const int brc = clut_batch_begin(c); if (brc) return brc; } // tables selected below stay resident until the batch's kernels are launched
-    // ---- staged sources (kJhMagic): the entropy-coded segment is decoded on the device first, into a blob of its own ----
-    {
-        size_t njh = 0, bytes = 0, nitems = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const JpegBlobHeader *H = srcs[i].hdr;
-            if (!H || H->magic != kJhMagic) continue;
-            ++njh;
-        }
-        if (njh) {
-            // per picture: the blob, states (nsub + 1 x 8), counts and prefix (nsub x 16 each)
-            std::vector<JhJob> jobs;
-            std::vector<JhItem> items;
-            std::vector<size_t> blob_off, scratch_off;
-            uint32_t max_blocks = 0;
-            for (size_t i = 0; i < n; ++i) {
-                const JpegBlobHeader *H = srcs[i].hdr;
-                if (!H || H->magic != kJhMagic) continue;
-                const JpegHuffStage &S = srcs[i].stage;
-                const uint32_t nsub = jh_subsequences(S);
-                blob_off.push_back(bytes); bytes += align_up(jh_blob_bytes(*H), 256);
-                scratch_off.push_back(bytes); bytes += align_up((size_t)(nsub + 2) * 8 + (size_t)nsub * 8 + (size_t)nsub * 32 + 32, 256);
-                JhJob j{};
-                j.stage = static_cast<const uint8_t *>(dsrc[i].data);
-                j.nsub = nsub;
-                for (uint32_t f = 0; f < nsub; f += kJhSubsPerItem) items.push_back({(uint32_t)jobs.size(), f});
-                c->last_jh_slot[i] = (int32_t)jobs.size();
-                jobs.push_back(j);
-                max_blocks = std::max(max_blocks, H->nblocks);
-            }
-            nitems = items.size();
-            FL_HIP(c, c->d_jh.reserve(bytes), "device entropy decode scratch");
-            FL_HIP(c, c->d_jherr.reserve(njh * 4), "device entropy decode error words");
-            FL_HIP(c, c->h_jherr.reserve(njh * 4), "device entropy decode error words");
-            const size_t jobs_b = align_up(njh * sizeof(JhJob), 256);
-            FL_HIP(c, c->h_jhjobs.reserve(jobs_b + nitems * sizeof(JhItem)), "device entropy decode descriptors");
-            FL_HIP(c, c->d_jhjobs.reserve(jobs_b + nitems * sizeof(JhItem)), "device entropy decode descriptors");
-            size_t k = 0;
-            for (size_t i = 0; i < n; ++i) {
-                if (c->last_jh_slot[i] < 0) continue;
-                JhJob &j = jobs[k];
-                uint8_t *base = static_cast<uint8_t *>(c->d_jh.p);
-                j.blob = base + blob_off[k];
-                j.states = reinterpret_cast<uint64_t *>(base + scratch_off[k]);
-                j.used = j.states + (j.nsub + 2u);
-                j.counts = reinterpret_cast<int32_t *>(base + scratch_off[k] + align_up((size_t)(2u * j.nsub + 2u) * 8, 16));
-                j.prefix = j.counts + (size_t)j.nsub * 4;
-                j.err = static_cast<uint32_t *>(c->d_jherr.p) + k;
-                dsrc[i].data = j.blob; // what the IDCT kernel reads from here on
-                c->stats.jpeg_device_huffman++;
-                ++k;
-            }
-            memcpy(c->h_jhjobs.p, jobs.data(), njh * sizeof(JhJob));
-            memcpy(static_cast<char *>(c->h_jhjobs.p) + jobs_b, items.data(), nitems * sizeof(JhItem));
-            FL_HIP(c, hipMemcpyAsync(c->d_jhjobs.p, c->h_jhjobs.p, jobs_b + nitems * sizeof(JhItem), hipMemcpyHostToDevice, st), "device entropy decode descriptors");
-            FL_HIP(c, launch_jpeg_huff(static_cast<const JhJob *>(c->d_jhjobs.p), jobs.data(), (uint32_t)njh,
-                                       reinterpret_cast<const JhItem *>(static_cast<const char *>(c->d_jhjobs.p) + jobs_b), (uint32_t)nitems, max_blocks, st),
-                   "device entropy decode kernels");
-            c->last_jh_n = (uint32_t)njh;
-        }
-    }
-    FL_HIP(c, c->d_dec.reserve(scratch), "JPEG decode scratch");
-    FL_HIP(c, c->h_decjobs.reserve(nj * sizeof(JpegDecJob)), "JPEG decode descriptors");
-    FL_HIP(c, c->d_decjobs.reserve(nj * sizeof(JpegDecJob)), "JPEG decode descriptors");
-    JpegDecJob *jobs = static_cast<JpegDecJob *>(c->h_decjobs.p);
-    size_t off = 0, k = 0;
-    uint32_t max_blocks = 0, max_w = 0, max_h = 0;
-    struct Cmyk { const void *raw; void *rgb; const void *clut; uint64_t px; bool ycck; };
-    std::vector<Cmyk> cmyk;
-    for (size_t i = 0; i < n; ++i) {
-        if (!srcs[i].hdr) continue;
-        const JpegBlobHeader &H = *srcs[i].hdr;
-        const size_t px = (size_t)H.width * H.height;
-        JpegDecJob &j = jobs[k++];
-        j.blob = dsrc[i].data;
-        j.planes = static_cast<uint8_t *>(c->d_dec.p) + off; off += align_up(H.plane_bytes, 256);
-        j.dst = static_cast<uint8_t *>(c->d_dec.p) + off; off += align_up(px * H.nc + 64, 256);
-        jpeg_color_job(H, j);
-        max_blocks = std::max(max_blocks, H.nblocks); max_w = std::max(max_w, H.width); max_h = std::max(max_h, H.height);
-        c->stats.jpeg_sources++;
-        c->stats.jpeg_upload_bytes += H.total_bytes;
-        uint8_t *pixels = j.dst;
-        uint32_t channels = H.nc;
-        if (H.nc == 4) {
-            // convert_jpeg_color_if_needed (handler.rs:398-466): raw CMYK / YCCK samples -> (YCCK loop) -> the profile's table
-            const void *clut = nullptr;
-            const int rc = select_clut(c, srcs[i].icc, srcs[i].icc_len, &clut);
-            if (rc) return rc;
-            uint8_t *rgb = static_cast<uint8_t *>(c->d_dec.p) + off; off += align_up((px + 3) / 4 * 12, 256);
-            cmyk.push_back({j.dst, rgb, clut, px, H.adobe_transform == 3u});
-            pixels = rgb;
-            channels = 3;
-            c->stats.cmyk_pixels += px;
-        }
-        dsrc[i].data = pixels;
-        dsrc[i].channels = channels;
-        dsrc[i].capacity = (uint64_t)px * channels;
-        dsrc[i].flags &= ~FLGPU_IMG_JPEG_SOURCE;
-    }
-    FL_HIP(c, hipMemcpyAsync(c->d_decjobs.p, jobs, nj * sizeof(JpegDecJob), hipMemcpyHostToDevice, st), "JPEG decode descriptors");
-    for (size_t base = 0; base < nj; base += 32768) { // grid.y / .z limits
-        const uint32_t cnt = (uint32_t)std::min<size_t>(32768, nj - base);
-        FL_HIP(c, launch_jpeg_decode(static_cast<const JpegDecJob *>(c->d_decjobs.p) + base, cnt, max_blocks, max_w, max_h, st), "JPEG decode kernels");
-    }
-    for (const Cmyk &m : cmyk) FL_HIP(c, launch_cmyk_clut(m.raw, m.rgb, m.clut, kCmykGrid, m.px, m.ycck, st), "CMYK kernel");
-    return FLGPU_OK;
-}
-
-// ---- PNG sources -----------------------------------------------------------------------------------------------------------------
-
-// The container walk has bounded what the file may make the library reserve (png_parse_info: below 2^31 bytes, and no more than
-// 1032 x its IDAT payload); here the file is held against what the caller announced.
-int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info)
-{
-    // (layout only: png_source_to_blob verifies the CRCs, so the file is summed once per request)
-    if (png_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error("PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)"); return FLGPU_ERR_UNSUPPORTED; }
-    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
-        c->set_error("FLGPU_IMG_PNG_SOURCE: width / height / channels do not match the file (see flgpu_png_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    return FLGPU_OK;
-}
-
-int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used)
-{
-    if (cap < sizeof(PngBlobHeader)) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    const int rc = png_decode_scanlines(src->data, (size_t)src->capacity, blob + sizeof(PngBlobHeader), cap - sizeof(PngBlobHeader), hdr);
-    if (rc == kPngParse) c->set_error("malformed PNG file (chunk CRC, Huffman code, distance, length, Adler-32 or filter byte)");
-    if (rc == kPngUnsupported) c->set_error("PNG stream holds more scanline data than its IHDR implies");
-    if (rc) return png_status(rc);
-    memcpy(blob, hdr, sizeof(*hdr));
-    *used = hdr->total_bytes;
-    return FLGPU_OK;
-}
-
-int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
-{
-    size_t np = 0, scratch = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const PngBlobHeader *H = srcs[i].png;
-        if (!H) continue;
-        ++np;
-        scratch += align_up((size_t)H->width * H->height * H->channels + 64, 256);
-        if (!H->direct) scratch += align_up((size_t)H->height * H->row_bytes + 64, 256);
-    }
-    if (!np) return FLGPU_OK;
-    FL_HIP(c, c->d_pngdec.reserve(scratch), "PNG decode scratch");
-    FL_HIP(c, c->h_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
-    FL_HIP(c, c->d_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
-    // jobs ordered by bpp (one launch per pixel size), behind them once more the ones the expand kernel takes
-    PngDecJob *jobs = static_cast<PngDecJob *>(c->h_pngjobs.p), *xjobs = jobs + np;
-    uint32_t per_bpp[4] = {0, 0, 0, 0}, nx = 0, max_px = 0;
-    size_t off = 0, k = 0;
-    for (uint32_t bpp = 1; bpp <= 4; ++bpp)
-        for (size_t i = 0; i < n; ++i) {
-            if (!srcs[i].png || srcs[i].png->bpp != bpp) continue;
-            const PngBlobHeader &H = *srcs[i].png;
-            PngDecJob &j = jobs[k++];
-            memset(&j, 0, sizeof(j));
-            j.blob = dsrc[i].data;
-            j.width = H.width; j.height = H.height; j.row_bytes = H.row_bytes; j.bpp = H.bpp;
-            j.pixels = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
-            j.rows = j.pixels;
-            if (!H.direct) {
-                j.rows = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.height * H.row_bytes + 64, 256);
-                xjobs[nx++] = j;
-                max_px = std::max(max_px, H.width * H.height);
-            }
-            per_bpp[bpp - 1]++;
-            if (!tl_force_host_huffman) { c->png_sources++; c->png_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
-            dsrc[i].data = j.pixels;
-            dsrc[i].channels = H.channels;
-            dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
-            dsrc[i].flags &= ~FLGPU_IMG_PNG_SOURCE;
-        }
-    if (k != np) { c->set_error("PNG source: pixel size outside 1..4 bytes"); return FLGPU_ERR_INVALID_ARG; }
-    FL_HIP(c, hipMemcpyAsync(c->d_pngjobs.p, jobs, (np + nx) * sizeof(PngDecJob), hipMemcpyHostToDevice, st), "PNG decode descriptors");
-    const PngDecJob *d_jobs = static_cast<const PngDecJob *>(c->d_pngjobs.p);
-    FL_HIP(c, launch_png_unfilter(d_jobs, per_bpp, st), "PNG unfilter kernel");
-    if (nx) FL_HIP(c, launch_png_expand(d_jobs + np, nx, max_px, st), "PNG expand kernel");
-    return FLGPU_OK;
-}
-
-// ---- lossless WebP sources ---------------------------------------------------------------------------------------------------------
-
-int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info)
-{
-    // (container and VP8L header only: webp_source_to_blob reads the stream itself, once per request)
-    if (webp_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed WebP file (RIFF size, chunk layout, VP8L signature or version)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error("WebP file not covered by the device decoder (lossy VP8, ALPH, animation)"); return FLGPU_ERR_UNSUPPORTED; }
-    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
-        c->set_error("FLGPU_IMG_WEBP_SOURCE: width / height / channels do not match the file (see flgpu_webp_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    return FLGPU_OK;
-}
-
-int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used)
-{
-    const int rc = webp_decode_residuals(src->data, (size_t)src->capacity, blob, cap, hdr);
-    if (rc == kWebpParse) c->set_error("malformed lossless WebP stream (prefix code, transform, backward reference, colour cache index or too few bytes)");
-    if (rc == kWebpUnsupported) c->set_error("lossless WebP stream with more code tables than the decoder's work area holds");
-    if (rc) return webp_status(rc);
-    *used = hdr->total_bytes;
-    return FLGPU_OK;
-}
-
-int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st)
-{
-    size_t np = 0, scratch = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const WebpBlobHeader *H = srcs[i].webp;
-        if (!H) continue;
-        ++np;
-        // the pixels, and at most two intermediate pictures of dwords (in front of and behind the predictor transform)
-        scratch += align_up((size_t)H->width * H->height * H->channels + 64, 256) + 2 * align_up((size_t)H->width * H->height * 4u + 64, 256);
-    }
-    if (!np) return FLGPU_OK;
-    const size_t run_bytes = 2 * np * sizeof(WebpRunJob), job_bytes = run_bytes + np * sizeof(WebpPredictJob);
-    FL_HIP(c, c->d_webpdec.reserve(scratch), "WebP decode scratch");
-    FL_HIP(c, c->h_webpjobs.reserve(job_bytes), "WebP decode descriptors");
-    FL_HIP(c, c->d_webpjobs.reserve(job_bytes), "WebP decode descriptors");
-    // descriptors: the runs in front of a predictor transform, the runs that end in pixels, the predictor transforms
-    WebpRunJob *ra = static_cast<WebpRunJob *>(c->h_webpjobs.p), *rb = ra + np;
-    WebpPredictJob *pj = reinterpret_cast<WebpPredictJob *>(static_cast<uint8_t *>(c->h_webpjobs.p) + run_bytes);
-    uint32_t na = 0, nb = 0, npred = 0, max_a = 0, max_b = 0;
-    size_t off = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (!srcs[i].webp) continue;
-        const WebpBlobHeader &H = *srcs[i].webp;
-        const uint8_t *blob = dsrc[i].data;
-        uint8_t *base = static_cast<uint8_t *>(c->d_webpdec.p);
-        uint8_t *pixels = base + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
-        const uint32_t *cur = reinterpret_cast<const uint32_t *>(blob + H.res_off);
-        uint32_t cw = H.xsize;
-        WebpRunJob run;
-        auto begin_run = [&] { memset(&run, 0, sizeof(run)); run.src = cur; run.src_w = cw; run.height = H.height; };
-        begin_run();
-        if (H.ntransforms > 4) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-        for (uint32_t k = H.ntransforms; k-- > 0;) { // the inverse transforms, last to first
-            if (H.ttype[k] == kWtPredictor) {
-                if (run.nops) { // what is pointwise in front of it goes into a picture of dwords first
-                    uint32_t *mid = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
-                    run.dst = mid; run.dst_w = cw; run.out_c = 0;
-                    ra[na++] = run;
-                    max_a = std::max(max_a, cw * H.height);
-                    cur = mid;
-                }
-                uint32_t *out = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
-                WebpPredictJob &p = pj[npred++];
-                memset(&p, 0, sizeof(p));
-                p.res = cur; p.modes = reinterpret_cast<const uint32_t *>(blob + H.toff[k]); p.out = out;
-                p.width = cw; p.height = H.height; p.bits = H.tbits[k];
-                if (H.twidth[k] != cw || p.bits < 2u || p.bits > 9u) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-                cur = out;
-                begin_run();
-                continue;
-            }
-            WebpOp &op = run.ops[run.nops++];
-            op.type = H.ttype[k];
-            op.data = reinterpret_cast<const uint32_t *>(blob + H.toff[k]);
-            if (op.type == kWtCrossColor) { op.bits = H.tbits[k]; op.width = H.twidth[k]; }
-            if (op.type == kWtColorIndexing) { op.bits = run.shift = webp_index_shift(H.tbits[k]); cw = H.twidth[k]; }
-        }
-        if (cw != H.width) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-        run.dst = pixels; run.dst_w = cw; run.out_c = H.channels;
-        rb[nb++] = run;
-        max_b = std::max(max_b, cw * H.height);
-        if (!tl_force_host_huffman) { c->webp_sources++; c->webp_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
-        dsrc[i].data = pixels;
-        dsrc[i].channels = H.channels;
-        dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
-        dsrc[i].flags &= ~FLGPU_IMG_WEBP_SOURCE;
-    }
-    FL_HIP(c, hipMemcpyAsync(c->d_webpjobs.p, c->h_webpjobs.p, job_bytes, hipMemcpyHostToDevice, st), "WebP decode descriptors");
-    const WebpRunJob *d_ra = static_cast<const WebpRunJob *>(c->d_webpjobs.p);
-    const WebpPredictJob *d_pj = reinterpret_cast<const WebpPredictJob *>(static_cast<const uint8_t *>(c->d_webpjobs.p) + run_bytes);
-    if (na) { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra, na, max_a, st), "WebP pointwise transform kernel"); }
-    if (npred) { ProfileScope ps(c, st, 3); FL_HIP(c, launch_webp_predict(d_pj, npred, st), "WebP predictor kernel"); }
-    { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra + np, nb, max_b, st), "WebP pointwise transform kernel"); }
-    return FLGPU_OK;
-}
-
-// ---- GIF files ---------------------------------------------------------------------------------------------------------------------
-
-// The compose phase: `blob` is the DEVICE copy of what gif_decode_blob left, H its header.  Runs gif_compose_kernel into scratch
-// and describes the H.frames composited canvases as device-resident Rgba8 sources in dsrc[0 .. H.frames).
-int decode_gif_sources(flgpu_ctx *c, const GifBlobHeader &H, const uint8_t *blob, flgpu_image *dsrc, hipStream_t st)
-{
-    const size_t plane = (size_t)H.width * H.height * 4u;
-    FL_HIP(c, c->d_gifdec.reserve((size_t)H.frames * plane + 256), "GIF decode scratch");
-    uint8_t *frames = static_cast<uint8_t *>(c->d_gifdec.p);
-    { ProfileScope ps(c, st, 5); FL_HIP(c, launch_gif_compose(blob, H.width, H.height, H.frames, frames, st), "GIF compose kernel"); }
-    for (uint32_t f = 0; f < H.frames; ++f) {
-        memset(&dsrc[f], 0, sizeof(dsrc[f]));
-        dsrc[f].data = frames + (size_t)f * plane;
-        dsrc[f].capacity = plane;
-        dsrc[f].width = H.width; dsrc[f].height = H.height; dsrc[f].channels = 4;
-    }
-    c->gif_sources++; c->gif_frames += H.frames; c->gif_upload_bytes += H.total_bytes;
-    return FLGPU_OK;
-}
-
-// The encode phase behind run_batch_device: the frames lie in d_out at `pitch`; the six kernels of fl_gif.hip leave the file and
-// its status record in scratch.  Enqueues only.
-static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t frames, size_t pitch, uint64_t frame_max, const uint8_t **file, hipStream_t st)
-{
-    GifEncJob J;
-    memset(&J, 0, sizeof(J));
-    J.w = plan.out_w; J.h = plan.out_h; J.c = plan.out_c; J.frames = frames;
-    J.px = plan.out_w * plan.out_h; J.nseg = (uint32_t)gif_segments(J.px);
-    J.pixels = static_cast<const uint8_t *>(c->d_out.p); J.pix_pitch = pitch;
-    J.idx_pitch = align_up((size_t)J.px, 16) + 16; J.body_pitch = align_up((size_t)frame_max, 16);
-    const size_t segs = (size_t)frames * J.nseg;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
-    const size_t o_status = carve(16), o_frec = carve((size_t)frames * kGifFrameRec * 4), o_ckeys = carve((size_t)frames * kGifColourSlots * 4),
-                 o_cvals = carve((size_t)frames * kGifColourSlots * 4), o_idx = carve((size_t)frames * J.idx_pitch),
-                 o_segs = carve(segs * kGifSegDwords * 4), o_bits = carve(segs * 4), o_off = carve(segs * 4),
-                 o_bodies = carve((size_t)frames * J.body_pitch), o_file = carve((size_t)gif_max_file_bytes(frames, frame_max));
-    FL_HIP(c, c->d_gifenc.reserve(off), "GIF encode scratch");
-    FL_HIP(c, c->h_gifstat.reserve(16), "pinned GIF encode status");
-    uint8_t *base = static_cast<uint8_t *>(c->d_gifenc.p);
-    J.status = reinterpret_cast<uint32_t *>(base + o_status); J.frec = reinterpret_cast<uint32_t *>(base + o_frec);
-    J.ckeys = reinterpret_cast<uint32_t *>(base + o_ckeys); J.cvals = reinterpret_cast<uint32_t *>(base + o_cvals);
-    J.indices = base + o_idx; J.segs = reinterpret_cast<uint32_t *>(base + o_segs);
-    J.seg_bits = reinterpret_cast<uint32_t *>(base + o_bits); J.seg_off = reinterpret_cast<uint32_t *>(base + o_off);
-    J.bodies = base + o_bodies; J.file = base + o_file;
-    *file = J.file;
-    FL_HIP(c, hipMemsetAsync(J.status, 0, 16, st), "GIF encode status");
-    { ProfileScope ps(c, st, 6); FL_HIP(c, launch_gif_encode(J, st), "GIF encode kernels"); }
-    FL_HIP(c, hipMemcpyAsync(c->h_gifstat.p, J.status, 16, hipMemcpyDeviceToHost, st), "GIF encode status D2H");
-    return FLGPU_OK;
-}
-
-int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind)
-{
-    if (!gif || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
-    // the serial half on the calling thread, before any device work and outside the context's lock: callers decode side by side
-    GifInfo info;
-    if (gif_parse_info(gif, n, info) != 0) { c->set_error("malformed GIF file (signature, logical screen, block layout, colour table or too few bytes)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error("GIF file not covered by the device decoder (no frames, a frame outside the canvas or without area, code size, frame count, decoded size)"); return FLGPU_ERR_UNSUPPORTED; }
-    flgpu_plan plan;
-    memset(&plan, 0, sizeof(plan));
-    const size_t canvas = (size_t)info.width * info.height * 4u;
-    if (params) {
-        if (fe_encoded(params->front_end)) return FLGPU_ERR_INVALID_ARG; // (GIF encode is not a per-picture front end: one file comes from all the frames, FLGPU_ENCODE_GIF below)
-        if (int rc = flgpu_plan_output(params, info.width, info.height, 4, &plan)) return rc;
-    }
-    const size_t each = params ? (size_t)plan.out_bytes : canvas;
-    // FLGPU_ENCODE_GIF: the file is attempted; the destination holds either outcome
-    const bool encode = params && (accept_flags & FLGPU_ENCODE_GIF) && gif_encodable(plan.out_w, plan.out_h, plan.out_c, info.frames, plan.out_bytes);
-    const uint64_t frame_max = encode ? gif_max_frame_bytes((uint64_t)plan.out_w * plan.out_h) : 0;
-    if (result_kind) *result_kind = FLGPU_RESULT_PIXELS;
-    if (encode && dst->capacity < gif_max_file_bytes(info.frames, std::max<uint64_t>(frame_max, plan.out_bytes))) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    if (dst->capacity < (uint64_t)each * info.frames) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    std::vector<uint8_t> blob(gif_blob_capacity(info));
-    GifBlobHeader H;
-    const int drc = gif_decode_blob(gif, n, blob.data(), blob.size(), &H);
-    if (drc == kGifParse) c->set_error("malformed GIF stream (an LZW code beyond the table, or fewer indices than the frame has pixels)");
-    if (drc == kGifUnsupported) c->set_error("GIF frame with an index beyond its colour table");
-    if (drc) return gif_status(drc);
-
-    flgpu_ctx *s = c->shard_ctx.empty() ? c : c->shard_ctx[0]; // one file, one device
-    std::lock_guard<std::mutex> g(s->mu);
-    FL_HIP(s, hipSetDevice(s->device), "hipSetDevice");
-    hipStream_t st = s->stream;
-    if (s->last_stream && s->last_stream != st && s->last_done) FL_HIP(s, hipStreamWaitEvent(st, s->last_done, 0), "stream handoff");
-    FL_HIP(s, s->d_in.reserve(H.total_bytes), "device input staging");
-    FL_HIP(s, s->h_stage_in.reserve(H.total_bytes), "pinned input staging");
-    memcpy(s->h_stage_in.p, blob.data(), H.total_bytes);
-    FL_HIP(s, hipMemcpyAsync(s->d_in.p, s->h_stage_in.p, H.total_bytes, hipMemcpyHostToDevice, st), "H2D");
-    std::vector<flgpu_image> dsrc(H.frames);
-    if (int rc = decode_gif_sources(s, H, static_cast<const uint8_t *>(s->d_in.p), dsrc.data(), st)) return rc;
-    s->gif_file_bytes += n;
-    if (frames) *frames = H.frames;
-    dst->width = info.width; dst->height = info.height; dst->channels = 4; dst->flags = 0;
-    if (!params) { // the composited frames themselves
-        FL_HIP(s, hipMemcpyAsync(dst->data, s->d_gifdec.p, canvas * H.frames, hipMemcpyDeviceToHost, st), "D2H");
-        FL_HIP(s, hipStreamSynchronize(st), "GIF decode sync");
-        dst->bytes = (uint64_t)canvas * H.frames;
-        return FLGPU_OK;
-    }
-    // the per-frame pipeline: every frame the same request, one device batch
-    const size_t pitch = align_up(plan.max_out_bytes, 256);
-    FL_HIP(s, s->d_out.reserve(pitch * H.frames), "device output staging");
-    FL_HIP(s, s->h_stage_out.reserve(std::max<size_t>(pitch * H.frames, encode ? (size_t)gif_max_file_bytes(H.frames, frame_max) : 0)), "pinned output staging");
-    std::vector<flgpu_image> ddst(H.frames);
-    for (uint32_t f = 0; f < H.frames; ++f) {
-        memset(&ddst[f], 0, sizeof(ddst[f]));
-        ddst[f].data = static_cast<uint8_t *>(s->d_out.p) + pitch * f;
-        ddst[f].capacity = plan.max_out_bytes;
-    }
-    int rc = run_batch_device(s, H.frames, dsrc.data(), params, true, ddst.data(), st);
-    if (rc) return rc;
-    if (encode) {
-        // the device decides: one small status record comes back, then the file or -- a frame above 256 colours -- the pixels
-        const uint8_t *file = nullptr;
-        rc = encode_gif_frames(s, plan, H.frames, pitch, frame_max, &file, st);
-        if (rc) return rc;
-        rc = collect_results(s, H.frames, ddst.data(), st);
-        if (rc) return rc;
-        const uint32_t *status = static_cast<const uint32_t *>(s->h_gifstat.p);
-        if (!status[0]) {
-            const uint64_t bytes = status[1];
-            if (bytes <= kGifFileHead || bytes > gif_max_file_bytes(H.frames, frame_max)) { s->set_error("GIF encode: file length outside its bounds"); return FLGPU_ERR_DEVICE; }
-            FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, file, bytes, hipMemcpyDeviceToHost, st), "D2H");
-            FL_HIP(s, hipStreamSynchronize(st), "GIF encode sync");
-            memcpy(dst->data, s->h_stage_out.p, bytes);
-            dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = FLGPU_IMG_ENCODED;
-            dst->bytes = bytes;
-            s->gif_encoded++; s->gif_encoded_bytes += bytes;
-            if (result_kind) *result_kind = FLGPU_RESULT_GIF_STREAM;
-            return FLGPU_OK;
-        }
-        s->gif_encode_fallbacks++;
-        FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, s->d_out.p, pitch * H.frames, hipMemcpyDeviceToHost, st), "D2H");
-        FL_HIP(s, hipStreamSynchronize(st), "GIF frames sync");
-        for (uint32_t f = 0; f < H.frames; ++f) memcpy(dst->data + each * f, static_cast<const uint8_t *>(s->h_stage_out.p) + pitch * f, each);
-        dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = ddst[0].flags;
-        dst->bytes = (uint64_t)each * H.frames;
-        return FLGPU_OK;
-    }
-    FL_HIP(s, hipMemcpyAsync(s->h_stage_out.p, s->d_out.p, pitch * H.frames, hipMemcpyDeviceToHost, st), "D2H");
-    rc = collect_results(s, H.frames, ddst.data(), st);
-    if (rc) return rc;
-    for (uint32_t f = 0; f < H.frames; ++f) memcpy(dst->data + each * f, static_cast<const uint8_t *>(s->h_stage_out.p) + pitch * f, each);
-    dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = ddst[0].flags;
-    dst->bytes = (uint64_t)each * H.frames;
-    return FLGPU_OK;
-}
-
-// Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway
-// asks for them in front of that wait and passes fetched = true below.
-int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st)
-{
-    if (!c->last_jh_n || c->last_jh_slot.size() != n) return FLGPU_OK;
-    FL_HIP(c, hipMemcpyAsync(c->h_jherr.p, c->d_jherr.p, (size_t)c->last_jh_n * 4, hipMemcpyDeviceToHost, st), "device entropy decode: error words D2H");
-    return FLGPU_OK;
-}
-
-int entropy_failures(flgpu_ctx *c, size_t n, std::vector<uint8_t> &bad, hipStream_t st, bool fetched)
-{
-    bad.assign(n, 0);
-    if (!c->last_jh_n || c->last_jh_slot.size() != n) return 0;
-    if (!fetched && (hipMemcpyAsync(c->h_jherr.p, c->d_jherr.p, (size_t)c->last_jh_n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
-        c->set_error("device entropy decode: error words D2H");
-        return -FLGPU_ERR_DEVICE;
-    }
-    int nbad = 0;
-    const uint32_t *e = static_cast<const uint32_t *>(c->h_jherr.p);
-    if (c->dbg->on(DBG_DEBUG_JH)) for (uint32_t k = 0; k < c->last_jh_n; ++k) fprintf(stderr, "device entropy decode: picture %u error word %u\n", k, e[k]);
-    for (size_t i = 0; i < n; ++i)
-        if (c->last_jh_slot[i] >= 0 && e[c->last_jh_slot[i]]) { bad[i] = 1; ++nbad; }
-    c->stats.jpeg_device_huffman_retries += (uint64_t)nbad;
-    return nbad;
-}
-
 int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, bool same_params,
                      flgpu_image *dsts, hipStream_t st)
 {
@@ -1788,63 +1239,27 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     FL_HIP(c, hipSetDevice(c->device), "hipSetDevice");
     std::vector<flgpu_image> dsrc(n), ddst(n);
     std::vector<flgpu_plan> plans(n);
-    // JPEG sources: the serial half (parsing + Huffman decoding) runs here, on the host; what is staged is the blob
+    // file sources (JPEG, PNG, lossless WebP): the serial half -- parsing, entropy decoding, inflate -- runs here, on the host; what is
+    // staged is the blob (fl_source.h)
     std::vector<std::vector<uint8_t>> blobs(n);
-    std::vector<JpegBlobHeader> jh(n);
-    std::vector<FileSrc> fsrc(n);
-    std::vector<std::vector<uint8_t>> iccs(n);
-    std::vector<PngBlobHeader> ph;
-    std::vector<WebpBlobHeader> wh;
+    std::vector<StagedSource> staged(n);
+    std::vector<const StagedSource *> staged_of(n);
     size_t in_b = 0, out_b = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!srcs[i].data || !dsts[i].data) return FLGPU_ERR_INVALID_ARG;
         int rc = flgpu_plan_output(&ps[i], srcs[i].width, srcs[i].height, srcs[i].channels, &plans[i]);
         if (rc) return rc;
-        uint64_t sb = (uint64_t)srcs[i].width * srcs[i].height * srcs[i].channels;
-        if (srcs[i].flags & FLGPU_IMG_JPEG_SOURCE) {
-            JpegInfo info;
-            if (jpeg_parse_info(srcs[i].data, (size_t)srcs[i].capacity, info) != 0) return FLGPU_ERR_INVALID_ARG;
-            if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-            rc = jpeg_source_precheck(c, &srcs[i], info);
+        SourceProbe probe;
+        rc = source_probe(c, &srcs[i], probe);
+        if (rc) return rc;
+        uint64_t sb = probe.capacity;
+        if (probe.kind != SRC_PIXELS) {
+            blobs[i].resize(probe.capacity);
+            rc = source_stage(c, &srcs[i], probe, blobs[i].data(), blobs[i].size(), staged[i]);
             if (rc) return rc;
-            blobs[i].resize(jpeg_source_capacity(c, &srcs[i], info));
-            size_t used = 0;
-            rc = jpeg_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &jh[i], &used);
-            if (rc) return rc;
-            stage_of(blobs[i].data(), jh[i], fsrc[i].stage);
-            blobs[i].resize(used);
-            fsrc[i].hdr = &jh[i];
-            if (jh[i].nc == 4 && c->cfg.use_embedded_profile && !info.icc.empty()) { iccs[i].swap(info.icc); fsrc[i].icc = iccs[i].data(); fsrc[i].icc_len = iccs[i].size(); }
-            c->stats.jpeg_file_bytes += srcs[i].capacity;
-            sb = used;
-        } else if (srcs[i].flags & FLGPU_IMG_PNG_SOURCE) {
-            // PNG sources: container + inflate here, on the host; what is staged is the header and the filtered scanlines
-            PngInfo info;
-            rc = png_source_info(c, &srcs[i], info);
-            if (rc) return rc;
-            if (ph.empty()) ph.resize(n);
-            blobs[i].resize(png_blob_bytes(info));
-            size_t used = 0;
-            rc = png_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &ph[i], &used);
-            if (rc) return rc;
-            fsrc[i].png = &ph[i];
-            if (!tl_force_host_huffman) c->png_file_bytes += srcs[i].capacity;
-            sb = used;
-        } else if (srcs[i].flags & FLGPU_IMG_WEBP_SOURCE) {
-            // lossless WebP sources: container + entropy decoding here, on the host; what is staged is header, sub-images and residuals
-            WebpInfo info;
-            rc = webp_source_info(c, &srcs[i], info);
-            if (rc) return rc;
-            if (wh.empty()) wh.resize(n);
-            blobs[i].resize(webp_blob_capacity(info, (size_t)srcs[i].capacity));
-            size_t used = 0;
-            rc = webp_source_to_blob(c, &srcs[i], blobs[i].data(), blobs[i].size(), &wh[i], &used);
-            if (rc) return rc;
-            fsrc[i].webp = &wh[i];
-            if (!tl_force_host_huffman) c->webp_file_bytes += srcs[i].capacity;
-            sb = used;
-        } else
-        if (srcs[i].capacity < sb) return FLGPU_ERR_INVALID_ARG;
+            sb = staged[i].used;
+        }
+        staged_of[i] = &staged[i];
         if (dsts[i].capacity < plans[i].out_bytes && !fe_encoded(ps[i].front_end)) return FLGPU_ERR_BUFFER_TOO_SMALL;
         dsrc[i] = srcs[i]; ddst[i] = dsts[i];
         dsrc[i].data = reinterpret_cast<uint8_t *>(in_b); dsrc[i].capacity = sb; in_b += align_up(sb, 256);
@@ -1858,14 +1273,12 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
     hipStream_t st = c->stream;
     for (size_t i = 0; i < n; ++i) {
         const size_t off = reinterpret_cast<size_t>(dsrc[i].data);
-        memcpy(static_cast<char *>(c->h_stage_in.p) + off, (fsrc[i].hdr || fsrc[i].png || fsrc[i].webp) ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
+        memcpy(static_cast<char *>(c->h_stage_in.p) + off, staged[i].kind != SRC_PIXELS ? blobs[i].data() : srcs[i].data, dsrc[i].capacity);
         dsrc[i].data = static_cast<uint8_t *>(c->d_in.p) + off;
         ddst[i].data = static_cast<uint8_t *>(c->d_out.p) + reinterpret_cast<size_t>(ddst[i].data);
     }
     FL_HIP(c, hipMemcpyAsync(c->d_in.p, c->h_stage_in.p, in_b, hipMemcpyHostToDevice, st), "H2D");
-    { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
-    { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
-    { int drc = decode_webp_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_sources(c, n, dsrc.data(), staged_of.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps, false, ddst.data(), st);
     if (rc) return rc;
     FL_HIP(c, hipMemcpyAsync(c->h_stage_out.p, c->d_out.p, out_b, hipMemcpyDeviceToHost, st), "D2H");
@@ -1875,8 +1288,8 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
         std::vector<uint8_t> bad;
         const int nbad = entropy_failures(c, n, bad, st);
         if (nbad < 0) return -nbad;
-        if (nbad > 0 && !tl_force_host_huffman) {
-            struct Force { Force() { tl_force_host_huffman = true; } ~Force() { tl_force_host_huffman = false; } } force;
+        if (nbad > 0 && !ForceHostHuffman::active()) {
+            ForceHostHuffman force;
             return run_batch_host(c, n, srcs, ps, dsts);
         }
     }

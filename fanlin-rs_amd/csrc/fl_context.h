@@ -1,6 +1,7 @@
 // fl_context.h -- internals of the host runtime behind the C ABI, shared by its translation units:
 //   fl_context.cpp   context lifetime, table arena + caches, stats, table export / import
 //   fl_batch.cpp     batch planner + launcher (device batches, host batches)
+//   fl_source.cpp    JPEG / PNG / WebP files as sources of a batch; fl_gifrun.cpp  a GIF file as a batch of its own (both: fl_source.h)
 //   fl_queue.cpp     persistent request-batching queue, lanes, sharding of flushed batches across the devices of a node
 //   fl_cmyk_ctx.cpp  CMYK device-link tables and their distribution to the devices (RCCL broadcast)
 //
@@ -35,6 +36,7 @@
 #include "fl_mfma.h"
 #include "fl_png.h"
 #include "fl_pngdec.h"
+#include "fl_source.h"
 #include "fl_tables.h"
 #include "fl_webpdec.h"
 #include "fl_webpll.h"
@@ -131,15 +133,7 @@ struct Request {
     PinBlock in, out;      // pinned staging filled / drained by the CALLER thread (parallel memcpy)
     uint64_t src_bytes = 0, out_bytes = 0;
     uint64_t weight = 0;   // algorithmic bytes: W*H*C + out_bytes (shard balancing)
-    bool jpeg = false;     // FLGPU_IMG_JPEG_SOURCE: `in` holds the coefficient blob the caller's thread decoded, jhdr its header
-    JpegBlobHeader jhdr;
-    JpegHuffStage jstage{}; // jhdr.magic == kJhMagic: `in` holds the staged entropy-coded segment, decoded on the device
-    std::vector<uint8_t> icc; // four-component source + use_embedded_profile: the file's own ICC profile
-    uint64_t file_bytes = 0;
-    bool png = false;      // FLGPU_IMG_PNG_SOURCE: `in` holds header + filtered scanlines the caller's thread inflated, phdr the header
-    PngBlobHeader phdr;
-    bool webp = false;     // FLGPU_IMG_WEBP_SOURCE: `in` holds header + sub-images + residuals the caller's thread entropy-decoded, whdr the header
-    WebpBlobHeader whdr;
+    StagedSource staged;   // a file source: `in` holds what the caller's thread decoded (or staged) of it, src_bytes = staged.used
     int status = 0;
     bool done = false;
     std::condition_variable cv; // the caller waits here (qmu): a lane wakes the callers of ITS batch, not every waiting caller
@@ -366,63 +360,6 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
 // front ends whose output is an encoded stream: its length is a result word, known once the batch has run
 inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS; }
-// JPEG sources of a batch: dsrc[i].data = DEVICE copy of the coefficient blob whose header (host copy) is hdrs[i], or
-// hdrs[i] == nullptr for ordinary pixel sources.  Runs the decode kernels into scratch and points dsrc[i] at the pixels.
-// (one entry per image of a batch: a JPEG file's blob header, a PNG file's, or neither for pixel sources)
-struct FileSrc {
-    const JpegBlobHeader *hdr = nullptr;
-    const uint8_t *icc = nullptr;
-    size_t icc_len = 0;
-    JpegHuffStage stage{}; // hdr->magic == kJhMagic: the staged segment's description (a host copy: the blob itself is on its way to the device)
-    const PngBlobHeader *png = nullptr; // a PNG source instead: dsrc[i].data = DEVICE copy of header + filtered scanlines
-    const WebpBlobHeader *webp = nullptr; // a lossless WebP source instead: dsrc[i].data = DEVICE copy of header + sub-images + residuals
-};
-int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
-// After the batch decode_jpeg_sources fed has completed on `st`: bad[i] = 1 where the device entropy decoder gave up on picture i
-// (its states did not settle, or the stream holds an invalid code word): the caller decodes that file on the host instead.
-// Returns the number of such pictures, or a negative FLGPU_ERR_* .
-int entropy_failures(flgpu_ctx *c, size_t n, std::vector<uint8_t> &bad, hipStream_t st, bool fetched = false);
-int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st);
-// internal status of a queued request: run it again with the host entropy decoder
-constexpr int FL_STATUS_RETRY_HOST_HUFFMAN = 1000;
-// Host half for one source: parses + Huffman-decodes `src` (a JPEG file) into `blob`; validates the declared size.
-int jpeg_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, JpegBlobHeader *hdr, size_t *used, bool host_huffman = false);
-// capacity of the buffer jpeg_source_to_blob fills: the coefficient blob's bound and, where the device may decode the file, the staging step's
-size_t jpeg_source_capacity(const flgpu_ctx *c, const flgpu_image *src, const JpegInfo &info);
-// set while a request is run again after the device entropy decoder gave up on its file (this thread's JPEG sources are then decoded on the host)
-extern thread_local bool tl_force_host_huffman;
-int device_huffman_policy(const flgpu_ctx *c, uint64_t file_bytes); // fl_batch.cpp
-inline void stage_of(const uint8_t *staged_blob, const JpegBlobHeader &hdr, JpegHuffStage &out)
-{
-    if (hdr.magic == kJhMagic) memcpy(&out, staged_blob + sizeof(JpegBlobHeader), sizeof(out));
-}
-// fl_cmyk_ctx.cpp: the device-link table for one conversion on context c: the embedded profile's if given and usable
-// (baked once, cached on c), else the configured one (c's own, or its clut_owner's)
-int select_clut(flgpu_ctx *c, const uint8_t *icc, uint64_t icc_len, const void **dev);
-int clut_batch_begin(flgpu_ctx *c);
-int jpeg_source_precheck(flgpu_ctx *c, const flgpu_image *src, const fl::JpegInfo &info);
-// PNG sources of a batch (srcs[i].png set): runs the unfilter / expand kernels into scratch and points dsrc[i] at the pixels.
-int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
-// Host half for one PNG source.  png_source_info: container walk + what the caller announced against the file (FLGPU_ERR_PARSE /
-// _UNSUPPORTED / _INVALID_ARG).  png_source_to_blob: inflates into blob[0 .. png_blob_bytes(info)), header in front.
-int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info);
-int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used);
-// Lossless WebP sources of a batch (srcs[i].webp set): runs the inverse transforms into scratch and points dsrc[i] at the pixels.
-int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const FileSrc *srcs, hipStream_t st);
-// Host half for one WebP source.  webp_source_info: container walk + what the caller announced against the file (FLGPU_ERR_PARSE /
-// _UNSUPPORTED / _INVALID_ARG).  webp_source_to_blob: entropy-decodes into blob[0 .. webp_blob_capacity(info, file bytes)), header in
-// front; *used = the bytes to upload (the decoder's work area behind them stays on the host).
-int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info);
-int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used);
-// A GIF file (not a source of a batch: it IS one).  The LZW stage runs on the calling thread, outside the context's lock; then blob
-// upload, gif_compose_kernel into scratch, and -- with params -- the frames as one device-resident Rgba8 batch with the same
-// params through run_batch_device: dst->data receives *frames results plan.out_bytes apart.  params == nullptr: the composited
-// frames themselves.  With FLGPU_ENCODE_GIF in accept_flags the encoder (fl_gif.hip) runs behind the batch and dst receives the
-// finished file, or -- a frame above 256 colours -- the same pixels; *result_kind says which.
-int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind);
-inline int gif_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kGifParse ? FLGPU_ERR_PARSE : rc == kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
-inline int webp_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kWebpParse ? FLGPU_ERR_PARSE : rc == kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
-inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FLGPU_ERR_PARSE : rc == kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------
 // contiguous split of n weighted items into n_shards shards of about equal weight: shard_of[i] is non-decreasing
@@ -432,6 +369,10 @@ void pin_release(flgpu_ctx *c, PinBlock &b);
 void stop_queue(flgpu_ctx *c); // joins the workers and destroys the lanes
 
 // ---- fl_cmyk_ctx.cpp ---------------------------------------------------------------------------------------------------
+// the device-link table for one conversion on context c: the embedded profile's if given and usable
+// (baked once, cached on c), else the configured one (c's own, or its clut_owner's)
+int select_clut(flgpu_ctx *c, const uint8_t *icc, uint64_t icc_len, const void **dev);
+int clut_batch_begin(flgpu_ctx *c);
 void release_cmyk(flgpu_ctx *c);
 
 } // namespace fl

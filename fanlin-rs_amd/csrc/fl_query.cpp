@@ -23,6 +23,7 @@
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_mfma.h"
+#include "fl_source.h"
 #include "fl_tables.h"
 
 namespace {
@@ -270,6 +271,43 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
     return rc;
 }
 
+/* The shared end of flgpu_process_{image,jpeg,png,webp}: rc and kind are the planner's verdict; as_is never reaches the device. */
+static int run_planned(flgpu_ctx *ctx, int rc, int kind, int *result_kind, const flgpu_image *src, const flgpu_params *p, flgpu_image *dst)
+{
+    if (result_kind) *result_kind = kind;
+    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
+    return flgpu_transform(ctx, src, p, dst);
+}
+
+/* flgpu_decode_{jpeg,png,webp}: the file as a source of the identity request -- no dimensions, no operation (and no orientation applied):
+   the result is the decoded picture */
+static int decode_file(flgpu_ctx *ctx, const uint8_t *file, uint64_t n, uint32_t w, uint32_t h, uint32_t channels, uint32_t source_flag, flgpu_image *dst)
+{
+    flgpu_image src;
+    memset(&src, 0, sizeof(src));
+    src.data = const_cast<uint8_t *>(file); src.capacity = n;
+    src.width = w; src.height = h; src.channels = channels; src.flags = source_flag;
+    flgpu_params p;
+    memset(&p, 0, sizeof(p));
+    return flgpu_transform(ctx, &src, &p, dst);
+}
+
+/* A file the device decoder does not take (plan_png, plan_webp): only as_is, which never decodes, gets through.  Geometry the planner
+   cannot take (2^31 bytes and more) must not hide the query's own verdict: parse it first */
+static int plan_undecodable(const char *query_string, flgpu_plan *plan, int *kind, int *out_format)
+{
+    flgpu_query q;
+    const int rc = flgpu_query_parse(query_string ? query_string : "", &q);
+    if (rc) return rc;
+    if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
+    if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
+    if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
+    memset(plan, 0, sizeof(*plan));
+    *kind = FLGPU_RESULT_AS_IS;
+    if (out_format) *out_format = FLGPU_OUT_KEEP;
+    return FLGPU_OK;
+}
+
 int flgpu_process_image_plan(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags,
                              int input_format, flgpu_plan *plan, int *result_kind)
 try {
@@ -284,10 +322,8 @@ try {
     flgpu_params p;
     flgpu_plan local;
     int kind = 0;
-    int rc = plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan ? plan : &local, &kind, out_format);
-    if (result_kind) *result_kind = kind;
-    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    return flgpu_transform(ctx, decoded, &p, dst);
+    const int rc = plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan ? plan : &local, &kind, out_format);
+    return run_planned(ctx, rc, kind, result_kind, decoded, &p, dst);
 } FL_ABI_CATCH
 
 int flgpu_jpeg_info_of(const uint8_t *jpeg, uint64_t n, flgpu_jpeg_info *info)
@@ -341,10 +377,8 @@ try {
     flgpu_plan local;
     uint8_t o = 1;
     int kind = 0;
-    int rc = plan_jpeg(jpeg, n, query_string, accept_flags, &src, &o, &p, plan ? plan : &local, &kind, out_format);
-    if (result_kind) *result_kind = kind;
-    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    return flgpu_transform(ctx, &src, &p, dst);
+    const int rc = plan_jpeg(jpeg, n, query_string, accept_flags, &src, &o, &p, plan ? plan : &local, &kind, out_format);
+    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
 } FL_ABI_CATCH
 
 int flgpu_debug_jpeg_blob(const uint8_t *jpeg, uint64_t n, uint8_t *blob, uint64_t capacity, uint64_t *used)
@@ -369,13 +403,7 @@ try {
     int rc = flgpu_jpeg_info_of(jpeg, n, &info);
     if (rc) return rc;
     if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    flgpu_image src;
-    memset(&src, 0, sizeof(src));
-    src.data = const_cast<uint8_t *>(jpeg); src.capacity = n;
-    src.width = info.width; src.height = info.height; src.channels = info.channels; src.flags = FLGPU_IMG_JPEG_SOURCE;
-    flgpu_params p;
-    memset(&p, 0, sizeof(p)); /* no dimensions, no operation: the pipeline is the identity, the result the decoded picture */
-    return flgpu_transform(ctx, &src, &p, dst);
+    return decode_file(ctx, jpeg, n, info.width, info.height, info.channels, FLGPU_IMG_JPEG_SOURCE, dst);
 } FL_ABI_CATCH
 
 /* ---- PNG sources ---------------------------------------------------------------------------------------------------- */
@@ -398,26 +426,13 @@ static int plan_png(const uint8_t *png, uint64_t n, const char *query_string, ui
     if (!png) return FLGPU_ERR_INVALID_ARG;
     fl::PngInfo info;
     if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    int rc;
     memset(src, 0, sizeof(*src));
     src->data = const_cast<uint8_t *>(png);
     src->capacity = n;
     /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
     src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
     src->flags = FLGPU_IMG_PNG_SOURCE;
-    if (!info.supported) {
-        /* geometry the planner cannot take (2^31 bytes and more) must not hide the query's own verdict: parse it first */
-        flgpu_query q;
-        rc = flgpu_query_parse(query_string ? query_string : "", &q);
-        if (rc) return rc;
-        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
-        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
-        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
-        memset(plan, 0, sizeof(*plan));
-        *kind = FLGPU_RESULT_AS_IS;
-        if (out_format) *out_format = FLGPU_OUT_KEEP;
-        return FLGPU_OK;
-    }
+    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
     /* the PNG decoder reports no orientation (handler.rs:206 sees none): 1 */
     return plan_request(src, 1, query_string, accept_flags, FLGPU_IN_PNG, p, plan, kind, out_format);
 }
@@ -437,10 +452,8 @@ try {
     flgpu_params p;
     flgpu_plan local;
     int kind = 0;
-    int rc = plan_png(png, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
-    if (result_kind) *result_kind = kind;
-    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    return flgpu_transform(ctx, &src, &p, dst);
+    const int rc = plan_png(png, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
+    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
 } FL_ABI_CATCH
 
 int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst)
@@ -450,13 +463,7 @@ try {
     fl::PngInfo info;
     if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE; // (CRCs: once, in flgpu_transform)
     if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    flgpu_image src;
-    memset(&src, 0, sizeof(src));
-    src.data = const_cast<uint8_t *>(png); src.capacity = n;
-    src.width = info.width; src.height = info.height; src.channels = info.channels; src.flags = FLGPU_IMG_PNG_SOURCE;
-    flgpu_params p;
-    memset(&p, 0, sizeof(p)); /* the pipeline is the identity, the result the decoded picture */
-    return flgpu_transform(ctx, &src, &p, dst);
+    return decode_file(ctx, png, n, info.width, info.height, info.channels, FLGPU_IMG_PNG_SOURCE, dst);
 } FL_ABI_CATCH
 
 int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
@@ -469,7 +476,7 @@ try {
     if (!out) return FLGPU_OK;
     if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
     const int rc = fl::png_decode_scanlines(png, (size_t)n, out, (size_t)capacity, nullptr);
-    return rc == 0 ? FLGPU_OK : rc == fl::kPngParse ? FLGPU_ERR_PARSE : rc == fl::kPngUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL;
+    return fl::png_status(rc);
 } FL_ABI_CATCH
 
 /* ---- lossless WebP sources -------------------------------------------------------------------------------------------- */
@@ -506,25 +513,13 @@ static int plan_webp(const uint8_t *webp, uint64_t n, const char *query_string, 
     if (!webp) return FLGPU_ERR_INVALID_ARG;
     fl::WebpInfo info;
     if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    int rc;
     memset(src, 0, sizeof(*src));
     src->data = const_cast<uint8_t *>(webp);
     src->capacity = n;
     /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
     src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
     src->flags = FLGPU_IMG_WEBP_SOURCE;
-    if (!info.supported) {
-        flgpu_query q;
-        rc = flgpu_query_parse(query_string ? query_string : "", &q);
-        if (rc) return rc;
-        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
-        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
-        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
-        memset(plan, 0, sizeof(*plan));
-        *kind = FLGPU_RESULT_AS_IS;
-        if (out_format) *out_format = FLGPU_OUT_KEEP;
-        return FLGPU_OK;
-    }
+    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
     /* ImageDecoder::orientation() falls back to exif_metadata(), which the WebP decoder implements (handler.rs:206) */
     const uint32_t o = webp_orientation(webp, info);
     return plan_request(src, (uint8_t)(o ? o : 1u), query_string, accept_flags, FLGPU_IN_WEBP, p, plan, kind, out_format);
@@ -545,10 +540,8 @@ try {
     flgpu_params p;
     flgpu_plan local;
     int kind = 0;
-    int rc = plan_webp(webp, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
-    if (result_kind) *result_kind = kind;
-    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    return flgpu_transform(ctx, &src, &p, dst);
+    const int rc = plan_webp(webp, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
+    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
 } FL_ABI_CATCH
 
 int flgpu_decode_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst)
@@ -558,13 +551,7 @@ try {
     fl::WebpInfo info;
     if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
     if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    flgpu_image src;
-    memset(&src, 0, sizeof(src));
-    src.data = const_cast<uint8_t *>(webp); src.capacity = n;
-    src.width = info.width; src.height = info.height; src.channels = info.channels; src.flags = FLGPU_IMG_WEBP_SOURCE;
-    flgpu_params p;
-    memset(&p, 0, sizeof(p)); /* the pipeline is the identity, the result the decoded picture (no orientation applied) */
-    return flgpu_transform(ctx, &src, &p, dst);
+    return decode_file(ctx, webp, n, info.width, info.height, info.channels, FLGPU_IMG_WEBP_SOURCE, dst);
 } FL_ABI_CATCH
 
 int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
@@ -582,16 +569,12 @@ try {
     uint8_t *blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
     fl::WebpBlobHeader H;
     const int rc = fl::webp_decode_residuals(webp, (size_t)n, blob, cap, &H);
-    if (rc) return rc == fl::kWebpParse ? FLGPU_ERR_PARSE : rc == fl::kWebpUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL;
+    if (rc) return fl::webp_status(rc);
     memcpy(out, blob, H.total_bytes);
     return FLGPU_OK;
 } FL_ABI_CATCH
 
 /* ---- GIF files -------------------------------------------------------------------------------------------------------- */
-
-extern "C++" { namespace fl { int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params *params, uint32_t accept_flags, flgpu_image *dst, uint32_t *frames, int *result_kind); } } // fl_batch.cpp
-
-static int gif_rc(int rc) { return rc == 0 ? FLGPU_OK : rc == fl::kGifParse ? FLGPU_ERR_PARSE : rc == fl::kGifUnsupported ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_BUFFER_TOO_SMALL; }
 
 // the host half into a buffer of this call's own: the blob in `work`, its header in H
 static int gif_blob(const uint8_t *gif, uint64_t n, const fl::GifInfo &I, std::unique_ptr<uint8_t[]> &work, uint8_t *&blob, fl::GifBlobHeader &H)
@@ -599,7 +582,7 @@ static int gif_blob(const uint8_t *gif, uint64_t n, const fl::GifInfo &I, std::u
     const size_t cap = fl::gif_blob_capacity(I);
     work.reset(new uint8_t[cap + 16u]);
     blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
-    return gif_rc(fl::gif_decode_blob(gif, (size_t)n, blob, cap, &H));
+    return fl::gif_status(fl::gif_decode_blob(gif, (size_t)n, blob, cap, &H));
 }
 
 int flgpu_gif_info_of(const uint8_t *gif, uint64_t n, flgpu_gif_info *info)
@@ -634,18 +617,7 @@ static int plan_gif(const uint8_t *gif, uint64_t n, const char *query_string, ui
     memset(&canvas, 0, sizeof(canvas));
     canvas.width = info.width; canvas.height = info.height; canvas.channels = 4; /* every frame is the Rgba8 canvas (handler.rs:327-333) */
     if (frames) *frames = info.frames;
-    if (!info.supported) { /* only as_is, which never decodes, gets past this (the canvas may be beyond what a plan can describe) */
-        flgpu_query q;
-        const int rc = flgpu_query_parse(query_string ? query_string : "", &q);
-        if (rc) return rc;
-        if (flgpu_query_unsupported_scale_size(&q)) return FLGPU_ERR_PARSE;
-        if (!flgpu_query_as_is(&q)) return FLGPU_ERR_UNSUPPORTED;
-        if (!plan || !kind) return FLGPU_ERR_INVALID_ARG;
-        memset(plan, 0, sizeof(*plan));
-        *kind = FLGPU_RESULT_AS_IS;
-        if (out_format) *out_format = FLGPU_OUT_KEEP;
-        return FLGPU_OK;
-    }
+    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format); /* (the canvas may be beyond what a plan can describe) */
     const int rc = plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
     /* FLGPU_ENCODE_GIF: the finished file is what will be attempted (a frame above 256 colours turns it back into pixels); the
        per-frame parameters stay as they are, one file comes from all the frames */

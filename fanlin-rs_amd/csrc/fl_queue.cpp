@@ -110,6 +110,29 @@ uint32_t lanes_per_device(const flgpu_ctx *c) { return std::min<uint32_t>(std::m
 uint32_t overflow_lanes_per_device(const flgpu_ctx *c) { return c->cfg.queue_lanes ? 0u : 4u; }
 uint32_t batch_per_device(const flgpu_ctx *c) { return c->cfg.max_batch ? c->cfg.max_batch : 16u; } // measured (round 5, tools/experiments/jh_lanes.sh, 64 callers on 16 cores): 4 lanes x 16 against round 4's 3 x 32 -- the same or more requests per second for files, pixels and blurred pixels, p99 14-19 ms -> 12-14 ms; equal at 128 callers
 
+// A turn at the host decoders (dec_mu / dec_cv / decoding): who holds one decodes its file on its own thread, no more of them at once than
+// the process has CPUs.  policy: device_huffman_policy's answer for a JPEG file; 0 for PNG and WebP files, which have no other decoder.
+struct DecodeTurn {
+    flgpu_ctx *c;
+    bool held; // this thread decodes (a JPEG that is not: it is only staged, the device decodes it)
+    DecodeTurn(flgpu_ctx *c_, int policy) : c(c_), held(policy == 0)
+    {
+        std::unique_lock<std::mutex> lk(c->dec_mu);
+        if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
+        // (round 5: a quarter of the CPUs, not half -- the device's decode kernels of a batch went from 1.9 to 1.1 ms, and with 64 callers on
+        // 16 CPUs every host decode beyond that takes 1.8 ms of CPU from threads that stage files: tools/experiments/jh_policy.sh)
+        if (policy == 1 && c->decoding < std::max(1u, c->dec_limit / 4u)) held = true;
+        if (held) {
+            // (bounded: a file that keeps its decoder busy for long -- a huge progressive picture -- must not park every other
+            // JPEG request behind it; after the deadline the caller decodes anyway, one runnable thread more than CPUs)
+            (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
+            c->decoding++;
+        }
+    }
+    ~DecodeTurn() { if (held) { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } }
+    DecodeTurn(const DecodeTurn &) = delete;
+};
+
 // One shard of a flushed batch on one lane: sources already sit in pinned blocks (copied there by the calling
 // threads), results are left in pinned blocks for the callers to copy out.
 int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
@@ -123,7 +146,7 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
     std::vector<flgpu_image> dsrc(n), ddst(n);
     std::vector<flgpu_params> ps(n);
     std::vector<uint64_t> dev_out(n);
-    std::vector<FileSrc> fsrc(n);
+    std::vector<const StagedSource *> staged(n);
     size_t in_b = 0, out_b = 0;
     for (size_t i = 0; i < n; ++i) {
         dsrc[i] = *batch[i]->src; ddst[i] = *batch[i]->dst; ps[i] = *batch[i]->p;
@@ -140,16 +163,9 @@ int run_batch_queued(flgpu_ctx *c, std::vector<Request *> &batch)
         dsrc[i].data = static_cast<uint8_t *>(c->d_in.p) + reinterpret_cast<size_t>(dsrc[i].data);
         ddst[i].data = static_cast<uint8_t *>(c->d_out.p) + reinterpret_cast<size_t>(ddst[i].data);
         FL_HIP(c, hipMemcpyAsync(dsrc[i].data, batch[i]->in.p, batch[i]->src_bytes, hipMemcpyHostToDevice, st), "H2D");
-        if (batch[i]->jpeg) {
-            fsrc[i].hdr = &batch[i]->jhdr; fsrc[i].stage = batch[i]->jstage; fsrc[i].icc = batch[i]->icc.empty() ? nullptr : batch[i]->icc.data(); fsrc[i].icc_len = batch[i]->icc.size();
-            c->stats.jpeg_file_bytes += batch[i]->file_bytes;
-        }
-        if (batch[i]->png) { fsrc[i].png = &batch[i]->phdr; c->png_file_bytes += batch[i]->file_bytes; }
-        if (batch[i]->webp) { fsrc[i].webp = &batch[i]->whdr; c->webp_file_bytes += batch[i]->file_bytes; }
+        staged[i] = &batch[i]->staged;
     }
-    { int drc = decode_jpeg_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
-    { int drc = decode_png_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
-    { int drc = decode_webp_sources(c, n, dsrc.data(), fsrc.data(), st); if (drc) return drc; }
+    { int drc = decode_sources(c, n, dsrc.data(), staged.data(), st); if (drc) return drc; }
     int rc = run_batch_device(c, n, dsrc.data(), ps.data(), false, ddst.data(), st);
     if (rc) return rc;
     // Encoded streams: their lengths are known only on the device (a 300x200 JPEG is ~16 KB of a 183 KB bound).  The first kSpecBytes of every stream
@@ -229,7 +245,7 @@ void worker_main(flgpu_ctx *c, flgpu_ctx *lane, uint32_t slot, bool overflow)
                 std::vector<Request *> all;
                 // (a batch also ends at kBatchSourceBytes of pixel sources, see above)
                 for (uint64_t bytes = 0; !c->queue.empty() && all.size() < max_batch && (all.empty() || bytes < kBatchSourceBytes * ndev);) {
-                    if (!c->queue.front()->jpeg) bytes += c->queue.front()->src_bytes;
+                    if (c->queue.front()->staged.kind != SRC_JPEG) bytes += c->queue.front()->src_bytes;
                     all.push_back(c->queue.front()); c->queue.pop_front();
                 }
                 c->collecting = false;
@@ -460,27 +476,11 @@ try {
     flgpu_plan plan;
     int rc = flgpu_plan_output(p, src->width, src->height, src->channels, &plan);
     if (rc) return rc;
-    const bool jsrc = (src->flags & FLGPU_IMG_JPEG_SOURCE) != 0;
-    JpegInfo jinfo;
-    if (jsrc) {
-        if (jpeg_parse_info(src->data, (size_t)src->capacity, jinfo) != 0) return FLGPU_ERR_INVALID_ARG;
-        if (!jinfo.supported) { c->set_error("JPEG stream not covered by the device decoder"); return FLGPU_ERR_UNSUPPORTED; }
-        const int prc = jpeg_source_precheck(c, src, jinfo); // before any block is reserved on the file's say-so
-        if (prc) return prc;
-    }
-    const bool psrc = !jsrc && (src->flags & FLGPU_IMG_PNG_SOURCE) != 0;
-    PngInfo pinfo;
-    if (psrc) {
-        const int prc = png_source_info(c, src, pinfo); // before any block is reserved on the file's say-so
-        if (prc) return prc;
-    }
-    const bool wsrc = !jsrc && !psrc && (src->flags & FLGPU_IMG_WEBP_SOURCE) != 0;
-    WebpInfo winfo;
-    if (wsrc) {
-        const int wrc = webp_source_info(c, src, winfo); // before any block is reserved on the file's say-so
-        if (wrc) return wrc;
-    }
-    if (!jsrc && !psrc && !wsrc && src->capacity < (uint64_t)src->width * src->height * src->channels) return FLGPU_ERR_INVALID_ARG;
+    SourceProbe probe;
+    rc = source_probe(c, src, probe); // before any block is reserved on the file's say-so
+    if (rc == FLGPU_ERR_UNSUPPORTED && probe.kind == SRC_JPEG && !probe.jpeg.supported) c->set_error("JPEG stream not covered by the device decoder");
+    if (rc) return rc;
+    const bool file = probe.kind != SRC_PIXELS;
     const bool enc = fe_encoded(p->front_end);
     if (!enc && dst->capacity < plan.out_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
     Request r{};
@@ -503,8 +503,8 @@ try {
     } admission{c};
     c->staging.fetch_add(1, std::memory_order_acq_rel);
     // buffers from flgpu_host_alloc are page-locked already: the DMA engine reads / writes them directly, no staging copy
-    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !jsrc && !psrc && !wsrc, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
-    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, jsrc ? jpeg_source_capacity(c, src, jinfo) : psrc ? png_blob_bytes(pinfo) : wsrc ? webp_blob_capacity(winfo, (size_t)src->capacity) : r.src_bytes);
+    const bool src_pinned = (src->flags & FLGPU_IMG_PINNED) != 0 && !file, dst_pinned = (dst->flags & FLGPU_IMG_PINNED) != 0 && dst->capacity >= r.out_bytes;
+    if (src_pinned) r.in = PinBlock{src->data, 0}; else r.in = pin_acquire(c, probe.capacity);
     if (dst_pinned) r.out = PinBlock{dst->data, 0}; else r.out = pin_acquire(c, r.out_bytes);
     auto give_back = [&] { if (!src_pinned) pin_release(c, r.in); if (!dst_pinned) pin_release(c, r.out); };
     if (!r.in.p || !r.out.p) {
@@ -512,11 +512,11 @@ try {
         give_back();
         return FLGPU_ERR_OOM;
     }
-    if (jsrc) {
-        // the serial half of the decoder (parsing + Huffman) on the caller's thread, straight into pinned memory:
-        // concurrent requests decode in parallel and only the coefficient blob crosses PCIe
-        size_t used = 0;
-        int jrc;
+    if (file) {
+        // the serial half of the decoder on the caller's thread, straight into pinned memory: concurrent requests decode in parallel and only
+        // the blob crosses PCIe -- JPEG: parsing + Huffman, the coefficient blob; PNG: chunk CRCs, inflate, Adler-32; lossless WebP: prefix
+        // codes, LZ77, colour cache.  All under one bound: no more host decoders at once than the process has CPUs.
+        int src_rc;
         {
             // Who decodes the entropy-coded segment?  A thread with an idle CPU under it does it fastest itself (~1.9 ms, and the
             // request skips six kernel launches); once half of the CPUs this process may use are decoding, further requests are
@@ -524,68 +524,11 @@ try {
             // device then work side by side, and a burst of callers no longer queues for CPUs.
             // No more host decoders at once than the process has CPUs: sixty-four runnable decoders on sixteen CPUs all finish late
             // (p99 of the request 60 ms against 20 ms with 32 callers, profiles/r03_latency_jpeg_sources.txt).
-            const int policy = device_huffman_policy(c, src->capacity);
-            bool on_host = policy == 0;
-            {
-                std::unique_lock<std::mutex> lk(c->dec_mu);
-                if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
-                // (round 5: a quarter of the CPUs, not half -- the device's decode kernels of a batch went from 1.9 to 1.1 ms, and with 64 callers on
-                // 16 CPUs every host decode beyond that takes 1.8 ms of CPU from threads that stage files: tools/experiments/jh_policy.sh)
-                if (policy == 1 && c->decoding < std::max(1u, c->dec_limit / 4u)) on_host = true;
-                if (on_host) {
-                    // (bounded: a file that keeps its decoder busy for long -- a huge progressive picture -- must not park every other
-                    // JPEG request behind it; after the deadline the caller decodes anyway, one runnable thread more than CPUs)
-                    (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
-                    c->decoding++;
-                }
-            }
-            struct Turn { flgpu_ctx *c; bool held; ~Turn() { if (held) { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } } } turn{c, on_host};
-            jrc = jpeg_source_to_blob(c, src, static_cast<uint8_t *>(r.in.p), r.in.cap, &r.jhdr, &used, on_host);
-            if (!jrc) stage_of(static_cast<const uint8_t *>(r.in.p), r.jhdr, r.jstage);
+            DecodeTurn turn(c, probe.kind == SRC_JPEG ? device_huffman_policy(c, src->capacity) : 0);
+            src_rc = source_stage(c, src, probe, r.in.p, r.in.cap, r.staged, turn.held);
         }
-        if (jrc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return jrc; }
-        r.jpeg = true;
-        if (r.jhdr.nc == 4 && c->cfg.use_embedded_profile) r.icc.swap(jinfo.icc);
-        r.file_bytes = src->capacity;
-        r.src_bytes = used;
-    } else if (psrc) {
-        // the serial half of the PNG decoder (chunk CRCs, inflate, Adler-32) on the caller's thread, straight into pinned memory, under the
-        // same bound as the host Huffman decoders: no more of them at once than the process has CPUs
-        size_t used = 0;
-        int prc;
-        {
-            {
-                std::unique_lock<std::mutex> lk(c->dec_mu);
-                if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
-                (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
-                c->decoding++;
-            }
-            struct Turn { flgpu_ctx *c; ~Turn() { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } } turn{c};
-            prc = png_source_to_blob(c, src, static_cast<uint8_t *>(r.in.p), r.in.cap, &r.phdr, &used);
-        }
-        if (prc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return prc; }
-        r.png = true;
-        r.file_bytes = src->capacity;
-        r.src_bytes = used;
-    } else if (wsrc) {
-        // the serial half of the lossless WebP decoder (prefix codes, LZ77, colour cache) on the caller's thread, straight into pinned
-        // memory, under the same bound as the other host decoders
-        size_t used = 0;
-        int wrc;
-        {
-            {
-                std::unique_lock<std::mutex> lk(c->dec_mu);
-                if (!c->dec_limit) c->dec_limit = c->cfg.decode_threads ? c->cfg.decode_threads : usable_cpus();
-                (void)c->dec_cv.wait_for(lk, std::chrono::milliseconds(250), [&] { return c->decoding < c->dec_limit; });
-                c->decoding++;
-            }
-            struct Turn { flgpu_ctx *c; ~Turn() { { std::lock_guard<std::mutex> lk(c->dec_mu); c->decoding--; } c->dec_cv.notify_one(); } } turn{c};
-            wrc = webp_source_to_blob(c, src, static_cast<uint8_t *>(r.in.p), r.in.cap, &r.whdr, &used);
-        }
-        if (wrc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return wrc; }
-        r.webp = true;
-        r.file_bytes = src->capacity;
-        r.src_bytes = used;
+        if (src_rc) { c->staging.fetch_sub(1, std::memory_order_acq_rel); give_back(); return src_rc; }
+        r.src_bytes = r.staged.used;
     } else
     if (!src_pinned) memcpy(r.in.p, src->data, r.src_bytes); // on the caller's thread: concurrent callers stage in parallel
     {
@@ -606,8 +549,8 @@ try {
     if (r.status == FL_STATUS_RETRY_HOST_HUFFMAN) {
         // the device entropy decoder gave up on this file (its subsequence states did not settle within the rounds it runs, or the
         // stream holds an invalid code word): once more, Huffman-decoded on this thread -- which either works or names the defect
-        if (tl_force_host_huffman) return FLGPU_ERR_DEVICE;
-        struct Force { Force() { tl_force_host_huffman = true; } ~Force() { tl_force_host_huffman = false; } } force;
+        if (ForceHostHuffman::active()) return FLGPU_ERR_DEVICE;
+        ForceHostHuffman force;
         return flgpu_transform(c, src, p, dst);
     }
     if (dst_pinned) dst->flags |= FLGPU_IMG_PINNED;
