@@ -13,20 +13,7 @@ import numpy as np
 import pytest
 
 import synth
-
-SEG = 32768
-
-
-def filtered_bytes(w, h, c):
-    return h * (1 + w * c)
-
-
-def max_out_bytes(w, h, c):
-    """The format's worst case as the header states it: every 32 KB segment as stored blocks + flush + chunk framing."""
-    f = filtered_bytes(w, h, c)
-    nseg = (f + SEG - 1) // SEG
-    lens = [SEG] * (nseg - 1) + [f - (nseg - 1) * SEG]
-    return 8 + 25 + 2 + 4 + 12 + 12 + sum(n + 5 * ((n + 65534) // 65535) + 5 + 12 for n in lens)
+from png_enc_model import SEG, check_stream, chunks_of, filter_rows, filtered_bytes, max_out_bytes, unfilter  # noqa: F401
 
 
 def _plan(fl, query, flags, fmt, w=1920, h=1080, c=4):
@@ -72,106 +59,7 @@ def test_plan_output_admits_front_end_4_only(fl):
     assert lib.flgpu_plan_output(C.byref(p), 64, 64, 3, C.byref(plan)) == fl.ERR_INVALID_ARG
 
 
-# ---------------------------------------------------------------------------------------------- stream checker --
-
-def filter_rows(px):
-    """png 0.17 filter() with AdaptiveFilterType::Adaptive, restated: (filter bytes, filtered stream)."""
-    h, w, c = px.shape
-    cur = px.reshape(h, w * c).astype(np.int32)
-    up = np.vstack([np.zeros((1, w * c), np.int32), cur[:-1]])
-    a = np.hstack([np.zeros((h, c), np.int32), cur[:, :-c]]) if w > 1 else np.zeros_like(cur)
-    ul = np.hstack([np.zeros((h, c), np.int32), up[:, :-c]]) if w > 1 else np.zeros_like(cur)
-    p = a + up - ul
-    pa, pb, pc = np.abs(p - a), np.abs(p - up), np.abs(p - ul)
-    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, up, ul))
-    cands = [(cur - pred) & 255 for pred in (a, up, (a + up) >> 1, paeth)]  # Sub, Up, Average, Paeth
-    scores = [np.abs(x.astype(np.uint8).view(np.int8).astype(np.int64)).sum(axis=1) for x in cands]
-    choice = np.ones(h, np.int64)
-    best = scores[0].copy()
-    for f in range(1, 4):
-        take = scores[f] <= best
-        best = np.where(take, scores[f], best)
-        choice = np.where(take, f + 1, choice)
-    out = np.empty((h, 1 + w * c), np.uint8)
-    out[:, 0] = choice
-    rows = np.stack(cands)[choice - 1, np.arange(h)]
-    out[:, 1:] = rows.astype(np.uint8)
-    return choice, out.tobytes()
-
-
-def unfilter(stream, w, h, c):
-    rb = w * c
-    rows = np.frombuffer(stream, np.uint8).reshape(h, 1 + rb)
-    out = np.zeros((h, rb), np.int32)
-    prev = np.zeros(rb, np.int32)
-    for y in range(h):
-        f, d = int(rows[y, 0]), rows[y, 1:].astype(np.int32)
-        r = np.zeros(rb, np.int32)
-        for x in range(rb):
-            a = r[x - c] if x >= c else 0
-            b = prev[x]
-            cc = prev[x - c] if x >= c else 0
-            if f == 0:
-                pr = 0
-            elif f == 1:
-                pr = a
-            elif f == 2:
-                pr = b
-            elif f == 3:
-                pr = (a + b) >> 1
-            else:
-                p = a + b - cc
-                pa, pb, pc = abs(p - a), abs(p - b), abs(p - cc)
-                pr = a if pa <= pb and pa <= pc else (b if pb <= pc else cc)
-            r[x] = (d[x] + pr) & 255
-        out[y] = r
-        prev = r
-    return out.astype(np.uint8).reshape(h, w, c)
-
-
-def chunks_of(data):
-    assert data[:8] == b"\x89PNG\r\n\x1a\n", "PNG signature"
-    pos, out = 8, []
-    while pos < len(data):
-        n, = struct.unpack(">I", data[pos:pos + 4])
-        typ, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
-        crc, = struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])
-        assert crc == zlib.crc32(typ + body), f"CRC of chunk {len(out)} ({typ})"
-        out.append((typ, body))
-        pos += 12 + n
-    assert pos == len(data), "trailing bytes"
-    return out
-
-
-def check_stream(data, pixels, quality):
-    """Every structural and content rule of the contract; returns the zlib stream."""
-    h, w, c = pixels.shape
-    ch = chunks_of(data)
-    types = [t for t, _ in ch]
-    assert types[0] == b"IHDR" and types[-1] == b"IEND" and ch[-1][1] == b""
-    assert len(types) >= 3 and all(t == b"IDAT" for t in types[1:-1]), types
-    assert struct.unpack(">IIBBBBB", ch[0][1]) == (w, h, 8, {1: 0, 2: 4, 3: 2, 4: 6}[c], 0, 0, 0)
-    z = b"".join(b for t, b in ch[1:-1])
-    assert z[0] == 0x78 and (z[0] * 256 + z[1]) % 31 == 0 and not (z[1] & 0x20)
-    assert z[1] >> 6 == (3 if quality < 50 else 2 if quality < 85 else 0), "FLEVEL follows the level"
-    d = zlib.decompressobj()
-    raw = d.decompress(z)
-    assert d.eof and d.unused_data == b"" and d.unconsumed_tail == b"", "zlib stream incomplete (or Adler-32 wrong)"
-    assert len(raw) == h * (1 + w * c)
-    choice, want = filter_rows(pixels)
-    got_filters = np.frombuffer(raw, np.uint8).reshape(h, 1 + w * c)[:, 0]
-    assert np.array_equal(got_filters, choice), "filter bytes differ from the adaptive rule"
-    assert raw == want, "filtered rows differ"
-    if h * w * c <= 64 * 64 * 4:
-        assert np.array_equal(unfilter(raw, w, h, c), pixels)
-    try:
-        from PIL import Image
-        im = np.asarray(Image.open(io.BytesIO(data)))
-        assert np.array_equal(im.reshape(h, w, c), pixels), "PIL decodes other pixels"
-    except ImportError:
-        pass
-    return z, raw
-
+# (the stream checker and the filter model: png_enc_model.py)
 
 # ---------------------------------------------------------------------------------------------------- corpus --
 
