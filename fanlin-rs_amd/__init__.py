@@ -29,9 +29,11 @@ LIB_PATH = os.environ.get("FLGPU_LIB") or os.path.join(_HERE, "libfanlin_gpu.so"
 
 FE_NONE, FE_JFIF444, FE_WEBP420, FE_JPEG, FE_PNG = 0, 1, 2, 3, 4
 FE_WEBP_LOSSLESS = 6  # (5 is not a front end)
+FE_WEBP_LOSSY = 9  # (7 and 8 are not front ends)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
+ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q < 100) on the device (FE_WEBP_LOSSY)
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
 ENCODE_GIF = 0x400  # accept_flags bit: State.process_gif finishes the image/gif body on the device where every frame has at most 256 colours
 IN_OTHER, IN_JPEG, IN_PNG, IN_WEBP, IN_GIF_FRAME = 0, 1, 2, 3, 4
@@ -46,7 +48,7 @@ def gif_max_frame_bytes(pixels: int) -> int:
     d = (12 * (pixels + 1 + (pixels + GIF_SEG_INDICES - 1) // GIF_SEG_INDICES) + 7) // 8
     return 8 + 10 + 768 + 1 + d + (d + 254) // 255 + 1
 _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESULT_PIXELS: FE_NONE, RESULT_PNG_STREAM: FE_PNG,
-              RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}
+              RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}  # (or FE_WEBP_LOSSY, by the clamped quality: result_front_end; both are streams)
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
 IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE, IMG_WEBP_SOURCE = 1, 2, 4, 8, 16, 32, 64
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -598,10 +600,24 @@ def _as_image_array(a: np.ndarray) -> np.ndarray:
     return a
 
 
+def result_front_end(kind: int, quality: int = 100) -> int:
+    """The front end behind a result kind.  RESULT_WEBP_STREAM is the lossless coder's at (clamped) quality 100 and the lossy
+    coder's below it."""
+    if kind == RESULT_WEBP_STREAM and min(max(int(quality), 1), 100) < 100:
+        return FE_WEBP_LOSSY
+    return _RESULT_FE[kind]
+
+
+def vp8_max_out_bytes(w: int, h: int) -> int:
+    """csrc/fl_vp8_core.h vp8_max_out_bytes: the worst case of a FE_WEBP_LOSSY file."""
+    mbs = ((w + 15) // 16) * ((h + 15) // 16)
+    return 80 + w * h + (7 * (1126 + 7 * mbs) + 7) // 8 + (7 * (384 * 19 * mbs + 256) + 7) // 8
+
+
 def _split_output(buf: np.ndarray, plan: flgpu_plan, front_end: int, flags: int, nbytes: int = 0):
     if front_end == FE_NONE:
         return buf[: plan.pixel_bytes].reshape(plan.out_h, plan.out_w, plan.out_c)
-    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS):
+    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS, FE_WEBP_LOSSY):
         return buf[:nbytes].tobytes()
     ny = plan.plane_w * plan.plane_h
     nc = plan.chroma_w * plan.chroma_h
@@ -678,7 +694,8 @@ class State:
         """State::process_image after the decoder (reference src/handler.rs:198-308): returns (mime, kind, payload) where
         payload is None (AS_IS), the JPEG body (bytes), WebP planes (Planes) or the pixels for a host encoder (ndarray);
         with ENCODE_PNG in the content flags a PNG input that stays PNG gives the PNG body (bytes, RESULT_PNG_STREAM); with
-        ENCODE_WEBP_LOSSLESS the WebP arm at quality 100 gives the lossless WebP body (bytes, RESULT_WEBP_STREAM)."""
+        ENCODE_WEBP_LOSSLESS the WebP arm at quality 100 gives the lossless WebP body (bytes, RESULT_WEBP_STREAM), with
+        ENCODE_WEBP_LOSSY the arm below quality 100 the lossy one (same kind)."""
         img = _as_image_array(decoded)
         src = flgpu_image(img.ctypes.data, img.nbytes, img.shape[1], img.shape[0], img.shape[2], 0)
         plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()

@@ -85,7 +85,8 @@ struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
 struct ScratchSizes {
     size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
     size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
-    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0;
+    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0;
+    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0;
 };
 
 // What passes between the phases of run_batch_device.
@@ -109,7 +110,8 @@ struct Batch {
     std::vector<JpegJob> jjobs;
     std::vector<PngJob> pjobs;
     std::vector<WebpJob> wjobs;
-    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img; // image of every front-end / encoder job: addresses its result words
+    std::vector<Vp8Job> vjobs;
+    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
     uint32_t jpeg_max_blocks = 0;
     size_t mid_floats_max = 0;
     bool has_results = false, has_err_word = false;
@@ -118,7 +120,7 @@ struct Batch {
     uint32_t *status_dev = nullptr;
     struct {
         const Job *jobs; const StreamItem *items; const FrontendJob *fjobs; const JpegJob *jjobs; const MfmaItem *mitems;
-        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs;
+        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs; const Vp8Job *vjobs;
     } d{}; // the arrays' device copies
     Batch(flgpu_ctx *c, size_t n_, flgpu_image *dsts_) : n(n_), dsts(dsts_), dbg(*c->dbg), work(n_) {}
 };
@@ -419,6 +421,18 @@ int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
     return FLGPU_OK;
 }
 
+// Lossy WebP: the front end's planes, the reconstruction (whole macroblocks), 400 levels and one record per macroblock, the sizes.
+int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s)
+{
+    if (!vp8_fits(pl.out_w, pl.out_h)) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
+    const uint64_t mbs = (uint64_t)vp8_mbs(pl.out_w) * vp8_mbs(pl.out_h);
+    s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
+    s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
+    s.vp8_mbs += mbs;
+    s.vp8_pics++;
+    return FLGPU_OK;
+}
+
 // Validates and plans every picture of the batch and sizes its scratch.  Nothing is enqueued before all of them have passed.
 int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, bool same_params)
 {
@@ -470,6 +484,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
+        if (w.p->front_end == FLGPU_FE_WEBP_LOSSY) rc = vp8_scratch(pl, B.scratch);
         if (rc) return rc;
     }
     return FLGPU_OK;
@@ -492,6 +507,11 @@ int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
     FL_HIP(c, c->d_webpll_tiles.reserve((size_t)sz.wll_tiles * sizeof(WebpllTile)), "WebP tile records");
     FL_HIP(c, c->d_webpll_pic.reserve((size_t)sz.wll_pics * kWebpllPicWords * sizeof(uint32_t)), "WebP per-picture scratch");
     FL_HIP(c, c->d_webpll_stream.reserve(sz.wll_stream), "WebP bit-stream scratch");
+    FL_HIP(c, c->d_vp8_planes.reserve(sz.vp8_planes), "lossy WebP plane scratch");
+    FL_HIP(c, c->d_vp8_rec.reserve(sz.vp8_rec), "lossy WebP reconstruction scratch");
+    FL_HIP(c, c->d_vp8_lev.reserve(sz.vp8_mbs * kVp8MbLevels * sizeof(int16_t)), "lossy WebP level scratch");
+    FL_HIP(c, c->d_vp8_info.reserve(sz.vp8_mbs * sizeof(uint32_t)), "lossy WebP macroblock records");
+    FL_HIP(c, c->d_vp8_sizes.reserve((size_t)sz.vp8_pics * kVp8SizeWords * sizeof(uint32_t)), "lossy WebP partition sizes");
     FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
     FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
     for (auto &w : B.work)
@@ -872,15 +892,31 @@ int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
     return webpll_scratch(pl, at);
 }
 
-// The planar front ends (JFIF444, WebP420): one launch per kind.
-void add_planes_launch(Batch &B, uint32_t kind, const std::vector<size_t> &pics)
+// The lossy WebP job reads the planes its own WebP420 front-end job writes to scratch (add_planes_launch with to_vp8).
+int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
+{
+    Vp8Job &j = encoder_job(B, B.vjobs, B.vjob_img, i);
+    const flgpu_plan &pl = B.work[i].plan;
+    j.src = static_cast<uint8_t *>(c->d_vp8_planes.p) + at.vp8_planes;
+    j.rec = static_cast<uint8_t *>(c->d_vp8_rec.p) + at.vp8_rec;
+    j.lev = static_cast<int16_t *>(c->d_vp8_lev.p) + at.vp8_mbs * kVp8MbLevels;
+    j.info = static_cast<uint32_t *>(c->d_vp8_info.p) + at.vp8_mbs;
+    j.sizes = static_cast<uint32_t *>(c->d_vp8_sizes.p) + (size_t)at.vp8_pics * kVp8SizeWords;
+    const uint32_t q = B.work[i].p->quality;
+    j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
+    return vp8_scratch(pl, at);
+}
+
+// The planar front ends (JFIF444, WebP420): one launch per kind.  to_vp8: the pictures are lossy WebP jobs (B.vjobs from `vjob0`
+// on, in the order of pics) and the planes go to the scratch those jobs read.
+void add_planes_launch(Batch &B, uint32_t kind, const std::vector<size_t> &pics, bool to_vp8 = false, size_t vjob0 = 0)
 {
     FeLaunch F{kind, (uint32_t)B.fjobs.size(), 0, 0, 0, true};
     for (size_t idx : pics) {
         const Work &w = B.work[idx];
         FrontendJob f; memset(&f, 0, sizeof(f));
         f.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-        f.dst = w.final_dst;
+        f.dst = to_vp8 ? const_cast<uint8_t *>(B.vjobs[vjob0 + B.fjobs.size() - F.base].src) : w.final_dst;
         f.w = w.plan.out_w; f.h = w.plan.out_h; f.c = w.plan.out_c;
         f.plane_w = w.plan.plane_w; f.plane_h = w.plan.plane_h; f.chroma_w = w.plan.chroma_w; f.chroma_h = w.plan.chroma_h;
         if (f.c != 4 || ((uintptr_t)f.src & 3u) || ((uintptr_t)f.dst & 3u)) F.rgba = false;
@@ -942,15 +978,18 @@ int build_launches(flgpu_ctx *c, Batch &B)
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
     for (auto &g : fe_groups) {
         ScratchSizes at;
+        const size_t vjob0 = B.vjobs.size();
         for (size_t i : g.second) {
             int rc = FLGPU_OK;
             if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
             if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
             if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, at);
+            if (g.first == FLGPU_FE_WEBP_LOSSY) rc = add_vp8_job(c, B, i, at);
             assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
             (void)rc;
         }
         if (g.first == FLGPU_FE_JFIF444 || g.first == FLGPU_FE_WEBP420) add_planes_launch(B, g.first, g.second);
+        if (g.first == FLGPU_FE_WEBP_LOSSY) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
     }
     FL_HIP(c, c->d_mid.reserve(B.mid_floats_max * 4), "f32 intermediate");
     return FLGPU_OK;
@@ -971,6 +1010,7 @@ template <class F> void desc_regions(Batch &B, F &&f)
     f(B.mwg, B.d.mwg);
     f(B.pjobs, B.d.pjobs);
     f(B.wjobs, B.d.wjobs);
+    f(B.vjobs, B.d.vjobs);
 }
 
 template <class J> void point_results(std::vector<J> &jobs, const std::vector<size_t> &image_of, uint32_t *J::*word, uint32_t *status)
@@ -1017,6 +1057,7 @@ int stage_descriptors(flgpu_ctx *c, Batch &B, hipStream_t st)
         point_results(B.fjobs, B.fjob_img, &FrontendJob::status, B.status_dev);
         point_results(B.pjobs, B.pjob_img, &PngJob::result, B.status_dev);
         point_results(B.wjobs, B.wjob_img, &WebpJob::result, B.status_dev);
+        point_results(B.vjobs, B.vjob_img, &Vp8Job::result, B.status_dev);
     }
     size_t off = 0;
     desc_regions(B, [&](const auto &v, auto &dev) {
@@ -1044,7 +1085,7 @@ int stage_descriptors(flgpu_ctx *c, Batch &B, hipStream_t st)
 
 // ---- launches --------------------------------------------------------------------------------------------------------------------
 
-// Enqueues the batch's kernels in their order -- orientation, stage 1, blur, planar front ends, JPEG, PNG, lossless WebP --, then the
+// Enqueues the batch's kernels in their order -- orientation, stage 1, blur, planar front ends, JPEG, PNG, lossless WebP, lossy WebP --, then the
 // plain copies of the requests that change nothing, and records the batch's events.
 int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
 {
@@ -1147,6 +1188,11 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
     if (!B.wjobs.empty()) {
         ProfileScope ps(c, st, 2);
         FL_HIP(c, launch_webpll_encode(B.d.wjobs, (uint32_t)B.wjobs.size(), B.scratch.wll_tiles, st), "lossless WebP encode");
+        c->stats.frontend_launches++;
+    }
+    if (!B.vjobs.empty()) {
+        ProfileScope ps(c, st, 7);
+        FL_HIP(c, launch_vp8_encode(B.d.vjobs, (uint32_t)B.vjobs.size(), st), "lossy WebP encode");
         c->stats.frontend_launches++;
     }
     // plain copies for requests that change nothing

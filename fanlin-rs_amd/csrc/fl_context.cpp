@@ -355,6 +355,7 @@ void resolve_pending(flgpu_ctx *c)
             else if (p.kind == 4) c->webp_pointwise_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 5) c->gif_compose_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 6) c->gif_encode_ns += (uint64_t)((double)ms * 1e6);
+            else if (p.kind == 7) c->webp_lossy_ns += (uint64_t)((double)ms * 1e6);
             else c->stats.frontend_ms += ms;
         }
         c->event_pool.push_back(p.a);
@@ -514,6 +515,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_mid.release(); c->d_tmp_a.release(); c->d_tmp_b.release(); c->d_tmp_o.release(); c->d_tmp_al.release(); c->d_in.release(); c->d_out.release();
     c->d_jpeg_coef.release(); c->d_jpeg_off.release(); c->d_jpeg_raw.release();
     c->d_png_filt.release(); c->d_png_chunks.release(); c->d_png_syms.release(); c->d_png_recs.release();
+    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release();
     c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
@@ -633,7 +635,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         resolve_pending(c);
         c->stats = flgpu_stats{};
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
-        c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = 0;
+        c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = c->webp_lossy_ns = 0;
         c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
         c->gif_encoded = c->gif_encode_fallbacks = c->gif_encoded_bytes = c->gif_encode_ns = 0;
     }
@@ -663,7 +665,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
-        {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns},
+        {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
         {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns},
         {"gif_encoded", &flgpu_ctx::gif_encoded}, {"gif_encode_fallbacks", &flgpu_ctx::gif_encode_fallbacks}, {"gif_encoded_bytes", &flgpu_ctx::gif_encoded_bytes},

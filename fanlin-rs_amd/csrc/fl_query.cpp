@@ -20,6 +20,7 @@
 #include "fl_gifsrc.h"
 #include "fl_gif.h"
 #include "fl_webpll.h"
+#include "fl_vp8_core.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_mfma.h"
@@ -261,13 +262,20 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
     const bool webp_lossless = input_format != FLGPU_IN_GIF_FRAME && p->front_end == FLGPU_FE_NONE &&
                                (fmt == FLGPU_OUT_WEBP || (fmt == FLGPU_OUT_KEEP && input_format == FLGPU_IN_WEBP)) &&
                                (accept_flags & FLGPU_ENCODE_WEBP_LOSSLESS);
+    /* the WebP arm below quality 100: the finished lossy image/webp body (handler.rs:293-297) when the caller opts in and no size
+       field of the format can overflow (fl_vp8_core.h vp8_fits); otherwise the planes, as before */
+    const bool webp_lossy = p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY);
     if (out_format) *out_format = fmt;
     rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
+    if (rc == FLGPU_OK && webp_lossy && fl::vp8_fits(plan->out_w, plan->out_h)) {
+        p->front_end = FLGPU_FE_WEBP_LOSSY;
+        rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
+    }
     if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {
         p->front_end = FLGPU_FE_WEBP_LOSSLESS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
-    *result_kind = p->front_end == FLGPU_FE_WEBP_LOSSLESS ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
     return rc;
 }
 
@@ -681,8 +689,8 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    /* front ends 0-4 and 6 (5 is not one) */
-    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
+    /* front ends 0-4, 6 and 9 (5, 7 and 8 are not) */
+    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && p->front_end != FLGPU_FE_WEBP_LOSSY) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
         return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
@@ -767,6 +775,17 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         if (plan->out_w > fl::kWebpllMaxSide || plan->out_h > fl::kWebpllMaxSide) return FLGPU_ERR_UNSUPPORTED;
         plan->out_bytes = 4ull * plan->out_w * plan->out_h;
         plan->max_out_bytes = fl::webpll_max_out_bytes(plan->out_w, plan->out_h);
+        break;
+    case FLGPU_FE_WEBP_LOSSY:
+        // the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the planes' bytes.
+        // max_out_bytes: the worst case of this coder's files (fl_vp8_core.h), so a dst of this capacity is never too small.
+        if (!fl::vp8_fits(plan->out_w, plan->out_h)) return FLGPU_ERR_UNSUPPORTED;
+        plan->plane_w = plan->out_w;
+        plan->plane_h = plan->out_h;
+        plan->chroma_w = (plan->out_w + 1u) >> 1;
+        plan->chroma_h = (plan->out_h + 1u) >> 1;
+        plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
+        plan->max_out_bytes = fl::vp8_max_out_bytes(plan->out_w, plan->out_h);
         break;
     case FLGPU_FE_WEBP420:
         plan->plane_w = plan->out_w;

@@ -1,0 +1,34 @@
+// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY): job descriptor, scratch sizes and the launch.
+// The format's limits and worst case, and everything the kernels compute, are in fl_vp8_core.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fl_vp8_core.h"
+
+namespace fl {
+
+constexpr uint32_t kVp8SizeWords = 12;  // per-picture scratch words: the sizes of partition 0 and of up to 8 token partitions
+
+// One picture of a lossy-WebP launch.  The planes launch of FLGPU_FE_WEBP420 has written src (scratch here, not the caller's dst)
+// and bit 0 of result[0].
+struct alignas(16) Vp8Job {
+    const uint8_t *src;   // Y | U | V | A planes, w x h luma, ceil(w / 2) x ceil(h / 2) chroma
+    uint8_t *dst;         // the WebP file
+    uint8_t *rec;         // scratch: the reconstruction, vp8_rec_bytes
+    int16_t *lev;         // scratch: kVp8MbLevels levels per macroblock
+    uint32_t *info;       // scratch: one record per macroblock
+    uint32_t *sizes;      // scratch: [kVp8SizeWords]
+    uint32_t *result;     // [0] bit 0: some pixel is not opaque; [1] = file bytes (0 if it did not fit dst_cap): the words and protocol of JpegJob
+    uint32_t w, h, c;
+    uint32_t dst_cap;     // bytes available at dst
+    uint32_t qi;          // quantiser index (vp8_quality_index of the clamped quality)
+    uint32_t pad[3];
+};
+
+inline uint64_t vp8_planes_bytes(uint64_t w, uint64_t h) { return 2u * w * h + 2u * ((w + 1u) / 2u) * ((h + 1u) / 2u); }
+
+// predict / transform / quantise / reconstruct -> partition sizes -> framing and alpha plane -> partitions; four stream-ordered launches
+hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t njobs, hipStream_t st);
+
+} // namespace fl

@@ -1,0 +1,161 @@
+// fl_vp8.hip -- the lossy WebP encoder on gfx950, so that what leaves the GPU for `webp=true` below quality 100 is the finished
+// image/webp body (reference src/handler.rs:293-297, webp::Encoder::encode(q)) instead of the Y | U | V | A planes.  Opt-in
+// (FLGPU_FE_WEBP_LOSSY).  The stream is a VP8 key frame of this encoder's own choices -- it decodes to exactly the encoder's
+// reconstruction, its bytes are not libwebp's; fl_vp8_core.h states the stream and holds all of its arithmetic, shared with the
+// host twin (tests/vp8_host.cpp) and restated in tests/vp8_model.py.  This file is the choreography:
+//   vp8_analyse_kernel  one wave per picture, macroblocks in raster order (a macroblock predicts from the reconstruction to its
+//                       left and above).  Within a macroblock the work spreads over the lanes phase by phase: 495 loads, 96 block
+//                       SSEs (4 modes x 24 blocks), 24 forward DCTs, 24 quantise / inverse DCT / reconstruct, 401 stores; the mode
+//                       pick and the Y2 block are one lane's.  The macroblock lives in LDS, the reconstruction in scratch.
+//   vp8_size_kernel     one lane per partition (partition 0 and up to 8 token partitions; 16 coder slots per picture, one lane in 16
+//                       codes): the boolean coder runs without storing and leaves the partition's size.  The probability table is
+//                       staged in LDS, a block's 16 levels are fetched whole.  The batch is the parallelism.
+//   vp8_frame_kernel    one workgroup per picture: the layout from the sizes; RIFF / VP8X / ALPH / VP8 framing, the raw alpha
+//                       plane where the planes kernel flagged a translucent pixel, the result word (0 if dst is too small).
+//   vp8_write_kernel    one lane per partition again: the same coder, storing at the partition's place in the file.
+// No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
+// A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fl_vp8.h"
+
+namespace fl {
+namespace {
+
+constexpr uint32_t kLaneSlots = 16;    // coder slots per picture in the coder kernels: slot 0 = partition 0, 1..8 = token partitions
+// Threads per coder slot, of which the first codes.  The coders' control flow is data, so lanes of one wave that code different
+// partitions serialise each other's branches, and at one lane per slot the whole batch is 256 waves, one per CU.  Measured per
+// batch of 1024 (profiles/pr_webp_lossy.txt): 1 -> 22.5 ms, 4 -> 21.4, 16 -> 19.2, 64 (a wave per coder) -> 29.7.
+constexpr uint32_t kLaneStride = 16;
+constexpr uint32_t kCoderThreads = 256;
+constexpr uint32_t kFrameThreads = 256;
+
+__device__ __forceinline__ Vp8Pic pic_of(const Vp8Job &j, const uint8_t *prob = kVp8CoefProb)
+{
+    Vp8Pic p;
+    vp8_pic_dims(p, j.w, j.h);
+    p.prob = prob;
+    p.src = j.src; p.rec = j.rec; p.lev = j.lev; p.info = j.info;
+    p.q = vp8_quant(j.qi);
+    return p;
+}
+
+__global__ __launch_bounds__(64) void vp8_analyse_kernel(const Vp8Job *__restrict__ jobs)
+{
+    __shared__ Vp8Mb m;
+    const Vp8Job &jb = jobs[blockIdx.x];
+    const Vp8Pic p = pic_of(jb);
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t mby = 0; mby < p.mbh; ++mby)
+        for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) {
+            for (uint32_t k = lane; k < kVp8LoadItems; k += 64u) vp8_phase_load(p, m, mbx, mby, k);
+            __syncthreads();
+            if (lane < 3u) vp8_phase_dc(m, mbx, mby, lane);
+            __syncthreads();
+            for (uint32_t k = lane; k < kVp8SseItems; k += 64u) vp8_phase_sse(m, k);
+            __syncthreads();
+            if (lane == 0u) vp8_phase_modes(m);
+            __syncthreads();
+            if (lane < 24u) vp8_phase_fdct(m, lane);
+            __syncthreads();
+            if (lane == 0u) vp8_phase_y2(p, m);
+            __syncthreads();
+            if (lane < 24u) vp8_phase_recon(p, m, mbx, mby, lane);
+            __syncthreads();
+            for (uint32_t k = lane; k <= kVp8MbLevels; k += 64u) vp8_phase_store(p, m, mbx, mby, k);
+            __syncthreads(); // the next macroblock overwrites m and reads this one's reconstruction
+        }
+}
+
+// The coders read a probability for every boolean: the table's 1056 bytes go to LDS first (all threads of the workgroup, before
+// any of them leaves).
+__device__ __forceinline__ void stage_prob(uint8_t *s_prob)
+{
+    for (uint32_t i = threadIdx.x; i < sizeof(kVp8CoefProb); i += kCoderThreads) s_prob[i] = kVp8CoefProb[i];
+    __syncthreads();
+}
+
+// the partition of lane slot `part` (0 = the first partition), counted or written
+__device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
+{
+    if (part == 0u) vp8_put_first_partition(bw, p, qi, nparts);
+    else vp8_put_token_partition(bw, p, part - 1u, nparts);
+}
+
+__global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+{
+    __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
+    stage_prob(s_prob);
+    const uint32_t t = blockIdx.x * kCoderThreads + threadIdx.x, slot = t / kLaneStride, job = slot / kLaneSlots, part = slot % kLaneSlots;
+    if (job >= njobs || t % kLaneStride) return;
+    const Vp8Job &jb = jobs[job];
+    const Vp8Pic p = pic_of(jb, s_prob);
+    const uint32_t nparts = vp8_partitions(p.mbh);
+    if (part >= kVp8SizeWords) return;
+    if (part > nparts) { jb.sizes[part] = 0u; return; }
+    Vp8Bool bw;
+    code_partition(bw, p, jb.qi, part, nparts);
+    jb.sizes[part] = bw.pos;
+}
+
+__device__ __forceinline__ Vp8Layout layout_of(const Vp8Job &jb, uint32_t nparts, uint32_t *size)
+{
+    for (uint32_t k = 0; k < 9u; ++k) size[k] = jb.sizes[k];
+    return vp8_layout(jb.w, jb.h, (jb.result[0] & 1u) != 0u, nparts, size);
+}
+
+__global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *__restrict__ jobs)
+{
+    const Vp8Job &jb = jobs[blockIdx.x];
+    const uint32_t nparts = vp8_partitions(vp8_mbs(jb.h));
+    uint32_t size[9];
+    const Vp8Layout L = layout_of(jb, nparts, size);
+    const bool alpha = (jb.result[0] & 1u) != 0u;
+    if (L.total > jb.dst_cap) { if (threadIdx.x == 0u) jb.result[1] = 0u; return; }
+    if (threadIdx.x == 0u) {
+        vp8_put_framing(jb.dst, L, jb.w, jb.h, alpha, nparts, size);
+        jb.result[1] = L.total;
+    }
+    if (alpha) {
+        const uint32_t npix = jb.w * jb.h;
+        const uint8_t *a = jb.src + npix + 2u * ((jb.w + 1u) / 2u) * ((jb.h + 1u) / 2u);
+        for (uint32_t i = threadIdx.x; i < npix; i += kFrameThreads) jb.dst[L.alph + 9u + i] = a[i];
+    }
+}
+
+__global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+{
+    __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
+    stage_prob(s_prob);
+    const uint32_t t = blockIdx.x * kCoderThreads + threadIdx.x, slot = t / kLaneStride, job = slot / kLaneSlots, part = slot % kLaneSlots;
+    if (job >= njobs || t % kLaneStride) return;
+    const Vp8Job &jb = jobs[job];
+    const Vp8Pic p = pic_of(jb, s_prob);
+    const uint32_t nparts = vp8_partitions(p.mbh);
+    if (part > nparts) return;
+    uint32_t size[9];
+    const Vp8Layout L = layout_of(jb, nparts, size);
+    if (L.total > jb.dst_cap) return; // vp8_frame_kernel has reported it
+    Vp8Bool bw;
+    bw.buf = jb.dst + L.part[part];
+    code_partition(bw, p, jb.qi, part, nparts);
+}
+
+} // namespace
+
+hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
+{
+    if (!njobs) return hipSuccess;
+    const uint32_t coder_blocks = (uint32_t)(((uint64_t)njobs * kLaneSlots * kLaneStride + kCoderThreads - 1u) / kCoderThreads);
+    hipLaunchKernelGGL(vp8_analyse_kernel, dim3(njobs), dim3(64), 0, st, jobs);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(vp8_size_kernel, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(vp8_frame_kernel, dim3(njobs), dim3(kFrameThreads), 0, st, jobs);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(vp8_write_kernel, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    return hipGetLastError();
+}
+
+} // namespace fl

@@ -31,6 +31,8 @@
  *                                       img.write_with_encoder, src/handler.rs:264-273 (row filters, deflate, framing)
  *   front_end = FLGPU_FE_WEBP_LOSSLESS  image's lossless WebP encoder for q == 100 after img.into_rgba8(),
  *                                       src/handler.rs:286-292 (transforms, prefix codes, runs, framing)
+ *   front_end = FLGPU_FE_WEBP_LOSSY     webp::Encoder::from_image(&img).encode(q) for q < 100, src/handler.rs:293-297
+ *                                       (a VP8 key-frame coder of this library's own choices, not libwebp's)
  *   params.filter = NEAREST             the per-frame pipeline of process_gif, src/handler.rs:327-353
  *   flgpu_process_image                 State::process_image after the decoder as one call, src/handler.rs:198-308
  *   flgpu_ycck_to_cmyk                  the YCCK loop of convert_jpeg_color_if_needed, src/handler.rs:423-438
@@ -120,11 +122,18 @@ typedef enum flgpu_front_end {
                               filters by the png crate's adaptive rule; compression from quality (< 50 best, < 85 default,
                               otherwise fast); decodes to exactly the FLGPU_FE_NONE pixels; dst->bytes long */
     /* 5 is not a front end */
-    FLGPU_FE_WEBP_LOSSLESS = 6 /* dst = the finished lossless WebP file (RIFF / VP8L) of image's encoder for q == 100
+    FLGPU_FE_WEBP_LOSSLESS = 6, /* dst = the finished lossless WebP file (RIFF / VP8L) of image's encoder for q == 100
                               (src/handler.rs:286-292): the FLGPU_FE_NONE pixels as img.into_rgba8() gives them,
                               subtract-green, predictor T (L on row 0), one group of prefix codes, runs of the previous pixel;
                               decodes to exactly into_rgba8() of the FLGPU_FE_NONE pixels; out_w, out_h <= 16384;
                               dst->bytes long */
+    /* 7 and 8 are not front ends */
+    FLGPU_FE_WEBP_LOSSY = 9 /* dst = a finished lossy WebP file (RIFF / VP8, or RIFF / VP8X + ALPH + VP8 where a pixel is not
+                              opaque) for the WebP arm below quality 100 (src/handler.rs:293-297): the FLGPU_FE_WEBP420 planes
+                              coded as one VP8 key frame -- every macroblock I16, modes by least SSE, one segment, loop filter
+                              level 0, default probabilities, quantiser from quality; the alpha plane uncompressed.  A valid file
+                              that decodes to exactly the coder's reconstruction; its bytes are not libwebp's.  out_w, out_h
+                              <= 16383 and at most about 21 000 macroblocks (see max_out_bytes); dst->bytes long */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
@@ -141,6 +150,10 @@ typedef enum flgpu_front_end {
  * every frame has at most 256 colours -- the exact-palette branch of the reference's GifEncoder (src/handler.rs:355-364).
  * Without it, and for files with a frame above 256 colours, the frames return as pixels, as before. */
 #define FLGPU_ENCODE_GIF 0x400u
+/* Not a content::Format bit: the caller wants the library to finish lossy image/webp bodies (FLGPU_FE_WEBP_LOSSY,
+ * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs below quality 100 (src/handler.rs:293-297) and the output fits the coder's
+ * limits.  Without it such requests return the FLGPU_FE_WEBP420 planes, as before. */
+#define FLGPU_ENCODE_WEBP_LOSSY 0x800u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -187,7 +200,8 @@ typedef struct flgpu_plan {
     uint64_t out_bytes;                /* bytes the call writes to dst (pixels or planes); for FLGPU_FE_JPEG a planning bound
                                           (about 1 byte per sample) that ordinary pictures stay far below; for FLGPU_FE_PNG
                                           the filtered rows, out_h * (1 + out_w * out_c); for FLGPU_FE_WEBP_LOSSLESS a planning
-                                          bound, the Rgba8 bytes 4 * out_w * out_h */
+                                          bound, the Rgba8 bytes 4 * out_w * out_h; for FLGPU_FE_WEBP_LOSSY a planning bound, the
+                                          bytes of the FLGPU_FE_WEBP420 planes */
     uint64_t max_out_bytes;            /* FLGPU_FE_JPEG: the worst case of the format (every 8x8 block of every component at its
                                           longest code, every byte stuffed): a dst of this capacity can never be too small, as
                                           JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).
@@ -195,6 +209,12 @@ typedef struct flgpu_plan {
                                           as stored blocks: 63 + sum over segments of (L + 5 * ceil(L / 65535) + 5 + 12).
                                           FLGPU_FE_WEBP_LOSSLESS: the worst case of the format, at most 60 bits per pixel after
                                           headers under 1 KB: 1024 + ceil(15 * out_w * out_h / 2).
+                                          FLGPU_FE_WEBP_LOSSY: the worst case of this coder's files: at most 7 bits per boolean,
+                                          19 booleans per coefficient, 384 coefficients and 7 mode booleans per macroblock M =
+                                          ceil(w / 16) * ceil(h / 16): 80 + w h + ceil(7 (1126 + 7 M) / 8) + ceil(7 (7296 M + 256) / 8).
+                                          Pictures for which a partition's worst case could overflow its size field (19 bits
+                                          for the first, 24 for a token partition) are not taken: FLGPU_ERR_UNSUPPORTED from
+                                          flgpu_plan_output, the planes from flgpu_process_*.
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 
@@ -338,8 +358,11 @@ int flgpu_transform(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *
  *                 finished "image/png" body (handler.rs:264-273), dst->bytes long
  *   WEBP_STREAM   the WebP arm at quality 100 (clamped 1..100, so 255 too; negotiated, or a WebP input that stays WebP) and
  *                 accept_flags has FLGPU_ENCODE_WEBP_LOSSLESS: dst holds the finished lossless "image/webp" body
- *                 (handler.rs:286-292), dst->bytes long; an output wider or taller than 16384 stays PIXELS
- *   WEBP_PLANES   lossy WebP was negotiated (handler.rs:286-297): dst holds Y | U | V for WebPEncode
+ *                 (handler.rs:286-292), dst->bytes long; an output wider or taller than 16384 stays PIXELS.
+ *                 Also the WebP arm below quality 100 when accept_flags has FLGPU_ENCODE_WEBP_LOSSY and the output is within
+ *                 FLGPU_FE_WEBP_LOSSY's limits: dst holds the finished lossy "image/webp" body (handler.rs:293-297)
+ *   WEBP_PLANES   lossy WebP was negotiated (handler.rs:286-297) without FLGPU_ENCODE_WEBP_LOSSY, or the output is over that
+ *                 coder's limits: dst holds Y | U | V for WebPEncode
  *   PIXELS        everything else (PNG without FLGPU_ENCODE_PNG, AVIF, lossless WebP without FLGPU_ENCODE_WEBP_LOSSLESS, GIF frames, ...): dst holds the DynamicImage pixels for
  *                 the crate's own encoder; *out_format says which container was negotiated
  * Errors: FLGPU_ERR_PARSE where axum answers 400 (bad query, or the size gate of src/main.rs:134-138). */
@@ -512,7 +535,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS
@@ -565,6 +588,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
  * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
+ * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files

@@ -85,6 +85,9 @@ public:
     // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours
     // (FLGPU_RESULT_GIF_STREAM)
     void encode_gif() { flags_ |= FLGPU_ENCODE_GIF; }
+    // not a content::Format bit: the library finishes lossy image/webp bodies, the WebP arm below quality 100
+    // (FLGPU_RESULT_WEBP_STREAM; outputs over FLGPU_FE_WEBP_LOSSY's limits still come back as planes)
+    void encode_webp_lossy() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY; }
     uint32_t flags() const { return flags_; }
 
 private:

@@ -52,6 +52,7 @@ pub const FE_WEBP420: u8 = 2;
 pub const FE_JPEG: u8 = 3;
 pub const FE_PNG: u8 = 4;
 pub const FE_WEBP_LOSSLESS: u8 = 6; // (5 is not a front end)
+pub const FE_WEBP_LOSSY: u8 = 9;    // (7 and 8 are not front ends)
 pub const FILTER_NEAREST: u8 = 1;
 const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
@@ -67,6 +68,8 @@ pub const ENCODE_PNG: u32 = 0x100;
 pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
 // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours (RESULT_GIF_STREAM)
 pub const ENCODE_GIF: u32 = 0x400;
+// not a content::Format bit: finish lossy image/webp bodies on the device, the WebP arm below quality 100 (RESULT_WEBP_STREAM)
+pub const ENCODE_WEBP_LOSSY: u32 = 0x800;
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
 pub const RESULT_WEBP_PLANES: c_int = 2;
@@ -189,7 +192,7 @@ impl Gpu {
         if let Some((w, h)) = q.dimensions() { p.has_dims = 1; p.w = w; p.h = h; }
         let mut plan = FlPlan::default();
         check(unsafe { flgpu_plan_output(&p, img.width(), img.height(), c, &mut plan) })?;
-        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, FE_PNG and FE_WEBP_LOSSLESS, where it is the
+        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS and FE_WEBP_LOSSY, where it is the
         // worst case of the format: with it the call cannot fail for lack of room, as `encode_image` into a Vec cannot.
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let src = FlImage { data: bytes.as_ptr() as *mut u8, capacity: bytes.len() as u64,
@@ -458,6 +461,19 @@ fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(
 // or, through `transform` where the handler has already taken the q == 100 WebP arm:
 //
 //     if let gpu::Outcome::Device { bytes, .. } = self.gpu.transform(&img, params, orientation.to_exif(), gpu::FE_WEBP_LOSSLESS, false)? {
+//         return Ok((ImageFormat::WebP.to_mime_type(), bytes));
+//     }
+//
+// The WebP arm below quality 100 (lines 293-297: `webp::Encoder::from_image(&img).encode(q)`): with ENCODE_WEBP_LOSSY the finished
+// lossy body instead of the Y | U | V | A planes -- RESULT_WEBP_STREAM again, so the match arm above serves both.  The file is a
+// VP8 key frame of the library's own coder (valid, not libwebp's bytes); outputs over its limits still come back as
+// RESULT_WEBP_PLANES for `WebPEncode`:
+//
+//     let accept = /* ... as above ... */ | gpu::ENCODE_WEBP_LOSSLESS | gpu::ENCODE_WEBP_LOSSY;
+//
+// or, through `transform` where the handler has already taken the q < 100 WebP arm:
+//
+//     if let gpu::Outcome::Device { bytes, .. } = self.gpu.transform(&img, params, orientation.to_exif(), gpu::FE_WEBP_LOSSY, false)? {
 //         return Ok((ImageFormat::WebP.to_mime_type(), bytes));
 //     }
 //

@@ -1,0 +1,106 @@
+"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
+planes from the device plus libwebp's WebPEncode per picture on the host's threads --, file sizes and Y-PSNR of both on the same
+planes, and the bytes that cross PCIe.  Prints plain text; under `rocprofv3 --kernel-trace --stats` (a run of its own, with
+--timing-only) the kernel statistics attribute device time to the four vp8_* kernels, the planes kernel and the resample kernel.
+
+    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only]
+"""
+import argparse
+import math
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def _psnr(a, b):
+    mse = float(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2))
+    return 99.0 if mse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse)
+
+
+def quality(fl, st):
+    import synth
+    import vp8_lib
+    import webp_lib
+    big = synth.photo(1080, 1920, 3, index=3)
+    print("# 1080p photo -> w=300&h=200&webp=true: device file | libwebp WebPEncode on the same planes, same quality")
+    for q in (1, 30, 75, 99):
+        pl = st.process_pixels(big, fl.make_params(300, 200, quality=q, front_end=fl.FE_WEBP420))
+        dev = st.process_pixels(big, fl.make_params(300, 200, quality=q, front_end=fl.FE_WEBP_LOSSY))
+        ref = webp_lib.encode_planes(pl.y, pl.u, pl.v, q)
+        dy, ry = vp8_lib.decode_yuv(dev)[0], vp8_lib.decode_yuv(ref)[0]
+        print(f"quality {q}: device {len(dev)} bytes, Y-PSNR {_psnr(dy, pl.y):.2f} dB | libwebp {len(ref)} bytes, {_psnr(ry, pl.y):.2f} dB | "
+              f"size ratio {len(dev) / len(ref):.3f}, planes {pl.y.nbytes * 2 + pl.u.nbytes * 2} bytes")
+
+
+def timing(fl, st, batch, iters, host_threads):
+    import torch
+    import synth
+    import webp_lib
+    nsrc = 16
+    srcs = [torch.from_numpy(synth.photo(1080, 1920, 3, index=40 + i)).cuda() for i in range(nsrc)]
+    shapes = [(1080, 1920, 3)] * batch
+    ptrs = [srcs[i % nsrc].data_ptr() for i in range(batch)]
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {}
+    for name, fe in (("FE_WEBP420", fl.FE_WEBP420), ("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY)):
+        p = fl.make_params(300, 200, quality=75, front_end=fe)
+        cap = (int(fl.plan_output(p, 1920, 1080, 3).max_out_bytes) + 255) // 256 * 256
+        dst = torch.empty(batch * cap, dtype=torch.uint8, device="cuda")
+        run = st.prepared_batch(ptrs, shapes, p, [dst.data_ptr() + i * cap for i in range(batch)], [cap] * batch)
+        run(stream)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            run(stream)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / iters
+        res = st.batch_results()
+        nbytes = [r[1] for r in res]
+        out[name] = (dt, nbytes)
+        print(f"{name}: {batch} x 1080p RGB8 -> w=300&h=200&webp=true&quality=75: {dt * 1e3:.2f} ms per batch, {batch / dt:.0f} images/s on the device, "
+              f"mean output {np.mean(nbytes):.0f} bytes")
+        if fe == fl.FE_WEBP420:
+            first = dst[:cap].cpu().numpy()
+    # the host half of the path this replaces: WebPEncode of the planes, one picture per call, on the host's threads
+    ny, nc = 300 * 200, 150 * 100
+    y, u, v = first[:ny].reshape(200, 300), first[ny:ny + nc].reshape(100, 150), first[ny + nc:ny + 2 * nc].reshape(100, 150)
+    webp_lib.load()
+    n = 16 * host_threads
+    with ThreadPoolExecutor(host_threads) as ex:
+        t0 = time.perf_counter()
+        files = list(ex.map(lambda _: webp_lib.encode_planes(y, u, v, 75), range(n)))
+        dth = (time.perf_counter() - t0) / n
+    dt_p, nb_p = out["FE_WEBP420"]
+    dt_l, nb_l = out["FE_WEBP_LOSSY"]
+    host_rate = 1.0 / dth
+    print(f"host WebPEncode of the planes on {host_threads} threads: {dth * 1e3:.3f} ms per picture, {host_rate:.0f} images/s ({len(files[0])} bytes)")
+    print(f"planes + host encode: {min(batch / dt_p, host_rate):.0f} images/s (the slower of the two stages); device encoder: {batch / dt_l:.0f} images/s")
+    print(f"encode adds {(dt_l - dt_p) * 1e3:.2f} ms per batch to the planes path")
+    print(f"PCIe per picture: up {1080 * 1920 * 3} bytes of source either way; down {int(np.mean(nb_p))} bytes of planes before, {np.mean(nb_l):.0f} bytes of file now "
+          f"({np.mean(nb_l) / np.mean(nb_p):.3f} x)")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--timing-only", action="store_true")
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    fl = g._load_package()
+    with fl.State(device=0) as st:
+        if not a.timing_only:
+            quality(fl, st)
+        timing(fl, st, a.batch, a.iters, a.host_threads)
+
+
+if __name__ == "__main__":
+    main()
