@@ -126,6 +126,13 @@ def huff_lengths(hist, limit):
     return lengths
 
 
+def unlimited_depth(hist):
+    """The longest code of the Moffat-Katajainen lengths before any fold (33 bits is past every depth a test histogram reaches)."""
+    depth = max(huff_lengths(list(hist), 33))
+    assert depth < 33
+    return depth
+
+
 def canonical(lengths):
     """Canonical codes (the deflate rule), bit-reversed for the LSB-first stream."""
     maxl = max(lengths) if lengths else 0
