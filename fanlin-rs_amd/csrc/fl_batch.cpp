@@ -392,7 +392,7 @@ int jpeg_scratch(const flgpu_plan &pl, ScratchSizes &s)
     if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions
     const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
     if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
-    s.jpeg_coef += align_up(units * sizeof(uint32_t), 256);
+    s.jpeg_coef += align_up(units * sizeof(JpegUnit), 256);
     s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
     s.jpeg_raw += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
     return FLGPU_OK;
@@ -855,7 +855,7 @@ int add_jpeg_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
 {
     JpegJob &j = encoder_job(B, B.jjobs, B.jjob_img, i);
     const flgpu_plan &pl = B.work[i].plan;
-    j.meta = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_coef.p) + at.jpeg_coef);
+    j.units = reinterpret_cast<JpegUnit *>(static_cast<char *>(c->d_jpeg_coef.p) + at.jpeg_coef);
     j.unit_off = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_off.p) + at.jpeg_off);
     j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_raw.p) + at.jpeg_raw);
     j.bx = pl.plane_w / 8u; j.by = pl.plane_h / 8u;

@@ -233,7 +233,7 @@ struct flgpu_ctx {
     uint64_t gif_encode_ns = 0;                        // HIP-event time of the encode kernels' launches (profile = 1)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
-    fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): block meta words, bit offsets, AC bits
+    fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): unit records, bit offsets, AC bits past a record
     fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
     fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes
     fl::DeviceBuf d_webpll_res, d_webpll_tok, d_webpll_tiles, d_webpll_pic, d_webpll_stream; // lossless WebP scratch (fl_webpll.hip): residuals, tokens, tile records, per-picture words, bit streams

@@ -8,12 +8,20 @@ namespace fl {
 // One image of a JPEG-encode launch (fl_jpeg.hip).
 #define FL_JPEG_RESULT_OVERFLOW 4u
 constexpr uint32_t kAcWordsPerUnit = 52; // 63 coefficients x (16-bit code + 10 value bits) = 1638 bits
+constexpr uint32_t kUnitAcWords = 3;     // AC code words a unit's record holds itself (96 bits: nearly every unit of a photograph)
+// What jpeg_dct_quant_kernel hands jpeg_pack_kernel per unit (unit = block * 3 + component): one 16-byte record, written and
+// read with one access.  A unit whose AC code is longer than 96 bits continues in its JpegJob::acbits slot, from word 3 on.
+struct alignas(16) JpegUnit {
+    uint32_t meta;                // quantised DC (low 16 bits, i16) | AC code bits << 16
+    uint32_t ac[kUnitAcWords];    // the AC code's first 96 bits from bit 0, most significant bit first; unused bits are zero
+};
 struct alignas(16) JpegJob {
     const uint8_t *src;   // interleaved pixels, w x h x c
     uint8_t *dst;         // the JFIF stream
-    uint32_t *meta;       // scratch: [unit] quantised DC (low 16 bits, i16) | AC code bits << 16; unit = block * 3 + component
+    JpegUnit *units;      // scratch: [unit] the unit's record; unit = block * 3 + component
     uint32_t *unit_off;   // scratch: units + 1 bit offsets
-    uint32_t *acbits;     // scratch: [unit][kAcWordsPerUnit] the block's AC code from bit 0, most significant bit first
+    uint32_t *acbits;     // scratch: [unit][kAcWordsPerUnit] the unit's AC code from bit 0, most significant bit first; only words
+                          // kUnitAcWords and up are written and read here (the slot keeps its worst-case size and every index)
     uint32_t *result;     // [0] |= flags (FL_JPEG_RESULT_OVERFLOW), [1] = stream bytes (0 if it did not fit dst_cap)
     uint32_t w, h, c;
     uint32_t bx, by;      // blocks per row / column
@@ -22,7 +30,8 @@ struct alignas(16) JpegJob {
     uint32_t dst_cap;     // bytes available at dst
 };
 
-// JPEG encode of njobs pictures: colour + FDCT + quantise (one wave per block), then entropy coding (one workgroup per picture)
+// JPEG encode of njobs pictures: colour + FDCT + quantise + AC coding (one wave per 16 blocks), then offsets, assembly, stuffing
+// and framing (one workgroup per picture)
 hipError_t launch_jpeg_encode(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
                               hipStream_t st);
 

@@ -15,13 +15,16 @@
 //                           zig-zag coefficient k, so the quantised units land in LDS in coding order, with a ballot of
 //                           their non-zero AC terms.  Coding: each lane Huffman-codes whole units on its own, walking
 //                           the set bits of the unit's mask (lane 16 k + b: component k of block b).
-//                           Out: quantised DC, AC bit count, AC bits (from bit 0).
+//                           Out: one 16-byte record per unit (JpegUnit: quantised DC, AC bit count, the first 96 bits
+//                           of the AC code); the rare longer code goes on in the unit's acbits slot.
 //   jpeg_pack_kernel        one workgroup per picture: DC code sizes (they need the previous block) + AC sizes ->
 //                           exclusive scan -> bit offset of every block; the blocks' bits are shifted into place in an
 //                           LDS window of the stream (atomics), then pad_byte, 0xFF -> 0xFF00 stuffing by a second
-//                           scan, header, EOI, length.  Long streams are handled window after window.
+//                           scan, header, EOI, length.  Long streams are handled window after window.  A unit costs
+//                           one 16-byte load, requested a round of 512 units ahead of its use.
 // HBM traffic is the pixels once (the input is the 240 KB picture the resample kernel just wrote, L2 resident) plus
-// the coefficient scratch; the kernels are VALU / LDS bound, not bandwidth bound.
+// the unit records (16 bytes per unit, written and read once, consecutive within a picture); the kernels are VALU / LDS
+// bound, not bandwidth bound.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -284,18 +287,31 @@ __device__ __forceinline__ void dct_quant_block(const uint32_t (&smp)[3], uint32
 }
 
 typedef __attribute__((address_space(1))) uint32_t global_u32; // (global, not flat, stores: they do not count against the LDS waits)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));     // a JpegUnit as one 16-byte access: x = meta, y z w = ac[0..2]
+typedef __attribute__((address_space(1))) u32x4 global_u32x4;
+static_assert(sizeof(JpegUnit) == sizeof(u32x4) && kUnitAcWords == 3u, "a unit's record is one 16-byte access");
 
-// Appends the `len` (<= 26) low bits of `code` to a lane's unit: full 32-bit words go to out[wi++], most significant bit first.
+// Appends the `len` (<= 26) low bits of `code` to a lane's unit, most significant bit first: the first kUnitAcWords full 32-bit
+// words stay in registers (they go out with the unit's record), the later ones go to out[wi], the unit's acbits slot.
 struct UnitBits {
     uint64_t acc;   // the low `pend` bits are pending (pend < 32 between calls)
     uint32_t pend, total, wi;
     global_u32 *out;
+    uint32_t w0, w1, w2;
+    __device__ __forceinline__ void word(uint32_t v)
+    {
+        w0 = wi == 0u ? v : w0;
+        w1 = wi == 1u ? v : w1;
+        w2 = wi == 2u ? v : w2;
+        if (wi >= kUnitAcWords) out[wi] = v;
+        ++wi;
+    }
     __device__ __forceinline__ void put(uint32_t code, uint32_t len)
     {
         acc = (acc << len) | code;
         pend += len;
         total += len;
-        if (pend >= 32u) { pend -= 32u; out[wi++] = (uint32_t)(acc >> pend); }
+        if (pend >= 32u) { pend -= 32u; word((uint32_t)(acc >> pend)); }
     }
 };
 
@@ -370,8 +386,8 @@ __device__ __forceinline__ void transform_blocks(const JpegJob &jb, const uint32
 // (dct_quant_block); each unit's quantised coefficients go to LDS in zig-zag order, with a ballot of their non-zero AC terms.
 // A block of one colour skips the transform.  Coding: every lane codes whole units by itself (BitWriter::write_block without
 // the DC term) -- lane 16 k + b component k of block b (see kBlocksPerWave) -- walking the set bits of the
-// unit's mask: one code word per step, however many coefficients its neighbours' units hold.  Out: quantised DC, AC bit count,
-// AC bits (from bit 0, the last word padded with zeros).
+// unit's mask: one code word per step, however many coefficients its neighbours' units hold.  Out: the unit's record (quantised
+// DC, AC bit count, AC bits from bit 0, the last word padded with zeros); AC words 3 and up go to the unit's acbits slot.
 __global__ __launch_bounds__(kJpegThreads) void jpeg_dct_quant_kernel(const JpegJob *__restrict__ jobs, const uint32_t *__restrict__ arena,
                                                                       uint32_t job_base)
 {
@@ -413,7 +429,7 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_dct_quant_kernel(const Jpeg
         const uint32_t unit = first * 3u + u;
         const int16_t *cf = w.coef[u];
         uint64_t m = w.nz[u];
-        UnitBits ub{0ull, 0u, 0u, unit * kAcWordsPerUnit, (global_u32 *)jb.acbits};
+        UnitBits ub{0ull, 0u, 0u, 0u, (global_u32 *)jb.acbits + (size_t)unit * kAcWordsPerUnit, 0u, 0u, 0u};
         uint32_t prev = 0;
         // the next coefficient is read one step ahead, so that a step waits for one LDS round trip (the table entry), not two
         uint32_t pos = (uint32_t)__builtin_ctzll(m | (1ull << 63));
@@ -434,8 +450,11 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_dct_quant_kernel(const Jpeg
             ub.put(((e & 0xffffu) << size) | value, (e >> 16) + size);          // <= 16 + 10 bits
         }
         if (prev != 63u) ub.put(eob & 0xffffu, eob >> 16);
-        if (ub.pend) ub.out[ub.wi] = (uint32_t)(ub.acc << (32u - ub.pend));            // the last word, padded with zeros
-        jb.meta[unit] = ((uint32_t)(uint16_t)cf[0]) | (ub.total << 16);         // quantised DC, AC bit count
+        if (ub.pend) ub.word((uint32_t)(ub.acc << (32u - ub.pend)));                    // the last word, padded with zeros
+        // the unit's record in one 16-byte store, behind the loop where the wave's lanes have met again: the records of a wave's
+        // 48 units are 768 consecutive bytes
+        const u32x4 rec = {((uint32_t)(uint16_t)cf[0]) | (ub.total << 16), ub.w0, ub.w1, ub.w2}; // quantised DC, AC bit count
+        ((global_u32x4 *)jb.units)[unit] = rec;
     }
 }
 
@@ -453,60 +472,110 @@ __device__ __forceinline__ void win_or(uint32_t *win, uint32_t wbase, uint64_t g
     if (lo && W + 1 >= wbase && W + 1 < (uint64_t)wbase + kWinWords) atomicOr(&win[W + 1 - wbase], lo);
 }
 
-__device__ __forceinline__ uint32_t dc_code(const JpegJob &jb, uint32_t u, uint32_t meta, uint32_t *len)
+constexpr uint32_t kDcCodes = 12; // DC size categories 0..11 (the difference of two quantised DC terms of 8-bit samples)
+
+// s_dc: the two DC code tables (luma, chroma), kDcCodes entries each, staged in LDS -- a table entry is then an LDS read behind
+// the unit's record, not a third dependent global load
+__device__ __forceinline__ uint32_t dc_code(const uint32_t *s_dc, uint32_t u, uint32_t meta, uint32_t prev_meta, uint32_t *len)
 {
-    // differential DC against the same component's previous block (encode_rgb: y_dcprev / cb_dcprev / cr_dcprev)
-    const int32_t dc = (int16_t)(meta & 0xffffu), prev = u >= 3u ? (int32_t)(int16_t)(jb.meta[u - 3u] & 0xffffu) : 0;
+    // differential DC against the same component's previous block (encode_rgb: y_dcprev / cb_dcprev / cr_dcprev); prev_meta is
+    // the meta word of unit u - 3, or 0 for a picture's first block
+    const int32_t dc = (int16_t)(meta & 0xffffu), prev = (int16_t)(prev_meta & 0xffffu);
     const int32_t diff = dc - prev;
     const uint32_t size = coef_size(diff);
     const uint32_t value = (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << size) - 1u);
-    const uint32_t e = kHuff.dc[(u % 3u) ? 1 : 0].e[size];
+    const uint32_t e = s_dc[((u % 3u) ? kDcCodes : 0u) + size];
     *len = (e >> 16) + size;                                   // <= 9 + 11 or 11 + 11 bits
     return (((e & 0xffffu) << size) | value) << (32u - *len);  // left-aligned
 }
+
+// What the pack kernel reads per unit: its record and the meta word of the same component's previous block, requested together.
+// The loads carry no condition (a unit index past the end reads the last unit, a first block's predecessor reads unit 0): behind
+// a branch the compiler cannot count the loads in flight and waits for all of them, the ones just requested included.  What
+// such a load returned is dropped when the value is taken (take_pack_unit).
+struct PackUnit { u32x4 rec; uint32_t prev; };
+__device__ __forceinline__ PackUnit load_pack_unit(const JpegJob &jb, uint32_t u, uint32_t u_end)
+{
+    const global_u32x4 *recs = (const global_u32x4 *)jb.units;
+    const uint32_t uc = min(u, u_end - 1u);                    // (u_end >= 3: a picture has at least one block)
+    PackUnit p;
+    p.rec = recs[uc];
+    p.prev = ((const global_u32 *)(recs + (max(uc, 3u) - 3u)))[0];
+    return p;
+}
+__device__ __forceinline__ PackUnit take_pack_unit(PackUnit p, uint32_t u, uint32_t u_end)
+{
+    if (u >= u_end) p.rec = u32x4{0u, 0u, 0u, 0u};             // no unit: no bits
+    if (u < 3u || u >= u_end) p.prev = 0u;
+    return p;
+}
+
+// Rounds of the first pass whose records are requested ahead of the round that uses them.  One round ahead took 32.4 us per
+// 1024 pictures of 300 x 200, all six rounds of such a picture (2,850 units) 35.6 us: 73 registers instead of 58 leave room for
+// three workgroups per CU, not four (profiles/pr_jpeg_unit_records.txt).  `make EXTRA=-DFL_JPEG_PACK_DEPTH=6` for the A/B.
+#ifndef FL_JPEG_PACK_DEPTH
+#define FL_JPEG_PACK_DEPTH 1
+#endif
+constexpr uint32_t kPackDepth = FL_JPEG_PACK_DEPTH;
 
 __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *__restrict__ jobs, const uint32_t *__restrict__ arena,
                                                                  uint32_t job_base)
 {
     __shared__ uint32_t s_win[kWinWords];
-    __shared__ uint32_t s_w[kPackWaves], s_carry, s_lo, s_hi;
+    __shared__ uint32_t s_w[kPackWaves], s_carry, s_lo, s_hi, s_dc[2u * kDcCodes];
     const JpegJob jb = jobs[job_base + blockIdx.x];
     const uint32_t tid = threadIdx.x;
     const uint32_t nunits = jb.bx * jb.by * 3u;
     constexpr uint32_t T = kPackThreads;
 
     // ---- bit offset of every block: DC code size (needs the previous block) + AC size, exclusive scan -- and, in the same pass,
-    // the block's code goes into the first window of the stream (win_or drops what lies beyond it): the words a thread will
-    // place are requested together with its meta word, BEFORE the scan, so that a picture whose stream fits one window (every
-    // 300 x 200 picture) costs one chain of dependent loads per 512 blocks instead of three ----
+    // the block's code goes into the first window of the stream (win_or drops what lies beyond it): a unit's record holds its
+    // meta word and the AC words nearly every unit ends with, so a picture whose stream fits one window (every 300 x 200 picture)
+    // costs one load per unit, and that load is requested a round ahead ----
+    // the records of the first kPackDepth rounds are on their way while the window is cleared
+    PackUnit ahead[kPackDepth];
+#pragma unroll
+    for (uint32_t j = 0; j < kPackDepth; ++j) ahead[j] = load_pack_unit(jb, j * T + tid, nunits);
     for (uint32_t i = tid; i < kWinWords; i += T) s_win[i] = 0u;
+    if (tid < 2u * kDcCodes) s_dc[tid] = kHuff.dc[tid / kDcCodes].e[tid % kDcCodes];
     if (tid == 0u) s_carry = 0u;
     __syncthreads();
-    for (uint32_t base = 0; base < nunits; base += T) {
-        const uint32_t u = base + tid;
-        uint32_t len = 0, dl = 0, dcw = 0, nw = 0, a0 = 0, a1 = 0;
-        if (u < nunits) {
-            const uint32_t m = jb.meta[u];
-            nw = ((m >> 16) + 31u) >> 5;
-            if (nw > 0u) a0 = jb.acbits[(size_t)u * kAcWordsPerUnit];
-            if (nw > 1u) a1 = jb.acbits[(size_t)u * kAcWordsPerUnit + 1u];
-            dcw = dc_code(jb, u, m, &dl);
-            len = dl + (m >> 16);
+    for (uint32_t base0 = 0; base0 < nunits; base0 += kPackDepth * T) {
+#pragma unroll
+        for (uint32_t j = 0; j < kPackDepth; ++j) {
+            const uint32_t base = base0 + j * T;
+            if (base >= nunits) break;                   // (uniform)
+            const uint32_t u = base + tid;
+            // round r + kPackDepth's records are requested before round r's scan: a round waits for a load that is already
+            // under way, not for a fresh round trip behind the two barriers
+            const PackUnit next = load_pack_unit(jb, u + kPackDepth * T, nunits);
+            const PackUnit cur = take_pack_unit(ahead[j], u, nunits);
+            ahead[j] = next;
+            const uint32_t m = cur.rec.x;                // (0 beyond the last unit: no bits)
+            const uint32_t nw = ((m >> 16) + 31u) >> 5;
+            uint32_t len = 0, dl = 0, dcw = 0;
+            if (u < nunits) {
+                dcw = dc_code(s_dc, u, m, cur.prev, &dl);
+                len = dl + (m >> 16);
+            }
+            uint32_t chunk;
+            const uint32_t ex = wg_exclusive_scan(len, s_w, &chunk);
+            const uint32_t carry = s_carry;
+            if (u < nunits) {
+                const uint32_t off = carry + ex;
+                ((global_u32 *)jb.unit_off)[u] = off;          // (global, not flat: see global_u32)
+                win_or(s_win, 0u, off, dcw);
+                // (a record's unused words are zero and win_or places no zero word: no test of nw for the first three)
+                win_or(s_win, 0u, (uint64_t)off + dl, cur.rec.y);
+                win_or(s_win, 0u, (uint64_t)off + dl + 32u, cur.rec.z);
+                win_or(s_win, 0u, (uint64_t)off + dl + 64u, cur.rec.w);
+                for (uint32_t w = kUnitAcWords; w < nw; ++w)
+                    win_or(s_win, 0u, (uint64_t)off + dl + 32u * w, ((const global_u32 *)jb.acbits)[(size_t)u * kAcWordsPerUnit + w]);
+            }
+            __syncthreads();
+            if (tid == 0u) s_carry = carry + chunk;
+            __syncthreads();
         }
-        uint32_t chunk;
-        const uint32_t ex = wg_exclusive_scan(len, s_w, &chunk);
-        const uint32_t carry = s_carry;
-        if (u < nunits) {
-            const uint32_t off = carry + ex;
-            jb.unit_off[u] = off;
-            win_or(s_win, 0u, off, dcw);
-            if (nw > 0u) win_or(s_win, 0u, (uint64_t)off + dl, a0);
-            if (nw > 1u) win_or(s_win, 0u, (uint64_t)off + dl + 32u, a1);
-            for (uint32_t w = 2; w < nw; ++w) win_or(s_win, 0u, (uint64_t)off + dl + 32u * w, jb.acbits[(size_t)u * kAcWordsPerUnit + w]);
-        }
-        __syncthreads();
-        if (tid == 0u) s_carry = carry + chunk;
-        __syncthreads();
     }
     const uint32_t total_bits = s_carry;
     if (tid == 0u) jb.unit_off[nunits] = total_bits;
@@ -538,13 +607,17 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
         for (uint32_t ub = u_lo; ub < u_hi; ub += T / 2u) {
             const uint32_t u = ub + (tid >> 1), j = tid & 1u;
             if (u < u_hi) {
-                const uint32_t m = jb.meta[u], off = jb.unit_off[u];
+                const PackUnit p = take_pack_unit(load_pack_unit(jb, u, u_hi), u, u_hi);
+                const uint32_t m = p.rec.x, off = jb.unit_off[u];
                 uint32_t dl;
-                const uint32_t dcw = dc_code(jb, u, m, &dl);
+                const uint32_t dcw = dc_code(s_dc, u, m, p.prev, &dl);
                 if (j == 0u) win_or(s_win, wbase, off, dcw);
                 const uint32_t nw = ((m >> 16) + 31u) >> 5;
-                for (uint32_t w = j; w < nw; w += 2u)
-                    win_or(s_win, wbase, (uint64_t)off + dl + 32u * w, jb.acbits[(size_t)u * kAcWordsPerUnit + w]);
+                // words j and j + 2 of the pair's split: lane 0 takes ac[0] and ac[2], lane 1 ac[1] (unused words are zero)
+                win_or(s_win, wbase, (uint64_t)off + dl + 32u * j, j ? p.rec.z : p.rec.y);
+                if (j == 0u) win_or(s_win, wbase, (uint64_t)off + dl + 64u, p.rec.w);
+                for (uint32_t w = j ? 3u : 4u; w < nw; w += 2u) // the words past the record: lane 1 goes on with 3, lane 0 with 4
+                    win_or(s_win, wbase, (uint64_t)off + dl + 32u * w, ((const global_u32 *)jb.acbits)[(size_t)u * kAcWordsPerUnit + w]);
             }
         }
         __syncthreads();
