@@ -51,6 +51,7 @@ _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESUL
               RESULT_WEBP_STREAM: FE_WEBP_LOSSLESS}  # (or FE_WEBP_LOSSY, by the clamped quality: result_front_end; both are streams)
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
 IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE, IMG_WEBP_SOURCE = 1, 2, 4, 8, 16, 32, 64
+IMG_VP8_SOURCE = 128
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 BATCH_SAME_PARAMS = 1
 (OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_OOM, ERR_DEVICE, ERR_PARSE, ERR_BUFFER_TOO_SMALL,
@@ -126,6 +127,15 @@ class flgpu_webp_info(C.Structure):
                                            "transforms", "color_cache_bits", "prefix_groups", "supported")]
 
 
+class flgpu_vp8_info(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "channels", "has_alpha", "extended", "animated", "exif_orientation", "supported",
+                                           "version", "segmentation", "update_map", "filter_type", "filter_level", "sharpness", "partitions",
+                                           "alpha_compression", "alpha_filter", "segment_quantizers", "segment_filter_levels",
+                                           "coef_prob_updates", "macroblocks", "bpred_macroblocks", "skipped_macroblocks",
+                                           "skipped_bpred_macroblocks", "bmodes_mask", "ymodes_mask", "uvmodes_mask", "cat6_tokens",
+                                           "blob_bytes")] + [("reserved", C.c_uint32 * 3)]
+
+
 class flgpu_gif_info(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "frames", "has_global_table", "interlaced_frames", "transparent_frames",
                                            "disposal_mask", "max_code_size")] + [("decoded_bytes", C.c_uint64), ("supported", C.c_uint32),
@@ -142,6 +152,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
+    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
@@ -222,6 +233,11 @@ def load_library() -> C.CDLL:
                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.flgpu_process_webp_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_int)]
         lib.flgpu_debug_webp_residuals.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_vp8_info_of"):  # (the same for lossy WebP sources)
+        lib.flgpu_vp8_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_vp8_info)]
+        lib.flgpu_decode_webp_lossy.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image)]
+        lib.flgpu_debug_vp8_blob.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.flgpu_debug_vp8_planes.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     if hasattr(lib, "flgpu_gif_info_of"):  # (the same for GIF files)
         lib.flgpu_gif_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_gif_info)]
         lib.flgpu_decode_gif.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image), C.POINTER(C.c_uint32)]
@@ -465,6 +481,29 @@ def debug_webp_residuals(data: bytes) -> bytes:
     return out[: used.value].tobytes()
 
 
+def vp8_info(data: bytes) -> dict:
+    """flgpu_vp8_info_of: container, frame header and -- for a supported file -- what the partitions of a lossy WebP file use (pure
+    host function); raises FanlinError(ERR_PARSE) if the file is damaged or is no lossy WebP."""
+    info = flgpu_vp8_info()
+    _check(load_library().flgpu_vp8_info_of(data, len(data), C.byref(info)))
+    return {n: getattr(info, n) for n, _ in flgpu_vp8_info._fields_ if n != "reserved"}
+
+
+def debug_vp8_blob(data: bytes) -> bytes:
+    """Host half of the lossy WebP decode front end alone: the blob that is uploaded (header, macroblock records, levels, ALPH plane)."""
+    lib = load_library()
+    used = C.c_uint64()
+    _check(lib.flgpu_debug_vp8_blob(data, len(data), None, 0, C.byref(used)))
+    out = np.zeros(max(used.value, 1), np.uint8)
+    _check(lib.flgpu_debug_vp8_blob(data, len(data), out.ctypes.data, out.nbytes, C.byref(used)))
+    return out[: used.value].tobytes()
+
+
+class LossyWebp(bytes):
+    """A lossy WebP file for State.process_batch: handed over as FLGPU_IMG_VP8_SOURCE.  (Bare ``bytes`` holding a WebP file are a
+    FLGPU_IMG_WEBP_SOURCE, which takes lossless files only.)"""
+
+
 def gif_info(data: bytes) -> dict:
     """flgpu_gif_info_of: canvas, frames and what the frames use, from the container and the LZW stage of a GIF file (pure host
     function); raises FanlinError(ERR_PARSE) if the file is damaged."""
@@ -485,6 +524,8 @@ def debug_gif_blob(data: bytes) -> bytes:
 
 def _source_info(data):
     """(header dict, source flag) of a file handed over as a source: PNG and WebP by their signatures, else JPEG."""
+    if isinstance(data, LossyWebp):
+        return vp8_info(bytes(data)), IMG_VP8_SOURCE
     if bytes(data[:8]) == PNG_SIGNATURE:
         return png_info(bytes(data)), IMG_PNG_SOURCE
     if bytes(data[:4]) == b"RIFF" and bytes(data[8:12]) == b"WEBP":
@@ -825,6 +866,42 @@ class State:
         fe = _RESULT_FE[kind.value]
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
 
+    # -- lossy WebP sources: the decode front end (handler.rs:205-220) -----------------------------------------------
+    def decode_webp_lossy(self, data: bytes) -> np.ndarray:
+        """flgpu_decode_webp_lossy: (h, w, 3 or 4) uint8, libwebp's WebPDecodeRGB / WebPDecodeRGBA; the EXIF orientation is not applied."""
+        info = vp8_info(data)
+        out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_decode_webp_lossy(self._ctx, data, len(data), C.byref(dst)), self._ctx)
+        return out
+
+    def process_vp8_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None):
+        """process_pixels with a lossy WebP FILE as the source (FLGPU_IMG_VP8_SOURCE): boolean decoding on this thread, the rest in
+        one device pass.  ``shape`` = (height, width, channels) to announce instead of what flgpu_vp8_info_of says."""
+        if shape is None:
+            info = vp8_info(data)
+            shape = (info["height"], info["width"], max(info["channels"], 1))
+        plan = plan_output(params, shape[1], shape[0], shape[2])
+        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
+        buf = C.create_string_buffer(data, len(data))
+        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_VP8_SOURCE)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
+        return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
+
+    def debug_vp8_planes(self, data: bytes, filtered: bool = True):
+        """flgpu_debug_vp8_planes: the device's (y, u, v) of a lossy WebP file, cut to the picture, before or behind the loop filter."""
+        info = vp8_info(data)
+        w, h = info["width"], info["height"]
+        mbw, mbh = (w + 15) // 16, (h + 15) // 16
+        used = C.c_uint64()
+        out = np.zeros(mbw * mbh * 384, np.uint8)
+        _check(self._lib.flgpu_debug_vp8_planes(self._ctx, data, len(data), int(filtered), out.ctypes.data, out.nbytes, C.byref(used)), self._ctx)
+        y = out[:mbw * mbh * 256].reshape(mbh * 16, mbw * 16)
+        u = out[mbw * mbh * 256:mbw * mbh * 320].reshape(mbh * 8, mbw * 8)
+        v = out[mbw * mbh * 320:].reshape(mbh * 8, mbw * 8)
+        return y[:h, :w].copy(), u[:(h + 1) // 2, :(w + 1) // 2].copy(), v[:(h + 1) // 2, :(w + 1) // 2].copy()
+
     # -- GIF files: decode, compositing and the per-frame pipeline (handler.rs:311-353) -------------------------------
     def decode_gif(self, data: bytes) -> np.ndarray:
         """GifDecoder::new(..).into_frames().collect_frames() on the device: (frames, h, w, 4) uint8, every frame the composited canvas."""
@@ -869,12 +946,16 @@ class State:
         """The lossless WebP decode front end's counters (flgpu_debug_get)."""
         return {k: self.debug_get(k) for k in ("webp_sources", "webp_file_bytes", "webp_upload_bytes")}
 
+    def vp8_counters(self) -> dict:
+        """The lossy WebP decode front end's counters (flgpu_debug_get): pictures decoded, their file bytes, what crossed PCIe for them."""
+        return {k: self.debug_get(k) for k in ("vp8_sources", "vp8_file_bytes", "vp8_upload_bytes")}
+
     def png_counters(self) -> dict:
         """The PNG decode front end's counters (flgpu_debug_get): pictures decoded, their file bytes, what crossed PCIe for them."""
         return {k: self.debug_get(k) for k in ("png_sources", "png_file_bytes", "png_upload_bytes")}
 
     def process_batch(self, images: Sequence, params: Sequence[flgpu_params]) -> List:
-        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file (decoded by the library)."""
+        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file, or a LossyWebp (decoded by the library)."""
         n = len(images)
         srcinfo = [_source_info(a) if isinstance(a, (bytes, bytearray)) else (None, 0) for a in images]
         infos = [s[0] for s in srcinfo]

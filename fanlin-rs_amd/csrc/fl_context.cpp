@@ -356,6 +356,7 @@ void resolve_pending(flgpu_ctx *c)
             else if (p.kind == 5) c->gif_compose_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 6) c->gif_encode_ns += (uint64_t)((double)ms * 1e6);
             else if (p.kind == 7) c->webp_lossy_ns += (uint64_t)((double)ms * 1e6);
+            else if (p.kind == 8) c->vp8_decode_ns += (uint64_t)((double)ms * 1e6);
             else c->stats.frontend_ms += ms;
         }
         c->event_pool.push_back(p.a);
@@ -520,6 +521,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
     c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();
+    c->d_vp8dec.release(); c->d_vp8jobs.release(); c->h_vp8jobs.release();
     c->d_gifdec.release();
     c->d_gifenc.release();
     c->h_gifstat.release();
@@ -636,6 +638,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         c->stats = flgpu_stats{};
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = c->webp_lossy_ns = 0;
+        c->vp8_sources = c->vp8_file_bytes = c->vp8_upload_bytes = c->vp8_decode_ns = 0;
         c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
         c->gif_encoded = c->gif_encode_fallbacks = c->gif_encoded_bytes = c->gif_encode_ns = 0;
     }
@@ -661,11 +664,13 @@ int flgpu_debug_set(flgpu_ctx *c, const char *key, int64_t value)
 int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value || !c->dbg) return FLGPU_ERR_INVALID_ARG;
-    // read-only counters of the PNG, lossless WebP and GIF decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
+    // read-only counters of the PNG, lossless WebP, lossy WebP and GIF decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
+        {"vp8_sources", &flgpu_ctx::vp8_sources}, {"vp8_file_bytes", &flgpu_ctx::vp8_file_bytes}, {"vp8_upload_bytes", &flgpu_ctx::vp8_upload_bytes},
+        {"vp8_decode_ns", &flgpu_ctx::vp8_decode_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
         {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns},
         {"gif_encoded", &flgpu_ctx::gif_encoded}, {"gif_encode_fallbacks", &flgpu_ctx::gif_encode_fallbacks}, {"gif_encoded_bytes", &flgpu_ctx::gif_encoded_bytes},

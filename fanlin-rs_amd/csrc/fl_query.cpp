@@ -514,11 +514,109 @@ try {
     return FLGPU_OK;
 } FL_ABI_CATCH
 
+// EXIF orientation of a lossy file: the same chunk, the same two forms
+static uint32_t vp8_orientation(const uint8_t *file, const fl::Vp8Info &I)
+{
+    fl::WebpInfo W;
+    W.exif_off = I.exif_off; W.exif_len = I.exif_len;
+    return webp_orientation(file, W);
+}
+
+// the picture of a WebP file is a `VP8 ` chunk (the first chunk, or the first image chunk behind VP8X)
+static bool webp_is_lossy(const uint8_t *d, uint64_t n)
+{
+    if (!d || n < 20 || memcmp(d, "RIFF", 4) || memcmp(d + 8, "WEBP", 4)) return false;
+    for (uint64_t pos = 12; n - pos >= 8;) {
+        if (!memcmp(d + pos, "VP8 ", 4)) return true;
+        if (!memcmp(d + pos, "VP8L", 4) || !memcmp(d + pos, "ANMF", 4)) return false;
+        const uint64_t len = (uint64_t)d[pos + 4] | (uint64_t)d[pos + 5] << 8 | (uint64_t)d[pos + 6] << 16 | (uint64_t)d[pos + 7] << 24;
+        if (len > n - pos - 8) return false;
+        pos += 8u + len + (len & 1u);
+        if (pos > n) return false;
+    }
+    return false;
+}
+
+int flgpu_vp8_info_of(const uint8_t *webp, uint64_t n, flgpu_vp8_info *info)
+try {
+    if (!webp || !info) return FLGPU_ERR_INVALID_ARG;
+    fl::Vp8Info I;
+    if (fl::vp8_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE;
+    memset(info, 0, sizeof(*info));
+    info->width = I.width; info->height = I.height; info->channels = I.channels; info->has_alpha = I.has_alpha;
+    info->extended = I.extended; info->animated = I.animated; info->exif_orientation = vp8_orientation(webp, I);
+    info->supported = I.supported; info->version = I.version; info->segmentation = I.segmentation; info->update_map = I.update_map;
+    info->filter_type = I.filter_simple; info->filter_level = I.filter_level; info->sharpness = I.sharpness; info->partitions = I.partitions;
+    info->alpha_compression = I.alpha_compression; info->alpha_filter = I.alpha_filter;
+    info->segment_quantizers = I.segment_quantizers; info->segment_filter_levels = I.segment_filter_levels;
+    info->coef_prob_updates = I.coef_prob_updates;
+    info->macroblocks = I.macroblocks; info->bpred_macroblocks = I.bpred_macroblocks; info->skipped_macroblocks = I.skipped_macroblocks;
+    info->skipped_bpred_macroblocks = I.skipped_bpred_macroblocks;
+    info->bmodes_mask = I.bmodes_mask; info->ymodes_mask = I.ymodes_mask; info->uvmodes_mask = I.uvmodes_mask;
+    info->cat6_tokens = I.cat6_tokens; info->blob_bytes = I.blob_bytes;
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
+static int plan_vp8(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
+                    flgpu_plan *plan, int *kind, int *out_format)
+{
+    // (container and frame header only here: flgpu_transform reads the partitions once; as_is serves the file unread)
+    fl::Vp8Info info;
+    if (fl::vp8_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    memset(src, 0, sizeof(*src));
+    src->data = const_cast<uint8_t *>(webp);
+    src->capacity = n;
+    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
+    src->flags = FLGPU_IMG_VP8_SOURCE;
+    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
+    const uint32_t o = vp8_orientation(webp, info);
+    return plan_request(src, (uint8_t)(o ? o : 1u), query_string, accept_flags, FLGPU_IN_WEBP, p, plan, kind, out_format);
+}
+
+int flgpu_decode_webp_lossy(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst)
+try {
+    if (!ctx || !dst || !dst->data || !webp) return FLGPU_ERR_INVALID_ARG;
+    fl::Vp8Info info;
+    if (fl::vp8_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
+    return decode_file(ctx, webp, n, info.width, info.height, info.channels, FLGPU_IMG_VP8_SOURCE, dst);
+} FL_ABI_CATCH
+
+int flgpu_debug_vp8_blob(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!webp || !used) return FLGPU_ERR_INVALID_ARG;
+    fl::Vp8Info I;
+    if (fl::vp8_parse_info(webp, (size_t)n, I, out == nullptr) != 0) return FLGPU_ERR_PARSE; // (the blob's size follows from the tokens)
+    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
+    if (!out) { *used = I.blob_bytes; return FLGPU_OK; }
+    // decoded into a buffer of the worst-case capacity, as flgpu_transform has it in its staging
+    const size_t cap = fl::vp8_blob_capacity(I);
+    std::unique_ptr<uint8_t[]> work(new uint8_t[cap + 16u]);
+    uint8_t *blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
+    fl::Vp8BlobHeader H;
+    const int rc = fl::vp8_decode_levels(webp, (size_t)n, blob, cap, &H);
+    if (rc) return fl::vp8_status(rc);
+    *used = H.total_bytes;
+    if (capacity < H.total_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    memcpy(out, blob, H.total_bytes);
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
+int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int filter, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!ctx || !webp || !used) return FLGPU_ERR_INVALID_ARG;
+    size_t u = 0;
+    const int rc = fl::debug_vp8_planes(ctx, webp, (size_t)n, filter, out, (size_t)capacity, &u);
+    *used = u;
+    return rc;
+} FL_ABI_CATCH
+
 static int plan_webp(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
                      flgpu_plan *plan, int *kind, int *out_format)
 {
     // (container and VP8L header only here: flgpu_transform reads the stream once; as_is serves the file unread, as the reference does)
     if (!webp) return FLGPU_ERR_INVALID_ARG;
+    if (webp_is_lossy(webp, n)) return plan_vp8(webp, n, query_string, accept_flags, src, p, plan, kind, out_format);
     fl::WebpInfo info;
     if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
     memset(src, 0, sizeof(*src));

@@ -1,10 +1,13 @@
-// fl_source.cpp -- JPEG / PNG / lossless WebP files as sources of a batch (fl_source.h): what a file may make the library reserve, the host
+// fl_source.cpp -- JPEG / PNG / lossless WebP / lossy WebP files as sources of a batch (fl_source.h): what a file may make the library reserve, the host
 // half on the thread that stages the file, and the decode launches in front of run_batch_device.
 #include <stdio.h>
 
 #include <algorithm>
+#include <mutex>
+#include <string>
 
 #include "fl_context.h"
+#include "fl_vp8_core.h"
 
 namespace fl {
 
@@ -306,6 +309,55 @@ static int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *bl
     return FLGPU_OK;
 }
 
+// The job lists of a batch's lossless pictures: the runs in front of a predictor transform, the runs that end in pixels, the predictor transforms.
+struct WebpJobLists {
+    WebpRunJob *ra = nullptr, *rb = nullptr;
+    WebpPredictJob *pj = nullptr;
+    uint32_t na = 0, nb = 0, npred = 0, max_a = 0, max_b = 0;
+};
+
+// The inverse transforms of one picture, last to first, as jobs on L: `pixels` receives H.channels interleaved bytes, the intermediate
+// pictures of dwords are taken from base + off.  (A lossless WebP source, and the VP8L-coded alpha plane of a lossy one.)
+static int webp_picture_jobs(flgpu_ctx *c, const WebpBlobHeader &H, const uint8_t *blob, uint8_t *base, size_t &off, uint8_t *pixels, WebpJobLists &L)
+{
+    const uint32_t *cur = reinterpret_cast<const uint32_t *>(blob + H.res_off);
+    uint32_t cw = H.xsize;
+    WebpRunJob run;
+    auto begin_run = [&] { memset(&run, 0, sizeof(run)); run.src = cur; run.src_w = cw; run.height = H.height; };
+    begin_run();
+    if (H.ntransforms > 4) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+    for (uint32_t k = H.ntransforms; k-- > 0;) { // the inverse transforms, last to first
+        if (H.ttype[k] == kWtPredictor) {
+            if (run.nops) { // what is pointwise in front of it goes into a picture of dwords first
+                uint32_t *mid = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
+                run.dst = mid; run.dst_w = cw; run.out_c = 0;
+                L.ra[L.na++] = run;
+                L.max_a = std::max(L.max_a, cw * H.height);
+                cur = mid;
+            }
+            uint32_t *out = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
+            WebpPredictJob &p = L.pj[L.npred++];
+            memset(&p, 0, sizeof(p));
+            p.res = cur; p.modes = reinterpret_cast<const uint32_t *>(blob + H.toff[k]); p.out = out;
+            p.width = cw; p.height = H.height; p.bits = H.tbits[k];
+            if (H.twidth[k] != cw || p.bits < 2u || p.bits > 9u) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+            cur = out;
+            begin_run();
+            continue;
+        }
+        WebpOp &op = run.ops[run.nops++];
+        op.type = H.ttype[k];
+        op.data = reinterpret_cast<const uint32_t *>(blob + H.toff[k]);
+        if (op.type == kWtCrossColor) { op.bits = H.tbits[k]; op.width = H.twidth[k]; }
+        if (op.type == kWtColorIndexing) { op.bits = run.shift = webp_index_shift(H.tbits[k]); cw = H.twidth[k]; }
+    }
+    if (cw != H.width) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+    run.dst = pixels; run.dst_w = cw; run.out_c = H.channels;
+    L.rb[L.nb++] = run;
+    L.max_b = std::max(L.max_b, cw * H.height);
+    return FLGPU_OK;
+}
+
 static int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource *const *srcs, hipStream_t st)
 {
     size_t np = 0, scratch = 0;
@@ -322,9 +374,9 @@ static int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
     FL_HIP(c, c->h_webpjobs.reserve(job_bytes), "WebP decode descriptors");
     FL_HIP(c, c->d_webpjobs.reserve(job_bytes), "WebP decode descriptors");
     // descriptors: the runs in front of a predictor transform, the runs that end in pixels, the predictor transforms
-    WebpRunJob *ra = static_cast<WebpRunJob *>(c->h_webpjobs.p), *rb = ra + np;
-    WebpPredictJob *pj = reinterpret_cast<WebpPredictJob *>(static_cast<uint8_t *>(c->h_webpjobs.p) + run_bytes);
-    uint32_t na = 0, nb = 0, npred = 0, max_a = 0, max_b = 0;
+    WebpJobLists L;
+    L.ra = static_cast<WebpRunJob *>(c->h_webpjobs.p); L.rb = L.ra + np;
+    L.pj = reinterpret_cast<WebpPredictJob *>(static_cast<uint8_t *>(c->h_webpjobs.p) + run_bytes);
     size_t off = 0;
     for (size_t i = 0; i < n; ++i) {
         if (srcs[i]->kind != SRC_WEBP) continue;
@@ -332,41 +384,7 @@ static int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
         const uint8_t *blob = dsrc[i].data;
         uint8_t *base = static_cast<uint8_t *>(c->d_webpdec.p);
         uint8_t *pixels = base + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
-        const uint32_t *cur = reinterpret_cast<const uint32_t *>(blob + H.res_off);
-        uint32_t cw = H.xsize;
-        WebpRunJob run;
-        auto begin_run = [&] { memset(&run, 0, sizeof(run)); run.src = cur; run.src_w = cw; run.height = H.height; };
-        begin_run();
-        if (H.ntransforms > 4) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-        for (uint32_t k = H.ntransforms; k-- > 0;) { // the inverse transforms, last to first
-            if (H.ttype[k] == kWtPredictor) {
-                if (run.nops) { // what is pointwise in front of it goes into a picture of dwords first
-                    uint32_t *mid = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
-                    run.dst = mid; run.dst_w = cw; run.out_c = 0;
-                    ra[na++] = run;
-                    max_a = std::max(max_a, cw * H.height);
-                    cur = mid;
-                }
-                uint32_t *out = reinterpret_cast<uint32_t *>(base + off); off += align_up((size_t)cw * H.height * 4u + 64, 256);
-                WebpPredictJob &p = pj[npred++];
-                memset(&p, 0, sizeof(p));
-                p.res = cur; p.modes = reinterpret_cast<const uint32_t *>(blob + H.toff[k]); p.out = out;
-                p.width = cw; p.height = H.height; p.bits = H.tbits[k];
-                if (H.twidth[k] != cw || p.bits < 2u || p.bits > 9u) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-                cur = out;
-                begin_run();
-                continue;
-            }
-            WebpOp &op = run.ops[run.nops++];
-            op.type = H.ttype[k];
-            op.data = reinterpret_cast<const uint32_t *>(blob + H.toff[k]);
-            if (op.type == kWtCrossColor) { op.bits = H.tbits[k]; op.width = H.twidth[k]; }
-            if (op.type == kWtColorIndexing) { op.bits = run.shift = webp_index_shift(H.tbits[k]); cw = H.twidth[k]; }
-        }
-        if (cw != H.width) { c->set_error("WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
-        run.dst = pixels; run.dst_w = cw; run.out_c = H.channels;
-        rb[nb++] = run;
-        max_b = std::max(max_b, cw * H.height);
+        if (int rc = webp_picture_jobs(c, H, blob, base, off, pixels, L)) return rc;
         if (!tl_force_host_huffman) { c->webp_sources++; c->webp_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
         dsrc[i].data = pixels;
         dsrc[i].channels = H.channels;
@@ -376,9 +394,153 @@ static int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
     FL_HIP(c, hipMemcpyAsync(c->d_webpjobs.p, c->h_webpjobs.p, job_bytes, hipMemcpyHostToDevice, st), "WebP decode descriptors");
     const WebpRunJob *d_ra = static_cast<const WebpRunJob *>(c->d_webpjobs.p);
     const WebpPredictJob *d_pj = reinterpret_cast<const WebpPredictJob *>(static_cast<const uint8_t *>(c->d_webpjobs.p) + run_bytes);
-    if (na) { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra, na, max_a, st), "WebP pointwise transform kernel"); }
-    if (npred) { ProfileScope ps(c, st, 3); FL_HIP(c, launch_webp_predict(d_pj, npred, st), "WebP predictor kernel"); }
-    { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra + np, nb, max_b, st), "WebP pointwise transform kernel"); }
+    if (L.na) { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra, L.na, L.max_a, st), "WebP pointwise transform kernel"); }
+    if (L.npred) { ProfileScope ps(c, st, 3); FL_HIP(c, launch_webp_predict(d_pj, L.npred, st), "WebP predictor kernel"); }
+    { ProfileScope ps(c, st, 4); FL_HIP(c, launch_webp_run(d_ra + np, L.nb, L.max_b, st), "WebP pointwise transform kernel"); }
+    return FLGPU_OK;
+}
+
+// ---- lossy WebP sources ------------------------------------------------------------------------------------------------------------
+
+static int vp8_source_info(flgpu_ctx *c, const flgpu_image *src, Vp8Info &info)
+{
+    // (container and frame header only: vp8_source_to_blob reads the partitions, once per request)
+    if (vp8_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed lossy WebP file (RIFF size, chunk layout, frame tag, start code, partition sizes or too few bytes)"); return FLGPU_ERR_PARSE; }
+    if (!info.supported) { c->set_error(std::string("lossy WebP file not covered by the device decoder: ") + (info.refused ? info.refused : "unknown feature")); return FLGPU_ERR_UNSUPPORTED; }
+    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
+        c->set_error("FLGPU_IMG_VP8_SOURCE: width / height / channels do not match the file (see flgpu_vp8_info_of)");
+        return FLGPU_ERR_INVALID_ARG;
+    }
+    return FLGPU_OK;
+}
+
+static int vp8_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, Vp8BlobHeader *hdr, size_t *used)
+{
+    const int rc = vp8_decode_levels(src->data, (size_t)src->capacity, blob, cap, hdr);
+    if (rc == kVp8Parse) c->set_error("malformed lossy WebP stream (a partition ends before its last macroblock, or a damaged ALPH stream)");
+    if (rc == kVp8Unsupported) c->set_error("lossy WebP file: ALPH stream with more code tables than the decoder's work area holds");
+    if (rc) return vp8_status(rc);
+    *used = hdr->total_bytes;
+    return FLGPU_OK;
+}
+
+// scratch of one picture: the padded planes, the alpha plane, the pixels
+static size_t vp8_scratch_bytes(const Vp8BlobHeader &H)
+{
+    // (a VP8L-coded alpha plane: its R, G, B, A bytes and at most two intermediate pictures of dwords, as for a lossless source)
+    return align_up((size_t)vp8_rec_bytes(H.mbw, H.mbh) + 64, 256) + (H.alpha ? align_up((size_t)H.width * H.height + 64, 256) : 0) +
+           (H.alpha == 2u ? 3 * align_up((size_t)H.width * H.height * 4u + 64, 256) : 0) + align_up((size_t)H.width * H.height * H.channels + 64, 256);
+}
+
+// jobs[0 .. n) over `scratch`: per picture the planes, the alpha plane where the blob has one, the pixels
+static void vp8_jobs(Vp8DecJob *jobs, uint8_t *scratch, const Vp8BlobHeader *const *H, const uint8_t *const *blobs, size_t n)
+{
+    size_t off = 0;
+    for (size_t k = 0; k < n; ++k) {
+        Vp8DecJob &j = jobs[k];
+        memset(&j, 0, sizeof(j));
+        j.blob = blobs[k];
+        j.planes = scratch + off; off += align_up((size_t)vp8_rec_bytes(H[k]->mbw, H[k]->mbh) + 64, 256);
+        if (H[k]->alpha) {
+            j.alpha = scratch + off; off += align_up((size_t)H[k]->width * H[k]->height + 64, 256);
+            j.alpha_src = blobs[k] + H[k]->alpha_off; j.alpha_stride = 1; // (a VP8L-coded plane: decode_vp8_sources points it at the green bytes)
+        }
+        j.dst = scratch + off; off += align_up((size_t)H[k]->width * H[k]->height * H[k]->channels + 64, 256);
+        j.width = H[k]->width; j.height = H[k]->height; j.channels = H[k]->channels; j.filtered = H[k]->filter_type != 0u;
+    }
+}
+
+static int decode_vp8_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource *const *srcs, hipStream_t st)
+{
+    // the pictures the loop filter runs on go first: its kernel is launched for that many workgroups
+    std::vector<size_t> order;
+    for (int filtered = 1; filtered >= 0; --filtered)
+        for (size_t i = 0; i < n; ++i)
+            if (srcs[i]->kind == SRC_VP8 && (srcs[i]->vp8.filter_type != 0u) == (filtered != 0)) order.push_back(i);
+    const size_t np = order.size();
+    if (!np) return FLGPU_OK;
+    size_t scratch = 0;
+    std::vector<const Vp8BlobHeader *> H(np);
+    std::vector<const uint8_t *> blobs(np);
+    for (size_t k = 0; k < np; ++k) {
+        H[k] = &srcs[order[k]]->vp8; blobs[k] = dsrc[order[k]].data;
+        if (H[k]->magic != kVp8BlobMagic || H[k]->mbw != vp8_mbs(H[k]->width) || H[k]->mbh != vp8_mbs(H[k]->height)) { c->set_error("lossy WebP source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+        scratch += vp8_scratch_bytes(*H[k]);
+    }
+    // descriptors: the decode jobs, and for the VP8L-coded alpha planes the lossless decoder's three job lists behind them
+    size_t ncoded = 0;
+    for (size_t k = 0; k < np; ++k) ncoded += H[k]->alpha == 2u;
+    const size_t dec_bytes = align_up(np * sizeof(Vp8DecJob), 256), run_bytes = 2 * ncoded * sizeof(WebpRunJob);
+    const size_t job_bytes = dec_bytes + run_bytes + ncoded * sizeof(WebpPredictJob);
+    FL_HIP(c, c->d_vp8dec.reserve(scratch), "lossy WebP decode scratch");
+    FL_HIP(c, c->h_vp8jobs.reserve(job_bytes), "lossy WebP decode descriptors");
+    FL_HIP(c, c->d_vp8jobs.reserve(job_bytes), "lossy WebP decode descriptors");
+    Vp8DecJob *jobs = static_cast<Vp8DecJob *>(c->h_vp8jobs.p);
+    uint8_t *base = static_cast<uint8_t *>(c->d_vp8dec.p);
+    vp8_jobs(jobs, base, H.data(), blobs.data(), np);
+    WebpJobLists L;
+    L.ra = reinterpret_cast<WebpRunJob *>(static_cast<uint8_t *>(c->h_vp8jobs.p) + dec_bytes); L.rb = L.ra + ncoded;
+    L.pj = reinterpret_cast<WebpPredictJob *>(static_cast<uint8_t *>(c->h_vp8jobs.p) + dec_bytes + run_bytes);
+    size_t off = 0;
+    for (size_t k = 0; k < np; ++k) off += vp8_scratch_bytes(*H[k]) - (H[k]->alpha == 2u ? 3 * align_up((size_t)H[k]->width * H[k]->height * 4u + 64, 256) : 0);
+    for (size_t k = 0; k < np; ++k) { // the alpha planes' own scratch lies behind every picture's planes and pixels
+        if (H[k]->alpha != 2u) continue;
+        const WebpBlobHeader &W = srcs[order[k]]->vp8_alpha;
+        if (W.magic != kWebpMagic || W.width != H[k]->width || W.height != H[k]->height || W.channels != 4u) { c->set_error("lossy WebP source: damaged alpha blob header"); return FLGPU_ERR_INVALID_ARG; }
+        uint8_t *rgba = base + off; off += align_up((size_t)W.width * W.height * 4u + 64, 256);
+        if (int rc = webp_picture_jobs(c, W, blobs[k] + H[k]->alpha_off, base, off, rgba, L)) return rc;
+        jobs[k].alpha_src = rgba + 1; jobs[k].alpha_stride = 4; // the green byte of R, G, B, A
+    }
+    for (size_t k = 0; k < np; ++k) {
+        const size_t i = order[k];
+        if (!tl_force_host_huffman) { c->vp8_sources++; c->vp8_upload_bytes += H[k]->total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
+        dsrc[i].data = jobs[k].dst;
+        dsrc[i].channels = H[k]->channels;
+        dsrc[i].capacity = (uint64_t)H[k]->width * H[k]->height * H[k]->channels;
+        dsrc[i].flags &= ~FLGPU_IMG_VP8_SOURCE;
+    }
+    FL_HIP(c, hipMemcpyAsync(c->d_vp8jobs.p, c->h_vp8jobs.p, job_bytes, hipMemcpyHostToDevice, st), "lossy WebP decode descriptors");
+    ProfileScope ps(c, st, 8);
+    if (ncoded) { // the existing inverse transforms on the alpha planes' residuals
+        const WebpRunJob *d_ra = reinterpret_cast<const WebpRunJob *>(static_cast<const uint8_t *>(c->d_vp8jobs.p) + dec_bytes);
+        const WebpPredictJob *d_pj = reinterpret_cast<const WebpPredictJob *>(static_cast<const uint8_t *>(c->d_vp8jobs.p) + dec_bytes + run_bytes);
+        if (L.na) FL_HIP(c, launch_webp_run(d_ra, L.na, L.max_a, st), "WebP pointwise transform kernel (alpha plane)");
+        if (L.npred) FL_HIP(c, launch_webp_predict(d_pj, L.npred, st), "WebP predictor kernel (alpha plane)");
+        FL_HIP(c, launch_webp_run(d_ra + ncoded, L.nb, L.max_b, st), "WebP pointwise transform kernel (alpha plane)");
+    }
+    FL_HIP(c, launch_vp8_decode(static_cast<const Vp8DecJob *>(c->d_vp8jobs.p), jobs, (uint32_t)np, st), "lossy WebP decode kernels");
+    return FLGPU_OK;
+}
+
+int debug_vp8_planes(flgpu_ctx *c, const uint8_t *file, size_t n, int filter, uint8_t *out, size_t capacity, size_t *used)
+{
+    Vp8Info info;
+    if (vp8_parse_info(file, n, info, false) != 0) return FLGPU_ERR_PARSE;
+    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
+    const size_t planes = (size_t)vp8_rec_bytes(vp8_mbs(info.width), vp8_mbs(info.height));
+    *used = planes;
+    if (!out) return FLGPU_OK;
+    if (capacity < planes) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const size_t cap = vp8_blob_capacity(info);
+    std::vector<uint8_t> work(cap + 16u);
+    uint8_t *blob = work.data() + ((16u - (reinterpret_cast<uintptr_t>(work.data()) & 15u)) & 15u);
+    Vp8BlobHeader H;
+    if (int rc = vp8_decode_levels(file, n, blob, cap, &H)) return vp8_status(rc);
+    std::lock_guard<std::mutex> g(c->mu);
+    FL_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    DeviceBuf d_blob, d_scratch, d_job;
+    struct Release { DeviceBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release{d_blob, d_scratch, d_job};
+    FL_HIP(c, d_blob.reserve(H.total_bytes), "lossy WebP blob");
+    FL_HIP(c, d_scratch.reserve(vp8_scratch_bytes(H)), "lossy WebP decode scratch");
+    FL_HIP(c, d_job.reserve(sizeof(Vp8DecJob)), "lossy WebP decode descriptors");
+    Vp8DecJob job;
+    const Vp8BlobHeader *hp = &H;
+    const uint8_t *bp = static_cast<const uint8_t *>(d_blob.p);
+    vp8_jobs(&job, static_cast<uint8_t *>(d_scratch.p), &hp, &bp, 1);
+    FL_HIP(c, hipMemcpy(d_blob.p, blob, H.total_bytes, hipMemcpyHostToDevice), "lossy WebP blob H2D");
+    FL_HIP(c, hipMemcpy(d_job.p, &job, sizeof(job), hipMemcpyHostToDevice), "lossy WebP decode descriptors");
+    FL_HIP(c, launch_vp8_decode(static_cast<const Vp8DecJob *>(d_job.p), &job, 1, nullptr, filter ? 2 : 1), "lossy WebP decode kernels");
+    FL_HIP(c, hipMemcpy(out, job.planes, planes, hipMemcpyDeviceToHost), "lossy WebP planes D2H");
     return FLGPU_OK;
 }
 
@@ -402,6 +564,10 @@ int source_probe(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
         if (int rc = webp_source_info(c, src, out.webp)) return rc;
         out.capacity = webp_blob_capacity(out.webp, (size_t)src->capacity);
         break;
+    case SRC_VP8:
+        if (int rc = vp8_source_info(c, src, out.vp8)) return rc;
+        out.capacity = vp8_blob_capacity(out.vp8);
+        break;
     case SRC_PIXELS:
         out.capacity = (size_t)src->width * src->height * src->channels;
         if (src->capacity < out.capacity) return FLGPU_ERR_INVALID_ARG;
@@ -423,6 +589,10 @@ int source_stage(flgpu_ctx *c, const flgpu_image *src, SourceProbe &probe, void 
         break;
     case SRC_PNG: rc = png_source_to_blob(c, src, blob, cap, &out.png, &out.used); break;
     case SRC_WEBP: rc = webp_source_to_blob(c, src, blob, cap, &out.webp, &out.used); break;
+    case SRC_VP8:
+        rc = vp8_source_to_blob(c, src, blob, cap, &out.vp8, &out.used);
+        if (!rc && out.vp8.alpha == 2u) memcpy(&out.vp8_alpha, blob + out.vp8.alpha_off, sizeof(out.vp8_alpha));
+        break;
     case SRC_PIXELS: return FLGPU_OK; // nothing to decode: the caller copies the pixels, or hands over its pinned buffer
     }
     if (rc) return rc;
@@ -438,10 +608,12 @@ int decode_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource
         if (staged[i]->kind == SRC_JPEG) c->stats.jpeg_file_bytes += staged[i]->file_bytes;
         if (staged[i]->kind == SRC_PNG && !tl_force_host_huffman) c->png_file_bytes += staged[i]->file_bytes;
         if (staged[i]->kind == SRC_WEBP && !tl_force_host_huffman) c->webp_file_bytes += staged[i]->file_bytes;
+        if (staged[i]->kind == SRC_VP8 && !tl_force_host_huffman) c->vp8_file_bytes += staged[i]->file_bytes;
     }
     if (int rc = decode_jpeg_sources(c, n, dsrc, staged, st)) return rc;
     if (int rc = decode_png_sources(c, n, dsrc, staged, st)) return rc;
-    return decode_webp_sources(c, n, dsrc, staged, st);
+    if (int rc = decode_webp_sources(c, n, dsrc, staged, st)) return rc;
+    return decode_vp8_sources(c, n, dsrc, staged, st);
 }
 
 // Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway

@@ -316,10 +316,10 @@ struct Decoder {
 };
 
 // transforms + main image of one VP8L payload into the arena; H is filled as the stream is read
-int decode_stream(const WebpInfo &info, Decoder &D, WebpBlobHeader &H)
+int decode_stream(const WebpInfo &info, Decoder &D, WebpBlobHeader &H, bool headerless = false)
 {
     Bits &b = D.b;
-    b.get(8); b.get(14); b.get(14); b.get(1); b.get(3); // signature, sizes, alpha, version: webp_parse_info has read them
+    if (!headerless) { b.get(8); b.get(14); b.get(14); b.get(1); b.get(3); } // signature, sizes, alpha, version: webp_parse_info has read them
     memset(&H, 0, sizeof(H));
     H.magic = kWebpMagic;
     H.width = info.width; H.height = info.height; H.channels = info.channels;
@@ -375,6 +375,22 @@ size_t work_bytes(const WebpInfo &info, size_t file_bytes)
     // entropy image, and the code tables: a group of five codes takes 280 bytes, its used symbols two bytes each, a first-level
     // table 2 KiB a code while there is room; a file cannot describe more symbols than it has bits
     return (size_t)webp_subsample(info.width, 2) * webp_subsample(info.height, 2) * 4u + ((size_t)256 << 10) + 2u * file_bytes;
+}
+
+// The deep header walk: transform headers and the main image's code groups, without the main image's pixels.  The sub-images in front
+// of them have to be entropy-decoded, into a work area of this call's own, bounded like the decode's.
+int walk_headers(const WebpInfo &info, const uint8_t *stream, size_t len, size_t file_bytes, bool headerless, WebpBlobHeader &H, uint32_t &cache_bits, uint32_t &groups)
+{
+    const size_t sub = align16((size_t)webp_subsample(info.width, 2) * webp_subsample(info.height, 2) * 4u);
+    std::vector<uint8_t> work(sizeof(WebpBlobHeader) + 2u * sub + 1024u + work_bytes(info, file_bytes) + 64u);
+    Decoder D(stream, len);
+    D.header_only = true;
+    uint8_t *base = work.data() + ((16u - (reinterpret_cast<uintptr_t>(work.data()) & 15u)) & 15u);
+    D.A = Arena{base, base + sizeof(WebpBlobHeader), work.data() + work.size()};
+    D.A.back -= reinterpret_cast<uintptr_t>(D.A.back) & 7u;
+    const int rc = decode_stream(info, D, H, headerless);
+    cache_bits = D.cache_bits0; groups = D.groups0;
+    return rc;
 }
 
 } // namespace
@@ -448,22 +464,54 @@ int webp_parse_info(const uint8_t *d, size_t n, WebpInfo &info, bool deep)
     info.supported = 1;
     if (!deep) return 0;
     // transform headers and the main image's code groups: their sub-images have to be entropy-decoded to get past them
-    WebpInfo small = info;
-    const size_t sub = align16((size_t)webp_subsample(info.width, 2) * webp_subsample(info.height, 2) * 4u);
-    std::vector<uint8_t> work(sizeof(WebpBlobHeader) + 2u * sub + 1024u + work_bytes(small, n) + 64u);
-    Decoder D(d + info.vp8l_off, info.vp8l_len);
-    D.header_only = true;
-    uint8_t *base = work.data() + ((16u - (reinterpret_cast<uintptr_t>(work.data()) & 15u)) & 15u);
-    D.A = Arena{base, base + sizeof(WebpBlobHeader), work.data() + work.size()};
-    D.A.back -= reinterpret_cast<uintptr_t>(D.A.back) & 7u;
     WebpBlobHeader H;
-    const int rc = decode_stream(info, D, H);
+    uint32_t cache_bits = 0, groups = 0;
+    const int rc = walk_headers(info, d + info.vp8l_off, info.vp8l_len, n, false, H, cache_bits, groups);
     if (rc == kWebpUnsupported) { info.supported = 0; info.channels = 0; return 0; }
     if (rc) return kWebpParse;
     for (uint32_t k = 0; k < H.ntransforms; ++k) info.transforms |= 1u << H.ttype[k];
-    info.color_cache_bits = D.cache_bits0;
-    info.prefix_groups = D.groups0;
+    info.color_cache_bits = cache_bits;
+    info.prefix_groups = groups;
     info.blob_bytes = H.total_bytes;
+    return 0;
+}
+
+// The VP8L-coded plane of a lossy picture's ALPH chunk: the stream without its five header bytes, the frame's sizes, the values in
+// the green channel.  The blob is a lossless picture's (four output channels: the device writes R, G, B, A and green is taken).
+static WebpInfo alpha_info(uint32_t width, uint32_t height)
+{
+    WebpInfo info;
+    info.width = width; info.height = height; info.channels = 4; info.has_alpha = 1; info.lossless = 1; info.supported = 1;
+    return info;
+}
+
+size_t webp_alpha_blob_capacity(uint32_t width, uint32_t height, size_t stream_bytes) { return webp_blob_capacity(alpha_info(width, height), stream_bytes); }
+
+int webp_decode_alpha_residuals(const uint8_t *d, size_t n, uint32_t width, uint32_t height, uint8_t *blob, size_t cap, WebpBlobHeader *hdr)
+{
+    const WebpInfo info = alpha_info(width, height);
+    if (!d || !width || !height || (uint64_t)width * height * 4u >= kWebpMaxDecoded) return kWebpParse;
+    if (!blob || (reinterpret_cast<uintptr_t>(blob) & 15u) || cap < sizeof(WebpBlobHeader) + 64u) return kWebpSmall;
+    Decoder D(d, n);
+    D.A = Arena{blob, blob + sizeof(WebpBlobHeader), blob + (cap & ~(size_t)7u)};
+    WebpBlobHeader H;
+    const int rc = decode_stream(info, D, H, true);
+    if (rc) return rc;
+    memcpy(blob, &H, sizeof(H));
+    if (hdr) *hdr = H;
+    return 0;
+}
+
+int webp_alpha_blob_bytes(const uint8_t *d, size_t n, uint32_t width, uint32_t height, uint32_t *bytes)
+{
+    // as the deep parse of a lossless file: the transforms' sub-images are decoded into a work area of this call's own, the plane is not
+    const WebpInfo info = alpha_info(width, height);
+    if (!d || !width || !height || (uint64_t)width * height * 4u >= kWebpMaxDecoded) return kWebpParse;
+    WebpBlobHeader H;
+    uint32_t cache_bits = 0, groups = 0;
+    const int rc = walk_headers(info, d, n, n, true, H, cache_bits, groups);
+    if (rc) return rc;
+    *bytes = H.total_bytes;
     return 0;
 }
 

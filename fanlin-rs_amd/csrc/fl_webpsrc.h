@@ -72,4 +72,11 @@ size_t webp_blob_capacity(const WebpInfo &info, size_t file_bytes);
 // header.  Nothing is allocated; every loop is bounded by the header's pixel count.
 int webp_decode_residuals(const uint8_t *data, size_t n, uint8_t *blob, size_t cap, WebpBlobHeader *hdr);
 
+// The VP8L-coded alpha plane of a LOSSY picture's ALPH chunk (fl_vp8src.cpp): the stream without the five header bytes, width and
+// height the frame's, the alpha values in the green channel.  The same blob (channels = 4), the same bounds; webp_alpha_blob_bytes
+// says what webp_decode_alpha_residuals will leave (it reads the transform headers into a work area of its own).
+size_t webp_alpha_blob_capacity(uint32_t width, uint32_t height, size_t stream_bytes);
+int webp_decode_alpha_residuals(const uint8_t *data, size_t n, uint32_t width, uint32_t height, uint8_t *blob, size_t cap, WebpBlobHeader *hdr);
+int webp_alpha_blob_bytes(const uint8_t *data, size_t n, uint32_t width, uint32_t height, uint32_t *bytes);
+
 } // namespace fl

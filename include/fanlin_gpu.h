@@ -106,6 +106,14 @@ typedef struct flgpu_image {
                                          inputs (src/handler.rs:205-220).  The residual picture crosses PCIe: 4 bytes per pixel, 1 / 2 / 4 / 8 x
                                          less for palette pictures.  Lossy and animated files: FLGPU_ERR_UNSUPPORTED (decode on the host);
                                          damaged files: FLGPU_ERR_PARSE. */
+#define FLGPU_IMG_VP8_SOURCE      128u /* in (src of flgpu_transform / flgpu_transform_batch): data holds a LOSSY WebP FILE (`VP8 `, with or without VP8X /
+                                         ALPH) of `capacity` bytes instead of pixels, width / height / channels say what it decodes to
+                                         (flgpu_vp8_info_of): the library decodes it itself -- container, first partition and token partitions
+                                         (the boolean coder; a compressed ALPH chunk's prefix codes) on the calling thread; dequantisation, inverse transforms, intra prediction, loop
+                                         filter, ALPH filters, chroma up-sampling and YUV -> RGB on the device.  Macroblock records and sparse
+                                         levels cross PCIe.  Files it does not cover (flgpu_vp8_info.supported == 0): FLGPU_ERR_UNSUPPORTED
+                                         (decode on the host); damaged files: FLGPU_ERR_PARSE.  A source kind of its own: a lossy file handed
+                                         in as FLGPU_IMG_WEBP_SOURCE stays FLGPU_ERR_UNSUPPORTED. */
 #define FLGPU_IMG_HAS_ALPHA       2u  /* WEBP420: some pixel is not opaque: the picture is WEBP_YUV420A for libwebp, i.e. the A
                                          plane behind V must be handed to WebPEncode too (for opaque pictures it is all 255) */
 
@@ -455,13 +463,55 @@ int flgpu_webp_info_of(const uint8_t *webp, uint64_t n, flgpu_webp_info *info);
 int flgpu_decode_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst);
 /* State::process_image for a WebP input from the file bytes on, input_format FLGPU_IN_WEBP (so an empty query is as_is), with the
  * file's EXIF orientation: query parsing, size gate, as_is, container negotiation, then entropy decode + inverse transforms + pixel
- * pipeline in one pass; with FLGPU_ENCODE_WEBP_LOSSLESS and quality=100 the result is the finished lossless WebP file.  Same
+ * pipeline in one pass (a lossless file as FLGPU_IMG_WEBP_SOURCE, a lossy one as FLGPU_IMG_VP8_SOURCE); with FLGPU_ENCODE_WEBP_LOSSLESS and quality=100 the result is the finished lossless WebP file.  Same
  * outcomes as flgpu_process_image; additionally FLGPU_ERR_UNSUPPORTED for files the decoder does not cover (the host then decodes
  * with its own decoder and calls flgpu_process_image) and FLGPU_ERR_PARSE for damaged ones. */
 int flgpu_process_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags,
                        flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format);
 int flgpu_process_webp_plan(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
                             int *result_kind);
+
+/* ---- lossy WebP sources (src/handler.rs:205-220: image-webp's VP8 decoder through the image crate) ------------------------- */
+typedef struct flgpu_vp8_info {
+    uint32_t width, height;
+    uint32_t channels;          /* of the picture the pipeline sees (0 if unsupported): 4 (Rgba8) if the VP8X header announces alpha, else 3 */
+    uint32_t has_alpha;         /* the VP8X alpha flag */
+    uint32_t extended;          /* the file starts with a VP8X chunk */
+    uint32_t animated;          /* VP8X animation flag, ANIM or ANMF (supported = 0) */
+    uint32_t exif_orientation;  /* 1..8 from the EXIF chunk, 0 = none (the pipeline then runs with 1) */
+    uint32_t supported;         /* 1 = FLGPU_IMG_VP8_SOURCE decodes it.  0: animation, the colour-space or clamping
+                                   bit set, non-zero loop-filter deltas, segment values in delta mode, 2^31 decoded bytes and more */
+    uint32_t version;           /* of the frame tag: 0..3 */
+    uint32_t segmentation;      /* segmentation enabled */
+    uint32_t update_map;        /* ... and the macroblocks carry segment ids */
+    uint32_t filter_type;       /* the header's bit: 0 = normal loop filter, 1 = simple */
+    uint32_t filter_level;      /* 0..63; 0 = no loop filter */
+    uint32_t sharpness;         /* 0..7 */
+    uint32_t partitions;        /* token partitions: 1, 2, 4 or 8 */
+    uint32_t alpha_compression; /* of the ALPH chunk: 0 = raw, 1 = lossless-coded (0 without a chunk) */
+    uint32_t alpha_filter;      /* 0 none, 1 horizontal, 2 vertical, 3 gradient */
+    uint32_t segment_quantizers;    /* different quantiser indices among the segments in use (1 without segmentation) */
+    uint32_t segment_filter_levels; /* different filter levels among them */
+    uint32_t coef_prob_updates; /* coefficient probabilities the header replaces */
+    /* from the partitions themselves (0 for an unsupported file): */
+    uint32_t macroblocks;
+    uint32_t bpred_macroblocks;         /* with sixteen sub-block modes */
+    uint32_t skipped_macroblocks;       /* with the skip flag set */
+    uint32_t skipped_bpred_macroblocks; /* of those, the ones whose inner edges are filtered all the same */
+    uint32_t bmodes_mask;       /* bit k = sub-block mode k seen: 0 DC, 1 TM, 2 VE, 3 HE, 4 RD, 5 VR, 6 LD, 7 VL, 8 HD, 9 HU */
+    uint32_t ymodes_mask;       /* bit k = 16x16 mode k seen: 0 DC, 1 V, 2 H, 3 TM */
+    uint32_t uvmodes_mask;      /* the same for the chroma modes */
+    uint32_t cat6_tokens;       /* tokens of the largest category */
+    uint32_t blob_bytes;        /* what crosses PCIe for the file */
+    uint32_t reserved[3];
+} flgpu_vp8_info;
+/* Container, frame header, and -- for a supported file -- the whole first partition and the token partitions (no device needed).
+ * FLGPU_ERR_PARSE if the bytes are not an intact lossy WebP file (also: a lossless one) or a partition ends early. */
+int flgpu_vp8_info_of(const uint8_t *webp, uint64_t n, flgpu_vp8_info *info);
+/* Decodes a supported lossy WebP to interleaved Rgb8 / Rgba8 pixels in HOST memory at dst->data (capacity >= width*height*channels),
+ * bit-equal to libwebp's WebPDecodeRGB / WebPDecodeRGBA; the EXIF orientation is not applied.  (flgpu_process_webp and
+ * flgpu_process_webp_plan take lossy files too: they go by the chunk type.) */
+int flgpu_decode_webp_lossy(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst);
 
 /* ---- GIF files (src/handler.rs:311-366, process_gif: the gif crate through the image crate) ------------------------------- */
 typedef struct flgpu_gif_info {
@@ -588,6 +638,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
  * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
+ * "vp8_sources", "vp8_file_bytes", "vp8_upload_bytes" the same for FLGPU_IMG_VP8_SOURCE pictures (per picture a 128-byte header, 48
+ * bytes per macroblock, the levels up to each block's last non-zero one, the raw ALPH plane or a compressed one's lossless blob), with flgpu_config.profile "vp8_decode_ns" =
+ * the HIP-event time of their decode kernels;
  * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
@@ -625,6 +678,16 @@ int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint
  * FLGPU_IMG_WEBP_SOURCE -- WebpBlobHeader, the mode / cross-colour images, the palette, the entropy-decoded residual picture.
  * out == NULL: *used = capacity to provide. */
 int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
+
+/* The host half of the lossy WebP decode front end alone (csrc/fl_vp8src.h): the blob flgpu_transform uploads for a
+ * FLGPU_IMG_VP8_SOURCE -- Vp8BlobHeader, one 48-byte record per macroblock, the levels up to each block's last non-zero one, the raw
+ * ALPH plane or, for a compressed chunk, the lossless decoder's blob (flgpu_debug_webp_residuals describes it).  out == NULL: *used = capacity to provide. */
+int flgpu_debug_vp8_blob(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
+
+/* The lossy WebP decoder's planes on the device (csrc/fl_vp8dec.h): Y | U | V padded to whole macroblocks (16 mbw x 16 mbh, then twice
+ * 8 mbw x 8 mbh), before (filter == 0) or behind the loop filter, so that a wrong pixel names its stage.  out == NULL: *used =
+ * capacity to provide. */
+int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int filter, uint8_t *out, uint64_t capacity, uint64_t *used);
 
 /* The host half of the GIF decode front end alone (csrc/fl_gifsrc.h): the blob flgpu_process_gif uploads, all fields little-endian
  * dwords, offsets in bytes from the blob's start:

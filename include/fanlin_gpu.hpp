@@ -184,9 +184,25 @@ public:
     // WebPDecoder::new's view of a file (src/handler.rs:205-220): false if the bytes are no intact WebP container
     static bool webp_info(const std::vector<uint8_t> &file, flgpu_webp_info &info) { return flgpu_webp_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
 
-    // State::process_image for a lossless WebP input from the file bytes on, with the file's EXIF orientation: entropy decode on this
+    // the same for a lossy WebP file (`VP8 `, with or without VP8X / ALPH): false if the bytes are no intact lossy WebP file
+    static bool vp8_info(const std::vector<uint8_t> &file, flgpu_vp8_info &info) { return flgpu_vp8_info_of(file.data(), file.size(), &info) == FLGPU_OK; }
+
+    // libwebp's WebPDecodeRGB / WebPDecodeRGBA of a lossy WebP file on the device: width x height x info.channels bytes, no orientation applied
+    std::vector<uint8_t> decode_webp_lossy(const std::vector<uint8_t> &file)
+    {
+        flgpu_vp8_info info;
+        check(flgpu_vp8_info_of(file.data(), file.size(), &info));
+        std::vector<uint8_t> px((size_t)info.width * info.height * (info.channels ? info.channels : 1u));
+        flgpu_image dst{px.data(), px.size(), 0, 0, 0, 0, 0};
+        check(flgpu_decode_webp_lossy(ctx_, file.data(), file.size(), &dst), ctx_);
+        return px;
+    }
+
+    // State::process_image for a WebP input from the file bytes on (lossless, or lossy: the library goes by the chunk type), with the
+    // file's EXIF orientation: entropy decode on this
     // thread, inverse transforms, pixel pipeline and (with FLGPU_ENCODE_WEBP_LOSSLESS in the content flags, quality=100) the lossless
-    // WebP encoder on the device.  Throws on files the decoder does not cover (FLGPU_ERR_UNSUPPORTED: lossy, animated) and on damaged
+    // WebP encoder on the device.  Throws on files the decoders do not cover (FLGPU_ERR_UNSUPPORTED: animated files, the refused frame-header
+    // features of a lossy one) and on damaged
     // ones (FLGPU_ERR_PARSE): the host then uses its own decoder.
     Processed process_webp(const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
     {

@@ -40,6 +40,20 @@ pub struct FlWebpInfo { width: u32, height: u32, channels: u32, has_alpha: u32, 
                         transforms: u32, color_cache_bits: u32, prefix_groups: u32, supported: u32 }
 
 #[repr(C)] #[derive(Default, Clone, Copy)]
+/// flgpu_vp8_info: what the VP8 decoder behind `WebPDecoder::new` meets in a lossy WebP file (src/handler.rs:205-220), for the decision
+/// "file bytes to the device, or the reference's own decoder".  `channels`: 3 Rgb8, 4 Rgba8 (the VP8X header announces alpha);
+/// `supported` = 0 for animation and the frame-header features no test file vouches for
+/// (tests/test_vp8_source_host.py checks this mirror).
+pub struct FlVp8Info {
+    pub width: u32, pub height: u32, pub channels: u32, pub has_alpha: u32, pub extended: u32, pub animated: u32, pub exif_orientation: u32,
+    pub supported: u32, pub version: u32, pub segmentation: u32, pub update_map: u32, pub filter_type: u32, pub filter_level: u32,
+    pub sharpness: u32, pub partitions: u32, pub alpha_compression: u32, pub alpha_filter: u32, pub segment_quantizers: u32,
+    pub segment_filter_levels: u32, pub coef_prob_updates: u32, pub macroblocks: u32, pub bpred_macroblocks: u32,
+    pub skipped_macroblocks: u32, pub skipped_bpred_macroblocks: u32, pub bmodes_mask: u32, pub ymodes_mask: u32, pub uvmodes_mask: u32,
+    pub cat6_tokens: u32, pub blob_bytes: u32, pub reserved: [u32; 3],
+}
+
+#[repr(C)] #[derive(Default, Clone, Copy)]
 /// flgpu_gif_info: what `GifDecoder::new(..).into_frames()` would meet in the file (src/handler.rs:311-321), for the decision "file
 /// bytes to the device, or the reference's own decoder".  `supported` = 0 for files the device decoder does not vouch for
 /// (tests/test_gif_source_host.py checks this mirror).
@@ -60,6 +74,8 @@ const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the 
 const IMG_PNG_SOURCE: u32 = 32;  // ... `data` holds the PNG FILE (flgpu_process_png sets it itself)
 #[allow(dead_code)]
 const IMG_WEBP_SOURCE: u32 = 64; // ... `data` holds the lossless WebP FILE (flgpu_process_webp sets it itself)
+#[allow(dead_code)]
+const IMG_VP8_SOURCE: u32 = 128; // ... `data` holds the lossy WebP FILE (flgpu_process_webp sets it itself)
 pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
 // not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
@@ -101,6 +117,7 @@ extern "C" {
     fn flgpu_process_webp_plan(webp: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
     fn flgpu_process_webp(ctx: *mut c_void, webp: *const u8, n: u64, query: *const c_char, accept: u32,
                           dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
+    fn flgpu_vp8_info_of(webp: *const u8, n: u64, info: *mut FlVp8Info) -> c_int;
     fn flgpu_gif_info_of(gif: *const u8, n: u64, info: *mut FlGifInfo) -> c_int;
     fn flgpu_process_gif_plan(gif: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, frames: *mut u32, kind: *mut c_int) -> c_int;
     fn flgpu_process_gif(ctx: *mut c_void, gif: *const u8, n: u64, query: *const c_char, accept: u32,
@@ -269,18 +286,27 @@ impl Gpu {
         if unsafe { flgpu_webp_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
     }
 
+    /// What the partitions of a lossy WebP file use, or None if the bytes are no intact lossy WebP file (a lossless one included).
+    pub fn vp8_info(original: &[u8]) -> Option<FlVp8Info> {
+        let mut info = FlVp8Info::default();
+        if unsafe { flgpu_vp8_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
+    }
+
     /// `process_image` for a lossless WebP input FROM THE FILE BYTES ON (src/handler.rs:198-308 in one call, input format WebP, the
     /// file's EXIF orientation): prefix codes + LZ77 + colour cache on this thread, inverse transforms + pixel pipeline (+ the lossless
-    /// WebP encoder with ENCODE_WEBP_LOSSLESS in `accept` and quality=100) in one device pass.  Ok(None): a file the decoder does not
-    /// cover (lossy, animated) or cannot read -- decode with the reference's own decoder, which also words the error, and use
+    /// WebP encoder with ENCODE_WEBP_LOSSLESS in `accept` and quality=100) in one device pass.  A lossy file goes the same way: the
+    /// boolean coder on this thread, reconstruction, loop filter and colour conversion on the device.  Ok(None): a file the decoders do
+    /// not cover (animated, a refused frame-header feature) or cannot read -- decode with the reference's own decoder, which also words the error, and use
     /// `transform`.  Otherwise as `process_png`: RESULT_AS_IS, RESULT_WEBP_STREAM, RESULT_WEBP_PLANES or RESULT_PIXELS.
     pub fn process_webp(&self, original: &[u8], query: &str, accept: u32)
         -> Result<Option<(c_int, c_int, FlPlan, Vec<u8>)>, Box<dyn std::error::Error>>
     {
         let q = std::ffi::CString::new(query)?;
         let (mut plan, mut kind, mut fmt) = (FlPlan::default(), 0 as c_int, 0 as c_int);
-        if Self::webp_info(original).map_or(true, |i| i.supported == 0) { return Ok(None); }
-        check(unsafe { flgpu_process_webp_plan(original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut plan, &mut kind) })?;
+        // (the plan reads container and headers only -- `vp8_info` would read every token of a lossy file, which the request does again)
+        let rc = unsafe { flgpu_process_webp_plan(original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut plan, &mut kind) };
+        if rc == ERR_UNSUPPORTED || rc == ERR_PARSE { return Ok(None); }
+        check(rc)?;
         if kind == RESULT_AS_IS { return Ok(Some((kind, 0, plan, Vec::new()))); }
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let mut dst = FlImage { data: out.as_mut_ptr(), capacity: out.len() as u64, width: 0, height: 0, channels: 0, flags: 0, bytes: 0 };
