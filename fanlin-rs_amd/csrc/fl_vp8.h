@@ -1,4 +1,4 @@
-// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY): job descriptor, scratch sizes and the launch.
+// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY and FLGPU_FE_WEBP_LOSSY_I4): job descriptor, scratch sizes and the launch.
 // The format's limits and worst case, and everything the kernels compute, are in fl_vp8_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@ struct alignas(16) Vp8Job {
     uint32_t *info;       // scratch: one record per macroblock
     uint32_t *sizes;      // scratch: [kVp8SizeWords]
     uint32_t *result;     // [0] bit 0: some pixel is not opaque; [1] = file bytes (0 if it did not fit dst_cap): the words and protocol of JpegJob
+    uint32_t *bm;         // scratch, FLGPU_FE_WEBP_LOSSY_I4 only (else nullptr): two words of sub-block modes per macroblock
     uint32_t w, h, c;
     uint32_t dst_cap;     // bytes available at dst
     uint32_t qi;          // quantiser index (vp8_quality_index of the clamped quality)
@@ -28,7 +29,8 @@ struct alignas(16) Vp8Job {
 
 inline uint64_t vp8_planes_bytes(uint64_t w, uint64_t h) { return 2u * w * h + 2u * ((w + 1u) / 2u) * ((h + 1u) / 2u); }
 
-// predict / transform / quantise / reconstruct -> partition sizes -> framing and alpha plane -> partitions; four stream-ordered launches
-hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t njobs, hipStream_t st);
+// predict / transform / quantise / reconstruct -> partition sizes -> framing and alpha plane -> partitions; four stream-ordered
+// launches for jobs[0 .. n_i16), the FLGPU_FE_WEBP_LOSSY pictures, and four for jobs[n_i16 .. n_i16 + n_i4), the _I4 ones
+hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t n_i16, uint32_t n_i4, hipStream_t st);
 
 } // namespace fl

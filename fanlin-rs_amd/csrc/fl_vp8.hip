@@ -13,12 +13,23 @@
 //   vp8_frame_kernel    one workgroup per picture: the layout from the sizes; RIFF / VP8X / ALPH / VP8 framing, the raw alpha
 //                       plane where the planes kernel flagged a translucent pixel, the result word (0 if dst is too small).
 //   vp8_write_kernel    one lane per partition again: the same coder, storing at the partition's place in the file.
+// The I4 variant (FLGPU_FE_WEBP_LOSSY_I4, fl_vp8_i4_core.h) has kernels of its own, so that the ones above stay as they are:
+//   vp8_analyse_i4_kernel  the same walk; after the mode pick a macroblock whose I16 error exceeds the penalty tries its luma as
+//                       sixteen sub-blocks, one after the other: 13 neighbour loads, 160 (mode, sample) errors over the 64 lanes
+//                       in three rounds, each mode's sixteen summed across its lanes, then the chosen mode's residual through
+//                       transform, quantiser and back on 16 lanes (4 for a transform pass).  The working copy and the trial's
+//                       levels are in LDS; the winner of the two trials is committed.
+//   vp8_size_kernel<true>, vp8_write_kernel<true>  the coder's instantiation with the mode tree in partition 0 and the type-3 / no-Y2
+//                       path in the tokens, a branch per macroblock on its mode record.
+// A batch's I16-only pictures come first in the job list, so each family is one range of it.
 // No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
 // A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fl_vp8.h"
+#include "fl_vp8_i4_core.h"
+#include "fl_wave.h"
 
 namespace fl {
 namespace {
@@ -36,7 +47,7 @@ __device__ __forceinline__ Vp8Pic pic_of(const Vp8Job &j, const uint8_t *prob = 
     Vp8Pic p;
     vp8_pic_dims(p, j.w, j.h);
     p.prob = prob;
-    p.src = j.src; p.rec = j.rec; p.lev = j.lev; p.info = j.info;
+    p.src = j.src; p.rec = j.rec; p.lev = j.lev; p.info = j.info; p.bm = j.bm;
     p.q = vp8_quant(j.qi);
     return p;
 }
@@ -68,6 +79,81 @@ __global__ __launch_bounds__(64) void vp8_analyse_kernel(const Vp8Job *__restric
         }
 }
 
+// the I4 trial of one sub-block; every step's items are independent, a barrier separates the steps
+__device__ __forceinline__ void i4_sub_block(const Vp8Pic &p, const Vp8Mb &m, Vp8I4 &t, uint32_t s, uint32_t lane)
+{
+    if (lane < kVp8I4EdgeItems) vp8_i4_phase_edges(m, t, s, lane);
+    __syncthreads();
+    // 160 items: lane l of round r has sample l % 16 of mode 4 r + l / 16, so a mode's sixteen errors sit in sixteen adjacent lanes
+#pragma unroll
+    for (uint32_t r = 0; r < 3u; ++r) {
+        const uint32_t k = r * 64u + lane;
+        uint32_t e = k < kVp8I4PredictItems ? vp8_i4_phase_predict(m, t, s, k) : 0u;
+        e = group_sum<16>(e);
+        if (k < kVp8I4PredictItems && (lane & 15u) == 0u) t.sse[k >> 4] = e;
+    }
+    __syncthreads();
+    if (lane == 0u) vp8_i4_phase_pick(t, s);
+    __syncthreads();
+    if (lane < 16u) vp8_i4_phase_residual(m, t, s, lane);
+    __syncthreads();
+    if (lane < 4u) vp8_i4_phase_fdct_rows(t, lane);
+    __syncthreads();
+    if (lane < 4u) vp8_i4_phase_fdct_cols(t, lane);
+    __syncthreads();
+    if (lane < 16u) vp8_i4_phase_quant(p, t, s, lane);
+    __syncthreads();
+    if (lane < 4u) vp8_i4_phase_idct_cols(t, lane);
+    __syncthreads();
+    if (lane < 4u) vp8_i4_phase_idct_rows(t, lane);
+    __syncthreads();
+    if (lane < 16u) vp8_i4_phase_recon(t, s, lane);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void vp8_analyse_i4_kernel(const Vp8Job *__restrict__ jobs)
+{
+    __shared__ Vp8Mb m;
+    __shared__ Vp8I4 t;
+    const Vp8Job &jb = jobs[blockIdx.x];
+    const Vp8Pic p = pic_of(jb);
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t mby = 0; mby < p.mbh; ++mby)
+        for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) {
+            for (uint32_t k = lane; k < kVp8LoadItems; k += 64u) vp8_phase_load(p, m, mbx, mby, k);
+            if (lane < kVp8I4BeginItems) vp8_i4_phase_begin(p, t, mbx, mby, lane);
+            __syncthreads();
+            if (lane < 3u) vp8_phase_dc(m, mbx, mby, lane);
+            __syncthreads();
+            for (uint32_t k = lane; k < kVp8SseItems; k += 64u) vp8_phase_sse(m, k);
+            __syncthreads();
+            if (lane == 0u) vp8_phase_modes(m);
+            __syncthreads();
+            const uint32_t s16 = vp8_i4_s16(m); // (every lane: the decision is the wave's)
+            bool i4 = false;
+            if (vp8_i4_worth_trying(p, s16)) {
+                for (uint32_t s = 0; s < 16u; ++s) i4_sub_block(p, m, t, s, lane);
+                i4 = vp8_i4_wins(p, t, s16);
+            }
+            if (i4) {
+                for (uint32_t k = lane; k < kVp8I4CommitItems; k += 64u) vp8_i4_phase_commit(p, m, t, mbx, mby, k);
+                __syncthreads();
+                if (lane < 8u) vp8_phase_fdct(m, 16u + lane);
+                __syncthreads();
+                if (lane < 8u) vp8_phase_recon(p, m, mbx, mby, 16u + lane);
+            } else {
+                if (lane < 24u) vp8_phase_fdct(m, lane);
+                __syncthreads();
+                if (lane == 0u) vp8_phase_y2(p, m);
+                __syncthreads();
+                if (lane < 24u) vp8_phase_recon(p, m, mbx, mby, lane);
+            }
+            __syncthreads();
+            for (uint32_t k = lane; k < kVp8I4StoreItems; k += 64u) vp8_i4_phase_store(p, m, t, i4, mbx, mby, k);
+            __syncthreads(); // the next macroblock overwrites m and t and reads this one's reconstruction and records
+        }
+}
+
 // The coders read a probability for every boolean: the table's 1056 bytes go to LDS first (all threads of the workgroup, before
 // any of them leaves).
 __device__ __forceinline__ void stage_prob(uint8_t *s_prob)
@@ -77,13 +163,13 @@ __device__ __forceinline__ void stage_prob(uint8_t *s_prob)
 }
 
 // the partition of lane slot `part` (0 = the first partition), counted or written
-__device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
+template <bool I4> __device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
 {
-    if (part == 0u) vp8_put_first_partition(bw, p, qi, nparts);
-    else vp8_put_token_partition(bw, p, part - 1u, nparts);
+    if (part == 0u) vp8_put_first_partition<I4>(bw, p, qi, nparts);
+    else vp8_put_token_partition<I4>(bw, p, part - 1u, nparts);
 }
 
-__global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
     stage_prob(s_prob);
@@ -95,7 +181,7 @@ __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *_
     if (part >= kVp8SizeWords) return;
     if (part > nparts) { jb.sizes[part] = 0u; return; }
     Vp8Bool bw;
-    code_partition(bw, p, jb.qi, part, nparts);
+    code_partition<I4>(bw, p, jb.qi, part, nparts);
     jb.sizes[part] = bw.pos;
 }
 
@@ -124,7 +210,7 @@ __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *
     }
 }
 
-__global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
     stage_prob(s_prob);
@@ -139,23 +225,30 @@ __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *
     if (L.total > jb.dst_cap) return; // vp8_frame_kernel has reported it
     Vp8Bool bw;
     bw.buf = jb.dst + L.part[part];
-    code_partition(bw, p, jb.qi, part, nparts);
+    code_partition<I4>(bw, p, jb.qi, part, nparts);
 }
 
 } // namespace
 
-hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
+template <bool I4> static hipError_t launch_family(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
 {
     if (!njobs) return hipSuccess;
     const uint32_t coder_blocks = (uint32_t)(((uint64_t)njobs * kLaneSlots * kLaneStride + kCoderThreads - 1u) / kCoderThreads);
-    hipLaunchKernelGGL(vp8_analyse_kernel, dim3(njobs), dim3(64), 0, st, jobs);
+    if (I4) hipLaunchKernelGGL(vp8_analyse_i4_kernel, dim3(njobs), dim3(64), 0, st, jobs);
+    else hipLaunchKernelGGL(vp8_analyse_kernel, dim3(njobs), dim3(64), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(vp8_size_kernel, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    hipLaunchKernelGGL(vp8_size_kernel<I4>, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(vp8_frame_kernel, dim3(njobs), dim3(kFrameThreads), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(vp8_write_kernel, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    hipLaunchKernelGGL(vp8_write_kernel<I4>, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     return hipGetLastError();
+}
+
+hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t n_i16, uint32_t n_i4, hipStream_t st)
+{
+    if (hipError_t e = launch_family<false>(jobs, n_i16, st)) return e;
+    return launch_family<true>(jobs + n_i16, n_i4, st);
 }
 
 } // namespace fl

@@ -8,9 +8,27 @@
 // filter level 0, default coefficient probabilities, 1 / 2 / 4 / 8 token partitions, mb_no_coeff_skip with a per-picture
 // probability.  Forward transforms and quantiser rounding are this encoder's own (integer only); everything the decoder repeats
 // -- dequantisation, inverse WHT, inverse DCT, prediction, clamping -- is the format's.
+//
+// The I4 variant (FLGPU_FE_WEBP_LOSSY_I4; tests/vp8_i4_model.py restates it, fl_vp8_i4_core.h holds its analysis phases): the same
+// stream, but a macroblock's luma may be B_PRED.  Per macroblock, in raster order:
+//   1. I16 trial: the phases above.  S16 = the prediction SSE of the chosen luma mode.  Chroma is as above whatever follows.
+//   2. I4 trial: the luma sub-blocks 0..15 in raster order.  Each forms the ten predictions B_DC, B_TM, B_VE, B_HE, B_LD, B_RD, B_VR,
+//      B_VL, B_HD, B_HU (the format's numbering) from the reconstruction -- the macroblock's own sub-blocks before it, the row
+//      above and the column to the left of the macroblock, borders and above-right as the decoder sees them (fl_vp8dec_core.h,
+//      whose predictor it calls) --, takes the one with the least SSE against the source (ties: the lowest number), transforms the
+//      residual, quantises all sixteen coefficients (DC: the y1_dc step, rounded to nearest; AC: the dead zone above), and
+//      reconstructs as the decoder will into a working copy that the next sub-block predicts from.  S4 = the sum of the sixteen
+//      chosen SSEs.
+//   3. The macroblock is B_PRED iff S4 + vp8_i4_penalty(y1_ac) < S16.  (So a macroblock with S16 <= penalty needs no I4 trial.)
+//   4. The chosen trial's levels, non-zero flags and reconstruction are the macroblock's; later macroblocks see only those.
+// In partition 0 a B_PRED macroblock writes 0 for the luma tree's first boolean and its sixteen modes through the sub-block tree
+// with kVp8BModeProb[above][left]; an I16 neighbour stands for DC -> B_DC, V -> B_VE, H -> B_HE, TM -> B_TM, outside the frame is
+// B_DC.  Its tokens have no Y2 block, its luma blocks are type 3 from coefficient 0, it leaves the Y2 context of its column and
+// row as it found them, and it is skipped when its 24 blocks are zero.
 #pragma once
 #include <stdint.h>
 
+#include "fl_vp8_dtables.h"
 #include "fl_vp8_tables.h"
 
 #if defined(__HIPCC__)
@@ -25,6 +43,7 @@ enum { VP8_DC = 0, VP8_V = 1, VP8_H = 2, VP8_TM = 3 };
 
 constexpr uint32_t kVp8MaxSide = 16383;     // the frame header holds 14 bits of width and of height
 constexpr uint32_t kVp8MbLevels = 25 * 16;  // levels of one macroblock in coding order: 16 Y, 4 U, 4 V blocks, then Y2
+constexpr uint32_t kVp8I4PenaltyShift = 9;  // vp8_i4_penalty
 constexpr int kVp8MaxLevel = 2047;          // the largest magnitude cat6 (67 + 11 bits) is asked to carry here
 
 // ---- worst cases ----------------------------------------------------------------------------------------------------------------
@@ -41,6 +60,14 @@ FL_VP8_HD uint64_t vp8_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (k
 // the first partition's size is a 19-bit field of the frame tag: the largest macroblock count whose worst case still fits it
 constexpr uint64_t kVp8MaxMbs = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0Bools) / kVp8Part0MbBools;
 static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBools * kVp8MaxMbs) + 7u) / 8u < (1ull << 19), "first partition size field");
+
+// The I4 variant's partition 0: a B_PRED macroblock has the skip flag, one luma-tree boolean, sixteen sub-block modes of at most 7
+// tree booleans (B_HD, B_HU: nodes 0, 1, 2, 3, 6, 7, 8) and 3 chroma-mode booleans: 1 + 1 + 16 x 7 + 3 = 117, against an I16
+// macroblock's 7.  Its tokens do not grow: 24 blocks x 16 coefficients = 384, what 16 (Y2) + 16 x 15 + 8 x 16 comes to.
+constexpr uint64_t kVp8Part0MbBoolsI4 = 1 + 1 + 16 * 7 + 3;
+FL_VP8_HD uint64_t vp8_i4_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBoolsI4 * mbs) + 7u) / 8u; }
+constexpr uint64_t kVp8MaxMbsI4 = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0Bools) / kVp8Part0MbBoolsI4; // 5111
+static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBoolsI4 * kVp8MaxMbsI4) + 7u) / 8u < (1ull << 19), "first partition size field");
 
 FL_VP8_HD uint32_t vp8_mbs(uint32_t px) { return (px + 15u) >> 4; }
 // token partitions: the largest of 1 / 2 / 4 / 8 that is not above the number of macroblock rows; row r goes to partition r mod n
@@ -65,6 +92,14 @@ FL_VP8_HD uint64_t vp8_max_out_bytes(uint64_t w, uint64_t h)
     const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
     return 12u + 18u + (8u + 1u + w * h + 1u) + 8u + 10u + 21u + vp8_part0_max_bytes(mbs) +
            (kVp8BoolBits * (kVp8MbTokenBools * mbs + 8u * kVp8FlushBools) + 7u) / 8u + 1u;
+}
+
+// the I4 variant: the same, with its own partition 0
+FL_VP8_HD bool vp8_i4_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsI4; }
+FL_VP8_HD uint64_t vp8_i4_max_out_bytes(uint64_t w, uint64_t h)
+{
+    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
+    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_part0_max_bytes(mbs);
 }
 
 // ---- quantiser --------------------------------------------------------------------------------------------------------------------
@@ -93,27 +128,40 @@ FL_VP8_HD int vp8_quantise(int c, int step, bool dc)
     return c < 0 ? -l : l;
 }
 
+// The I4 variant's penalty on S4, from the y1_ac step: what the sixteen mode codes and the lost Y2 block are worth in squared error
+// at that step (DESIGN.md holds the table it was tuned on).  Positive, so a macroblock whose I16 prediction is exact stays I16.
+FL_VP8_HD uint32_t vp8_i4_penalty(uint32_t y1_ac)
+{
+    const uint64_t sq = (uint64_t)y1_ac * y1_ac, v = (sq * sq) >> kVp8I4PenaltyShift; // (steps are below 2^9: below 2^27)
+    return v < 1u ? 1u : (uint32_t)v;
+}
+
 // ---- transforms -------------------------------------------------------------------------------------------------------------------
 FL_VP8_HD int vp8_clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
 // forward DCT of a 4x4 residual d (raster) -> out (raster); the encoder's own
+// (its two passes apart, row i and column i: the I4 trial gives each to a lane)
+FL_VP8_HD void vp8_fdct_row(const int *d, int *t, int i)
+{
+    const int a0 = d[4 * i] + d[4 * i + 3], a1 = d[4 * i + 1] + d[4 * i + 2], a2 = d[4 * i + 1] - d[4 * i + 2], a3 = d[4 * i] - d[4 * i + 3];
+    t[4 * i] = (a0 + a1) * 8;
+    t[4 * i + 1] = (a2 * 2217 + a3 * 5352 + 1812) >> 9;
+    t[4 * i + 2] = (a0 - a1) * 8;
+    t[4 * i + 3] = (a3 * 2217 - a2 * 5352 + 937) >> 9;
+}
+FL_VP8_HD void vp8_fdct_col(const int *t, int *out, int i)
+{
+    const int a0 = t[i] + t[12 + i], a1 = t[4 + i] + t[8 + i], a2 = t[4 + i] - t[8 + i], a3 = t[i] - t[12 + i];
+    out[i] = (a0 + a1 + 7) >> 4;
+    out[4 + i] = ((a2 * 2217 + a3 * 5352 + 12000) >> 16) + (a3 != 0);
+    out[8 + i] = (a0 - a1 + 7) >> 4;
+    out[12 + i] = (a3 * 2217 - a2 * 5352 + 51000) >> 16;
+}
 FL_VP8_HD void vp8_fdct(const int *d, int *out)
 {
     int t[16];
-    for (int i = 0; i < 4; ++i) {
-        const int a0 = d[4 * i] + d[4 * i + 3], a1 = d[4 * i + 1] + d[4 * i + 2], a2 = d[4 * i + 1] - d[4 * i + 2], a3 = d[4 * i] - d[4 * i + 3];
-        t[4 * i] = (a0 + a1) * 8;
-        t[4 * i + 1] = (a2 * 2217 + a3 * 5352 + 1812) >> 9;
-        t[4 * i + 2] = (a0 - a1) * 8;
-        t[4 * i + 3] = (a3 * 2217 - a2 * 5352 + 937) >> 9;
-    }
-    for (int i = 0; i < 4; ++i) {
-        const int a0 = t[i] + t[12 + i], a1 = t[4 + i] + t[8 + i], a2 = t[4 + i] - t[8 + i], a3 = t[i] - t[12 + i];
-        out[i] = (a0 + a1 + 7) >> 4;
-        out[4 + i] = ((a2 * 2217 + a3 * 5352 + 12000) >> 16) + (a3 != 0);
-        out[8 + i] = (a0 - a1 + 7) >> 4;
-        out[12 + i] = (a3 * 2217 - a2 * 5352 + 51000) >> 16;
-    }
+    for (int i = 0; i < 4; ++i) vp8_fdct_row(d, t, i);
+    for (int i = 0; i < 4; ++i) vp8_fdct_col(t, out, i);
 }
 
 // forward Walsh-Hadamard transform of the 16 luma DCs (raster over the blocks); the encoder's own
@@ -148,31 +196,40 @@ FL_VP8_HD int vp8_mul1(int a) { return ((a * 20091) >> 16) + a; }
 FL_VP8_HD int vp8_mul2(int a) { return (a * 35468) >> 16; }
 
 // the format's inverse DCT: dequantised coefficients (raster) -> the residual to add to the prediction (raster), before clamping
+FL_VP8_HD void vp8_idct_col(const int *in, int *t, int i) // vertical pass, column i
+{
+    const int a = in[i] + in[8 + i], b = in[i] - in[8 + i];
+    const int c = vp8_mul2(in[4 + i]) - vp8_mul1(in[12 + i]), d = vp8_mul1(in[4 + i]) + vp8_mul2(in[12 + i]);
+    t[4 * i] = a + d; t[4 * i + 1] = b + c; t[4 * i + 2] = b - c; t[4 * i + 3] = a - d;
+}
+FL_VP8_HD void vp8_idct_row(const int *t, int *res, int i) // horizontal pass, row i
+{
+    const int dc = t[i] + 4, a = dc + t[8 + i], b = dc - t[8 + i];
+    const int c = vp8_mul2(t[4 + i]) - vp8_mul1(t[12 + i]), d = vp8_mul1(t[4 + i]) + vp8_mul2(t[12 + i]);
+    res[4 * i] = (a + d) >> 3; res[4 * i + 1] = (b + c) >> 3; res[4 * i + 2] = (b - c) >> 3; res[4 * i + 3] = (a - d) >> 3;
+}
 FL_VP8_HD void vp8_idct(const int *in, int *res)
 {
     int t[16];
-    for (int i = 0; i < 4; ++i) { // vertical pass, column i
-        const int a = in[i] + in[8 + i], b = in[i] - in[8 + i];
-        const int c = vp8_mul2(in[4 + i]) - vp8_mul1(in[12 + i]), d = vp8_mul1(in[4 + i]) + vp8_mul2(in[12 + i]);
-        t[4 * i] = a + d; t[4 * i + 1] = b + c; t[4 * i + 2] = b - c; t[4 * i + 3] = a - d;
-    }
-    for (int i = 0; i < 4; ++i) { // horizontal pass, row i
-        const int dc = t[i] + 4, a = dc + t[8 + i], b = dc - t[8 + i];
-        const int c = vp8_mul2(t[4 + i]) - vp8_mul1(t[12 + i]), d = vp8_mul1(t[4 + i]) + vp8_mul2(t[12 + i]);
-        res[4 * i] = (a + d) >> 3; res[4 * i + 1] = (b + c) >> 3; res[4 * i + 2] = (b - c) >> 3; res[4 * i + 3] = (a - d) >> 3;
-    }
+    for (int i = 0; i < 4; ++i) vp8_idct_col(in, t, i);
+    for (int i = 0; i < 4; ++i) vp8_idct_row(t, res, i);
 }
 
 // ---- one picture ------------------------------------------------------------------------------------------------------------------
 // What every phase needs to know about the picture.  src: the planes of FLGPU_FE_WEBP420 (Y | U | V | A, unpadded).  rec: the
 // reconstruction, planes padded to whole macroblocks (Y 16 mbw x 16 mbh, then U and V 8 mbw x 8 mbh each).  lev: kVp8MbLevels
 // levels per macroblock in coding order.  info: per macroblock, luma mode | chroma mode << 2 | non-zero flags << 4 (bit k of the
-// flags: block k in the order of lev; a macroblock whose flags are all 0 is skipped).
+// flags: block k in the order of lev; a macroblock whose flags are all 0 is skipped).  bm (the I4 variant only): two words per
+// macroblock, sixteen nibbles, sub-block b in nibble b & 7 of word b >> 3: the sub-block's mode (fl_vp8_dtables.h's numbers) in a
+// B_PRED macroblock, 12 + the mode an I16 macroblock stands for in a neighbour's context otherwise.  A B_PRED macroblock has no
+// Y2 block; bits 24 and 25 of its flags carry the Y2 context it passes on untouched, of its row (what the macroblock to its left
+// has in bit 24) and of its column (what the one above passes on), and do not count towards "skipped".
 struct Vp8Pic {
     const uint8_t *src;
     uint8_t *rec;
     int16_t *lev;
     uint32_t *info;
+    uint32_t *bm = nullptr;
     const uint8_t *prob;   // kVp8CoefProb, or a copy of it in faster memory (the kernels keep one in LDS)
     uint32_t w, h, cw, ch, mbw, mbh;
     Vp8Quant q;
@@ -455,17 +512,71 @@ FL_VP8_HD void vp8_put_block(Vp8Bool &bw, const uint8_t *tab, const int16_t *src
 
 FL_VP8_HD uint32_t vp8_nz(const Vp8Pic &p, uint32_t mbx, uint32_t mby) { return p.info[(uint64_t)mby * p.mbw + mbx] >> 4; }
 
-// the tokens of one macroblock; contexts are the non-zero flags of the neighbouring blocks (0 outside the frame)
-FL_VP8_HD void vp8_put_mb(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32_t mby)
+// ---- the I4 variant's records ---------------------------------------------------------------------------------------------------
+constexpr uint32_t kVp8BmI16 = 12;            // nibble of an I16 macroblock's record: 12 + its context mode (0..3)
+constexpr uint32_t kVp8NzBlocks = 0xffffffu;  // the 24 blocks a B_PRED macroblock codes
+FL_VP8_HD uint32_t vp8_bm_nibble(const Vp8Pic &p, uint64_t mb, uint32_t b) { return (p.bm[2u * mb + (b >> 3)] >> (4u * (b & 7u))) & 15u; }
+FL_VP8_HD bool vp8_is_i4(const Vp8Pic &p, uint64_t mb) { return (p.bm[2u * mb] & 15u) < kVp8BmI16; }
+FL_VP8_HD uint32_t vp8_bm_context(uint32_t nibble) { return nibble < kVp8BmI16 ? nibble : nibble - kVp8BmI16; }
+// the mode an I16 macroblock stands for in the context of a neighbouring sub-block
+FL_VP8_HD uint32_t vp8_context_mode(uint32_t ymode) { return ymode == VP8_DC ? VP8_B_DC : ymode == VP8_V ? VP8_B_VE : ymode == VP8_H ? VP8_B_HE : VP8_B_TM; }
+// the flags that decide whether a macroblock is skipped
+template <bool I4> FL_VP8_HD uint32_t vp8_coded(const Vp8Pic &p, uint64_t mb)
 {
+    const uint32_t nz = p.info[mb] >> 4;
+    if (I4) return vp8_is_i4(p, mb) ? nz & kVp8NzBlocks : nz;
+    return nz;
+}
+
+// one sub-block mode through the tree of section 11.2 (fl_vp8_dtables.h draws it); pr: the nine probabilities of its context
+FL_VP8_HD void vp8_put_bmode(Vp8Bool &bw, uint32_t m, const uint8_t *pr)
+{
+    bw.put(m != VP8_B_DC, pr[0]);
+    if (m == VP8_B_DC) return;
+    bw.put(m != VP8_B_TM, pr[1]);
+    if (m == VP8_B_TM) return;
+    bw.put(m != VP8_B_VE, pr[2]);
+    if (m == VP8_B_VE) return;
+    const bool far = m == VP8_B_LD || m >= VP8_B_VL;
+    bw.put(far, pr[3]);
+    if (!far) {
+        bw.put(m != VP8_B_HE, pr[4]);
+        if (m != VP8_B_HE) bw.put(m == VP8_B_VR, pr[5]);
+        return;
+    }
+    bw.put(m != VP8_B_LD, pr[6]);
+    if (m == VP8_B_LD) return;
+    bw.put(m != VP8_B_VL, pr[7]);
+    if (m != VP8_B_VL) bw.put(m == VP8_B_HU, pr[8]);
+}
+
+// the sixteen modes of B_PRED macroblock (mbx, mby), each in the context of the modes above it and to its left
+FL_VP8_HD void vp8_put_bmodes(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32_t mby)
+{
+    const uint64_t mb = (uint64_t)mby * p.mbw + mbx;
+    for (uint32_t b = 0; b < 16u; ++b) {
+        const uint32_t above = (b >> 2) ? vp8_bm_nibble(p, mb, b - 4u) : mby ? vp8_bm_context(vp8_bm_nibble(p, mb - p.mbw, b + 12u)) : (uint32_t)VP8_B_DC;
+        const uint32_t left = (b & 3u) ? vp8_bm_nibble(p, mb, b - 1u) : mbx ? vp8_bm_context(vp8_bm_nibble(p, mb - 1u, b + 3u)) : (uint32_t)VP8_B_DC;
+        vp8_put_bmode(bw, vp8_bm_nibble(p, mb, b), kVp8BModeProb + (above * 10u + left) * 9u);
+    }
+}
+
+// the tokens of one macroblock; contexts are the non-zero flags of the neighbouring blocks (0 outside the frame)
+template <bool I4 = false> FL_VP8_HD void vp8_put_mb(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32_t mby)
+{
+    const uint64_t mb = (uint64_t)mby * p.mbw + mbx;
+    const bool i4 = I4 && vp8_is_i4(p, mb);
     const uint32_t nz = vp8_nz(p, mbx, mby);
-    if (!nz) return; // skipped
+    if (!(i4 ? nz & kVp8NzBlocks : nz)) return; // skipped
     const uint32_t lnz = mbx ? vp8_nz(p, mbx - 1u, mby) : 0u, tnz = mby ? vp8_nz(p, mbx, mby - 1u) : 0u;
-    const int16_t *lev = p.lev + ((uint64_t)mby * p.mbw + mbx) * kVp8MbLevels;
-    vp8_put_block(bw, p.prob, lev + 24 * 16, 1, 0, (int)((lnz >> 24) & 1u) + (int)((tnz >> 24) & 1u));
+    const int16_t *lev = p.lev + mb * kVp8MbLevels;
+    if (!i4) {
+        const uint32_t t24 = I4 && mby && vp8_is_i4(p, mb - p.mbw) ? tnz >> 25 : tnz >> 24;
+        vp8_put_block(bw, p.prob, lev + 24 * 16, 1, 0, (int)((lnz >> 24) & 1u) + (int)(t24 & 1u));
+    }
     for (uint32_t b = 0; b < 16; ++b) {
         const uint32_t l = (b & 3u) ? nz >> (b - 1u) : lnz >> (b + 3u), t = (b >> 2) ? nz >> (b - 4u) : tnz >> (b + 12u);
-        vp8_put_block(bw, p.prob, lev + b * 16, 0, 1, (int)(l & 1u) + (int)(t & 1u));
+        vp8_put_block(bw, p.prob, lev + b * 16, i4 ? 3 : 0, i4 ? 0 : 1, (int)(l & 1u) + (int)(t & 1u));
     }
     for (uint32_t b = 16; b < 24; ++b) {
         const uint32_t l = (b & 1u) ? nz >> (b - 1u) : lnz >> (b + 1u), t = (b & 2u) ? nz >> (b - 2u) : tnz >> (b + 2u);
@@ -474,10 +585,10 @@ FL_VP8_HD void vp8_put_mb(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32_t m
 }
 
 // token partition `part` of `nparts`: the macroblock rows part, part + nparts, ...
-FL_VP8_HD void vp8_put_token_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t part, uint32_t nparts)
+template <bool I4 = false> FL_VP8_HD void vp8_put_token_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t part, uint32_t nparts)
 {
     for (uint32_t mby = part; mby < p.mbh; mby += nparts)
-        for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) vp8_put_mb(bw, p, mbx, mby);
+        for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) vp8_put_mb<I4>(bw, p, mbx, mby);
     bw.flush();
 }
 
@@ -489,11 +600,11 @@ FL_VP8_HD uint32_t vp8_skip_prob(uint32_t mbs, uint32_t skipped)
 }
 
 // partition 0: the frame header and every macroblock's skip flag and modes
-FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts)
+template <bool I4 = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts)
 {
     const uint32_t mbs = p.mbw * p.mbh;
     uint32_t skipped = 0;
-    for (uint32_t mb = 0; mb < mbs; ++mb) skipped += (p.info[mb] >> 4) == 0u;
+    for (uint32_t mb = 0; mb < mbs; ++mb) skipped += vp8_coded<I4>(p, mb) == 0u;
     const uint32_t ps = vp8_skip_prob(mbs, skipped);
     bw.literal(0, 1);                       // colour space
     bw.literal(0, 1);                       // clamping is needed
@@ -509,10 +620,15 @@ FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi
     bw.literal(ps, 8);
     for (uint32_t mb = 0; mb < mbs; ++mb) {
         const uint32_t info = p.info[mb], ym = info & 3u, uvm = (info >> 2) & 3u;
-        bw.put((info >> 4) == 0u, ps);
-        bw.put(1, kVp8YModeProb[0]);
-        bw.put(ym >= 2u, kVp8YModeProb[1]);
-        bw.put(ym & 1u, ym >= 2u ? kVp8YModeProb[3] : kVp8YModeProb[2]);
+        bw.put(vp8_coded<I4>(p, mb) == 0u, ps);
+        if (I4 && vp8_is_i4(p, mb)) {
+            bw.put(0, kVp8YModeProb[0]);
+            vp8_put_bmodes(bw, p, mb % p.mbw, mb / p.mbw);
+        } else {
+            bw.put(1, kVp8YModeProb[0]);
+            bw.put(ym >= 2u, kVp8YModeProb[1]);
+            bw.put(ym & 1u, ym >= 2u ? kVp8YModeProb[3] : kVp8YModeProb[2]);
+        }
         bw.put(uvm != 0u, kVp8UvModeProb[0]);
         if (uvm) { bw.put(uvm != 1u, kVp8UvModeProb[1]); if (uvm != 1u) bw.put(uvm == 3u, kVp8UvModeProb[2]); }
     }

@@ -13,6 +13,13 @@ template <typename T, class Op> __device__ __forceinline__ T wave_reduce(T v, Op
     for (int o = 32; o > 0; o >>= 1) v = op(v, (T)__shfl_xor(v, o, 64));
     return v;
 }
+// the sum over each group of N adjacent lanes (N a power of two, the groups aligned to N); every lane of a group gets it
+template <int N> __device__ __forceinline__ uint32_t group_sum(uint32_t v)
+{
+#pragma unroll
+    for (int o = N / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor(v, o, 64);
+    return v;
+}
 template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
 __device__ __forceinline__ uint32_t wave_xor(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a ^ b; }); }
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return max(a, b); }); }

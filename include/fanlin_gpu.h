@@ -136,12 +136,18 @@ typedef enum flgpu_front_end {
                               decodes to exactly into_rgba8() of the FLGPU_FE_NONE pixels; out_w, out_h <= 16384;
                               dst->bytes long */
     /* 7 and 8 are not front ends */
-    FLGPU_FE_WEBP_LOSSY = 9 /* dst = a finished lossy WebP file (RIFF / VP8, or RIFF / VP8X + ALPH + VP8 where a pixel is not
+    FLGPU_FE_WEBP_LOSSY = 9, /* dst = a finished lossy WebP file (RIFF / VP8, or RIFF / VP8X + ALPH + VP8 where a pixel is not
                               opaque) for the WebP arm below quality 100 (src/handler.rs:293-297): the FLGPU_FE_WEBP420 planes
                               coded as one VP8 key frame -- every macroblock I16, modes by least SSE, one segment, loop filter
                               level 0, default probabilities, quantiser from quality; the alpha plane uncompressed.  A valid file
                               that decodes to exactly the coder's reconstruction; its bytes are not libwebp's.  out_w, out_h
                               <= 16383 and at most about 21 000 macroblocks (see max_out_bytes); dst->bytes long */
+    FLGPU_FE_WEBP_LOSSY_I4 = 10 /* FLGPU_FE_WEBP_LOSSY where a macroblock's luma may also be B_PRED: sixteen 4x4 sub-blocks, each with
+                              the one of the ten sub-block predictors that has the least SSE, tried against the macroblock's I16
+                              coding and taken when its prediction error plus a penalty from the quantiser is the smaller.
+                              Same planes in, same containers, same kind of result; smaller files at equal quality, a slower
+                              analysis.  out_w, out_h <= 16383 and at most 5111 macroblocks (the first partition's 19-bit size
+                              must hold sixteen sub-block modes per macroblock); dst->bytes long */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
@@ -162,6 +168,9 @@ typedef enum flgpu_front_end {
  * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs below quality 100 (src/handler.rs:293-297) and the output fits the coder's
  * limits.  Without it such requests return the FLGPU_FE_WEBP420 planes, as before. */
 #define FLGPU_ENCODE_WEBP_LOSSY 0x800u
+/* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies come from FLGPU_FE_WEBP_LOSSY_I4
+ * where the output fits that front end's limits (FLGPU_FE_WEBP_LOSSY otherwise).  Alone it does nothing. */
+#define FLGPU_ENCODE_WEBP_LOSSY_I4 0x1000u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -585,7 +594,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS
@@ -641,7 +650,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "vp8_sources", "vp8_file_bytes", "vp8_upload_bytes" the same for FLGPU_IMG_VP8_SOURCE pictures (per picture a 128-byte header, 48
  * bytes per macroblock, the levels up to each block's last non-zero one, the raw ALPH plane or a compressed one's lossless blob), with flgpu_config.profile "vp8_decode_ns" =
  * the HIP-event time of their decode kernels;
- * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY);
+ * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files

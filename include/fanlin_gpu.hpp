@@ -88,6 +88,8 @@ public:
     // not a content::Format bit: the library finishes lossy image/webp bodies, the WebP arm below quality 100
     // (FLGPU_RESULT_WEBP_STREAM; outputs over FLGPU_FE_WEBP_LOSSY's limits still come back as planes)
     void encode_webp_lossy() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY; }
+    // ... and from FLGPU_FE_WEBP_LOSSY_I4 (macroblocks may be B_PRED: smaller files, a slower analysis) where the output fits it
+    void encode_webp_lossy_i4() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_I4; }
     uint32_t flags() const { return flags_; }
 
 private:

@@ -1,9 +1,9 @@
-"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
+"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY and, with --i4, FLGPU_FE_WEBP_LOSSY_I4 beside it): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
 planes from the device plus libwebp's WebPEncode per picture on the host's threads --, file sizes and Y-PSNR of both on the same
 planes, and the bytes that cross PCIe.  Prints plain text; under `rocprofv3 --kernel-trace --stats` (a run of its own, with
 --timing-only) the kernel statistics attribute device time to the four vp8_* kernels, the planes kernel and the resample kernel.
 
-    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only]
+    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--events]
 """
 import argparse
 import math
@@ -24,7 +24,7 @@ def _psnr(a, b):
     return 99.0 if mse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse)
 
 
-def quality(fl, st):
+def quality(fl, st, i4=False):
     import synth
     import vp8_lib
     import webp_lib
@@ -37,9 +37,15 @@ def quality(fl, st):
         dy, ry = vp8_lib.decode_yuv(dev)[0], vp8_lib.decode_yuv(ref)[0]
         print(f"quality {q}: device {len(dev)} bytes, Y-PSNR {_psnr(dy, pl.y):.2f} dB | libwebp {len(ref)} bytes, {_psnr(ry, pl.y):.2f} dB | "
               f"size ratio {len(dev) / len(ref):.3f}, planes {pl.y.nbytes * 2 + pl.u.nbytes * 2} bytes")
+        if i4:
+            dev4 = st.process_pixels(big, fl.make_params(300, 200, quality=q, front_end=fl.FE_WEBP_LOSSY_I4))
+            info = fl.vp8_info(dev4)
+            print(f"quality {q}: I4 file has {info['bpred_macroblocks']} B_PRED macroblocks of {13 * 19}, sub-block modes seen {info['bmodes_mask']:#05x}")
+            print(f"quality {q}: I4 file {len(dev4)} bytes, Y-PSNR {_psnr(vp8_lib.decode_yuv(dev4)[0], pl.y):.2f} dB | {len(dev4) / len(dev):.3f} of the I16-only "
+                  f"file, size ratio to libwebp {len(dev4) / len(ref):.3f}")
 
 
-def timing(fl, st, batch, iters, host_threads):
+def timing(fl, st, batch, iters, host_threads, i4=False, events=False):
     import torch
     import synth
     import webp_lib
@@ -49,8 +55,10 @@ def timing(fl, st, batch, iters, host_threads):
     ptrs = [srcs[i % nsrc].data_ptr() for i in range(batch)]
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
-    for name, fe in (("FE_WEBP420", fl.FE_WEBP420), ("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY)):
+    kinds = [("FE_WEBP420", fl.FE_WEBP420), ("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY)] + ([("FE_WEBP_LOSSY_I4", fl.FE_WEBP_LOSSY_I4)] if i4 else [])
+    for name, fe in kinds:
         p = fl.make_params(300, 200, quality=75, front_end=fe)
+        ns0 = (st.stats(), st.debug_get("webp_lossy_ns"))[1] if events else 0
         cap = (int(fl.plan_output(p, 1920, 1080, 3).max_out_bytes) + 255) // 256 * 256
         dst = torch.empty(batch * cap, dtype=torch.uint8, device="cuda")
         run = st.prepared_batch(ptrs, shapes, p, [dst.data_ptr() + i * cap for i in range(batch)], [cap] * batch)
@@ -68,6 +76,10 @@ def timing(fl, st, batch, iters, host_threads):
               f"mean output {np.mean(nbytes):.0f} bytes")
         if fe == fl.FE_WEBP420:
             first = dst[:cap].cpu().numpy()
+        if events and fe != fl.FE_WEBP420:
+            st.stats()  # (resolves the pending events)
+            ns = st.debug_get("webp_lossy_ns")
+            print(f"{name}: webp_lossy_ns {(ns - ns0) / (iters + 1) / 1e6:.2f} ms per batch (HIP events around the encoder's launches)")
     # the host half of the path this replaces: WebPEncode of the planes, one picture per call, on the host's threads
     ny, nc = 300 * 200, 150 * 100
     y, u, v = first[:ny].reshape(200, 300), first[ny:ny + nc].reshape(100, 150), first[ny + nc:ny + 2 * nc].reshape(100, 150)
@@ -83,6 +95,10 @@ def timing(fl, st, batch, iters, host_threads):
     print(f"host WebPEncode of the planes on {host_threads} threads: {dth * 1e3:.3f} ms per picture, {host_rate:.0f} images/s ({len(files[0])} bytes)")
     print(f"planes + host encode: {min(batch / dt_p, host_rate):.0f} images/s (the slower of the two stages); device encoder: {batch / dt_l:.0f} images/s")
     print(f"encode adds {(dt_l - dt_p) * 1e3:.2f} ms per batch to the planes path")
+    if i4:
+        dt_4, nb_4 = out["FE_WEBP_LOSSY_I4"]
+        print(f"I4 encode adds {(dt_4 - dt_p) * 1e3:.2f} ms per batch to the planes path: {batch / dt_4:.0f} images/s, mean file {np.mean(nb_4):.0f} bytes "
+              f"({np.mean(nb_4) / np.mean(nb_l):.3f} of the I16-only file)")
     print(f"PCIe per picture: up {1080 * 1920 * 3} bytes of source either way; down {int(np.mean(nb_p))} bytes of planes before, {np.mean(nb_l):.0f} bytes of file now "
           f"({np.mean(nb_l) / np.mean(nb_p):.3f} x)")
 
@@ -93,13 +109,15 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--timing-only", action="store_true")
+    ap.add_argument("--events", action="store_true", help="a profiling context: also report webp_lossy_ns per batch")
+    ap.add_argument("--i4", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_I4")
     a = ap.parse_args()
     import __graft_entry__ as g
     fl = g._load_package()
-    with fl.State(device=0) as st:
+    with fl.State(device=0, profile=a.events) as st:
         if not a.timing_only:
-            quality(fl, st)
-        timing(fl, st, a.batch, a.iters, a.host_threads)
+            quality(fl, st, a.i4)
+        timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events)
 
 
 if __name__ == "__main__":
