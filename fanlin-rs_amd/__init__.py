@@ -31,11 +31,14 @@ FE_NONE, FE_JFIF444, FE_WEBP420, FE_JPEG, FE_PNG = 0, 1, 2, 3, 4
 FE_WEBP_LOSSLESS = 6  # (5 is not a front end)
 FE_WEBP_LOSSY = 9  # (7 and 8 are not front ends)
 FE_WEBP_LOSSY_I4 = 10  # FE_WEBP_LOSSY whose macroblocks may be B_PRED (sixteen 4x4 sub-block predictors)
+FE_WEBP_LOSSY_AP = 12  # FE_WEBP_LOSSY with per-picture coefficient probabilities (11 is not a front end)
+FE_WEBP_LOSSY_I4_AP = 13  # FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q < 100) on the device (FE_WEBP_LOSSY)
 ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
+ENCODE_WEBP_LOSSY_PROBS = 0x2000  # accept_flags bit: with ENCODE_WEBP_LOSSY (and _I4), FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, nothing
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
 ENCODE_GIF = 0x400  # accept_flags bit: State.process_gif finishes the image/gif body on the device where every frame has at most 256 colours
 IN_OTHER, IN_JPEG, IN_PNG, IN_WEBP, IN_GIF_FRAME = 0, 1, 2, 3, 4
@@ -645,10 +648,14 @@ def _as_image_array(a: np.ndarray) -> np.ndarray:
 
 def result_front_end(kind: int, quality: int = 100, accept_flags: int = 0, w: int = 1, h: int = 1) -> int:
     """The front end behind a result kind.  RESULT_WEBP_STREAM is the lossless coder's at (clamped) quality 100 and the lossy
-    coder's below it: FE_WEBP_LOSSY_I4 where accept_flags has ENCODE_WEBP_LOSSY_I4 and the w x h output is within its limits."""
+    coder's below it: FE_WEBP_LOSSY_I4 where accept_flags has ENCODE_WEBP_LOSSY_I4 and the w x h output is within its limits; with
+    ENCODE_WEBP_LOSSY_PROBS the adaptive-probability variant of either (FE_WEBP_LOSSY_AP where the output is over FE_WEBP_LOSSY_I4_AP's
+    limits)."""
     if kind == RESULT_WEBP_STREAM and min(max(int(quality), 1), 100) < 100:
-        i4 = accept_flags & ENCODE_WEBP_LOSSY_I4 and ((w + 15) // 16) * ((h + 15) // 16) <= VP8_I4_MAX_MBS
-        return FE_WEBP_LOSSY_I4 if i4 else FE_WEBP_LOSSY
+        mbs = ((w + 15) // 16) * ((h + 15) // 16)
+        if accept_flags & ENCODE_WEBP_LOSSY_PROBS:
+            return FE_WEBP_LOSSY_I4_AP if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_AP_MAX_MBS else FE_WEBP_LOSSY_AP
+        return FE_WEBP_LOSSY_I4 if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_MAX_MBS else FE_WEBP_LOSSY
     return _RESULT_FE[kind]
 
 
@@ -669,10 +676,24 @@ def vp8_i4_max_out_bytes(w: int, h: int) -> int:
     return 80 + w * h + (7 * (1126 + VP8_I4_PART0_MB_BOOLS * mbs) + 7) // 8 + (7 * (384 * 19 * mbs + 256) + 7) // 8
 
 
+VP8_AP_PART0_BOOLS = 29 + 1056 * 9 + 9 + 32  # csrc/fl_vp8_core.h kVp8Part0BoolsAp: every update flag may carry 8 bits
+VP8_I4_AP_MAX_MBS = (((1 << 19) - 1) * 8 // 7 - VP8_AP_PART0_BOOLS) // VP8_I4_PART0_MB_BOOLS  # kVp8MaxMbsI4Ap
+
+
+def vp8_ap_max_out_bytes(w: int, h: int) -> int:
+    """csrc/fl_vp8_core.h vp8_ap_max_out_bytes: the worst case of a FE_WEBP_LOSSY_AP file (FE_WEBP_LOSSY's plus 1056 literals)."""
+    return vp8_max_out_bytes(w, h) + 7 * (VP8_AP_PART0_BOOLS - 1126) // 8
+
+
+def vp8_i4_ap_max_out_bytes(w: int, h: int) -> int:
+    """csrc/fl_vp8_core.h vp8_i4_ap_max_out_bytes: the worst case of a FE_WEBP_LOSSY_I4_AP file."""
+    return vp8_i4_max_out_bytes(w, h) + 7 * (VP8_AP_PART0_BOOLS - 1126) // 8
+
+
 def _split_output(buf: np.ndarray, plan: flgpu_plan, front_end: int, flags: int, nbytes: int = 0):
     if front_end == FE_NONE:
         return buf[: plan.pixel_bytes].reshape(plan.out_h, plan.out_w, plan.out_c)
-    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS, FE_WEBP_LOSSY, FE_WEBP_LOSSY_I4):
+    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS, FE_WEBP_LOSSY, FE_WEBP_LOSSY_I4, FE_WEBP_LOSSY_AP, FE_WEBP_LOSSY_I4_AP):
         return buf[:nbytes].tobytes()
     ny = plan.plane_w * plan.plane_h
     nc = plan.chroma_w * plan.chroma_h
@@ -750,7 +771,8 @@ class State:
         payload is None (AS_IS), the JPEG body (bytes), WebP planes (Planes) or the pixels for a host encoder (ndarray);
         with ENCODE_PNG in the content flags a PNG input that stays PNG gives the PNG body (bytes, RESULT_PNG_STREAM); with
         ENCODE_WEBP_LOSSLESS the WebP arm at quality 100 gives the lossless WebP body (bytes, RESULT_WEBP_STREAM), with
-        ENCODE_WEBP_LOSSY the arm below quality 100 the lossy one (same kind; with ENCODE_WEBP_LOSSY_I4 too, FE_WEBP_LOSSY_I4's)."""
+        ENCODE_WEBP_LOSSY the arm below quality 100 the lossy one (same kind; with ENCODE_WEBP_LOSSY_I4 and / or ENCODE_WEBP_LOSSY_PROBS
+        too, the file of the variant they select)."""
         img = _as_image_array(decoded)
         src = flgpu_image(img.ctypes.data, img.nbytes, img.shape[1], img.shape[0], img.shape[2], 0)
         plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()

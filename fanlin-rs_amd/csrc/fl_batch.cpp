@@ -86,7 +86,7 @@ struct ScratchSizes {
     size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
     size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
     size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0;
-    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0;
+    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
 };
 
 // What passes between the phases of run_batch_device.
@@ -111,7 +111,7 @@ struct Batch {
     std::vector<PngJob> pjobs;
     std::vector<WebpJob> wjobs;
     std::vector<Vp8Job> vjobs;
-    uint32_t vjobs_i16 = 0; // the first of them: FLGPU_FE_WEBP_LOSSY's; the rest are FLGPU_FE_WEBP_LOSSY_I4's
+    uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
     std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
     uint32_t jpeg_max_blocks = 0;
     size_t mid_floats_max = 0;
@@ -423,12 +423,18 @@ int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
 }
 
 // Lossy WebP: the front end's planes, the reconstruction (whole macroblocks), 400 levels and one record per macroblock, the sizes;
-// the I4 variant's pictures also two words of sub-block modes per macroblock.
-int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, bool i4)
+// the I4 variants' pictures also two words of sub-block modes per macroblock, the adaptive-probability variants' a table.
+bool vp8_fe_i4(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_I4_AP; }
+bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP; }
+bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe); }
+int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
 {
-    if (!(i4 ? vp8_i4_fits(pl.out_w, pl.out_h) : vp8_fits(pl.out_w, pl.out_h))) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
+    const bool i4 = vp8_fe_i4(fe), ap = vp8_fe_ap(fe);
+    const bool fits = ap ? (i4 ? vp8_i4_ap_fits(pl.out_w, pl.out_h) : vp8_ap_fits(pl.out_w, pl.out_h)) : i4 ? vp8_i4_fits(pl.out_w, pl.out_h) : vp8_fits(pl.out_w, pl.out_h);
+    if (!fits) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
     const uint64_t mbs = (uint64_t)vp8_mbs(pl.out_w) * vp8_mbs(pl.out_h);
     if (i4) s.vp8_i4_mbs += mbs;
+    if (ap) s.vp8_ap_pics++;
     s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
     s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
     s.vp8_mbs += mbs;
@@ -487,7 +493,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
-        if (w.p->front_end == FLGPU_FE_WEBP_LOSSY || w.p->front_end == FLGPU_FE_WEBP_LOSSY_I4) rc = vp8_scratch(pl, B.scratch, w.p->front_end == FLGPU_FE_WEBP_LOSSY_I4);
+        if (vp8_fe(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, w.p->front_end);
         if (rc) return rc;
     }
     return FLGPU_OK;
@@ -515,6 +521,7 @@ int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
     FL_HIP(c, c->d_vp8_lev.reserve(sz.vp8_mbs * kVp8MbLevels * sizeof(int16_t)), "lossy WebP level scratch");
     FL_HIP(c, c->d_vp8_info.reserve(sz.vp8_mbs * sizeof(uint32_t)), "lossy WebP macroblock records");
     FL_HIP(c, c->d_vp8_bm.reserve(sz.vp8_i4_mbs * 2u * sizeof(uint32_t)), "lossy WebP sub-block mode records");
+    FL_HIP(c, c->d_vp8_tab.reserve((size_t)sz.vp8_ap_pics * kVp8TabBytes), "lossy WebP probability tables");
     FL_HIP(c, c->d_vp8_sizes.reserve((size_t)sz.vp8_pics * kVp8SizeWords * sizeof(uint32_t)), "lossy WebP partition sizes");
     FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
     FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
@@ -897,8 +904,9 @@ int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
 }
 
 // The lossy WebP job reads the planes its own WebP420 front-end job writes to scratch (add_planes_launch with to_vp8).
-int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, bool i4)
+int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, uint32_t fe)
 {
+    const bool i4 = vp8_fe_i4(fe);
     Vp8Job &j = encoder_job(B, B.vjobs, B.vjob_img, i);
     const flgpu_plan &pl = B.work[i].plan;
     j.src = static_cast<uint8_t *>(c->d_vp8_planes.p) + at.vp8_planes;
@@ -906,10 +914,11 @@ int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, bool i4)
     j.lev = static_cast<int16_t *>(c->d_vp8_lev.p) + at.vp8_mbs * kVp8MbLevels;
     j.info = static_cast<uint32_t *>(c->d_vp8_info.p) + at.vp8_mbs;
     j.bm = i4 ? static_cast<uint32_t *>(c->d_vp8_bm.p) + at.vp8_i4_mbs * 2u : nullptr;
+    j.tab = vp8_fe_ap(fe) ? static_cast<uint8_t *>(c->d_vp8_tab.p) + (size_t)at.vp8_ap_pics * kVp8TabBytes : nullptr;
     j.sizes = static_cast<uint32_t *>(c->d_vp8_sizes.p) + (size_t)at.vp8_pics * kVp8SizeWords;
     const uint32_t q = B.work[i].p->quality;
     j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
-    return vp8_scratch(pl, at, i4);
+    return vp8_scratch(pl, at, fe);
 }
 
 // The planar front ends (JFIF444, WebP420): one launch per kind.  to_vp8: the pictures are lossy WebP jobs (B.vjobs from `vjob0`
@@ -981,8 +990,10 @@ int build_launches(flgpu_ctx *c, Batch &B)
     // workgroup bound their waits and report an expired one here instead of delivering pixels that were never synchronised
     B.has_results = !fe_groups.empty();
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
-    ScratchSizes vp8_at; // (FLGPU_FE_WEBP_LOSSY and _I4 are two groups that share the lossy WebP scratch; _LOSSY's jobs come first)
-    static_assert(FLGPU_FE_WEBP_LOSSY < FLGPU_FE_WEBP_LOSSY_I4, "launch_vp8_encode takes the I16-only jobs first");
+    ScratchSizes vp8_at; // (the lossy WebP front ends are up to four groups that share the lossy WebP scratch, in the families' order)
+    static_assert(FLGPU_FE_WEBP_LOSSY < FLGPU_FE_WEBP_LOSSY_I4 && FLGPU_FE_WEBP_LOSSY_I4 < FLGPU_FE_WEBP_LOSSY_AP && FLGPU_FE_WEBP_LOSSY_AP < FLGPU_FE_WEBP_LOSSY_I4_AP,
+                  "launch_vp8_encode takes one range of jobs per family, in this order");
+    static_assert(vp8_family(FLGPU_FE_WEBP_LOSSY) == 0 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4) == 1 && vp8_family(FLGPU_FE_WEBP_LOSSY_AP) == 2 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP) == 3, "vp8_family");
     for (auto &g : fe_groups) {
         ScratchSizes at;
         const size_t vjob0 = B.vjobs.size();
@@ -991,13 +1002,12 @@ int build_launches(flgpu_ctx *c, Batch &B)
             if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
             if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
             if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, at);
-            if (g.first == FLGPU_FE_WEBP_LOSSY) { rc = add_vp8_job(c, B, i, vp8_at, false); B.vjobs_i16++; }
-            if (g.first == FLGPU_FE_WEBP_LOSSY_I4) rc = add_vp8_job(c, B, i, vp8_at, true);
+            if (vp8_fe(g.first)) { rc = add_vp8_job(c, B, i, vp8_at, g.first); B.vjobs_fam[vp8_family(g.first)]++; }
             assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
             (void)rc;
         }
         if (g.first == FLGPU_FE_JFIF444 || g.first == FLGPU_FE_WEBP420) add_planes_launch(B, g.first, g.second);
-        if (g.first == FLGPU_FE_WEBP_LOSSY || g.first == FLGPU_FE_WEBP_LOSSY_I4) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
+        if (vp8_fe(g.first)) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
     }
     FL_HIP(c, c->d_mid.reserve(B.mid_floats_max * 4), "f32 intermediate");
     return FLGPU_OK;
@@ -1200,7 +1210,7 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
     }
     if (!B.vjobs.empty()) {
         ProfileScope ps(c, st, 7);
-        FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_i16, (uint32_t)B.vjobs.size() - B.vjobs_i16, st), "lossy WebP encode");
+        FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_fam, st), "lossy WebP encode");
         c->stats.frontend_launches++;
     }
     // plain copies for requests that change nothing

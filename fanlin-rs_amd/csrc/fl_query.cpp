@@ -268,15 +268,20 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
     if (out_format) *out_format = fmt;
     rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     if (rc == FLGPU_OK && webp_lossy && fl::vp8_fits(plan->out_w, plan->out_h)) {
-        const bool i4 = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_I4) && fl::vp8_i4_fits(plan->out_w, plan->out_h);
-        p->front_end = i4 ? FLGPU_FE_WEBP_LOSSY_I4 : FLGPU_FE_WEBP_LOSSY;
+        // _I4 and _PROBS each select a variant where the output fits it; an output over the B_PRED variant's limit with _PROBS (5039
+        // macroblocks, 72 fewer than without) takes the I16-only adaptive coder, never the non-adaptive B_PRED one
+        const bool want_i4 = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_I4) != 0, want_ap = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_PROBS) != 0;
+        if (want_ap && fl::vp8_ap_fits(plan->out_w, plan->out_h))
+            p->front_end = want_i4 && fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4_AP : FLGPU_FE_WEBP_LOSSY_AP;
+        else
+            p->front_end = want_i4 && fl::vp8_i4_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4 : FLGPU_FE_WEBP_LOSSY;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
     if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {
         p->front_end = FLGPU_FE_WEBP_LOSSLESS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
-    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY || p->front_end == FLGPU_FE_WEBP_LOSSY_I4) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY || p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
     return rc;
 }
 
@@ -788,8 +793,9 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    /* front ends 0-4, 6, 9 and 10 (5, 7 and 8 are not) */
-    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && p->front_end != FLGPU_FE_WEBP_LOSSY && p->front_end != FLGPU_FE_WEBP_LOSSY_I4) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
+    /* front ends 0-4, 6, 9, 10, 12 and 13 (5, 7, 8 and 11 are not) */
+    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && p->front_end != FLGPU_FE_WEBP_LOSSY && p->front_end != FLGPU_FE_WEBP_LOSSY_I4 &&
+         p->front_end != FLGPU_FE_WEBP_LOSSY_AP && p->front_end != FLGPU_FE_WEBP_LOSSY_I4_AP) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
         return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
@@ -876,18 +882,25 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->max_out_bytes = fl::webpll_max_out_bytes(plan->out_w, plan->out_h);
         break;
     case FLGPU_FE_WEBP_LOSSY:
-    case FLGPU_FE_WEBP_LOSSY_I4: {
+    case FLGPU_FE_WEBP_LOSSY_I4:
+    case FLGPU_FE_WEBP_LOSSY_AP:
+    case FLGPU_FE_WEBP_LOSSY_I4_AP: {
         // the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the planes' bytes.
         // max_out_bytes: the worst case of this coder's files (fl_vp8_core.h), so a dst of this capacity is never too small.
-        // (the I4 variant's partition 0 is larger per macroblock: fewer macroblocks, a larger worst case)
-        const bool i4 = p->front_end == FLGPU_FE_WEBP_LOSSY_I4;
-        if (!(i4 ? fl::vp8_i4_fits(plan->out_w, plan->out_h) : fl::vp8_fits(plan->out_w, plan->out_h))) return FLGPU_ERR_UNSUPPORTED;
+        // (the I4 variants' partition 0 is larger per macroblock, the adaptive-probability variants' by its 1056 literals: fewer
+        // macroblocks, a larger worst case)
+        const bool i4 = p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP;
+        const bool ap = p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP;
+        const bool fits = ap ? (i4 ? fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) : fl::vp8_ap_fits(plan->out_w, plan->out_h))
+                             : (i4 ? fl::vp8_i4_fits(plan->out_w, plan->out_h) : fl::vp8_fits(plan->out_w, plan->out_h));
+        if (!fits) return FLGPU_ERR_UNSUPPORTED;
         plan->plane_w = plan->out_w;
         plan->plane_h = plan->out_h;
         plan->chroma_w = (plan->out_w + 1u) >> 1;
         plan->chroma_h = (plan->out_h + 1u) >> 1;
         plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
-        plan->max_out_bytes = i4 ? fl::vp8_i4_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_max_out_bytes(plan->out_w, plan->out_h);
+        plan->max_out_bytes = ap ? (i4 ? fl::vp8_i4_ap_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_ap_max_out_bytes(plan->out_w, plan->out_h))
+                                 : (i4 ? fl::vp8_i4_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_max_out_bytes(plan->out_w, plan->out_h));
         break;
     }
     case FLGPU_FE_WEBP420:

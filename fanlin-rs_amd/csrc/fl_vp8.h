@@ -1,4 +1,4 @@
-// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY and FLGPU_FE_WEBP_LOSSY_I4): job descriptor, scratch sizes and the launch.
+// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY, _I4, _AP and _I4_AP): job descriptor, scratch sizes and the launch.
 // The format's limits and worst case, and everything the kernels compute, are in fl_vp8_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,13 +24,21 @@ struct alignas(16) Vp8Job {
     uint32_t w, h, c;
     uint32_t dst_cap;     // bytes available at dst
     uint32_t qi;          // quantiser index (vp8_quality_index of the clamped quality)
-    uint32_t pad[3];
+    uint32_t pad[1];
+    uint8_t *tab;         // scratch, the adaptive-probability variants only (else nullptr): the picture's table, kVp8TabBytes
 };
+static_assert(sizeof(Vp8Job) == 96, "the job record keeps its size");
 
 inline uint64_t vp8_planes_bytes(uint64_t w, uint64_t h) { return 2u * w * h + 2u * ((w + 1u) / 2u) * ((h + 1u) / 2u); }
 
-// predict / transform / quantise / reconstruct -> partition sizes -> framing and alpha plane -> partitions; four stream-ordered
-// launches for jobs[0 .. n_i16), the FLGPU_FE_WEBP_LOSSY pictures, and four for jobs[n_i16 .. n_i16 + n_i4), the _I4 ones
-hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t n_i16, uint32_t n_i4, hipStream_t st);
+constexpr uint32_t kVp8TabBytes = 4 * 8 * 3 * 11; // the coefficient probability table of one picture
+// The families of a launch in the order of their front ends, which is the order of their jobs: FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP.
+constexpr uint32_t kVp8Families = 4;
+constexpr uint32_t vp8_family(uint32_t front_end) { return front_end == 9u ? 0u : front_end == 10u ? 1u : front_end == 12u ? 2u : 3u; }
+
+// predict / transform / quantise / reconstruct -> (the adaptive variants: token statistics and the picture's table ->) partition
+// sizes -> framing and alpha plane -> partitions; four or five stream-ordered launches per family that has pictures: n[f] jobs of
+// family f, one range after the other
+hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st);
 
 } // namespace fl

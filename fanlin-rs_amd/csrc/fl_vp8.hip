@@ -21,13 +21,22 @@
 //                       levels are in LDS; the winner of the two trials is committed.
 //   vp8_size_kernel<true>, vp8_write_kernel<true>  the coder's instantiation with the mode tree in partition 0 and the type-3 / no-Y2
 //                       path in the tokens, a branch per macroblock on its mode record.
-// A batch's I16-only pictures come first in the job list, so each family is one range of it.
+// The adaptive-probability variants (FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP; fl_vp8_ap_core.h) share the analysis kernels
+// and add one launch between the analysis and the size kernel:
+//   vp8_stats_kernel<I4>  one workgroup per picture.  The (macroblock, block) pairs spread over its 256 threads; each fetches its
+//                       block's levels whole, takes its contexts from the macroblock records and runs the coder's own token walk
+//                       into a counting sink: 2 x 1056 counters in LDS (8448 B), LDS atomics.  After a barrier thread i < 1056
+//                       applies the rule to entry i and stores the picture's table (1056 B of scratch).
+//   vp8_size_kernel<I4, true>, vp8_write_kernel<I4, true>  the coders, staging the picture's table instead of the default one (a
+//                       coder workgroup is exactly one picture) and writing the updates into partition 0.
+// A batch's pictures are grouped by front end in the job list, so each of the four families is one range of it.
 // No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
 // A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fl_vp8.h"
+#include "fl_vp8_ap_core.h"
 #include "fl_vp8_i4_core.h"
 #include "fl_wave.h"
 
@@ -41,6 +50,9 @@ constexpr uint32_t kLaneSlots = 16;    // coder slots per picture in the coder k
 constexpr uint32_t kLaneStride = 16;
 constexpr uint32_t kCoderThreads = 256;
 constexpr uint32_t kFrameThreads = 256;
+constexpr uint32_t kStatsThreads = 256;
+// the adaptive coders stage one table per workgroup: a workgroup's slots must be exactly one picture's
+static_assert(kCoderThreads / kLaneStride == kLaneSlots && kCoderThreads % kLaneStride == 0, "a coder workgroup is one picture");
 
 __device__ __forceinline__ Vp8Pic pic_of(const Vp8Job &j, const uint8_t *prob = kVp8CoefProb)
 {
@@ -154,25 +166,50 @@ __global__ __launch_bounds__(64) void vp8_analyse_i4_kernel(const Vp8Job *__rest
         }
 }
 
-// The coders read a probability for every boolean: the table's 1056 bytes go to LDS first (all threads of the workgroup, before
-// any of them leaves).
-__device__ __forceinline__ void stage_prob(uint8_t *s_prob)
+// The counting sink of the token walk on the device: Vp8Count's counters in LDS, shared by the workgroup.
+struct Vp8LdsCount {
+    const uint8_t *tab;
+    uint32_t *cnt;
+    __device__ __forceinline__ void node(int bit, const uint8_t *p) { atomicAdd(cnt + (bit ? kVp8CoefProbs : 0u) + (uint32_t)(p - tab), 1u); }
+    __device__ __forceinline__ void put(int, uint32_t) {}
+};
+
+// The picture's probability table from its token statistics.  No thread waits on another workgroup.
+template <bool I4> __global__ __launch_bounds__(kStatsThreads) void vp8_stats_kernel(const Vp8Job *__restrict__ jobs)
 {
-    for (uint32_t i = threadIdx.x; i < sizeof(kVp8CoefProb); i += kCoderThreads) s_prob[i] = kVp8CoefProb[i];
+    __shared__ uint32_t s_cnt[kVp8CountWords];
+    const Vp8Job &jb = jobs[blockIdx.x];
+    const Vp8Pic p = pic_of(jb); // (p.prob: the default table; the walk only takes addresses in it)
+    for (uint32_t i = threadIdx.x; i < kVp8CountWords; i += kStatsThreads) s_cnt[i] = 0u;
+    __syncthreads();
+    Vp8LdsCount sink{p.prob, s_cnt};
+    const uint32_t items = p.mbw * p.mbh * kVp8MbBlocks; // (under vp8_fits: below 2^20)
+    for (uint32_t k = threadIdx.x; k < items; k += kStatsThreads) vp8_ap_count_item<I4>(sink, p, k);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kVp8CoefProbs; i += kStatsThreads) jb.tab[i] = vp8_ap_decide(i, s_cnt[i], s_cnt[kVp8CoefProbs + i]);
+}
+
+// The coders read a probability for every boolean: the table's 1056 bytes go to LDS first (all threads of the workgroup, before
+// any of them leaves).  AP: the table of the workgroup's picture.
+template <bool AP> __device__ __forceinline__ void stage_prob(uint8_t *s_prob, const Vp8Job *jobs)
+{
+    const uint8_t *tab = AP ? jobs[blockIdx.x].tab : kVp8CoefProb;
+    for (uint32_t i = threadIdx.x; i < sizeof(kVp8CoefProb); i += kCoderThreads) s_prob[i] = tab[i];
     __syncthreads();
 }
 
 // the partition of lane slot `part` (0 = the first partition), counted or written
-template <bool I4> __device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
+template <bool I4, bool AP> __device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
 {
-    if (part == 0u) vp8_put_first_partition<I4>(bw, p, qi, nparts);
+    if (part == 0u) vp8_put_first_partition<I4, AP>(bw, p, qi, nparts);
     else vp8_put_token_partition<I4>(bw, p, part - 1u, nparts);
 }
 
-template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
-    stage_prob(s_prob);
+    if (AP && blockIdx.x >= njobs) return; // (never: the grid is one workgroup per picture)
+    stage_prob<AP>(s_prob, jobs);
     const uint32_t t = blockIdx.x * kCoderThreads + threadIdx.x, slot = t / kLaneStride, job = slot / kLaneSlots, part = slot % kLaneSlots;
     if (job >= njobs || t % kLaneStride) return;
     const Vp8Job &jb = jobs[job];
@@ -181,7 +218,7 @@ template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_size_ker
     if (part >= kVp8SizeWords) return;
     if (part > nparts) { jb.sizes[part] = 0u; return; }
     Vp8Bool bw;
-    code_partition<I4>(bw, p, jb.qi, part, nparts);
+    code_partition<I4, AP>(bw, p, jb.qi, part, nparts);
     jb.sizes[part] = bw.pos;
 }
 
@@ -210,10 +247,11 @@ __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *
     }
 }
 
-template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
-    stage_prob(s_prob);
+    if (AP && blockIdx.x >= njobs) return; // (never: the grid is one workgroup per picture)
+    stage_prob<AP>(s_prob, jobs);
     const uint32_t t = blockIdx.x * kCoderThreads + threadIdx.x, slot = t / kLaneStride, job = slot / kLaneSlots, part = slot % kLaneSlots;
     if (job >= njobs || t % kLaneStride) return;
     const Vp8Job &jb = jobs[job];
@@ -225,30 +263,38 @@ template <bool I4> __global__ __launch_bounds__(kCoderThreads) void vp8_write_ke
     if (L.total > jb.dst_cap) return; // vp8_frame_kernel has reported it
     Vp8Bool bw;
     bw.buf = jb.dst + L.part[part];
-    code_partition<I4>(bw, p, jb.qi, part, nparts);
+    code_partition<I4, AP>(bw, p, jb.qi, part, nparts);
 }
 
 } // namespace
 
-template <bool I4> static hipError_t launch_family(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
+template <bool I4, bool AP> static hipError_t launch_family(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
 {
     if (!njobs) return hipSuccess;
     const uint32_t coder_blocks = (uint32_t)(((uint64_t)njobs * kLaneSlots * kLaneStride + kCoderThreads - 1u) / kCoderThreads);
     if (I4) hipLaunchKernelGGL(vp8_analyse_i4_kernel, dim3(njobs), dim3(64), 0, st, jobs);
     else hipLaunchKernelGGL(vp8_analyse_kernel, dim3(njobs), dim3(64), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(vp8_size_kernel<I4>, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    if (AP) {
+        hipLaunchKernelGGL(vp8_stats_kernel<I4>, dim3(njobs), dim3(kStatsThreads), 0, st, jobs);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL((vp8_size_kernel<I4, AP>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(vp8_frame_kernel, dim3(njobs), dim3(kFrameThreads), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(vp8_write_kernel<I4>, dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    hipLaunchKernelGGL((vp8_write_kernel<I4, AP>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     return hipGetLastError();
 }
 
-hipError_t launch_vp8_encode(const Vp8Job *jobs, uint32_t n_i16, uint32_t n_i4, hipStream_t st)
+hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st)
 {
-    if (hipError_t e = launch_family<false>(jobs, n_i16, st)) return e;
-    return launch_family<true>(jobs + n_i16, n_i4, st);
+    if (hipError_t e = launch_family<false, false>(jobs, n[0], st)) return e;
+    jobs += n[0];
+    if (hipError_t e = launch_family<true, false>(jobs, n[1], st)) return e;
+    jobs += n[1];
+    if (hipError_t e = launch_family<false, true>(jobs, n[2], st)) return e;
+    return launch_family<true, true>(jobs + n[2], n[3], st);
 }
 
 } // namespace fl

@@ -25,6 +25,12 @@
 // with kVp8BModeProb[above][left]; an I16 neighbour stands for DC -> B_DC, V -> B_VE, H -> B_HE, TM -> B_TM, outside the frame is
 // B_DC.  Its tokens have no Y2 block, its luma blocks are type 3 from coefficient 0, it leaves the Y2 context of its column and
 // row as it found them, and it is skipped when its 24 blocks are zero.
+//
+// The adaptive-probability variants (FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP; fl_vp8_ap_core.h states the rule,
+// tests/vp8_ap_model.py restates it): the same macroblocks, levels and modes as the front end each stands beside, but the picture's
+// token-tree branches are counted first, a coefficient probability table is derived from the counts, partition 0 carries the
+// updates (flag i is 1 and followed by the 8-bit probability where the picture's table differs from the default), and the token
+// partitions are coded with that table.  The reconstruction does not change.
 #pragma once
 #include <stdint.h>
 
@@ -69,6 +75,18 @@ FL_VP8_HD uint64_t vp8_i4_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits *
 constexpr uint64_t kVp8MaxMbsI4 = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0Bools) / kVp8Part0MbBoolsI4; // 5111
 static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBoolsI4 * kVp8MaxMbsI4) + 7u) / 8u < (1ull << 19), "first partition size field");
 
+// The adaptive-probability variants' partition 0: each of the 1056 flags may be followed by an 8-bit probability.
+constexpr uint64_t kVp8Part0BoolsAp = 29 + 1056 * 9 + 9 + 32; // 9574
+FL_VP8_HD uint64_t vp8_ap_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBools * mbs) + 7u) / 8u; }
+FL_VP8_HD uint64_t vp8_i4_ap_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBoolsI4 * mbs) + 7u) / 8u; }
+constexpr uint64_t kVp8MaxMbsAp = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0BoolsAp) / kVp8Part0MbBools;
+constexpr uint64_t kVp8MaxMbsI4Ap = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0BoolsAp) / kVp8Part0MbBoolsI4; // 5039
+static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBools * kVp8MaxMbsAp) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBoolsI4 * kVp8MaxMbsI4Ap) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert(kVp8MaxMbsI4Ap == 5039, "the B_PRED variant with updates: 72 macroblocks fewer than without");
+// (the 1056 literals are whole bytes of worst case: the partition-0 term grows by exactly 7 x 8448 / 8 = 7392)
+static_assert(kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) % 8u == 0 && kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) / 8u == 7392, "the updates' worst case");
+
 FL_VP8_HD uint32_t vp8_mbs(uint32_t px) { return (px + 15u) >> 4; }
 // token partitions: the largest of 1 / 2 / 4 / 8 that is not above the number of macroblock rows; row r goes to partition r mod n
 FL_VP8_HD uint32_t vp8_partitions(uint32_t mb_rows) { return mb_rows >= 8 ? 8u : mb_rows >= 4 ? 4u : mb_rows >= 2 ? 2u : 1u; }
@@ -100,6 +118,21 @@ FL_VP8_HD uint64_t vp8_i4_max_out_bytes(uint64_t w, uint64_t h)
 {
     const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
     return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_part0_max_bytes(mbs);
+}
+
+// the adaptive-probability variants: the same, with their own partition 0.  The I16-only one stays bound by the 24-bit token
+// partition field (about 21 000 macroblocks; kVp8MaxMbsAp is four times that), the B_PRED one by kVp8MaxMbsI4Ap.
+FL_VP8_HD bool vp8_ap_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsAp; }
+FL_VP8_HD bool vp8_i4_ap_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsI4Ap; }
+FL_VP8_HD uint64_t vp8_ap_max_out_bytes(uint64_t w, uint64_t h)
+{
+    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
+    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_ap_part0_max_bytes(mbs);
+}
+FL_VP8_HD uint64_t vp8_i4_ap_max_out_bytes(uint64_t w, uint64_t h)
+{
+    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
+    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_ap_part0_max_bytes(mbs);
 }
 
 // ---- quantiser --------------------------------------------------------------------------------------------------------------------
@@ -230,7 +263,7 @@ struct Vp8Pic {
     int16_t *lev;
     uint32_t *info;
     uint32_t *bm = nullptr;
-    const uint8_t *prob;   // kVp8CoefProb, or a copy of it in faster memory (the kernels keep one in LDS)
+    const uint8_t *prob;   // kVp8CoefProb or, in the adaptive-probability variants, the picture's table; the kernels keep a copy in LDS
     uint32_t w, h, cw, ch, mbw, mbh;
     Vp8Quant q;
 };
@@ -457,6 +490,8 @@ struct Vp8Bool {
         }
         low <<= shift;
     }
+    // the sink of the token walk (vp8_put_block): a boolean whose probability is an entry of the coefficient table, here just coded
+    FL_VP8_HD void node(int bit, const uint8_t *p) { put(bit, *p); }
     FL_VP8_HD void literal(uint32_t v, int bits) { for (int b = bits - 1; b >= 0; --b) put((int)((v >> b) & 1u), 128u); }
     FL_VP8_HD void flush() { for (int i = 0; i < 32; ++i) put(0, 128u); }
 };
@@ -465,8 +500,10 @@ struct Vp8Bool {
 FL_VP8_HD const uint8_t *vp8_prob(const uint8_t *tab, int type, int n, int ctx) { return tab + ((type * 8 + kVp8Band[n]) * 3 + ctx) * 11; }
 
 // the tokens of one block: src = its 16 levels in coding order (32 bytes, 16-byte aligned: fetched whole, not one by one), from
-// position `first`
-FL_VP8_HD void vp8_put_block(Vp8Bool &bw, const uint8_t *tab, const int16_t *src, int type, int first, int ctx)
+// position `first`.  The one walk of the token tree: `bw` is a sink with node(bit, p) for a boolean whose probability is the entry p
+// of the coefficient table and put(bit, prob) for any other (sign and extra bits) -- Vp8Bool codes both, Vp8Count
+// (fl_vp8_ap_core.h) counts the first kind per entry and drops the second.
+template <class Sink> FL_VP8_HD void vp8_put_block(Sink &bw, const uint8_t *tab, const int16_t *src, int type, int first, int ctx)
 {
     int16_t lev[16];
     __builtin_memcpy(lev, __builtin_assume_aligned(src, 16), sizeof(lev));
@@ -474,29 +511,29 @@ FL_VP8_HD void vp8_put_block(Vp8Bool &bw, const uint8_t *tab, const int16_t *src
     for (int i = first; i < 16; ++i) if (lev[i]) last = i;
     int n = first;
     const uint8_t *p = vp8_prob(tab, type, n, ctx);
-    bw.put(last >= 0, p[0]);
+    bw.node(last >= 0, p);
     if (last < 0) return;
     while (n < 16) {
         const int c = lev[n++];
         const int v = c < 0 ? -c : c;
-        if (v == 0) { bw.put(0, p[1]); p = vp8_prob(tab, type, n, 0); continue; }
-        bw.put(1, p[1]);
-        if (v == 1) { bw.put(0, p[2]); p = vp8_prob(tab, type, n, 1); }
+        if (v == 0) { bw.node(0, p + 1); p = vp8_prob(tab, type, n, 0); continue; }
+        bw.node(1, p + 1);
+        if (v == 1) { bw.node(0, p + 2); p = vp8_prob(tab, type, n, 1); }
         else {
-            bw.put(1, p[2]);
+            bw.node(1, p + 2);
             if (v <= 4) {
-                bw.put(0, p[3]);
-                bw.put(v != 2, p[4]);
-                if (v != 2) bw.put(v == 4, p[5]);
+                bw.node(0, p + 3);
+                bw.node(v != 2, p + 4);
+                if (v != 2) bw.node(v == 4, p + 5);
             } else {
-                bw.put(1, p[3]);
+                bw.node(1, p + 3);
                 int cat;
-                if (v <= 10) { bw.put(0, p[6]); cat = v > 6; bw.put(cat, p[7]); }
+                if (v <= 10) { bw.node(0, p + 6); cat = v > 6; bw.node(cat, p + 7); }
                 else {
-                    bw.put(1, p[6]);
+                    bw.node(1, p + 6);
                     cat = v < 19 ? 2 : v < 35 ? 3 : v < 67 ? 4 : 5;
-                    bw.put(cat >= 4, p[8]);
-                    bw.put(cat & 1, p[cat >= 4 ? 10 : 9]);
+                    bw.node(cat >= 4, p + 8);
+                    bw.node(cat & 1, p + (cat >= 4 ? 10 : 9));
                 }
                 const int extra = v - (int)kVp8CatBase[cat];
                 for (int k = (int)kVp8CatBits[cat] - 1, t = 0; k >= 0; --k, ++t) bw.put((extra >> k) & 1, kVp8CatProb[cat][t]);
@@ -505,7 +542,7 @@ FL_VP8_HD void vp8_put_block(Vp8Bool &bw, const uint8_t *tab, const int16_t *src
         }
         bw.put(c < 0, 128u);
         if (n == 16) return;
-        bw.put(n <= last, p[0]);
+        bw.node(n <= last, p);
         if (n > last) return;
     }
 }
@@ -561,31 +598,57 @@ FL_VP8_HD void vp8_put_bmodes(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32
     }
 }
 
-// the tokens of one macroblock; contexts are the non-zero flags of the neighbouring blocks (0 outside the frame)
-template <bool I4 = false> FL_VP8_HD void vp8_put_mb(Vp8Bool &bw, const Vp8Pic &p, uint32_t mbx, uint32_t mby)
+// What the blocks of one macroblock are coded with: its own non-zero flags, those of the macroblocks to the left and above (0
+// outside the frame), the Y2 context from above, whether it is B_PRED, its levels.  coded == 0: it is skipped.
+struct Vp8MbCtx {
+    uint32_t coded, nz, lnz, tnz, t24;
+    bool i4;
+    const int16_t *lev;
+};
+template <bool I4> FL_VP8_HD Vp8MbCtx vp8_mb_ctx(const Vp8Pic &p, uint32_t mbx, uint32_t mby)
 {
     const uint64_t mb = (uint64_t)mby * p.mbw + mbx;
-    const bool i4 = I4 && vp8_is_i4(p, mb);
-    const uint32_t nz = vp8_nz(p, mbx, mby);
-    if (!(i4 ? nz & kVp8NzBlocks : nz)) return; // skipped
-    const uint32_t lnz = mbx ? vp8_nz(p, mbx - 1u, mby) : 0u, tnz = mby ? vp8_nz(p, mbx, mby - 1u) : 0u;
-    const int16_t *lev = p.lev + mb * kVp8MbLevels;
-    if (!i4) {
-        const uint32_t t24 = I4 && mby && vp8_is_i4(p, mb - p.mbw) ? tnz >> 25 : tnz >> 24;
-        vp8_put_block(bw, p.prob, lev + 24 * 16, 1, 0, (int)((lnz >> 24) & 1u) + (int)(t24 & 1u));
+    Vp8MbCtx c;
+    c.i4 = I4 && vp8_is_i4(p, mb);
+    c.nz = vp8_nz(p, mbx, mby);
+    c.coded = c.i4 ? c.nz & kVp8NzBlocks : c.nz;
+    c.lnz = c.tnz = c.t24 = 0u;
+    c.lev = p.lev + mb * kVp8MbLevels;
+    if (!c.coded) return c;
+    c.lnz = mbx ? vp8_nz(p, mbx - 1u, mby) : 0u;
+    c.tnz = mby ? vp8_nz(p, mbx, mby - 1u) : 0u;
+    if (!c.i4) c.t24 = I4 && mby && vp8_is_i4(p, mb - p.mbw) ? c.tnz >> 25 : c.tnz >> 24;
+    return c;
+}
+// the tokens of block b of a coded macroblock, b in the order of lev: 0..15 luma, 16..23 chroma, 24 the Y2 block (an I16 macroblock's only)
+template <class Sink> FL_VP8_HD void vp8_put_mb_block(Sink &bw, const uint8_t *tab, const Vp8MbCtx &c, uint32_t b)
+{
+    if (b == 24u) {
+        if (!c.i4) vp8_put_block(bw, tab, c.lev + 24 * 16, 1, 0, (int)((c.lnz >> 24) & 1u) + (int)(c.t24 & 1u));
+    } else if (b < 16u) {
+        const uint32_t l = (b & 3u) ? c.nz >> (b - 1u) : c.lnz >> (b + 3u), t = (b >> 2) ? c.nz >> (b - 4u) : c.tnz >> (b + 12u);
+        vp8_put_block(bw, tab, c.lev + b * 16, c.i4 ? 3 : 0, c.i4 ? 0 : 1, (int)(l & 1u) + (int)(t & 1u));
+    } else {
+        const uint32_t l = (b & 1u) ? c.nz >> (b - 1u) : c.lnz >> (b + 1u), t = (b & 2u) ? c.nz >> (b - 2u) : c.tnz >> (b + 2u);
+        vp8_put_block(bw, tab, c.lev + b * 16, 2, 0, (int)(l & 1u) + (int)(t & 1u));
     }
-    for (uint32_t b = 0; b < 16; ++b) {
-        const uint32_t l = (b & 3u) ? nz >> (b - 1u) : lnz >> (b + 3u), t = (b >> 2) ? nz >> (b - 4u) : tnz >> (b + 12u);
-        vp8_put_block(bw, p.prob, lev + b * 16, i4 ? 3 : 0, i4 ? 0 : 1, (int)(l & 1u) + (int)(t & 1u));
-    }
-    for (uint32_t b = 16; b < 24; ++b) {
-        const uint32_t l = (b & 1u) ? nz >> (b - 1u) : lnz >> (b + 1u), t = (b & 2u) ? nz >> (b - 2u) : tnz >> (b + 2u);
-        vp8_put_block(bw, p.prob, lev + b * 16, 2, 0, (int)(l & 1u) + (int)(t & 1u));
-    }
+}
+constexpr uint32_t kVp8MbBlocks = 25;
+
+// the tokens of one macroblock in the stream's order: Y2, luma, chroma
+template <bool I4 = false, class Sink> FL_VP8_HD void vp8_put_mb(Sink &bw, const Vp8Pic &p, uint32_t mbx, uint32_t mby)
+{
+    const Vp8MbCtx c = vp8_mb_ctx<I4>(p, mbx, mby);
+    if (!c.coded) return; // skipped
+    vp8_put_mb_block(bw, p.prob, c, 24u);
+    for (uint32_t b = 0; b < 16; ++b) vp8_put_mb_block(bw, p.prob, c, b);
+    for (uint32_t b = 16; b < 24; ++b) vp8_put_mb_block(bw, p.prob, c, b);
 }
 
 // token partition `part` of `nparts`: the macroblock rows part, part + nparts, ...
-template <bool I4 = false> FL_VP8_HD void vp8_put_token_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t part, uint32_t nparts)
+// (always inlined: with four coder kernels per variant calling it, the compiler would otherwise keep it a function of its own,
+// whose block buffer then lives in scratch memory instead of LDS)
+template <bool I4 = false> __attribute__((always_inline)) FL_VP8_HD void vp8_put_token_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t part, uint32_t nparts)
 {
     for (uint32_t mby = part; mby < p.mbh; mby += nparts)
         for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) vp8_put_mb<I4>(bw, p, mbx, mby);
@@ -599,8 +662,9 @@ FL_VP8_HD uint32_t vp8_skip_prob(uint32_t mbs, uint32_t skipped)
     return pr < 1u ? 1u : pr;
 }
 
-// partition 0: the frame header and every macroblock's skip flag and modes
-template <bool I4 = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts)
+// partition 0: the frame header and every macroblock's skip flag and modes.  AP (the adaptive-probability variants): p.prob is the
+// picture's table, and entry i is updated exactly where it differs from the default one (the rule never picks an equal value)
+template <bool I4 = false, bool AP = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts)
 {
     const uint32_t mbs = p.mbw * p.mbh;
     uint32_t skipped = 0;
@@ -615,7 +679,11 @@ template <bool I4 = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, c
     bw.literal(qi, 7);
     for (int i = 0; i < 5; ++i) bw.literal(0, 1); // no quantiser deltas
     bw.literal(0, 1);                       // refresh_entropy_probs
-    for (int i = 0; i < 4 * 8 * 3 * 11; ++i) bw.put(0, kVp8CoefUpdateProb[i]);
+    for (int i = 0; i < 4 * 8 * 3 * 11; ++i) {
+        const bool update = AP && p.prob[i] != kVp8CoefProb[i];
+        bw.put(update, kVp8CoefUpdateProb[i]);
+        if (update) bw.literal(p.prob[i], 8);
+    }
     bw.literal(1, 1);                       // mb_no_coeff_skip
     bw.literal(ps, 8);
     for (uint32_t mb = 0; mb < mbs; ++mb) {

@@ -142,12 +142,22 @@ typedef enum flgpu_front_end {
                               level 0, default probabilities, quantiser from quality; the alpha plane uncompressed.  A valid file
                               that decodes to exactly the coder's reconstruction; its bytes are not libwebp's.  out_w, out_h
                               <= 16383 and at most about 21 000 macroblocks (see max_out_bytes); dst->bytes long */
-    FLGPU_FE_WEBP_LOSSY_I4 = 10 /* FLGPU_FE_WEBP_LOSSY where a macroblock's luma may also be B_PRED: sixteen 4x4 sub-blocks, each with
+    FLGPU_FE_WEBP_LOSSY_I4 = 10, /* FLGPU_FE_WEBP_LOSSY where a macroblock's luma may also be B_PRED: sixteen 4x4 sub-blocks, each with
                               the one of the ten sub-block predictors that has the least SSE, tried against the macroblock's I16
                               coding and taken when its prediction error plus a penalty from the quantiser is the smaller.
                               Same planes in, same containers, same kind of result; smaller files at equal quality, a slower
                               analysis.  out_w, out_h <= 16383 and at most 5111 macroblocks (the first partition's 19-bit size
                               must hold sixteen sub-block modes per macroblock); dst->bytes long */
+    /* 11 is not a front end */
+    FLGPU_FE_WEBP_LOSSY_AP = 12, /* FLGPU_FE_WEBP_LOSSY with per-picture coefficient probabilities: the same macroblocks, modes and
+                              levels -- the same reconstruction --, but the picture's token-tree branches are counted, a
+                              probability is derived per tree node, and the frame header updates the nodes where that pays for
+                              its flag and 8 bits; the tokens are coded with the picture's table.  Smaller files, never more
+                              than a byte per partition larger; one more kernel launch.  Limits of FLGPU_FE_WEBP_LOSSY;
+                              dst->bytes long */
+    FLGPU_FE_WEBP_LOSSY_I4_AP = 13 /* FLGPU_FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities, as above.  out_w, out_h <=
+                              16383 and at most 5039 macroblocks (the first partition must also hold 1056 updates); dst->bytes
+                              long */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
@@ -171,6 +181,10 @@ typedef enum flgpu_front_end {
 /* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies come from FLGPU_FE_WEBP_LOSSY_I4
  * where the output fits that front end's limits (FLGPU_FE_WEBP_LOSSY otherwise).  Alone it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_I4 0x1000u
+/* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies are coded with per-picture
+ * coefficient probabilities: FLGPU_FE_WEBP_LOSSY_AP, or with FLGPU_ENCODE_WEBP_LOSSY_I4 as well FLGPU_FE_WEBP_LOSSY_I4_AP where the
+ * output fits that front end's limits (FLGPU_FE_WEBP_LOSSY_AP otherwise).  Alone, or with only _I4, it does nothing. */
+#define FLGPU_ENCODE_WEBP_LOSSY_PROBS 0x2000u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -232,6 +246,9 @@ typedef struct flgpu_plan {
                                           Pictures for which a partition's worst case could overflow its size field (19 bits
                                           for the first, 24 for a token partition) are not taken: FLGPU_ERR_UNSUPPORTED from
                                           flgpu_plan_output, the planes from flgpu_process_*.
+                                          FLGPU_FE_WEBP_LOSSY_I4: the same with 117 mode booleans per macroblock instead of 7.
+                                          FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP: the worst case of the front end each
+                                          stands beside plus 7392 bytes, 1056 updates of 8 booleans: 9574 where 1126 stands above.
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 
@@ -594,7 +611,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS
@@ -650,7 +667,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "vp8_sources", "vp8_file_bytes", "vp8_upload_bytes" the same for FLGPU_IMG_VP8_SOURCE pictures (per picture a 128-byte header, 48
  * bytes per macroblock, the levels up to each block's last non-zero one, the raw ALPH plane or a compressed one's lossless blob), with flgpu_config.profile "vp8_decode_ns" =
  * the HIP-event time of their decode kernels;
- * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4);
+ * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files

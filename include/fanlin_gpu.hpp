@@ -90,6 +90,9 @@ public:
     void encode_webp_lossy() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY; }
     // ... and from FLGPU_FE_WEBP_LOSSY_I4 (macroblocks may be B_PRED: smaller files, a slower analysis) where the output fits it
     void encode_webp_lossy_i4() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_I4; }
+    // ... with per-picture coefficient probabilities (FLGPU_FE_WEBP_LOSSY_AP, or FLGPU_FE_WEBP_LOSSY_I4_AP after encode_webp_lossy_i4():
+    // the same pictures in fewer bytes)
+    void encode_webp_lossy_probs() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_PROBS; }
     uint32_t flags() const { return flags_; }
 
 private:

@@ -1,9 +1,9 @@
-"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY and, with --i4, FLGPU_FE_WEBP_LOSSY_I4 beside it): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
+"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY and, with --i4 / --probs, FLGPU_FE_WEBP_LOSSY_I4 / the adaptive-probability front ends beside it): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
 planes from the device plus libwebp's WebPEncode per picture on the host's threads --, file sizes and Y-PSNR of both on the same
 planes, and the bytes that cross PCIe.  Prints plain text; under `rocprofv3 --kernel-trace --stats` (a run of its own, with
 --timing-only) the kernel statistics attribute device time to the four vp8_* kernels, the planes kernel and the resample kernel.
 
-    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--events]
+    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--probs] [--events]
 """
 import argparse
 import math
@@ -24,7 +24,7 @@ def _psnr(a, b):
     return 99.0 if mse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse)
 
 
-def quality(fl, st, i4=False):
+def quality(fl, st, i4=False, probs=False):
     import synth
     import vp8_lib
     import webp_lib
@@ -43,9 +43,15 @@ def quality(fl, st, i4=False):
             print(f"quality {q}: I4 file has {info['bpred_macroblocks']} B_PRED macroblocks of {13 * 19}, sub-block modes seen {info['bmodes_mask']:#05x}")
             print(f"quality {q}: I4 file {len(dev4)} bytes, Y-PSNR {_psnr(vp8_lib.decode_yuv(dev4)[0], pl.y):.2f} dB | {len(dev4) / len(dev):.3f} of the I16-only "
                   f"file, size ratio to libwebp {len(dev4) / len(ref):.3f}")
+        if probs:
+            for name, fe, old in [("FE_WEBP_LOSSY_AP", fl.FE_WEBP_LOSSY_AP, dev)] + ([("FE_WEBP_LOSSY_I4_AP", fl.FE_WEBP_LOSSY_I4_AP, dev4)] if i4 else []):
+                new = st.process_pixels(big, fl.make_params(300, 200, quality=q, front_end=fe))
+                same = all(np.array_equal(a, b) for a, b in zip(vp8_lib.decode_yuv(new), vp8_lib.decode_yuv(old)))
+                print(f"quality {q}: {name} file {len(new)} bytes | {len(new) / len(old):.3f} of the non-adaptive file ({len(old)}), size ratio to libwebp "
+                      f"{len(new) / len(ref):.3f}, decodes to the non-adaptive file's planes: {same}")
 
 
-def timing(fl, st, batch, iters, host_threads, i4=False, events=False):
+def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=False):
     import torch
     import synth
     import webp_lib
@@ -56,6 +62,8 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False):
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
     kinds = [("FE_WEBP420", fl.FE_WEBP420), ("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY)] + ([("FE_WEBP_LOSSY_I4", fl.FE_WEBP_LOSSY_I4)] if i4 else [])
+    if probs:
+        kinds += [("FE_WEBP_LOSSY_AP", fl.FE_WEBP_LOSSY_AP)] + ([("FE_WEBP_LOSSY_I4_AP", fl.FE_WEBP_LOSSY_I4_AP)] if i4 else [])
     for name, fe in kinds:
         p = fl.make_params(300, 200, quality=75, front_end=fe)
         ns0 = (st.stats(), st.debug_get("webp_lossy_ns"))[1] if events else 0
@@ -99,6 +107,12 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False):
         dt_4, nb_4 = out["FE_WEBP_LOSSY_I4"]
         print(f"I4 encode adds {(dt_4 - dt_p) * 1e3:.2f} ms per batch to the planes path: {batch / dt_4:.0f} images/s, mean file {np.mean(nb_4):.0f} bytes "
               f"({np.mean(nb_4) / np.mean(nb_l):.3f} of the I16-only file)")
+    for name in ("FE_WEBP_LOSSY_AP", "FE_WEBP_LOSSY_I4_AP"):
+        if name in out:
+            dt_a, nb_a = out[name]
+            dt_o, nb_o = out[name[:-3]]
+            print(f"{name}: {(dt_a - dt_o) * 1e3:+.2f} ms per batch against {name[:-3]}: {batch / dt_a:.0f} images/s, mean file {np.mean(nb_a):.0f} bytes "
+                  f"({np.mean(nb_a) / np.mean(nb_o):.3f} of the non-adaptive file)")
     print(f"PCIe per picture: up {1080 * 1920 * 3} bytes of source either way; down {int(np.mean(nb_p))} bytes of planes before, {np.mean(nb_l):.0f} bytes of file now "
           f"({np.mean(nb_l) / np.mean(nb_p):.3f} x)")
 
@@ -111,13 +125,14 @@ def main():
     ap.add_argument("--timing-only", action="store_true")
     ap.add_argument("--events", action="store_true", help="a profiling context: also report webp_lossy_ns per batch")
     ap.add_argument("--i4", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_I4")
+    ap.add_argument("--probs", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_AP (and, with --i4, FLGPU_FE_WEBP_LOSSY_I4_AP)")
     a = ap.parse_args()
     import __graft_entry__ as g
     fl = g._load_package()
     with fl.State(device=0, profile=a.events) as st:
         if not a.timing_only:
-            quality(fl, st, a.i4)
-        timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events)
+            quality(fl, st, a.i4, a.probs)
+        timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events, a.probs)
 
 
 if __name__ == "__main__":
