@@ -33,11 +33,16 @@ FE_WEBP_LOSSY = 9  # (7 and 8 are not front ends)
 FE_WEBP_LOSSY_I4 = 10  # FE_WEBP_LOSSY whose macroblocks may be B_PRED (sixteen 4x4 sub-block predictors)
 FE_WEBP_LOSSY_AP = 12  # FE_WEBP_LOSSY with per-picture coefficient probabilities (11 is not a front end)
 FE_WEBP_LOSSY_I4_AP = 13  # FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities
+# the loop-filtered twin of each of the four: the frame header's loop filter level is picked on the device (14 and 15 are not front ends)
+FE_WEBP_LOSSY_LF, FE_WEBP_LOSSY_I4_LF, FE_WEBP_LOSSY_AP_LF, FE_WEBP_LOSSY_I4_AP_LF = 16, 17, 18, 19
+VP8_LF_TWIN = {9: 16, 10: 17, 12: 18, 13: 19}  # front end -> its loop-filtered twin
+FE_WEBP_LOSSY_ALL = (9, 10, 12, 13, 16, 17, 18, 19)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q < 100) on the device (FE_WEBP_LOSSY)
 ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
+ENCODE_WEBP_LOSSY_FILTER = 0x4000  # accept_flags bit: with ENCODE_WEBP_LOSSY, the loop-filtered twin of whatever the other bits select; alone, or without it, nothing
 ENCODE_WEBP_LOSSY_PROBS = 0x2000  # accept_flags bit: with ENCODE_WEBP_LOSSY (and _I4), FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, nothing
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
 ENCODE_GIF = 0x400  # accept_flags bit: State.process_gif finishes the image/gif body on the device where every frame has at most 256 colours
@@ -157,7 +162,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
-    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob",
+    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
@@ -243,6 +248,9 @@ def load_library() -> C.CDLL:
         lib.flgpu_decode_webp_lossy.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image)]
         lib.flgpu_debug_vp8_blob.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.flgpu_debug_vp8_planes.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_debug_vp8_filter_costs"):  # (the lossy WebP encoder's loop-filtered variants)
+        lib.flgpu_debug_vp8_filter_costs.argtypes = [C.c_void_p, C.POINTER(flgpu_image), C.POINTER(flgpu_params), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                     C.POINTER(C.c_uint32)]
     if hasattr(lib, "flgpu_gif_info_of"):  # (the same for GIF files)
         lib.flgpu_gif_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_gif_info)]
         lib.flgpu_decode_gif.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image), C.POINTER(C.c_uint32)]
@@ -650,12 +658,14 @@ def result_front_end(kind: int, quality: int = 100, accept_flags: int = 0, w: in
     """The front end behind a result kind.  RESULT_WEBP_STREAM is the lossless coder's at (clamped) quality 100 and the lossy
     coder's below it: FE_WEBP_LOSSY_I4 where accept_flags has ENCODE_WEBP_LOSSY_I4 and the w x h output is within its limits; with
     ENCODE_WEBP_LOSSY_PROBS the adaptive-probability variant of either (FE_WEBP_LOSSY_AP where the output is over FE_WEBP_LOSSY_I4_AP's
-    limits)."""
+    limits); with ENCODE_WEBP_LOSSY_FILTER the loop-filtered twin of that."""
     if kind == RESULT_WEBP_STREAM and min(max(int(quality), 1), 100) < 100:
         mbs = ((w + 15) // 16) * ((h + 15) // 16)
         if accept_flags & ENCODE_WEBP_LOSSY_PROBS:
-            return FE_WEBP_LOSSY_I4_AP if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_AP_MAX_MBS else FE_WEBP_LOSSY_AP
-        return FE_WEBP_LOSSY_I4 if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_MAX_MBS else FE_WEBP_LOSSY
+            fe = FE_WEBP_LOSSY_I4_AP if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_AP_MAX_MBS else FE_WEBP_LOSSY_AP
+        else:
+            fe = FE_WEBP_LOSSY_I4 if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_MAX_MBS else FE_WEBP_LOSSY
+        return VP8_LF_TWIN[fe] if accept_flags & ENCODE_WEBP_LOSSY_FILTER else fe
     return _RESULT_FE[kind]
 
 
@@ -693,7 +703,7 @@ def vp8_i4_ap_max_out_bytes(w: int, h: int) -> int:
 def _split_output(buf: np.ndarray, plan: flgpu_plan, front_end: int, flags: int, nbytes: int = 0):
     if front_end == FE_NONE:
         return buf[: plan.pixel_bytes].reshape(plan.out_h, plan.out_w, plan.out_c)
-    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS, FE_WEBP_LOSSY, FE_WEBP_LOSSY_I4, FE_WEBP_LOSSY_AP, FE_WEBP_LOSSY_I4_AP):
+    if front_end in (FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS) + FE_WEBP_LOSSY_ALL:
         return buf[:nbytes].tobytes()
     ny = plan.plane_w * plan.plane_h
     nc = plan.chroma_w * plan.chroma_h
@@ -937,6 +947,16 @@ class State:
         u = out[mbw * mbh * 256:mbw * mbh * 320].reshape(mbh * 8, mbw * 8)
         v = out[mbw * mbh * 320:].reshape(mbh * 8, mbw * 8)
         return y[:h, :w].copy(), u[:(h + 1) // 2, :(w + 1) // 2].copy(), v[:(h + 1) // 2, :(w + 1) // 2].copy()
+
+    def debug_vp8_filter_costs(self, image: np.ndarray, params: flgpu_params) -> dict:
+        """flgpu_debug_vp8_filter_costs: one picture through a loop-filtered lossy WebP front end's ordinary launches -> dict(levels =
+        the four candidate levels, D = their squared-error words as the device left them, chosen = the level in the frame header).
+        debug_set("vp8_filter_base", v) forces the base level the candidates are made from (-1: from the quantiser)."""
+        img = _as_image_array(image)
+        src = flgpu_image(img.ctypes.data, img.nbytes, img.shape[1], img.shape[0], img.shape[2], 0)
+        levels, costs, chosen = (C.c_uint32 * 4)(), (C.c_uint64 * 4)(), C.c_uint32()
+        _check(self._lib.flgpu_debug_vp8_filter_costs(self._ctx, C.byref(src), C.byref(params), levels, costs, C.byref(chosen)), self._ctx)
+        return dict(levels=list(levels), D=list(costs), chosen=int(chosen.value))
 
     # -- GIF files: decode, compositing and the per-frame pipeline (handler.rs:311-353) -------------------------------
     def decode_gif(self, data: bytes) -> np.ndarray:

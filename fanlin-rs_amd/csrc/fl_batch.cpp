@@ -85,7 +85,7 @@ struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
 struct ScratchSizes {
     size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
     size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
-    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0;
+    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0, vp8_lf = 0;
     uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
 };
 
@@ -111,7 +111,7 @@ struct Batch {
     std::vector<PngJob> pjobs;
     std::vector<WebpJob> wjobs;
     std::vector<Vp8Job> vjobs;
-    uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
+    uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
     std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
     uint32_t jpeg_max_blocks = 0;
     size_t mid_floats_max = 0;
@@ -423,10 +423,12 @@ int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
 }
 
 // Lossy WebP: the front end's planes, the reconstruction (whole macroblocks), 400 levels and one record per macroblock, the sizes;
-// the I4 variants' pictures also two words of sub-block modes per macroblock, the adaptive-probability variants' a table.
-bool vp8_fe_i4(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_I4_AP; }
-bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP; }
-bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe); }
+// the I4 variants' pictures also two words of sub-block modes per macroblock, the adaptive-probability variants' a table, the
+// loop-filtered variants' four cost words and three working copies of the reconstruction.
+bool vp8_fe_lf(uint32_t fe) { return fe >= FLGPU_FE_WEBP_LOSSY_LF && fe <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
+bool vp8_fe_i4(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
+bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_AP_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
+bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe) || vp8_fe_lf(fe); }
 int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
 {
     const bool i4 = vp8_fe_i4(fe), ap = vp8_fe_ap(fe);
@@ -435,6 +437,7 @@ int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
     const uint64_t mbs = (uint64_t)vp8_mbs(pl.out_w) * vp8_mbs(pl.out_h);
     if (i4) s.vp8_i4_mbs += mbs;
     if (ap) s.vp8_ap_pics++;
+    if (vp8_fe_lf(fe)) s.vp8_lf += vp8_lf_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h));
     s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
     s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
     s.vp8_mbs += mbs;
@@ -522,6 +525,7 @@ int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
     FL_HIP(c, c->d_vp8_info.reserve(sz.vp8_mbs * sizeof(uint32_t)), "lossy WebP macroblock records");
     FL_HIP(c, c->d_vp8_bm.reserve(sz.vp8_i4_mbs * 2u * sizeof(uint32_t)), "lossy WebP sub-block mode records");
     FL_HIP(c, c->d_vp8_tab.reserve((size_t)sz.vp8_ap_pics * kVp8TabBytes), "lossy WebP probability tables");
+    FL_HIP(c, c->d_vp8_lf.reserve(sz.vp8_lf), "lossy WebP loop filter scratch");
     FL_HIP(c, c->d_vp8_sizes.reserve((size_t)sz.vp8_pics * kVp8SizeWords * sizeof(uint32_t)), "lossy WebP partition sizes");
     FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
     FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
@@ -916,6 +920,8 @@ int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, uint32_t fe)
     j.bm = i4 ? static_cast<uint32_t *>(c->d_vp8_bm.p) + at.vp8_i4_mbs * 2u : nullptr;
     j.tab = vp8_fe_ap(fe) ? static_cast<uint8_t *>(c->d_vp8_tab.p) + (size_t)at.vp8_ap_pics * kVp8TabBytes : nullptr;
     j.sizes = static_cast<uint32_t *>(c->d_vp8_sizes.p) + (size_t)at.vp8_pics * kVp8SizeWords;
+    j.lf = vp8_fe_lf(fe) ? static_cast<uint8_t *>(c->d_vp8_lf.p) + at.vp8_lf : nullptr;
+    j.lf_base = (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, B.dbg.get(DBG_VP8_FILTER_BASE)));
     const uint32_t q = B.work[i].p->quality;
     j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
     return vp8_scratch(pl, at, fe);
@@ -990,10 +996,12 @@ int build_launches(flgpu_ctx *c, Batch &B)
     // workgroup bound their waits and report an expired one here instead of delivering pixels that were never synchronised
     B.has_results = !fe_groups.empty();
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
-    ScratchSizes vp8_at; // (the lossy WebP front ends are up to four groups that share the lossy WebP scratch, in the families' order)
+    ScratchSizes vp8_at; // (the lossy WebP front ends are up to eight groups that share the lossy WebP scratch, in the families' order)
     static_assert(FLGPU_FE_WEBP_LOSSY < FLGPU_FE_WEBP_LOSSY_I4 && FLGPU_FE_WEBP_LOSSY_I4 < FLGPU_FE_WEBP_LOSSY_AP && FLGPU_FE_WEBP_LOSSY_AP < FLGPU_FE_WEBP_LOSSY_I4_AP,
                   "launch_vp8_encode takes one range of jobs per family, in this order");
     static_assert(vp8_family(FLGPU_FE_WEBP_LOSSY) == 0 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4) == 1 && vp8_family(FLGPU_FE_WEBP_LOSSY_AP) == 2 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP) == 3, "vp8_family");
+    static_assert(FLGPU_FE_WEBP_LOSSY_I4_AP < FLGPU_FE_WEBP_LOSSY_LF && vp8_family(FLGPU_FE_WEBP_LOSSY_LF) == 4 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_LF) == 5 &&
+                  vp8_family(FLGPU_FE_WEBP_LOSSY_AP_LF) == 6 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP_LF) == 7, "the loop-filtered twins follow in the same order");
     for (auto &g : fe_groups) {
         ScratchSizes at;
         const size_t vjob0 = B.vjobs.size();
@@ -1375,6 +1383,26 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
 } // namespace fl
 
 // ---- diagnostics -----------------------------------------------------------------------------------------------------------------
+// One picture through the ordinary launch sequence of a loop-filtered lossy WebP front end; then the cost words its filter launch
+// left (the picture is the batch's only one, so its scratch is the start of d_vp8_lf) and what every consumer derives from them.
+extern "C" int flgpu_debug_vp8_filter_costs(flgpu_ctx *c, const flgpu_image *src, const flgpu_params *p, uint32_t *levels, uint64_t *costs, uint32_t *chosen)
+try {
+    if (!c || !src || !p || !levels || !costs || !chosen || !c->dbg || !vp8_fe_lf(p->front_end) || !c->shard_ctx.empty()) return FLGPU_ERR_INVALID_ARG;
+    flgpu_plan plan;
+    if (int rc = flgpu_plan_output(p, src->width, src->height, src->channels, &plan)) return rc;
+    std::vector<uint8_t> file(plan.max_out_bytes);
+    flgpu_image dst{};
+    dst.data = file.data(); dst.capacity = file.size();
+    std::lock_guard<std::mutex> g(c->mu);
+    if (int rc = run_batch_host(c, 1, src, p, &dst)) return rc;
+    FL_HIP(c, hipMemcpy(costs, c->d_vp8_lf.p, kVp8LfCandidates * sizeof(uint64_t), hipMemcpyDeviceToHost), "lossy WebP filter costs D2H");
+    const uint32_t q = p->quality;
+    const uint32_t base = vp8_lf_base_of(vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q), (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, c->dbg->get(DBG_VP8_FILTER_BASE))));
+    for (uint32_t k = 0; k < kVp8LfCandidates; ++k) levels[k] = vp8_lf_candidate(base, k);
+    *chosen = vp8_lf_choice(base, costs);
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
 extern "C" int flgpu_debug_assign_items(uint32_t pictures, uint32_t strips, uint32_t tiles, uint32_t workgroups, uint32_t capacity, uint32_t *job_of, uint32_t *strip_of,
                                         uint32_t *tile0_of, uint32_t *tile1_of, uint32_t *lists, uint32_t *nitems)
 {

@@ -367,7 +367,7 @@ void resolve_pending(flgpu_ctx *c)
 
 const char *const kDebugKeyNames[DBG_COUNT] = {
     "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first", "mfma_arith", "force_bands", "no_tile", "no_place4",
-    "host_huffman", "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh",
+    "host_huffman", "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base",
 };
 
 DebugSwitches::DebugSwitches()
@@ -375,6 +375,7 @@ DebugSwitches::DebugSwitches()
     for (auto &x : v) x.store(0, std::memory_order_relaxed);
     v[DBG_DEVICE_HUFFMAN_MIN_BYTES].store(16384, std::memory_order_relaxed); // small files are decoded faster by the thread that holds them than by six kernel launches
     v[DBG_MFMA_SPIN_LIMIT].store((int64_t)kMfmaDefaultSpinLimit, std::memory_order_relaxed);
+    v[DBG_VP8_FILTER_BASE].store(-1, std::memory_order_relaxed);
     for (uint32_t k = 0; k < DBG_COUNT; ++k) initial[k] = v[k].load(std::memory_order_relaxed);
 }
 
@@ -516,7 +517,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_mid.release(); c->d_tmp_a.release(); c->d_tmp_b.release(); c->d_tmp_o.release(); c->d_tmp_al.release(); c->d_in.release(); c->d_out.release();
     c->d_jpeg_coef.release(); c->d_jpeg_off.release(); c->d_jpeg_raw.release();
     c->d_png_filt.release(); c->d_png_chunks.release(); c->d_png_syms.release(); c->d_png_recs.release();
-    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release(); c->d_vp8_bm.release(); c->d_vp8_tab.release();
+    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release(); c->d_vp8_bm.release(); c->d_vp8_tab.release(); c->d_vp8_lf.release();
     c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();

@@ -161,6 +161,7 @@ enum DebugKey : uint32_t {
     DBG_MFMA_SPIN_LIMIT,          // bound of the matrix-pipe kernel's LDS-counter waits (default kMfmaDefaultSpinLimit; 0 = every wait expires)
     DBG_DEBUG_MFMA,               // print every matrix-pipe plan
     DBG_DEBUG_JH,                 // print why a staged file went back to the host decoder
+    DBG_VP8_FILTER_BASE,          // the lossy WebP encoder's loop-filtered variants: -1 (default) = the base level from the quantiser, 0..63 = forced
     DBG_COUNT
 };
 struct DebugSwitches {
@@ -238,7 +239,7 @@ struct flgpu_ctx {
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): unit records, bit offsets, AC bits past a record
     fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
-    fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes, d_vp8_bm, d_vp8_tab; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables
+    fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes, d_vp8_bm, d_vp8_tab, d_vp8_lf; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables, the loop-filtered variants' cost words and working copies
     fl::DeviceBuf d_webpll_res, d_webpll_tok, d_webpll_tiles, d_webpll_pic, d_webpll_stream; // lossless WebP scratch (fl_webpll.hip): residuals, tokens, tile records, per-picture words, bit streams
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front
@@ -365,7 +366,8 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
 int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
 // front ends whose output is an encoded stream: its length is a result word, known once the batch has run
-inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS || fe == FLGPU_FE_WEBP_LOSSY || fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP; }
+inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS || fe == FLGPU_FE_WEBP_LOSSY || fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP ||
+           (fe >= FLGPU_FE_WEBP_LOSSY_LF && fe <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF); }
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------
 // contiguous split of n weighted items into n_shards shards of about equal weight: shard_of[i] is non-decreasing

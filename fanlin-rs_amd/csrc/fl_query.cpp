@@ -275,13 +275,17 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
             p->front_end = want_i4 && fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4_AP : FLGPU_FE_WEBP_LOSSY_AP;
         else
             p->front_end = want_i4 && fl::vp8_i4_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4 : FLGPU_FE_WEBP_LOSSY;
+        // _FILTER: the loop-filtered twin of whichever front end the other bits selected (the same limits)
+        if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_FILTER)
+            p->front_end = p->front_end == FLGPU_FE_WEBP_LOSSY ? FLGPU_FE_WEBP_LOSSY_LF : p->front_end == FLGPU_FE_WEBP_LOSSY_I4 ? FLGPU_FE_WEBP_LOSSY_I4_LF
+                           : p->front_end == FLGPU_FE_WEBP_LOSSY_AP ? FLGPU_FE_WEBP_LOSSY_AP_LF : FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
     if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {
         p->front_end = FLGPU_FE_WEBP_LOSSLESS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
-    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY || p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY || p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || (p->front_end >= FLGPU_FE_WEBP_LOSSY_LF && p->front_end <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF)) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
     return rc;
 }
 
@@ -793,9 +797,9 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    /* front ends 0-4, 6, 9, 10, 12 and 13 (5, 7, 8 and 11 are not) */
+    /* front ends 0-4, 6, 9, 10, 12, 13 and 16-19 (5, 7, 8, 11, 14 and 15 are not) */
     if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && p->front_end != FLGPU_FE_WEBP_LOSSY && p->front_end != FLGPU_FE_WEBP_LOSSY_I4 &&
-         p->front_end != FLGPU_FE_WEBP_LOSSY_AP && p->front_end != FLGPU_FE_WEBP_LOSSY_I4_AP) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
+         p->front_end != FLGPU_FE_WEBP_LOSSY_AP && p->front_end != FLGPU_FE_WEBP_LOSSY_I4_AP && !(p->front_end >= FLGPU_FE_WEBP_LOSSY_LF && p->front_end <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF)) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
         return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
@@ -884,13 +888,17 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     case FLGPU_FE_WEBP_LOSSY:
     case FLGPU_FE_WEBP_LOSSY_I4:
     case FLGPU_FE_WEBP_LOSSY_AP:
-    case FLGPU_FE_WEBP_LOSSY_I4_AP: {
+    case FLGPU_FE_WEBP_LOSSY_I4_AP:
+    case FLGPU_FE_WEBP_LOSSY_LF:
+    case FLGPU_FE_WEBP_LOSSY_I4_LF:
+    case FLGPU_FE_WEBP_LOSSY_AP_LF:
+    case FLGPU_FE_WEBP_LOSSY_I4_AP_LF: {
         // the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the planes' bytes.
         // max_out_bytes: the worst case of this coder's files (fl_vp8_core.h), so a dst of this capacity is never too small.
         // (the I4 variants' partition 0 is larger per macroblock, the adaptive-probability variants' by its 1056 literals: fewer
-        // macroblocks, a larger worst case)
-        const bool i4 = p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP;
-        const bool ap = p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP;
+        // macroblocks, a larger worst case; the loop-filtered variants have their twins' limits and worst case: the bound is per boolean)
+        const bool i4 = p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_LF || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
+        const bool ap = p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_AP_LF || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
         const bool fits = ap ? (i4 ? fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) : fl::vp8_ap_fits(plan->out_w, plan->out_h))
                              : (i4 ? fl::vp8_i4_fits(plan->out_w, plan->out_h) : fl::vp8_fits(plan->out_w, plan->out_h));
         if (!fits) return FLGPU_ERR_UNSUPPORTED;

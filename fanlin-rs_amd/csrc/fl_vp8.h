@@ -1,10 +1,11 @@
-// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY, _I4, _AP and _I4_AP): job descriptor, scratch sizes and the launch.
+// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP and their loop-filtered twins): job descriptor, scratch sizes and the launch.
 // The format's limits and worst case, and everything the kernels compute, are in fl_vp8_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fl_vp8_core.h"
+#include "fl_vp8_lf_core.h"
 
 namespace fl {
 
@@ -24,21 +25,27 @@ struct alignas(16) Vp8Job {
     uint32_t w, h, c;
     uint32_t dst_cap;     // bytes available at dst
     uint32_t qi;          // quantiser index (vp8_quality_index of the clamped quality)
-    uint32_t pad[1];
+    int32_t lf_base;      // the loop-filtered variants: -1 = the base level from qi, 0..63 = forced (flgpu_debug_set "vp8_filter_base")
     uint8_t *tab;         // scratch, the adaptive-probability variants only (else nullptr): the picture's table, kVp8TabBytes
+    uint8_t *lf;          // scratch, the loop-filtered variants only (else nullptr): four 64-bit cost words (kVp8LfCostBytes), then
+                          // three working copies of the reconstruction, vp8_rec_bytes rounded up to 256 each
+    uint64_t pad;
 };
-static_assert(sizeof(Vp8Job) == 96, "the job record keeps its size");
+static_assert(sizeof(Vp8Job) == 112, "the job record: 96 bytes before the loop-filtered variants, their scratch pointer and padding to 16");
 
 inline uint64_t vp8_planes_bytes(uint64_t w, uint64_t h) { return 2u * w * h + 2u * ((w + 1u) / 2u) * ((h + 1u) / 2u); }
 
 constexpr uint32_t kVp8TabBytes = 4 * 8 * 3 * 11; // the coefficient probability table of one picture
-// The families of a launch in the order of their front ends, which is the order of their jobs: FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP.
-constexpr uint32_t kVp8Families = 4;
-constexpr uint32_t vp8_family(uint32_t front_end) { return front_end == 9u ? 0u : front_end == 10u ? 1u : front_end == 12u ? 2u : 3u; }
+// The families of a launch in the order of their front ends, which is the order of their jobs: FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP,
+// then the loop-filtered twin of each in the same order (family f + 4: front end 16 + f).
+constexpr uint32_t kVp8Families = 8;
+constexpr uint32_t vp8_family(uint32_t front_end) { return front_end >= 16u ? 4u + (front_end - 16u) : front_end == 9u ? 0u : front_end == 10u ? 1u : front_end == 12u ? 2u : 3u; }
+// scratch of one loop-filtered picture behind Vp8Job::lf
+inline uint64_t vp8_lf_bytes(uint32_t mbw, uint32_t mbh) { return kVp8LfCostBytes + (kVp8LfCandidates - 1u) * ((vp8_rec_bytes(mbw, mbh) + 255u) & ~(uint64_t)255u); }
 
 // predict / transform / quantise / reconstruct -> (the adaptive variants: token statistics and the picture's table ->) partition
-// sizes -> framing and alpha plane -> partitions; four or five stream-ordered launches per family that has pictures: n[f] jobs of
-// family f, one range after the other
+// (the loop-filtered variants: candidate levels filtered and measured ->) sizes -> framing and alpha plane -> partitions; four to
+// six stream-ordered launches per family that has pictures: n[f] jobs of family f, one range after the other
 hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st);
 
 } // namespace fl

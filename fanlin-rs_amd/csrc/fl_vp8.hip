@@ -29,7 +29,18 @@
 //                       applies the rule to entry i and stores the picture's table (1056 B of scratch).
 //   vp8_size_kernel<I4, true>, vp8_write_kernel<I4, true>  the coders, staging the picture's table instead of the default one (a
 //                       coder workgroup is exactly one picture) and writing the updates into partition 0.
-// A batch's pictures are grouped by front end in the job list, so each of the four families is one range of it.
+// The loop-filtered variants (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF; fl_vp8_lf_core.h) share all of the above and add one
+// launch in front of the first that codes partition 0 (the stats kernel where there is one, else the size kernel): the level's six
+// bits move the boolean coder's state, so the sizes depend on it.
+//   vp8_lf_kernel<I4>   one workgroup per (picture, candidate level).  Candidate 0 measures the reconstruction as it is.  The others
+//                       copy it to a working copy of their own in scratch (the filter cascades in place; `rec` stays unfiltered for
+//                       the coder's contexts) and run the decode front end's filter on it in vp8dec_filter_kernel's schedule:
+//                       anti-diagonals d = x + 2 y, eight macroblocks of 32 lines a round, eight barrier-separated steps a
+//                       macroblock -- which equals raster order.  Then all 256 threads sum the squared error over the visible
+//                       samples in 64 bits and one thread stores the candidate's word.
+//   vp8_size_kernel<I4, AP, true>, vp8_write_kernel<I4, AP, true>  the coders; the partition-0 lane derives the level from the
+//                       picture's four words (vp8_lf_choice) and writes it into the frame header.
+// A batch's pictures are grouped by front end in the job list, so each of the eight families is one range of it.
 // No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
 // A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
 #include <hip/hip_runtime.h>
@@ -38,6 +49,7 @@
 #include "fl_vp8.h"
 #include "fl_vp8_ap_core.h"
 #include "fl_vp8_i4_core.h"
+#include "fl_vp8_lf_core.h"
 #include "fl_wave.h"
 
 namespace fl {
@@ -51,6 +63,7 @@ constexpr uint32_t kLaneStride = 16;
 constexpr uint32_t kCoderThreads = 256;
 constexpr uint32_t kFrameThreads = 256;
 constexpr uint32_t kStatsThreads = 256;
+constexpr uint32_t kLfThreads = 256;
 // the adaptive coders stage one table per workgroup: a workgroup's slots must be exactly one picture's
 static_assert(kCoderThreads / kLaneStride == kLaneSlots && kCoderThreads % kLaneStride == 0, "a coder workgroup is one picture");
 
@@ -189,6 +202,73 @@ template <bool I4> __global__ __launch_bounds__(kStatsThreads) void vp8_stats_ke
     for (uint32_t i = threadIdx.x; i < kVp8CoefProbs; i += kStatsThreads) jb.tab[i] = vp8_ap_decide(i, s_cnt[i], s_cnt[kVp8CoefProbs + i]);
 }
 
+// the macroblock rows that have a macroblock on anti-diagonal d: y in [lo, lo + count), x = d - 2 y
+__device__ __forceinline__ uint32_t lf_diagonal(const Vp8Pic &p, uint32_t d, uint32_t &lo)
+{
+    lo = d >= p.mbw ? (d - p.mbw + 2u) >> 1 : 0u;
+    const uint32_t hi = min(p.mbh - 1u, d >> 1);
+    return hi >= lo ? hi - lo + 1u : 0u;
+}
+
+// the level the loop-filtered coders write: a function of the picture's base level and its four cost words
+__device__ __forceinline__ uint32_t lf_level_of(const Vp8Job &jb)
+{
+    const uint64_t *cost = reinterpret_cast<const uint64_t *>(jb.lf);
+    const uint64_t D[kVp8LfCandidates] = {cost[0], cost[1], cost[2], cost[3]};
+    return vp8_lf_choice(vp8_lf_base_of(jb.qi, jb.lf_base), D);
+}
+
+// One candidate level of one picture: filter a copy of the reconstruction as a decoder will, measure it against the source.
+// Every barrier is in control flow uniform over the workgroup; no workgroup waits on another.
+template <bool I4> __global__ __launch_bounds__(kLfThreads) void vp8_lf_kernel(const Vp8Job *__restrict__ jobs)
+{
+    __shared__ uint64_t s_sum[kLfThreads / 64u];
+    const Vp8Job &jb = jobs[blockIdx.x / kVp8LfCandidates];
+    const uint32_t cand = blockIdx.x % kVp8LfCandidates;
+    const Vp8Pic p = pic_of(jb);
+    const uint32_t base = vp8_lf_base_of(jb.qi, jb.lf_base);
+    uint64_t *cost = reinterpret_cast<uint64_t *>(jb.lf);
+    if (base == 0u) { if (threadIdx.x == 0u) cost[cand] = 0u; return; } // (uniform) nothing is evaluated
+    const uint8_t *pix = p.rec;
+    if (cand) { // (uniform)
+        const uint64_t bytes = vp8_rec_bytes(p.mbw, p.mbh), pitch = (bytes + 255u) & ~(uint64_t)255u;
+        uint8_t *copy = jb.lf + kVp8LfCostBytes + (cand - 1u) * pitch;
+        // (384 bytes a macroblock, both buffers 256-byte aligned: whole 16-byte words)
+        for (uint64_t i = threadIdx.x; i < bytes / 16u; i += kLfThreads) reinterpret_cast<uint4 *>(copy)[i] = reinterpret_cast<const uint4 *>(p.rec)[i];
+        __syncthreads();
+        const Vp8DecPic dp = vp8_lf_pic(p, copy);
+        Vp8MbRecord r = vp8_lf_record<false>(p, 0u, vp8_lf_candidate(base, cand)); // the limits; `inner` per macroblock below
+        const uint32_t slot = threadIdx.x / kVp8dFilterLanes, lane = threadIdx.x % kVp8dFilterLanes;
+        constexpr uint32_t kSlots = kLfThreads / kVp8dFilterLanes;
+        const uint32_t ndiag = p.mbw + 2u * (p.mbh - 1u);
+        for (uint32_t d = 0; d < ndiag; ++d) {
+            uint32_t lo;
+            const uint32_t count = lf_diagonal(p, d, lo);
+            for (uint32_t b0 = 0; b0 < count; b0 += kSlots) {
+                const bool active = b0 + slot < count;
+                const uint32_t mby = active ? lo + b0 + slot : 0u, mbx = active ? d - 2u * mby : 0u;
+                r.inner = vp8_lf_inner<I4>(p, (uint64_t)mby * p.mbw + mbx);
+                for (uint32_t s = 0; s < kVp8dFilterSteps; ++s) {
+                    if (active) vp8d_filter(dp, r, mbx, mby, s, lane);
+                    __syncthreads(); // the edges of a macroblock overlap, and the next diagonal reads what this one wrote
+                }
+            }
+        }
+        pix = copy;
+    }
+    uint64_t sum = 0;
+    const uint32_t items = vp8_lf_items(p);
+    for (uint32_t i = threadIdx.x; i < items; i += kLfThreads) sum += vp8_lf_sq_diff(p, pix, i);
+    sum = wave_sum<unsigned long long>(sum);
+    if ((threadIdx.x & 63u) == 0u) s_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint64_t t = 0;
+        for (uint32_t k = 0; k < kLfThreads / 64u; ++k) t += s_sum[k];
+        cost[cand] = t;
+    }
+}
+
 // The coders read a probability for every boolean: the table's 1056 bytes go to LDS first (all threads of the workgroup, before
 // any of them leaves).  AP: the table of the workgroup's picture.
 template <bool AP> __device__ __forceinline__ void stage_prob(uint8_t *s_prob, const Vp8Job *jobs)
@@ -199,13 +279,13 @@ template <bool AP> __device__ __forceinline__ void stage_prob(uint8_t *s_prob, c
 }
 
 // the partition of lane slot `part` (0 = the first partition), counted or written
-template <bool I4, bool AP> __device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t part, uint32_t nparts)
+template <bool I4, bool AP, bool LF> __device__ __forceinline__ void code_partition(Vp8Bool &bw, const Vp8Pic &p, const Vp8Job &jb, uint32_t part, uint32_t nparts)
 {
-    if (part == 0u) vp8_put_first_partition<I4, AP>(bw, p, qi, nparts);
+    if (part == 0u) vp8_put_first_partition<I4, AP, LF>(bw, p, jb.qi, nparts, LF ? lf_level_of(jb) : 0u);
     else vp8_put_token_partition<I4>(bw, p, part - 1u, nparts);
 }
 
-template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4, bool AP = false, bool LF = false> __global__ __launch_bounds__(kCoderThreads) void vp8_size_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
     if (AP && blockIdx.x >= njobs) return; // (never: the grid is one workgroup per picture)
@@ -218,7 +298,7 @@ template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) 
     if (part >= kVp8SizeWords) return;
     if (part > nparts) { jb.sizes[part] = 0u; return; }
     Vp8Bool bw;
-    code_partition<I4, AP>(bw, p, jb.qi, part, nparts);
+    code_partition<I4, AP, LF>(bw, p, jb, part, nparts);
     jb.sizes[part] = bw.pos;
 }
 
@@ -247,7 +327,7 @@ __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *
     }
 }
 
-template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
+template <bool I4, bool AP = false, bool LF = false> __global__ __launch_bounds__(kCoderThreads) void vp8_write_kernel(const Vp8Job *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint8_t s_prob[sizeof(kVp8CoefProb)];
     if (AP && blockIdx.x >= njobs) return; // (never: the grid is one workgroup per picture)
@@ -263,38 +343,50 @@ template <bool I4, bool AP = false> __global__ __launch_bounds__(kCoderThreads) 
     if (L.total > jb.dst_cap) return; // vp8_frame_kernel has reported it
     Vp8Bool bw;
     bw.buf = jb.dst + L.part[part];
-    code_partition<I4, AP>(bw, p, jb.qi, part, nparts);
+    code_partition<I4, AP, LF>(bw, p, jb, part, nparts);
 }
 
 } // namespace
 
-template <bool I4, bool AP> static hipError_t launch_family(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
+template <bool I4, bool AP, bool LF> static hipError_t launch_family(const Vp8Job *jobs, uint32_t njobs, hipStream_t st)
 {
     if (!njobs) return hipSuccess;
     const uint32_t coder_blocks = (uint32_t)(((uint64_t)njobs * kLaneSlots * kLaneStride + kCoderThreads - 1u) / kCoderThreads);
     if (I4) hipLaunchKernelGGL(vp8_analyse_i4_kernel, dim3(njobs), dim3(64), 0, st, jobs);
     else hipLaunchKernelGGL(vp8_analyse_kernel, dim3(njobs), dim3(64), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
+    if (LF) {
+        hipLaunchKernelGGL(vp8_lf_kernel<I4>, dim3(njobs * kVp8LfCandidates), dim3(kLfThreads), 0, st, jobs);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
     if (AP) {
         hipLaunchKernelGGL(vp8_stats_kernel<I4>, dim3(njobs), dim3(kStatsThreads), 0, st, jobs);
         if (hipError_t e = hipGetLastError()) return e;
     }
-    hipLaunchKernelGGL((vp8_size_kernel<I4, AP>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    hipLaunchKernelGGL((vp8_size_kernel<I4, AP, LF>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(vp8_frame_kernel, dim3(njobs), dim3(kFrameThreads), 0, st, jobs);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL((vp8_write_kernel<I4, AP>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
+    hipLaunchKernelGGL((vp8_write_kernel<I4, AP, LF>), dim3(coder_blocks), dim3(kCoderThreads), 0, st, jobs, njobs);
     return hipGetLastError();
 }
 
 hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st)
 {
-    if (hipError_t e = launch_family<false, false>(jobs, n[0], st)) return e;
+    if (hipError_t e = launch_family<false, false, false>(jobs, n[0], st)) return e;
     jobs += n[0];
-    if (hipError_t e = launch_family<true, false>(jobs, n[1], st)) return e;
+    if (hipError_t e = launch_family<true, false, false>(jobs, n[1], st)) return e;
     jobs += n[1];
-    if (hipError_t e = launch_family<false, true>(jobs, n[2], st)) return e;
-    return launch_family<true, true>(jobs + n[2], n[3], st);
+    if (hipError_t e = launch_family<false, true, false>(jobs, n[2], st)) return e;
+    jobs += n[2];
+    if (hipError_t e = launch_family<true, true, false>(jobs, n[3], st)) return e;
+    jobs += n[3];
+    if (hipError_t e = launch_family<false, false, true>(jobs, n[4], st)) return e;
+    jobs += n[4];
+    if (hipError_t e = launch_family<true, false, true>(jobs, n[5], st)) return e;
+    jobs += n[5];
+    if (hipError_t e = launch_family<false, true, true>(jobs, n[6], st)) return e;
+    return launch_family<true, true, true>(jobs + n[6], n[7], st);
 }
 
 } // namespace fl

@@ -31,6 +31,10 @@
 // token-tree branches are counted first, a coefficient probability table is derived from the counts, partition 0 carries the
 // updates (flag i is 1 and followed by the 8-bit probability where the picture's table differs from the default), and the token
 // partitions are coded with that table.  The reconstruction does not change.
+//
+// The loop-filtered variants (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF; fl_vp8_lf_core.h states the rule,
+// tests/vp8_lf_model.py restates it): the same again, but the frame header's loop filter level is the one of four candidates whose
+// filtered reconstruction is nearest to the source; what a decoder shows is that filtered picture.
 #pragma once
 #include <stdint.h>
 
@@ -167,6 +171,21 @@ FL_VP8_HD uint32_t vp8_i4_penalty(uint32_t y1_ac)
 {
     const uint64_t sq = (uint64_t)y1_ac * y1_ac, v = (sq * sq) >> kVp8I4PenaltyShift; // (steps are below 2^9: below 2^27)
     return v < 1u ? 1u : (uint32_t)v;
+}
+
+// ---- loop filter strength ---------------------------------------------------------------------------------------------------------
+// The format's limits of a macroblock from its filter level (1..63) and the frame's sharpness: o[0] = the edge limit of inner edges
+// (macroblock edges add 4), o[1] = the interior limit, o[2] = the high-edge-variance threshold of a key frame.  The decode front
+// end's host half and the encoder's loop-filtered variants share it.
+FL_VP8_HD void vp8_filter_strength(int level, int sharpness, uint8_t *o)
+{
+    int ilevel = level;
+    if (sharpness > 0) {
+        ilevel >>= sharpness > 4 ? 2 : 1;
+        if (ilevel > 9 - sharpness) ilevel = 9 - sharpness;
+    }
+    if (ilevel < 1) ilevel = 1;
+    o[0] = (uint8_t)(2 * level + ilevel); o[1] = (uint8_t)ilevel; o[2] = (uint8_t)(level >= 40 ? 2 : level >= 15 ? 1 : 0);
 }
 
 // ---- transforms -------------------------------------------------------------------------------------------------------------------
@@ -664,7 +683,8 @@ FL_VP8_HD uint32_t vp8_skip_prob(uint32_t mbs, uint32_t skipped)
 
 // partition 0: the frame header and every macroblock's skip flag and modes.  AP (the adaptive-probability variants): p.prob is the
 // picture's table, and entry i is updated exactly where it differs from the default one (the rule never picks an equal value)
-template <bool I4 = false, bool AP = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts)
+// LF (the loop-filtered variants, fl_vp8_lf_core.h): `level` is the loop filter level of the frame header; else it is 0
+template <bool I4 = false, bool AP = false, bool LF = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts, uint32_t level = 0u)
 {
     const uint32_t mbs = p.mbw * p.mbh;
     uint32_t skipped = 0;
@@ -673,7 +693,7 @@ template <bool I4 = false, bool AP = false> FL_VP8_HD void vp8_put_first_partiti
     bw.literal(0, 1);                       // colour space
     bw.literal(0, 1);                       // clamping is needed
     bw.literal(0, 1);                       // no segments
-    bw.literal(0, 1); bw.literal(0, 6); bw.literal(0, 3); // normal filter, level 0, sharpness 0
+    bw.literal(0, 1); bw.literal(LF ? level : 0u, 6); bw.literal(0, 3); // normal filter, its level, sharpness 0
     bw.literal(0, 1);                       // no filter deltas
     bw.literal(nparts == 8u ? 3u : nparts == 4u ? 2u : nparts == 2u ? 1u : 0u, 2);
     bw.literal(qi, 7);

@@ -168,13 +168,7 @@ void filter_strength(const Frame &F, int s, uint8_t *o)
     level = clampi(level, 0, 63);
     o[0] = o[1] = o[2] = 0;
     if (F.level == 0 || level == 0) return; // (a frame at level 0 is not filtered at all, whatever its segments say)
-    int ilevel = level;
-    if (F.sharpness > 0) {
-        ilevel >>= F.sharpness > 4 ? 2 : 1;
-        if (ilevel > 9 - F.sharpness) ilevel = 9 - F.sharpness;
-    }
-    if (ilevel < 1) ilevel = 1;
-    o[0] = (uint8_t)(2 * level + ilevel); o[1] = (uint8_t)ilevel; o[2] = (uint8_t)(level >= 40 ? 2 : level >= 15 ? 1 : 0);
+    vp8_filter_strength(level, F.sharpness, o);
 }
 
 // the tokens of one block into lev[0 .. 16) (coding order, zeroed by the caller); returns the position behind the last non-zero level

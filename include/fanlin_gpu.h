@@ -155,9 +155,21 @@ typedef enum flgpu_front_end {
                               its flag and 8 bits; the tokens are coded with the picture's table.  Smaller files, never more
                               than a byte per partition larger; one more kernel launch.  Limits of FLGPU_FE_WEBP_LOSSY;
                               dst->bytes long */
-    FLGPU_FE_WEBP_LOSSY_I4_AP = 13 /* FLGPU_FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities, as above.  out_w, out_h <=
+    FLGPU_FE_WEBP_LOSSY_I4_AP = 13, /* FLGPU_FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities, as above.  out_w, out_h <=
                               16383 and at most 5039 macroblocks (the first partition must also hold 1056 updates); dst->bytes
                               long */
+    /* 14 and 15 are not front ends */
+    FLGPU_FE_WEBP_LOSSY_LF = 16, /* FLGPU_FE_WEBP_LOSSY with a loop filter level picked on the device: the same macroblocks, modes,
+                              levels and containers, but the frame header's 6-bit level (normal filter, sharpness 0, no deltas) is
+                              the one of four candidates -- 0, ceil(L0 / 2), L0, min(63, L0 + ceil(L0 / 2)), L0 a base level from
+                              the quantiser -- whose filtered reconstruction has the least squared error against the source
+                              planes (ties: the lowest).  A decoder shows that filtered picture, never a worse one than
+                              FLGPU_FE_WEBP_LOSSY's by that measure.  One more kernel launch and three working copies of the
+                              reconstruction in scratch.  L0 = 0 (quality 97 and up): FLGPU_FE_WEBP_LOSSY's file byte for byte.
+                              Limits and max_out_bytes of FLGPU_FE_WEBP_LOSSY; dst->bytes long */
+    FLGPU_FE_WEBP_LOSSY_I4_LF = 17,    /* FLGPU_FE_WEBP_LOSSY_I4 with the loop filter level picked as above; its limits */
+    FLGPU_FE_WEBP_LOSSY_AP_LF = 18,    /* FLGPU_FE_WEBP_LOSSY_AP with the loop filter level picked as above; its limits */
+    FLGPU_FE_WEBP_LOSSY_I4_AP_LF = 19  /* FLGPU_FE_WEBP_LOSSY_I4_AP with the loop filter level picked as above; its limits */
 } flgpu_front_end;
 
 /* content::Format bits (src/content.rs:15-16). */
@@ -185,6 +197,10 @@ typedef enum flgpu_front_end {
  * coefficient probabilities: FLGPU_FE_WEBP_LOSSY_AP, or with FLGPU_ENCODE_WEBP_LOSSY_I4 as well FLGPU_FE_WEBP_LOSSY_I4_AP where the
  * output fits that front end's limits (FLGPU_FE_WEBP_LOSSY_AP otherwise).  Alone, or with only _I4, it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_PROBS 0x2000u
+/* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies come from the loop-filtered twin
+ * (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF) of whichever front end the other bits select, fall-backs included.  Alone, or
+ * without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
+#define FLGPU_ENCODE_WEBP_LOSSY_FILTER 0x4000u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -249,6 +265,8 @@ typedef struct flgpu_plan {
                                           FLGPU_FE_WEBP_LOSSY_I4: the same with 117 mode booleans per macroblock instead of 7.
                                           FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP: the worst case of the front end each
                                           stands beside plus 7392 bytes, 1056 updates of 8 booleans: 9574 where 1126 stands above.
+                                          FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF: the twin's (the bound is per boolean; the
+                                          level's six were counted all along).
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 
@@ -611,7 +629,7 @@ int flgpu_transform_batch(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, con
 int flgpu_transform_batch_device(flgpu_ctx *ctx, size_t n, const flgpu_image *srcs, const flgpu_params *ps,
                                  flgpu_image *dsts, void *hip_stream, uint32_t flags);
 /* What only the device knows when flgpu_transform_batch_device returns -- the length of an encoded stream
- * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
+ * (FLGPU_FE_JPEG, FLGPU_FE_PNG, FLGPU_FE_WEBP_LOSSLESS, FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP and their four _LF twins: dsts[i].bytes, 0 + FLGPU_ERR_BUFFER_TOO_SMALL if it did not fit dsts[i].capacity) and
  * FLGPU_IMG_HAS_ALPHA of the WebP front end: waits for the most recent device batch of this context and completes
  * the same dsts[] array.  The host-memory entry points do this themselves.
  * It is ALSO where a device-side failure of the batch surfaces: the matrix-pipe resample kernel bounds its waits on LDS
@@ -657,7 +675,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * context, its queue lanes and its device shards.  Keys (csrc/fl_context.h DebugKey): "no_mfma", "force_generic", "no_wtile",
  * "no_luma_mid" (a grey picture on a grey frame is blurred as Rgba8, not as one channel), "wtile_first", "mfma_arith" (0 full width,
  * 1 packed), "force_bands", "no_tile", "no_place4", "host_huffman", "device_huffman_always", "device_huffman_min_bytes",
- * "mfma_spin_limit", "debug_mfma", "debug_jh"; "reset" restores every default.
+ * "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base" (see flgpu_debug_vp8_filter_costs); "reset" restores every default.
  * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
  * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
  * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines);
@@ -667,7 +685,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "vp8_sources", "vp8_file_bytes", "vp8_upload_bytes" the same for FLGPU_IMG_VP8_SOURCE pictures (per picture a 128-byte header, 48
  * bytes per macroblock, the levels up to each block's last non-zero one, the raw ALPH plane or a compressed one's lossless blob), with flgpu_config.profile "vp8_decode_ns" =
  * the HIP-event time of their decode kernels;
- * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP);
+ * with flgpu_config.profile "webp_lossy_ns" = the HIP-event time of the lossy WebP encoder's launches (FLGPU_FE_WEBP_LOSSY, FLGPU_FE_WEBP_LOSSY_I4, FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP and their four _LF twins);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files
@@ -714,6 +732,14 @@ int flgpu_debug_vp8_blob(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t
  * 8 mbw x 8 mbh), before (filter == 0) or behind the loop filter, so that a wrong pixel names its stage.  out == NULL: *used =
  * capacity to provide. */
 int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int filter, uint8_t *out, uint64_t capacity, uint64_t *used);
+
+/* The loop-filtered lossy WebP front ends' choice (csrc/fl_vp8_lf_core.h): one picture (host memory, as for flgpu_transform) through
+ * the ordinary launch sequence of params->front_end (FLGPU_FE_WEBP_LOSSY_LF .. FLGPU_FE_WEBP_LOSSY_I4_AP_LF, else
+ * FLGPU_ERR_INVALID_ARG), then levels[4] = the candidate levels, costs[4] = the 64-bit squared-error words the filter launch left
+ * for them (all 0 where the base level is 0: nothing is evaluated) and *chosen = the level in the file's frame header.
+ * flgpu_debug_set(ctx, "vp8_filter_base", v): -1 (the default) takes the base level from the quantiser, 0..63 forces it; candidates
+ * and choice are still made on the device; only these four front ends look at it.  Single-device contexts. */
+int flgpu_debug_vp8_filter_costs(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *params, uint32_t *levels, uint64_t *costs, uint32_t *chosen);
 
 /* The host half of the GIF decode front end alone (csrc/fl_gifsrc.h): the blob flgpu_process_gif uploads, all fields little-endian
  * dwords, offsets in bytes from the blob's start:

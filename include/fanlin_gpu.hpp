@@ -93,6 +93,8 @@ public:
     // ... with per-picture coefficient probabilities (FLGPU_FE_WEBP_LOSSY_AP, or FLGPU_FE_WEBP_LOSSY_I4_AP after encode_webp_lossy_i4():
     // the same pictures in fewer bytes)
     void encode_webp_lossy_probs() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_PROBS; }
+    // ... with a loop filter level picked on the device: the _LF twin of whichever front end the calls above select
+    void encode_webp_lossy_filter() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_FILTER; }
     uint32_t flags() const { return flags_; }
 
 private:

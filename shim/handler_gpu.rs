@@ -70,6 +70,11 @@ pub const FE_WEBP_LOSSY: u8 = 9;    // (7 and 8 are not front ends)
 pub const FE_WEBP_LOSSY_I4: u8 = 10; // FE_WEBP_LOSSY whose macroblocks may be B_PRED
 pub const FE_WEBP_LOSSY_AP: u8 = 12; // FE_WEBP_LOSSY with per-picture coefficient probabilities (11 is not a front end)
 pub const FE_WEBP_LOSSY_I4_AP: u8 = 13; // FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities
+// the loop-filtered twin of each of the four: the frame header's loop filter level is picked on the device (14 and 15 are not front ends)
+pub const FE_WEBP_LOSSY_LF: u8 = 16;
+pub const FE_WEBP_LOSSY_I4_LF: u8 = 17;
+pub const FE_WEBP_LOSSY_AP_LF: u8 = 18;
+pub const FE_WEBP_LOSSY_I4_AP_LF: u8 = 19;
 pub const FILTER_NEAREST: u8 = 1;
 const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
@@ -90,6 +95,7 @@ pub const ENCODE_GIF: u32 = 0x400;
 // not a content::Format bit: finish lossy image/webp bodies on the device, the WebP arm below quality 100 (RESULT_WEBP_STREAM)
 pub const ENCODE_WEBP_LOSSY: u32 = 0x800;
 pub const ENCODE_WEBP_LOSSY_I4: u32 = 0x1000; // with ENCODE_WEBP_LOSSY: the bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
+pub const ENCODE_WEBP_LOSSY_FILTER: u32 = 0x4000; // with ENCODE_WEBP_LOSSY: the loop-filtered twin of whatever the other bits select; alone, or without it, it does nothing
 pub const ENCODE_WEBP_LOSSY_PROBS: u32 = 0x2000; // with ENCODE_WEBP_LOSSY (and _I4): FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, it does nothing
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
@@ -214,7 +220,7 @@ impl Gpu {
         if let Some((w, h)) = q.dimensions() { p.has_dims = 1; p.w = w; p.h = h; }
         let mut plan = FlPlan::default();
         check(unsafe { flgpu_plan_output(&p, img.width(), img.height(), c, &mut plan) })?;
-        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS and the four FE_WEBP_LOSSY* front ends, where it is the
+        // allocated by Rust: no cross-allocator frees.  max_out_bytes == out_bytes except for FE_JPEG, FE_PNG, FE_WEBP_LOSSLESS and the eight FE_WEBP_LOSSY* front ends, where it is the
         // worst case of the format: with it the call cannot fail for lack of room, as `encode_image` into a Vec cannot.
         let mut out = vec![0u8; plan.max_out_bytes as usize];
         let src = FlImage { data: bytes.as_ptr() as *mut u8, capacity: bytes.len() as u64,

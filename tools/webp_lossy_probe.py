@@ -1,9 +1,15 @@
-"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY and, with --i4 / --probs, FLGPU_FE_WEBP_LOSSY_I4 / the adaptive-probability front ends beside it): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
+"""Lossy WebP probe (FLGPU_FE_WEBP_LOSSY and, with --i4 / --probs / --filter, FLGPU_FE_WEBP_LOSSY_I4 / the adaptive-probability front ends / the
+loop-filtered twin of each beside it): throughput of the device encoder beside the path it replaces -- the FLGPU_FE_WEBP420
 planes from the device plus libwebp's WebPEncode per picture on the host's threads --, file sizes and Y-PSNR of both on the same
 planes, and the bytes that cross PCIe.  Prints plain text; under `rocprofv3 --kernel-trace --stats` (a run of its own, with
 --timing-only) the kernel statistics attribute device time to the four vp8_* kernels, the planes kernel and the resample kernel.
 
-    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--probs] [--events]
+    python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--probs] [--filter] [--events]
+                                     [--quality 75]
+--filter: in the quality part, per loop-filtered front end the chosen level, the file against its twin's, the Y-PSNR gain and a
+block-edge measure (mean absolute luma step across macroblock edges over the mean absolute step elsewhere) of the twin's file, the
+filtered file and libwebp's own file on the same planes; in the timing part each loop-filtered family right after its twin, and the
+histogram of the levels the batch's files carry.
 """
 import argparse
 import math
@@ -24,7 +30,25 @@ def _psnr(a, b):
     return 99.0 if mse == 0 else 10.0 * math.log10(255.0 * 255.0 / mse)
 
 
-def quality(fl, st, i4=False, probs=False):
+def _edge_measure(y):
+    """Mean absolute step across macroblock edges over the mean absolute step elsewhere (both directions)."""
+    y = y.astype(np.int64)
+    dx, dy = np.abs(np.diff(y, axis=1)), np.abs(np.diff(y, axis=0))
+    ex, ey = (np.arange(1, y.shape[1]) % 16) == 0, (np.arange(1, y.shape[0]) % 16) == 0
+    edge = float(dx[:, ex].sum() + dy[ey].sum()) / (dx[:, ex].size + dy[ey].size)
+    rest = float(dx[:, ~ex].sum() + dy[~ey].sum()) / (dx[:, ~ex].size + dy[~ey].size)
+    return edge / rest if rest else 0.0
+
+
+def _lf_kinds(fl, i4, probs):
+    kinds = [("FE_WEBP_LOSSY_LF", fl.FE_WEBP_LOSSY_LF, fl.FE_WEBP_LOSSY)] + ([("FE_WEBP_LOSSY_I4_LF", fl.FE_WEBP_LOSSY_I4_LF, fl.FE_WEBP_LOSSY_I4)] if i4 else [])
+    if probs:
+        kinds += [("FE_WEBP_LOSSY_AP_LF", fl.FE_WEBP_LOSSY_AP_LF, fl.FE_WEBP_LOSSY_AP)]
+        kinds += [("FE_WEBP_LOSSY_I4_AP_LF", fl.FE_WEBP_LOSSY_I4_AP_LF, fl.FE_WEBP_LOSSY_I4_AP)] if i4 else []
+    return kinds
+
+
+def quality(fl, st, i4=False, probs=False, filt=False):
     import synth
     import vp8_lib
     import webp_lib
@@ -49,9 +73,19 @@ def quality(fl, st, i4=False, probs=False):
                 same = all(np.array_equal(a, b) for a, b in zip(vp8_lib.decode_yuv(new), vp8_lib.decode_yuv(old)))
                 print(f"quality {q}: {name} file {len(new)} bytes | {len(new) / len(old):.3f} of the non-adaptive file ({len(old)}), size ratio to libwebp "
                       f"{len(new) / len(ref):.3f}, decodes to the non-adaptive file's planes: {same}")
+        if filt:
+            print(f"quality {q}: libwebp's file: filter level {fl.vp8_info(ref)['filter_level']}, block-edge measure {_edge_measure(ry):.3f} (source planes {_edge_measure(pl.y):.3f})")
+            for name, fe, twin_fe in _lf_kinds(fl, i4, probs):
+                p = fl.make_params(300, 200, quality=q, front_end=fe)
+                new, twin = st.process_pixels(big, p), st.process_pixels(big, fl.make_params(300, 200, quality=q, front_end=twin_fe))
+                c = st.debug_vp8_filter_costs(big, p)
+                ny, ty = vp8_lib.decode_yuv(new)[0], vp8_lib.decode_yuv(twin)[0]
+                print(f"quality {q}: {name}: levels {c['levels']} D {c['D']} -> level {c['chosen']}; file {len(new)} bytes against the twin's {len(twin)}; "
+                      f"Y-PSNR {_psnr(ny, pl.y):.2f} dB against {_psnr(ty, pl.y):.2f} ({_psnr(ny, pl.y) - _psnr(ty, pl.y):+.2f}); block-edge measure "
+                      f"{_edge_measure(ny):.3f} against the twin's {_edge_measure(ty):.3f}")
 
 
-def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=False):
+def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=False, filt=False, q=75):
     import torch
     import synth
     import webp_lib
@@ -64,8 +98,11 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=Fal
     kinds = [("FE_WEBP420", fl.FE_WEBP420), ("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY)] + ([("FE_WEBP_LOSSY_I4", fl.FE_WEBP_LOSSY_I4)] if i4 else [])
     if probs:
         kinds += [("FE_WEBP_LOSSY_AP", fl.FE_WEBP_LOSSY_AP)] + ([("FE_WEBP_LOSSY_I4_AP", fl.FE_WEBP_LOSSY_I4_AP)] if i4 else [])
+    if filt:  # each loop-filtered family right after its twin
+        twins = {twin_fe: (name, fe) for name, fe, twin_fe in _lf_kinds(fl, i4, probs)}
+        kinds = [k for name, fe in kinds for k in ([(name, fe)] + ([twins[fe]] if fe in twins else []))]
     for name, fe in kinds:
-        p = fl.make_params(300, 200, quality=75, front_end=fe)
+        p = fl.make_params(300, 200, quality=q, front_end=fe)
         ns0 = (st.stats(), st.debug_get("webp_lossy_ns"))[1] if events else 0
         cap = (int(fl.plan_output(p, 1920, 1080, 3).max_out_bytes) + 255) // 256 * 256
         dst = torch.empty(batch * cap, dtype=torch.uint8, device="cuda")
@@ -80,10 +117,16 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=Fal
         res = st.batch_results()
         nbytes = [r[1] for r in res]
         out[name] = (dt, nbytes)
-        print(f"{name}: {batch} x 1080p RGB8 -> w=300&h=200&webp=true&quality=75: {dt * 1e3:.2f} ms per batch, {batch / dt:.0f} images/s on the device, "
+        print(f"{name}: {batch} x 1080p RGB8 -> w=300&h=200&webp=true&quality={q}: {dt * 1e3:.2f} ms per batch, {batch / dt:.0f} images/s on the device, "
               f"mean output {np.mean(nbytes):.0f} bytes")
         if fe == fl.FE_WEBP420:
             first = dst[:cap].cpu().numpy()
+        if name.endswith("_LF"):
+            hist = {}
+            for i in range(batch):
+                lv = fl.vp8_info(dst[i * cap:i * cap + nbytes[i]].cpu().numpy().tobytes())["filter_level"]
+                hist[lv] = hist.get(lv, 0) + 1
+            print(f"{name}: levels chosen over the batch {dict(sorted(hist.items()))}")
         if events and fe != fl.FE_WEBP420:
             st.stats()  # (resolves the pending events)
             ns = st.debug_get("webp_lossy_ns")
@@ -95,7 +138,7 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=Fal
     n = 16 * host_threads
     with ThreadPoolExecutor(host_threads) as ex:
         t0 = time.perf_counter()
-        files = list(ex.map(lambda _: webp_lib.encode_planes(y, u, v, 75), range(n)))
+        files = list(ex.map(lambda _: webp_lib.encode_planes(y, u, v, q), range(n)))
         dth = (time.perf_counter() - t0) / n
     dt_p, nb_p = out["FE_WEBP420"]
     dt_l, nb_l = out["FE_WEBP_LOSSY"]
@@ -107,6 +150,12 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=Fal
         dt_4, nb_4 = out["FE_WEBP_LOSSY_I4"]
         print(f"I4 encode adds {(dt_4 - dt_p) * 1e3:.2f} ms per batch to the planes path: {batch / dt_4:.0f} images/s, mean file {np.mean(nb_4):.0f} bytes "
               f"({np.mean(nb_4) / np.mean(nb_l):.3f} of the I16-only file)")
+    for name in ("FE_WEBP_LOSSY_LF", "FE_WEBP_LOSSY_I4_LF", "FE_WEBP_LOSSY_AP_LF", "FE_WEBP_LOSSY_I4_AP_LF"):
+        if name in out:
+            dt_a, nb_a = out[name]
+            dt_o, nb_o = out[name[:-3]]
+            print(f"{name}: {(dt_a - dt_o) * 1e3:+.2f} ms per batch against {name[:-3]}: {batch / dt_a:.0f} images/s, mean file {np.mean(nb_a):.0f} bytes "
+                  f"({np.mean(nb_a) / np.mean(nb_o):.4f} of the twin's)")
     for name in ("FE_WEBP_LOSSY_AP", "FE_WEBP_LOSSY_I4_AP"):
         if name in out:
             dt_a, nb_a = out[name]
@@ -126,13 +175,15 @@ def main():
     ap.add_argument("--events", action="store_true", help="a profiling context: also report webp_lossy_ns per batch")
     ap.add_argument("--i4", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_I4")
     ap.add_argument("--probs", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_AP (and, with --i4, FLGPU_FE_WEBP_LOSSY_I4_AP)")
+    ap.add_argument("--filter", action="store_true", help="also the loop-filtered twin (FLGPU_FE_WEBP_LOSSY_LF, ...) of every front end selected")
+    ap.add_argument("--quality", type=int, default=75, help="the timing part's quality")
     a = ap.parse_args()
     import __graft_entry__ as g
     fl = g._load_package()
     with fl.State(device=0, profile=a.events) as st:
         if not a.timing_only:
-            quality(fl, st, a.i4, a.probs)
-        timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events, a.probs)
+            quality(fl, st, a.i4, a.probs, a.filter)
+        timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events, a.probs, a.filter, a.quality)
 
 
 if __name__ == "__main__":
