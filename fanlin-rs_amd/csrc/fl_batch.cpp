@@ -1185,13 +1185,16 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
             FL_HIP(c, launch_wtile(m, st), "window-tile matrix-pipe kernel (blur)");
             c->stats.mfma_launches++;
             c->stats.wtile_launches++;
+            c->blur_wtile_launches++;
         } else if (L.blur_tiled && !B.dbg.on(DBG_FORCE_GENERIC)) {
             L.g.pre = L.k.filtered; // channels to filter, see blur_tile_kernel
             L.g.blur_lanes = L.k.lanes;
             FL_HIP(c, launch_blur_tile(L.g, L.blur_grid_x, L.lds, st), "blur kernel");
+            c->blur_tile_launches++;
         } else {
             FL_HIP(c, launch_vpass_generic(L.g, st), "blur vertical pass");
             FL_HIP(c, launch_hpass_generic(L.g, st), "blur horizontal pass");
+            c->blur_generic_launches++;
         }
         c->stats.blur_launches++;
     }

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 
+#include "fl_blur.h"
 #include "fl_kernel_common.h"
 #include "fl_kernels.h"
 
@@ -20,27 +21,9 @@ namespace fl {
 //   hand-off        the BLUR_TY unrounded f32 rows go to LDS, lane-contiguous.
 //   horizontal pass lane <-> output column.  Neighbouring lanes read neighbouring pixels (ratio 1), so the
 //                   LDS reads are conflict free; one weight read feeds BLUR_TY rows x C channels of FMAs.
+// BLUR_TY, BLUR_MAXTAPS, the lanes per workgroup (blur_threads) and the LDS bytes are in fl_blur.h, where a host-only
+// program can read them too.
 // ---------------------------------------------------------------------------
-
-constexpr int BLUR_TY = 8;        // output rows per workgroup (colour)
-constexpr int BLUR_TY_MONO = 8;   // ... when one channel is filtered (16 measured slower: 0.80 vs 0.61 ms, more zero-weight FMAs per band)
-__host__ __device__ inline int blur_ty(uint32_t channels_filtered) { return channels_filtered == 1 ? BLUR_TY_MONO : BLUR_TY; }
-constexpr uint32_t BLUR_MAXTAPS = 128;            // sigma <= 20 gives 81 taps
-__host__ __device__ constexpr uint32_t blur_midw(uint32_t threads) { return threads + BLUR_MAXTAPS; } // columns of the f32 hand-off rows in LDS
-
-__host__ __device__ inline uint32_t blur_tiles_t(uint32_t w, uint32_t taps, uint32_t threads) { const uint32_t cap = threads - (taps - 1); return (w + cap - 1) / cap; }
-// Lanes per workgroup: a tile of tw output columns needs tw + taps - 1 lanes in the vertical pass, so the width that
-// wastes the fewest lane slots wins (300 columns, 41 taps: 1 tile of 384 lanes instead of 2 of 256)
-__host__ __device__ inline uint32_t blur_threads(uint32_t w, uint32_t taps)
-{
-    uint32_t best = 256, cost = 0xffffffffu;
-    for (uint32_t t = 256; t <= 512; t += 128) {
-        const uint32_t c = blur_tiles_t(w, taps, t) * t;
-        if (c < cost) { cost = c; best = t; }
-    }
-    return best;
-}
-__host__ __device__ inline uint32_t blur_tiles(uint32_t w, uint32_t taps) { return blur_tiles_t(w, taps, blur_threads(w, taps)); }
 
 // CS = channels stored per pixel, C = channels filtered.  C < CS only for opaque Rgba8 pictures (every
 // letterboxed output of an opaque source): the alpha plane is the constant 255 (any normalised filter
@@ -78,7 +61,7 @@ __global__ __launch_bounds__(THREADS) void blur_tile_kernel(const Job *__restric
     const uint32_t cl = blk[hd.tiles_off + 2 * tile], ncols = blk[hd.tiles_off + 2 * tile + 1]; // ncols <= T by construction
     const uint32_t top = blk[hd.bands_off + 2 * band], nrows = blk[hd.bands_off + 2 * band + 1];
 
-    // LDS: [ wv: rv x TY | mid: TY x (T + htaps) x MS | wh: htaps x nrows_h (distinct weight vectors) ]
+    // LDS: [ wv: rv x TY | mid: TY x blur_midw(T) x MS | wh: htaps x nrows_h (distinct weight vectors) ] -- sized by blur_lds_bytes_of (fl_blur.h)
     float *wv = fl_lds;
     const uint32_t wv_floats = (hd.rv * TY + 3u) & ~3u;
     constexpr uint32_t midw = blur_midw(THREADS); // compile-time row pitch: row offsets fold into the ds_read immediates
@@ -210,16 +193,7 @@ __global__ __launch_bounds__(THREADS) void blur_tile_kernel(const Job *__restric
 
 // host-side sizing and the launch wrapper (called from the host runtime; asynchronous on `st`)
 
-size_t blur_lds_bytes(uint32_t w, uint32_t channels, uint32_t vtaps, uint32_t htaps)
-{
-    const size_t BLUR_TY = (size_t)blur_ty(channels);
-    const uint32_t ms = channels == 3 ? 4 : channels;
-    const uint32_t nt = blur_tiles(w, htaps), tw = (w + nt - 1) / nt;
-    const size_t wv = (((size_t)(BLUR_TY + vtaps) * BLUR_TY + 3) & ~(size_t)3); // rv <= BLUR_TY + vtaps - 1
-    (void)tw;
-    const size_t rows_h = std::min<size_t>(w, 2 * (size_t)htaps); // distinct horizontal weight vectors: <= htaps (borders) + 1 (interior)
-    return (wv + (size_t)BLUR_TY * blur_midw(blur_threads(w, htaps)) * ms + (size_t)htaps * rows_h) * sizeof(float);
-}
+size_t blur_lds_bytes(uint32_t w, uint32_t channels, uint32_t vtaps, uint32_t htaps) { return blur_lds_bytes_of(w, channels, vtaps, htaps); }
 
 uint32_t blur_tile_count(uint32_t w, uint32_t htaps) { return blur_tiles(w, htaps); }
 uint32_t blur_lanes(uint32_t w, uint32_t htaps) { return blur_threads(w, htaps); }

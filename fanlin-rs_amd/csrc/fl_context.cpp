@@ -637,6 +637,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         (void)hipSetDevice(c->device);
         resolve_pending(c);
         c->stats = flgpu_stats{};
+        c->blur_wtile_launches = c->blur_tile_launches = c->blur_generic_launches = 0;
         c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = c->webp_lossy_ns = 0;
         c->vp8_sources = c->vp8_file_bytes = c->vp8_upload_bytes = c->vp8_decode_ns = 0;
@@ -665,7 +666,7 @@ int flgpu_debug_set(flgpu_ctx *c, const char *key, int64_t value)
 int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value || !c->dbg) return FLGPU_ERR_INVALID_ARG;
-    // read-only counters of the PNG, lossless WebP, lossy WebP and GIF decode front ends (flgpu_stats keeps its size): this context's and its lanes' / shards'
+    // read-only counters of the PNG, lossless WebP, lossy WebP and GIF decode front ends and of the blur's routes (flgpu_stats keeps its size): this context's and its lanes' / shards'
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
@@ -675,7 +676,11 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
         {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns},
         {"gif_encoded", &flgpu_ctx::gif_encoded}, {"gif_encode_fallbacks", &flgpu_ctx::gif_encode_fallbacks}, {"gif_encoded_bytes", &flgpu_ctx::gif_encoded_bytes},
-        {"gif_encode_ns", &flgpu_ctx::gif_encode_ns}};
+        {"gif_encode_ns", &flgpu_ctx::gif_encode_ns},
+        // which kernel served a blur launch (their sum moves as flgpu_stats::blur_launches does): the window-tile matrix-pipe kernel,
+        // blur_tile_kernel, the generic two passes
+        {"blur_wtile_launches", &flgpu_ctx::blur_wtile_launches}, {"blur_tile_launches", &flgpu_ctx::blur_tile_launches},
+        {"blur_generic_launches", &flgpu_ctx::blur_generic_launches}};
     for (const auto &k : counters) {
         if (strcmp(key, k.name)) continue;
         uint64_t sum;

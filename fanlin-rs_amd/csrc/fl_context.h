@@ -254,6 +254,7 @@ struct flgpu_ctx {
     hipEvent_t last_done = nullptr;
 
     flgpu_stats stats{};
+    uint64_t blur_wtile_launches = 0, blur_tile_launches = 0, blur_generic_launches = 0; // which kernel served each of stats.blur_launches (flgpu_debug_get; guarded by mu)
     struct Pending { hipEvent_t a, b; int kind; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> event_pool;

@@ -53,11 +53,15 @@ void build_strip(const HostAxis &h, uint32_t x0, uint32_t x1, uint32_t lanes, ui
 
 // Everything the blur kernel needs for one (width, height, sigma), as one arena block so that a workgroup
 // reaches its tables with two dependent loads instead of a chain through the generic axis tables:
-//   header  : nt, nb, tw_full, htaps, rv (rows of a dense vertical table), tiles_off, bands_off, vdense_off, htiles_off (relative words)
+//   header  : BlurPlanHeader (fl_types.h): nt, nb, tw_full (output columns of a full tile), htaps, rv (rows of a dense vertical
+//             table), nrows_h (distinct horizontal weight vectors) and the offsets of the five areas below, in words from the header
 //   tiles   : per column tile  { first source column, number of source columns }
 //   bands   : per row band     { first source row, number of source rows }
 //   vdense  : per band, rv x ty floats: weight of source row (top + r) in output row (y0 + o), 0 outside the window
-//   htiles  : per tile, hleft[tw_full] then weights tap-major [htaps][tw_full]
+//   htiles  : per tile, tw_full pairs { hleft = the column's first tap relative to the tile's first source column, id of its weight vector }
+//   hrows   : the distinct weight vectors, zero padded to htaps, tap-major [htaps][nrows_h] -- all interior columns share one vector,
+//             only the columns within 2 sigma of a border have their own (nrows_h <= min(w, 2 htaps), which blur_lds_bytes sizes for)
+// nt = blur_tiles(w, htaps) and ty = blur_ty(channels filtered) of fl_blur.h.
 void build_blur_plan(const HostAxis &v, const HostAxis &h, uint32_t nt, uint32_t ty, std::vector<uint32_t> &out);
 
 // libwebp picture_csp_enc.c InitGammaTables: kGammaToLinearTab[256] then kLinearToGammaTab[33], as int32.

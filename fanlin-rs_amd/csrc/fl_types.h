@@ -53,7 +53,7 @@ struct alignas(16) Job {
     uint32_t fill;          // r | g<<8 | b<<16 | 255<<24
     uint32_t vtab, htab;    // arena word offsets of the AxisTable headers (vertical, horizontal)
     uint32_t mid_off;       // generic path: float offset of this job's f32 intermediate
-    uint32_t pad0;          // blur jobs: arena word offset of the horizontal weight tiles
+    uint32_t pad0;          // blur jobs: arena word offset of blur_tile_kernel's table block (BlurPlanHeader), 0 = none
     uint32_t pad1;
 };
 

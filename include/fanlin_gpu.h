@@ -689,7 +689,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files
- * it handed back as pixels (a frame above 256 colours), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time.
+ * it handed back as pixels (a frame above 256 colours), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
+ * "blur_wtile_launches", "blur_tile_launches", "blur_generic_launches" = the blur launches (flgpu_stats.blur_launches is their sum)
+ * served by the window-tile matrix-pipe kernel, by the f32 LDS-tile kernel and by the generic two passes.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
  * (they pick another resample or blur kernel).  Unknown key: FLGPU_ERR_INVALID_ARG. */
 int flgpu_debug_set(flgpu_ctx *ctx, const char *key, int64_t value);

@@ -222,11 +222,18 @@ def test_edge_distributions(fl, gpu_state, oracle, monkeypatch):
 
 # ----------------------------------------------------------------------------- blur --
 
+def blur_routes(st):
+    """The blur launches so far by the kernel that served them: window-tile matrix-pipe kernel, blur_tile_kernel, generic two passes."""
+    return np.array([st.debug_get(k) for k in ("blur_wtile_launches", "blur_tile_launches", "blur_generic_launches")])
+
+
 @pytest.mark.parametrize("sigma", [10.0, 20.0])
 def test_blur_only(fl, gpu_state, oracle, sigma, monkeypatch):
     gpu_state.debug_set("no_wtile", 1)   # the f32 vector blur kernel and its bit-exact bar (the matrix-pipe blur: tests/test_wtile.py)
     img = synth.uniform(200, 300, 4, index=20)
+    before = blur_routes(gpu_state)
     got = gpu_state.process_pixels(img, fl.make_params(blur_sigma=sigma))
+    assert (blur_routes(gpu_state) - before).tolist() == [0, 1, 0], "meant to run on blur_tile_kernel, not on the generic passes (same arithmetic, same bar)"
     assert np.array_equal(got, oracle.blur(img, sigma, arith=oracle_lib.ARITH_FMA))
     assert maxdiff(got, oracle.blur(img, sigma, arith=oracle_lib.ARITH_REF)) <= TOL_LSB
 
@@ -252,10 +259,13 @@ def test_blur_channel_shortcuts_are_exact(fl, gpu_state, oracle, kw):
 def test_blur_wide_image_tiles(fl, gpu_state, oracle, monkeypatch):
     gpu_state.debug_set("no_wtile", 1)   # (as above)
     img = synth.uniform(90, 700, 3, index=23)       # several column tiles, halo across tile borders
+    before = blur_routes(gpu_state)
     got = gpu_state.process_pixels(img, fl.make_params(blur_sigma=20.0))
+    assert (blur_routes(gpu_state) - before).tolist() == [0, 1, 0]
     assert np.array_equal(got, oracle.blur(img, 20.0, arith=oracle_lib.ARITH_FMA))
     tiny = synth.uniform(5, 7, 4, index=24)         # window larger than the image on both axes
     got = gpu_state.process_pixels(tiny, fl.make_params(blur_sigma=10.0))
+    assert (blur_routes(gpu_state) - before).tolist() == [0, 2, 0]
     assert np.array_equal(got, oracle.blur(tiny, 10.0, arith=oracle_lib.ARITH_FMA))
 
 
