@@ -45,6 +45,7 @@ ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those
 ENCODE_WEBP_LOSSY_FILTER = 0x4000  # accept_flags bit: with ENCODE_WEBP_LOSSY, the loop-filtered twin of whatever the other bits select; alone, or without it, nothing
 ENCODE_WEBP_LOSSY_PROBS = 0x2000  # accept_flags bit: with ENCODE_WEBP_LOSSY (and _I4), FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, nothing
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
+ENCODE_GIF_QUANTIZE = 0x8000  # accept_flags bit: with ENCODE_GIF, a frame above 256 colours is quantised on the device (the library's own rule) and the file is finished; alone, nothing
 ENCODE_GIF = 0x400  # accept_flags bit: State.process_gif finishes the image/gif body on the device where every frame has at most 256 colours
 IN_OTHER, IN_JPEG, IN_PNG, IN_WEBP, IN_GIF_FRAME = 0, 1, 2, 3, 4
 RESULT_AS_IS, RESULT_JPEG_STREAM, RESULT_WEBP_PLANES, RESULT_PIXELS, RESULT_PNG_STREAM, RESULT_WEBP_STREAM = 0, 1, 2, 3, 4, 5
@@ -971,7 +972,8 @@ class State:
     def process_gif(self, data: bytes, query_string: str, content: "Format" = None):
         """process_gif from the file bytes on: (mime, kind, payload); payload is the file itself for AS_IS, else the list of the
         frames' pixels (out_h, out_w, out_c), in frame order, for the host's GIF encoder.  With ENCODE_GIF in the content flags
-        and no frame above 256 colours the payload is the finished file (bytes, RESULT_GIF_STREAM)."""
+        and no frame above 256 colours the payload is the finished file (bytes, RESULT_GIF_STREAM); with ENCODE_GIF_QUANTIZE as well
+        frames above 256 colours are quantised on the device and the payload is the file then too."""
         plan, kind, fmt, frames = flgpu_plan(), C.c_int(), C.c_int(), C.c_uint32()
         flags = content.flags if content else 0
         qs = query_string.encode()
@@ -997,6 +999,10 @@ class State:
     def gif_encode_counters(self) -> dict:
         """The GIF encoder's counters (flgpu_debug_get): files finished on the device, their bytes, files handed back as pixels."""
         return {k: self.debug_get(k) for k in ("gif_encoded", "gif_encode_fallbacks", "gif_encoded_bytes")}
+
+    def gif_quantized_frames(self) -> int:
+        """Frames above 256 colours that ENCODE_GIF_QUANTIZE gave a table on the device (flgpu_debug_get)."""
+        return self.debug_get("gif_quantized_frames")
 
     def webp_counters(self) -> dict:
         """The lossless WebP decode front end's counters (flgpu_debug_get)."""

@@ -642,7 +642,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = c->webp_lossy_ns = 0;
         c->vp8_sources = c->vp8_file_bytes = c->vp8_upload_bytes = c->vp8_decode_ns = 0;
         c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
-        c->gif_encoded = c->gif_encode_fallbacks = c->gif_encoded_bytes = c->gif_encode_ns = 0;
+        c->gif_encoded = c->gif_encode_fallbacks = c->gif_encoded_bytes = c->gif_encode_ns = c->gif_quantized_frames = 0;
     }
     const size_t nl = c->n_lanes.load(std::memory_order_acquire);
     for (size_t i = 0; i < nl; ++i) (void)flgpu_reset_stats(c->lanes[i]);
@@ -676,7 +676,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},
         {"gif_upload_bytes", &flgpu_ctx::gif_upload_bytes}, {"gif_compose_ns", &flgpu_ctx::gif_compose_ns},
         {"gif_encoded", &flgpu_ctx::gif_encoded}, {"gif_encode_fallbacks", &flgpu_ctx::gif_encode_fallbacks}, {"gif_encoded_bytes", &flgpu_ctx::gif_encoded_bytes},
-        {"gif_encode_ns", &flgpu_ctx::gif_encode_ns},
+        {"gif_encode_ns", &flgpu_ctx::gif_encode_ns}, {"gif_quantized_frames", &flgpu_ctx::gif_quantized_frames},
         // which kernel served a blur launch (their sum moves as flgpu_stats::blur_launches does): the window-tile matrix-pipe kernel,
         // blur_tile_kernel, the generic two passes
         {"blur_wtile_launches", &flgpu_ctx::blur_wtile_launches}, {"blur_tile_launches", &flgpu_ctx::blur_tile_launches},

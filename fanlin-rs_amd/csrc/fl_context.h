@@ -234,6 +234,7 @@ struct flgpu_ctx {
     fl::DeviceBuf d_gifenc;                            // GIF encode (fl_gif.hip): status, frame records, colour tables, indices, segments, frame bodies, the file
     fl::PinnedBuf h_gifstat;                           // its status record {a frame above 256 colours, file bytes}
     uint64_t gif_encoded = 0, gif_encode_fallbacks = 0, gif_encoded_bytes = 0; // files finished on the device, files handed back as pixels, bytes of the former
+    uint64_t gif_quantized_frames = 0;                 // frames above 256 colours that FLGPU_ENCODE_GIF_QUANTIZE gave a table (in files counted as gif_encoded)
     uint64_t gif_encode_ns = 0;                        // HIP-event time of the encode kernels' launches (profile = 1)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fl_gif_quant_core.h"
+
 namespace fl {
 
 // A frame's indices are LZW-coded in independent segments of kGifSegIndices: each one starts from an empty table and closes
@@ -21,7 +23,8 @@ static_assert(kGifSegIndices <= 3838, "a segment must not be able to fill the LZ
 static_assert((uint64_t)(kGifSegIndices + 2) * 12 <= (uint64_t)(kGifSegDwords - 2) * 32, "segment scratch too small");
 
 // frame record words
-enum { kGrColours = 0, kGrTableBits = 1, kGrCodeSize = 2, kGrTransparent = 3, kGrHeadBytes = 4, kGrDataBits = 5, kGrBytes = 6 };
+enum { kGrColours = 0, kGrTableBits = 1, kGrCodeSize = 2, kGrTransparent = 3, kGrHeadBytes = 4, kGrDataBits = 5, kGrBytes = 6,
+       kGrQuant = 7 /* 0 = exact palette; else the quantiser's mark, s and clear bit (fl_gif_quant_core.h) */ };
 constexpr uint32_t kGifNoTransparent = 0xffffffffu;
 
 inline uint64_t gif_segments(uint64_t pixels) { return (pixels + kGifSegIndices - 1) / kGifSegIndices; }
@@ -46,11 +49,19 @@ inline bool gif_encodable(uint64_t w, uint64_t h, uint32_t c, uint64_t frames, u
     return px <= (1ull << 27) && gif_max_file_bytes(frames, gif_max_frame_bytes(px) > pixel_bytes ? gif_max_frame_bytes(px) : pixel_bytes) < (1ull << 31);
 }
 
+// The quantiser's cells of one frame: the hash slots of s = 0, 1, 2, or the direct table of s = 3, which takes more than
+// kGifQuantHashCells colours and so as many pixels.
+inline uint32_t gif_quant_stride(uint64_t pixels) { return pixels > kGifQuantHashCells ? kGifQuantCells : kGifQuantHashSlots; }
+// What a file may ask of the quantiser: frames of at most kGifQuantMaxPixels (the 64-bit products) and at most 1 GiB of cells
+// (20 bytes a cell and frame).  A file beyond either is treated as without FLGPU_ENCODE_GIF_QUANTIZE.
+inline bool gif_quantizable(uint64_t pixels, uint64_t frames) { return pixels <= kGifQuantMaxPixels && frames * gif_quant_stride(pixels) * 20u <= (1ull << 30); }
+
 // One animation of a GIF-encode launch: `frames` pictures of w x h pixels with c = 2 (LumaA8) or 4 (Rgba8) channels.
 struct GifEncJob {
     const uint8_t *pixels;   // frame f at pixels + f * pix_pitch (256-byte aligned)
     uint64_t pix_pitch;
-    uint32_t *status;        // [0] = a frame has more than 256 colours (nothing else is valid then), [1] = file bytes
+    uint32_t *status;        // [0] = a frame has more than 256 colours and is not quantised (nothing else is valid then), [1] = file bytes,
+                             // [2] = frames the quantiser gave their table
     uint32_t *frec;          // [frame][kGifFrameRec]
     uint32_t *ckeys, *cvals; // [frame][kGifColourSlots] colour -> index, as the palette kernel's hash left it
     uint8_t *indices;        // frame f at indices + f * idx_pitch
@@ -62,9 +73,15 @@ struct GifEncJob {
     uint64_t idx_pitch, body_pitch;
     uint32_t w, h, c, frames;
     uint32_t px, nseg;       // pixels and segments of one frame
+    // FLGPU_ENCODE_GIF_QUANTIZE (fl_gifquant.hip): quant != 0 marks a frame above 256 colours instead of the file.  Per frame
+    // 4 x qstride words of cells (n, sum r, sum g, sum b, an array each) and qstride words box << 24 | representative.
+    uint32_t quant, qstride;
+    uint32_t *qcells, *qbox;
 };
 
 // palette -> indices -> LZW segments -> scan -> pack -> file; six stream-ordered launches, nothing waits between workgroups
+// (with job.quant three more behind the palette kernel: cells -> split -> nearest entry, launch_gif_quantize)
 hipError_t launch_gif_encode(const GifEncJob &job, hipStream_t st);
+void launch_gif_quantize(const GifEncJob &job, hipStream_t st);
 
 } // namespace fl

@@ -4,7 +4,8 @@
 // Frame::from_rgba_speed): alpha != 0 becomes 255, the palette is the distinct (r, g, b, a) tuples in ascending order, padded
 // with zeros to 2, 4 .. 256 entries, the transparent index is that of the LAST pixel with alpha 0, every frame is a full-canvas
 // image with a local table, disposal 1, delay 0.  Above 256 colours the reference runs NeuQuant; here the file's overflow flag
-// is set, every later kernel returns at once and the caller takes the pixels instead.
+// is set, every later kernel returns at once and the caller takes the pixels instead -- or, where the job says so
+// (FLGPU_ENCODE_GIF_QUANTIZE), the frame is marked and fl_gifquant.hip gives it a table and indices of the library's own rule.
 //
 // LZW is serial, so a frame's indices are cut into segments of kGifSegIndices that are coded independently, each from an empty
 // table and closed by a clear code: a decoder sees one ordinary stream.  The segments' bit strings are then gathered into the
@@ -69,8 +70,14 @@ __global__ __launch_bounds__(kGifThreads) void gif_palette_kernel(GifEncJob J)
     if (tpos) atomicMax(&s_tpos, tpos);
     __syncthreads();
     const uint32_t n = s_count;
-    if (n > 256u) { // NeuQuant's ground: the caller gets the pixels
-        if (tid == 0u) J.status[0] = 1u;
+    if (n > 256u) { // NeuQuant's ground: the caller gets the pixels, or -- J.quant -- this frame its table from fl_gifquant.hip
+        if (J.quant) {
+            uint4 *cells = reinterpret_cast<uint4 *>(J.qcells + (size_t)f * 4u * J.qstride);
+            for (uint32_t i = tid; i < J.qstride; i += kGifThreads) cells[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (tid == 0u) J.frec[(size_t)f * kGifFrameRec + kGrQuant] = kGqMarked;
+        } else if (tid == 0u) {
+            J.status[0] = 1u;
+        }
         return;
     }
     for (uint32_t i = tid; i < kGifColourSlots; i += kGifThreads) {
@@ -103,14 +110,15 @@ __global__ __launch_bounds__(kGifThreads) void gif_palette_kernel(GifEncJob J)
         body[18u + 3u * tsize] = (uint8_t)mcs;
         uint32_t *rec = J.frec + (size_t)f * kGifFrameRec;
         rec[kGrColours] = n; rec[kGrTableBits] = tbits; rec[kGrCodeSize] = mcs; rec[kGrTransparent] = t;
-        rec[kGrHeadBytes] = 19u + 3u * tsize;
+        rec[kGrHeadBytes] = 19u + 3u * tsize; rec[kGrQuant] = 0u;
     }
 }
 
 // One index byte per pixel, four pixels a thread: the frame's colour -> index table in LDS, 16-byte reads of Rgba8, dword stores.
+// (A frame the quantiser took has its indices from gif_qindex_kernel.)
 __global__ __launch_bounds__(kGifThreads) void gif_index_kernel(GifEncJob J)
 {
-    if (J.status[0]) return;
+    if (J.status[0] || J.frec[(size_t)blockIdx.y * kGifFrameRec + kGrQuant]) return;
     __shared__ uint32_t s_k[kGifColourSlots];
     __shared__ uint8_t s_v[kGifColourSlots];
     const uint32_t f = blockIdx.y, tid = threadIdx.x;
@@ -294,7 +302,9 @@ hipError_t launch_gif_encode(const GifEncJob &J, hipStream_t st)
     const uint32_t quads = (J.px + 3u) / 4u;
     const uint32_t max_dw = (uint32_t)((12ull * (J.px + 1ull + J.nseg) + 31u) / 32u);
     auto groups = [](uint64_t items, uint32_t cap) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + kGifThreads - 1) / kGifThreads, 1), cap); };
+    if (J.quant && (!gif_quantizable(J.px, J.frames) || J.qstride != gif_quant_stride(J.px) || !J.qcells || !J.qbox)) return hipErrorInvalidValue;
     gif_palette_kernel<<<dim3(J.frames), dim3(kGifThreads), 0, st>>>(J);
+    if (J.quant) launch_gif_quantize(J, st);
     gif_index_kernel<<<dim3(groups(quads, 64), J.frames), dim3(kGifThreads), 0, st>>>(J);
     gif_lzw_kernel<<<dim3(J.frames * J.nseg), dim3(64), 0, st>>>(J);
     gif_scan_kernel<<<dim3(J.frames), dim3(kGifThreads), 0, st>>>(J);

@@ -26,7 +26,8 @@ static int decode_gif_sources(flgpu_ctx *c, const GifBlobHeader &H, const uint8_
 
 // The encode phase behind run_batch_device: the frames lie in d_out at `pitch`; the six kernels of fl_gif.hip leave the file and
 // its status record in scratch.  Enqueues only.
-static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t frames, size_t pitch, uint64_t frame_max, const uint8_t **file, hipStream_t st)
+// `quantize` (FLGPU_ENCODE_GIF_QUANTIZE): frames above 256 colours get a table from fl_gifquant.hip, whose cells are planned here too.
+static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t frames, size_t pitch, uint64_t frame_max, bool quantize, const uint8_t **file, hipStream_t st)
 {
     GifEncJob J;
     memset(&J, 0, sizeof(J));
@@ -34,13 +35,16 @@ static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t fram
     J.px = plan.out_w * plan.out_h; J.nseg = (uint32_t)gif_segments(J.px);
     J.pixels = static_cast<const uint8_t *>(c->d_out.p); J.pix_pitch = pitch;
     J.idx_pitch = align_up((size_t)J.px, 16) + 16; J.body_pitch = align_up((size_t)frame_max, 16);
+    J.quant = quantize && gif_quantizable(J.px, frames) ? 1u : 0u; // (else a frame above 256 colours sends the file back as pixels, as without the bit)
+    J.qstride = gif_quant_stride(J.px);
     const size_t segs = (size_t)frames * J.nseg;
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
     const size_t o_status = carve(16), o_frec = carve((size_t)frames * kGifFrameRec * 4), o_ckeys = carve((size_t)frames * kGifColourSlots * 4),
                  o_cvals = carve((size_t)frames * kGifColourSlots * 4), o_idx = carve((size_t)frames * J.idx_pitch),
                  o_segs = carve(segs * kGifSegDwords * 4), o_bits = carve(segs * 4), o_off = carve(segs * 4),
-                 o_bodies = carve((size_t)frames * J.body_pitch), o_file = carve((size_t)gif_max_file_bytes(frames, frame_max));
+                 o_bodies = carve((size_t)frames * J.body_pitch), o_file = carve((size_t)gif_max_file_bytes(frames, frame_max)),
+                 o_qcells = carve(J.quant ? (size_t)frames * 4u * J.qstride * 4 : 0), o_qbox = carve(J.quant ? (size_t)frames * J.qstride * 4 : 0);
     FL_HIP(c, c->d_gifenc.reserve(off), "GIF encode scratch");
     FL_HIP(c, c->h_gifstat.reserve(16), "pinned GIF encode status");
     uint8_t *base = static_cast<uint8_t *>(c->d_gifenc.p);
@@ -49,6 +53,7 @@ static int encode_gif_frames(flgpu_ctx *c, const flgpu_plan &plan, uint32_t fram
     J.indices = base + o_idx; J.segs = reinterpret_cast<uint32_t *>(base + o_segs);
     J.seg_bits = reinterpret_cast<uint32_t *>(base + o_bits); J.seg_off = reinterpret_cast<uint32_t *>(base + o_off);
     J.bodies = base + o_bodies; J.file = base + o_file;
+    if (J.quant) { J.qcells = reinterpret_cast<uint32_t *>(base + o_qcells); J.qbox = reinterpret_cast<uint32_t *>(base + o_qbox); }
     *file = J.file;
     FL_HIP(c, hipMemsetAsync(J.status, 0, 16, st), "GIF encode status");
     { ProfileScope ps(c, st, 6); FL_HIP(c, launch_gif_encode(J, st), "GIF encode kernels"); }
@@ -73,6 +78,7 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
     const size_t each = params ? (size_t)plan.out_bytes : canvas;
     // FLGPU_ENCODE_GIF: the file is attempted; the destination holds either outcome
     const bool encode = params && (accept_flags & FLGPU_ENCODE_GIF) && gif_encodable(plan.out_w, plan.out_h, plan.out_c, info.frames, plan.out_bytes);
+    const bool quantize = encode && (accept_flags & FLGPU_ENCODE_GIF_QUANTIZE);
     const uint64_t frame_max = encode ? gif_max_frame_bytes((uint64_t)plan.out_w * plan.out_h) : 0;
     if (result_kind) *result_kind = FLGPU_RESULT_PIXELS;
     if (encode && dst->capacity < gif_max_file_bytes(info.frames, std::max<uint64_t>(frame_max, plan.out_bytes))) return FLGPU_ERR_BUFFER_TOO_SMALL;
@@ -124,9 +130,10 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
         return FLGPU_OK;
     };
     if (encode) {
-        // the device decides: one small status record comes back, then the file or -- a frame above 256 colours -- the pixels
+        // the device decides: one small status record comes back, then the file or -- a frame above 256 colours that is not
+        // quantised -- the pixels
         const uint8_t *file = nullptr;
-        rc = encode_gif_frames(s, plan, H.frames, pitch, frame_max, &file, st);
+        rc = encode_gif_frames(s, plan, H.frames, pitch, frame_max, quantize, &file, st);
         if (rc) return rc;
         rc = collect_results(s, H.frames, ddst.data(), st);
         if (rc) return rc;
@@ -139,7 +146,7 @@ int run_gif_host(flgpu_ctx *c, const uint8_t *gif, size_t n, const flgpu_params 
             memcpy(dst->data, s->h_stage_out.p, bytes);
             dst->width = plan.out_w; dst->height = plan.out_h; dst->channels = plan.out_c; dst->flags = FLGPU_IMG_ENCODED;
             dst->bytes = bytes;
-            s->gif_encoded++; s->gif_encoded_bytes += bytes;
+            s->gif_encoded++; s->gif_encoded_bytes += bytes; s->gif_quantized_frames += status[2];
             if (result_kind) *result_kind = FLGPU_RESULT_GIF_STREAM;
             return FLGPU_OK;
         }

@@ -735,8 +735,9 @@ static int plan_gif(const uint8_t *gif, uint64_t n, const char *query_string, ui
     if (frames) *frames = info.frames;
     if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format); /* (the canvas may be beyond what a plan can describe) */
     const int rc = plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
-    /* FLGPU_ENCODE_GIF: the finished file is what will be attempted (a frame above 256 colours turns it back into pixels); the
-       per-frame parameters stay as they are, one file comes from all the frames */
+    /* FLGPU_ENCODE_GIF: the finished file is what will be attempted (a frame above 256 colours turns it back into pixels, unless
+       FLGPU_ENCODE_GIF_QUANTIZE has it quantised -- the plan is the same either way); the per-frame parameters stay as they are,
+       one file comes from all the frames */
     if (rc == FLGPU_OK && *kind == FLGPU_RESULT_PIXELS && (accept_flags & FLGPU_ENCODE_GIF) &&
         fl::gif_encodable(plan->out_w, plan->out_h, plan->out_c, info.frames, plan->out_bytes)) {
         *kind = FLGPU_RESULT_GIF_STREAM;

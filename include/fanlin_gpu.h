@@ -184,7 +184,8 @@ typedef enum flgpu_front_end {
 #define FLGPU_ENCODE_WEBP_LOSSLESS 0x200u
 /* Not a content::Format bit: the caller wants flgpu_process_gif to finish the image/gif body (FLGPU_RESULT_GIF_STREAM) where
  * every frame has at most 256 colours -- the exact-palette branch of the reference's GifEncoder (src/handler.rs:355-364).
- * Without it, and for files with a frame above 256 colours, the frames return as pixels, as before. */
+ * Without it, and for files with a frame above 256 colours (but see FLGPU_ENCODE_GIF_QUANTIZE), the frames return as pixels, as
+ * before. */
 #define FLGPU_ENCODE_GIF 0x400u
 /* Not a content::Format bit: the caller wants the library to finish lossy image/webp bodies (FLGPU_FE_WEBP_LOSSY,
  * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs below quality 100 (src/handler.rs:293-297) and the output fits the coder's
@@ -201,6 +202,12 @@ typedef enum flgpu_front_end {
  * (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF) of whichever front end the other bits select, fall-backs included.  Alone, or
  * without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_FILTER 0x4000u
+/* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
+ * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
+ * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
+ * to the library's model, not to the reference's bytes.  Frames of at most 256 colours keep the exact palette and their bytes.
+ * Alone, or without FLGPU_ENCODE_GIF, it does nothing. */
+#define FLGPU_ENCODE_GIF_QUANTIZE 0x8000u
 
 /* Output container chosen at src/handler.rs:256-261. */
 typedef enum flgpu_out_format { FLGPU_OUT_KEEP = 0, FLGPU_OUT_WEBP = 1, FLGPU_OUT_AVIF = 2 } flgpu_out_format;
@@ -601,6 +608,9 @@ int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image
  *   GIF_STREAM  dst->data holds the finished file, dst->bytes long, dst->flags has FLGPU_IMG_ENCODED
  *   PIXELS      a frame has more than 256 colours (the reference runs NeuQuant there; the library does not restate it): bytes,
  *               flags and layout exactly as without the bit
+ * With FLGPU_ENCODE_GIF_QUANTIZE as well, such a frame gets a local table of at most 256 entries from the library's own quantiser
+ * (one entry, behind the others, for all pixels of alpha 0) and the outcome is GIF_STREAM; only a file whose frames have more than
+ * 2^22 pixels still returns as PIXELS when a frame exceeds 256 colours.  Capacity and plan are those of FLGPU_ENCODE_GIF.
  * The device decides; the host reads a status record of two words and downloads the file or the pixels, never both.  The LZW
  * stream is not the gif crate's byte for byte (every 2,048 indices it restarts from a clear code, so that segments are coded
  * side by side); it decodes to exactly the frames' indices.  Outputs that are not LumaA8 / Rgba8, sides above 65,535 and
@@ -689,7 +699,8 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "gif_sources" = GIF files decoded, "gif_frames" = their frames, "gif_file_bytes" = their file bytes, "gif_upload_bytes" = what
  * crossed PCIe for them (the blob below), and with flgpu_config.profile "gif_compose_ns" = the compose kernel's HIP-event time;
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files
- * it handed back as pixels (a frame above 256 colours), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
+ * it handed back as pixels (a frame above 256 colours), "gif_quantized_frames" = frames above 256 colours that
+ * FLGPU_ENCODE_GIF_QUANTIZE gave a table (their files count as "gif_encoded"), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
  * "blur_wtile_launches", "blur_tile_launches", "blur_generic_launches" = the blur launches (flgpu_stats.blur_launches is their sum)
  * served by the window-tile matrix-pipe kernel, by the f32 LDS-tile kernel and by the generic two passes.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB

@@ -85,6 +85,8 @@ public:
     // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours
     // (FLGPU_RESULT_GIF_STREAM)
     void encode_gif() { flags_ |= FLGPU_ENCODE_GIF; }
+    // ... and also where a frame has more: such a frame is quantised on the device to at most 256 entries (the library's own rule)
+    void encode_gif_quantize() { flags_ |= FLGPU_ENCODE_GIF | FLGPU_ENCODE_GIF_QUANTIZE; }
     // not a content::Format bit: the library finishes lossy image/webp bodies, the WebP arm below quality 100
     // (FLGPU_RESULT_WEBP_STREAM; outputs over FLGPU_FE_WEBP_LOSSY's limits still come back as planes)
     void encode_webp_lossy() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY; }

@@ -92,6 +92,9 @@ pub const ENCODE_PNG: u32 = 0x100;
 pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
 // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours (RESULT_GIF_STREAM)
 pub const ENCODE_GIF: u32 = 0x400;
+// with ENCODE_GIF: a frame above 256 colours is quantised on the device (the library's own integer rule, not NeuQuant) and the file is
+// still finished; alone it does nothing.  Opt-in: pass ENCODE_GIF | ENCODE_GIF_QUANTIZE in process_gif below to never take the pixels.
+pub const ENCODE_GIF_QUANTIZE: u32 = 0x8000;
 // not a content::Format bit: finish lossy image/webp bodies on the device, the WebP arm below quality 100 (RESULT_WEBP_STREAM)
 pub const ENCODE_WEBP_LOSSY: u32 = 0x800;
 pub const ENCODE_WEBP_LOSSY_I4: u32 = 0x1000; // with ENCODE_WEBP_LOSSY: the bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
