@@ -39,6 +39,7 @@ VP8_LF_TWIN = {9: 16, 10: 17, 12: 18, 13: 19}  # front end -> its loop-filtered 
 FE_WEBP_LOSSY_ALL = (9, 10, 12, 13, 16, 17, 18, 19)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
+DECODE_PNG_ADAM7 = 0x10000  # accept_flags bit, not a content::Format bit: State.process_png also takes Adam7-interlaced files
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q < 100) on the device (FE_WEBP_LOSSY)
 ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
@@ -63,6 +64,7 @@ _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESUL
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
 IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE, IMG_WEBP_SOURCE = 1, 2, 4, 8, 16, 32, 64
 IMG_VP8_SOURCE = 128
+IMG_PNG_ADAM7 = 256  # beside IMG_PNG_SOURCE: the caller also hands in Adam7-interlaced PNG files
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 BATCH_SAME_PARAMS = 1
 (OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_OOM, ERR_DEVICE, ERR_PARSE, ERR_BUFFER_TOO_SMALL,
@@ -162,6 +164,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_transform_batch", "flgpu_transform_batch_device", "flgpu_batch_results", "flgpu_plan_shards", "flgpu_devices",
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
+    "flgpu_png_info_of_flags", "flgpu_decode_png_flags", "flgpu_debug_png_scanlines_flags",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
     "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
@@ -237,6 +240,10 @@ def load_library() -> C.CDLL:
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.flgpu_process_png_plan.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint32, C.POINTER(flgpu_plan), C.POINTER(C.c_int)]
         lib.flgpu_debug_png_scanlines.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_png_info_of_flags"):  # (Adam7-interlaced PNG sources)
+        lib.flgpu_png_info_of_flags.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(flgpu_png_info)]
+        lib.flgpu_decode_png_flags.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(flgpu_image)]
+        lib.flgpu_debug_png_scanlines_flags.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     if hasattr(lib, "flgpu_webp_info_of"):  # (the same for lossless WebP sources)
         lib.flgpu_webp_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_webp_info)]
         lib.flgpu_decode_webp.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image)]
@@ -460,20 +467,31 @@ def jpeg_info(data: bytes) -> dict:
     return {n: getattr(info, n) for n, _ in flgpu_jpeg_info._fields_}
 
 
-def png_info(data: bytes) -> dict:
-    """flgpu_png_info_of: header fields of a PNG file (pure host function); raises FanlinError(ERR_PARSE) if the container is damaged."""
+def png_info(data: bytes, adam7: bool = False) -> dict:
+    """flgpu_png_info_of: header fields of a PNG file (pure host function); raises FanlinError(ERR_PARSE) if the container is damaged.
+    ``adam7``: flgpu_png_info_of_flags with IMG_PNG_ADAM7 -- an Adam7-interlaced file of up to 8 bits per sample is supported too."""
     info = flgpu_png_info()
-    _check(load_library().flgpu_png_info_of(data, len(data), C.byref(info)))
+    if adam7:
+        _check(load_library().flgpu_png_info_of_flags(data, len(data), IMG_PNG_ADAM7, C.byref(info)))
+    else:
+        _check(load_library().flgpu_png_info_of(data, len(data), C.byref(info)))
     return {n: getattr(info, n) for n, _ in flgpu_png_info._fields_}
 
 
-def debug_png_scanlines(data: bytes) -> bytes:
-    """Host half of the PNG decode front end alone: the inflated IDAT stream (filtered scanlines), Adler-32 and filter bytes checked."""
+def debug_png_scanlines(data: bytes, adam7: bool = False) -> bytes:
+    """Host half of the PNG decode front end alone: the inflated IDAT stream (filtered scanlines), Adler-32 and filter bytes checked.
+    ``adam7``: flgpu_debug_png_scanlines_flags with IMG_PNG_ADAM7 -- for an interlaced file the seven passes' scanlines back to back."""
     lib = load_library()
     used = C.c_uint64()
-    _check(lib.flgpu_debug_png_scanlines(data, len(data), None, 0, C.byref(used)))
+    if adam7:
+        def call(out, cap):
+            return lib.flgpu_debug_png_scanlines_flags(data, len(data), IMG_PNG_ADAM7, out, cap, C.byref(used))
+    else:
+        def call(out, cap):
+            return lib.flgpu_debug_png_scanlines(data, len(data), out, cap, C.byref(used))
+    _check(call(None, 0))
     out = np.zeros(max(used.value, 1), np.uint8)
-    _check(lib.flgpu_debug_png_scanlines(data, len(data), out.ctypes.data, used.value, C.byref(used)))
+    _check(call(out.ctypes.data, used.value))
     return out[: used.value].tobytes()
 
 
@@ -513,6 +531,11 @@ def debug_vp8_blob(data: bytes) -> bytes:
     return out[: used.value].tobytes()
 
 
+class Adam7Png(bytes):
+    """A PNG file for State.process_batch that may be Adam7-interlaced: handed over as FLGPU_IMG_PNG_SOURCE | FLGPU_IMG_PNG_ADAM7.
+    (Bare ``bytes`` holding a PNG file are a FLGPU_IMG_PNG_SOURCE alone, for which an interlaced file is ERR_UNSUPPORTED.)"""
+
+
 class LossyWebp(bytes):
     """A lossy WebP file for State.process_batch: handed over as FLGPU_IMG_VP8_SOURCE.  (Bare ``bytes`` holding a WebP file are a
     FLGPU_IMG_WEBP_SOURCE, which takes lossless files only.)"""
@@ -540,6 +563,8 @@ def _source_info(data):
     """(header dict, source flag) of a file handed over as a source: PNG and WebP by their signatures, else JPEG."""
     if isinstance(data, LossyWebp):
         return vp8_info(bytes(data)), IMG_VP8_SOURCE
+    if isinstance(data, Adam7Png):
+        return png_info(bytes(data), adam7=True), IMG_PNG_SOURCE | IMG_PNG_ADAM7
     if bytes(data[:8]) == PNG_SIGNATURE:
         return png_info(bytes(data)), IMG_PNG_SOURCE
     if bytes(data[:4]) == b"RIFF" and bytes(data[8:12]) == b"WEBP":
@@ -836,31 +861,36 @@ class State:
         return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
 
     # -- PNG sources: the decode front end (handler.rs:218-220) ----------------------------------------------------
-    def decode_png(self, data: bytes) -> np.ndarray:
-        """DynamicImage::from_decoder(PngDecoder::new(..)) on the device: (h, w, 1..4) uint8."""
-        info = png_info(data)
+    def decode_png(self, data: bytes, adam7: bool = False) -> np.ndarray:
+        """DynamicImage::from_decoder(PngDecoder::new(..)) on the device: (h, w, 1..4) uint8.  ``adam7``: flgpu_decode_png_flags with
+        IMG_PNG_ADAM7 -- Adam7-interlaced files are decoded too."""
+        info = png_info(data, adam7)
         out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_decode_png(self._ctx, data, len(data), C.byref(dst)), self._ctx)
+        if adam7:
+            _check(self._lib.flgpu_decode_png_flags(self._ctx, data, len(data), IMG_PNG_ADAM7, C.byref(dst)), self._ctx)
+        else:
+            _check(self._lib.flgpu_decode_png(self._ctx, data, len(data), C.byref(dst)), self._ctx)
         return out
 
-    def process_png_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None):
+    def process_png_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None, adam7: bool = False):
         """process_pixels with a PNG FILE as the source (FLGPU_IMG_PNG_SOURCE): inflate on this thread, the rest in one device pass.
-        ``shape`` = (height, width, channels) to announce instead of what flgpu_png_info_of says (tests of rejected inputs)."""
+        ``shape`` = (height, width, channels) to announce instead of what flgpu_png_info_of says (tests of rejected inputs).
+        ``adam7``: the source carries FLGPU_IMG_PNG_ADAM7 as well -- it may be an Adam7-interlaced file."""
         if shape is None:
-            info = png_info(data)
+            info = png_info(data, adam7)
             shape = (info["height"], info["width"], max(info["channels"], 1))
         plan = plan_output(params, shape[1], shape[0], shape[2])
         out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
         buf = C.create_string_buffer(data, len(data))
-        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_PNG_SOURCE)
+        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_PNG_SOURCE | (IMG_PNG_ADAM7 if adam7 else 0))
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
         _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
         return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
 
     def process_png(self, data: bytes, query_string: str, content: "Format" = None):
         """State::process_image for a PNG input from the file bytes on: (mime, kind, payload) as process_image; AS_IS hands the
-        file itself back."""
+        file itself back.  With DECODE_PNG_ADAM7 in the content flags Adam7-interlaced files are taken too."""
         plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
         flags = content.flags if content else 0
         qs = query_string.encode()
@@ -1017,7 +1047,7 @@ class State:
         return {k: self.debug_get(k) for k in ("png_sources", "png_file_bytes", "png_upload_bytes")}
 
     def process_batch(self, images: Sequence, params: Sequence[flgpu_params]) -> List:
-        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file, or a LossyWebp (decoded by the library)."""
+        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file, or a LossyWebp, or an Adam7Png (decoded by the library)."""
         n = len(images)
         srcinfo = [_source_info(a) if isinstance(a, (bytes, bytearray)) else (None, 0) for a in images]
         infos = [s[0] for s in srcinfo]

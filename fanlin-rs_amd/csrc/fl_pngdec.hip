@@ -85,7 +85,7 @@ template <uint32_t BPP> __global__ __launch_bounds__(kPdThreads) void png_unfilt
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t h = J.height, rb = J.row_bytes;
     const size_t stride = (size_t)rb + 1u;
-    const uint8_t *__restrict__ scan = J.blob + sizeof(PngBlobHeader);
+    const uint8_t *__restrict__ scan = J.blob + sizeof(PngBlobHeader) + J.scan_off; // (a pass of an Adam7 picture: a picture of its own, no row above its first)
     uint8_t *out = J.rows;
     const uint32_t ns = rb / BPP;                                      // steps (pixels) per row: row_bytes is a multiple of BPP
     const uint32_t nc = (ns + 2u * kPdChunk - 2u) / kPdChunk;        // chunk steps per band: lane 63 reaches pixel ns - 1 at step ns + 62
@@ -181,37 +181,85 @@ template <uint32_t BPP> __global__ __launch_bounds__(kPdThreads) void png_unfilt
     }
 }
 
-// One thread per output pixel: the unfiltered rows of a palette, sub-byte or tRNS picture -> Luma8 / LumaA8 / Rgb8 / Rgba8.
+// What a picture's header says about its samples: the same for every pixel of a job.
+struct PngSampleKind {
+    uint32_t ct, d, ch, trns;
+    uint32_t per, mask, scale; // samples per byte, the sample's bits, 255 / 85 / 17 / 1
+};
+__device__ __forceinline__ PngSampleKind png_sample_kind(const PngBlobHeader *__restrict__ H)
+{
+    PngSampleKind K;
+    K.ct = H->color_type; K.d = H->bit_depth; K.ch = H->channels; K.trns = H->has_trns;
+    K.per = 8u / K.d; K.mask = (1u << K.d) - 1u; K.scale = 255u / K.mask;
+    return K;
+}
+
+// One pixel, for png_expand_kernel and png_adam7_kernel alike: sample x of an unfiltered row -> Luma8 / LumaA8 / Rgb8 / Rgba8 at o.
 // Grey samples are scaled x255 / x85 / x17, the tRNS key is compared on the raw sample, the palette (256 entries, tRNS
-// folded in, entries beyond PLTE opaque black) is read from the header.
+// folded in, entries beyond PLTE opaque black) is read from the header; 8-bit colour types are copied (png_expand_kernel meets
+// those only with a key; png_adam7_kernel without one too, and grey + alpha and RGBA).
+__device__ __forceinline__ void png_expand_sample(const PngBlobHeader *__restrict__ H, const PngSampleKind &K, const uint8_t *__restrict__ row, uint32_t x, uint8_t *__restrict__ o)
+{
+    if (K.ct == 2u) { // Rgb8 (+ key)
+        const uint32_t r = row[3u * x], g = row[3u * x + 1u], b = row[3u * x + 2u];
+        o[0] = (uint8_t)r; o[1] = (uint8_t)g; o[2] = (uint8_t)b;
+        if (K.ch == 4u) o[3] = (r == H->key[0] && g == H->key[1] && b == H->key[2]) ? 0u : 255u;
+        return;
+    }
+    if (K.ct == 6u) { o[0] = row[4u * x]; o[1] = row[4u * x + 1u]; o[2] = row[4u * x + 2u]; o[3] = row[4u * x + 3u]; return; }
+    if (K.ct == 4u) { o[0] = row[2u * x]; o[1] = row[2u * x + 1u]; return; }
+    const uint32_t byte = row[x / K.per];
+    const uint32_t v = (byte >> (8u - K.d * (x % K.per + 1u))) & K.mask;
+    if (K.ct == 3u) {
+        const uint32_t e = H->palette[v];
+        o[0] = (uint8_t)e; o[1] = (uint8_t)(e >> 8); o[2] = (uint8_t)(e >> 16);
+        if (K.ch == 4u) o[3] = (uint8_t)(e >> 24);
+    } else {
+        o[0] = (uint8_t)(v * K.scale);
+        if (K.trns) o[1] = v == H->key[0] ? 0u : 255u;
+    }
+}
+
+// One thread per output pixel: the unfiltered rows of a palette, sub-byte or tRNS picture -> pixels.
 __global__ __launch_bounds__(256) void png_expand_kernel(const PngDecJob *__restrict__ jobs)
 {
     const PngDecJob &J = jobs[blockIdx.y];
     const PngBlobHeader *__restrict__ H = reinterpret_cast<const PngBlobHeader *>(J.blob);
     const uint32_t w = J.width, rb = J.row_bytes;
     const uint32_t npx = w * J.height; // below 2^31 (png_parse_info)
-    const uint32_t ct = H->color_type, d = H->bit_depth, ch = H->channels, trns = H->has_trns;
-    const uint32_t per = 8u / d, mask = (1u << d) - 1u, scale = 255u / mask;
+    const PngSampleKind K = png_sample_kind(H);
     for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < npx; p += gridDim.x * 256u) {
         const uint32_t y = p / w, x = p - y * w;
-        const uint8_t *row = J.rows + (size_t)y * rb;
-        uint8_t *o = J.pixels + (size_t)p * ch;
-        if (ct == 2u) { // Rgb8 + key
-            const uint32_t r = row[3u * x], g = row[3u * x + 1u], b = row[3u * x + 2u];
-            o[0] = (uint8_t)r; o[1] = (uint8_t)g; o[2] = (uint8_t)b;
-            o[3] = (r == H->key[0] && g == H->key[1] && b == H->key[2]) ? 0u : 255u;
-            continue;
-        }
-        const uint32_t byte = row[x / per];
-        const uint32_t v = (byte >> (8u - d * (x % per + 1u))) & mask;
-        if (ct == 3u) {
-            const uint32_t e = H->palette[v];
-            o[0] = (uint8_t)e; o[1] = (uint8_t)(e >> 8); o[2] = (uint8_t)(e >> 16);
-            if (ch == 4u) o[3] = (uint8_t)(e >> 24);
-        } else {
-            o[0] = (uint8_t)(v * scale);
-            if (trns) o[1] = v == H->key[0] ? 0u : 255u;
-        }
+        png_expand_sample(H, K, J.rows + (size_t)y * rb, x, J.pixels + (size_t)p * K.ch);
+    }
+}
+
+// The pass of pixel (x & 7, y & 7) (fl_png_adam7.h)
+__constant__ Adam7Map c_adam7_map = adam7_map();
+
+// An Adam7 picture put together: one thread per output pixel, as above, but the sample comes from the unfiltered rows of the pass
+// the pixel belongs to -- pass (x & 7, y & 7) of the table, there sample ((x - x0) / dx, (y - y0) / dy).  The seven passes' sizes
+// and offsets are worked out once per workgroup (adam7_pass, the function the host cut the unfilter jobs with) and kept in LDS.
+// Stores are coalesced as png_expand_kernel's are; loads are a strided gather inside the pass rows (an odd picture row reads one
+// row of pass 7, an even one rows of up to four passes).  This kernel runs for every Adam7 picture, 8-bit ones without a key
+// included: their unfiltered rows are not yet the picture.
+__global__ __launch_bounds__(256) void png_adam7_kernel(const PngDecJob *__restrict__ jobs)
+{
+    __shared__ Adam7Pass s_pass[kAdam7Passes];
+    const PngDecJob &J = jobs[blockIdx.y];
+    const PngBlobHeader *__restrict__ H = reinterpret_cast<const PngBlobHeader *>(J.blob);
+    const uint32_t w = J.width;
+    const uint32_t npx = w * J.height; // below 2^31 (png_parse_info)
+    const PngSampleKind K = png_sample_kind(H);
+    if (threadIdx.x < kAdam7Passes) s_pass[threadIdx.x] = adam7_pass(w, J.height, png_pixel_bits(*H), threadIdx.x);
+    __syncthreads();
+    for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < npx; p += gridDim.x * 256u) {
+        const uint32_t y = p / w, x = p - y * w;
+        const uint32_t pass = c_adam7_map.pass[8u * (y & 7u) + (x & 7u)];
+        const Adam7Geom G = adam7_geom(pass);
+        const uint32_t px = (x - G.x0) >> G.sx, py = (y - G.y0) >> G.sy;
+        const Adam7Pass &P = s_pass[pass];
+        png_expand_sample(H, K, J.rows + P.rows_off + (size_t)py * P.row_bytes, px, J.pixels + (size_t)p * K.ch);
     }
 }
 
@@ -246,6 +294,17 @@ hipError_t launch_png_expand(const PngDecJob *jobs, uint32_t njobs, uint32_t max
     for (uint32_t base = 0; base < njobs; base += 32768u) { // grid.y limit
         const uint32_t cnt = std::min<uint32_t>(32768u, njobs - base);
         png_expand_kernel<<<dim3(gx, cnt), dim3(256), 0, st>>>(jobs + base);
+        FL_LAUNCH_CHECK();
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_png_adam7(const PngDecJob *jobs, uint32_t njobs, uint32_t max_pixels, hipStream_t st)
+{
+    const uint32_t gx = std::min<uint32_t>(std::max<uint32_t>((max_pixels + 255u) / 256u, 1u), 4096u);
+    for (uint32_t base = 0; base < njobs; base += 32768u) { // grid.y limit
+        const uint32_t cnt = std::min<uint32_t>(32768u, njobs - base);
+        png_adam7_kernel<<<dim3(gx, cnt), dim3(256), 0, st>>>(jobs + base);
         FL_LAUNCH_CHECK();
     }
     return hipSuccess;

@@ -90,7 +90,8 @@ struct Container {
 };
 
 // verify = false: lengths and layout only (a caller that sizes its buffers first and lets png_decode_scanlines check the CRCs, once)
-int walk(const uint8_t *data, size_t n, Container &C, bool verify)
+// adam7 = true: an interlaced file of depth <= 8 is supported, bounded on its seven passes' scanlines
+int walk(const uint8_t *data, size_t n, Container &C, bool verify, bool adam7)
 {
     auto crc_ok = [verify](const Chunk &c) { return !verify || chunk_crc_ok(c); };
     PngInfo &I = C.info;
@@ -156,6 +157,7 @@ int walk(const uint8_t *data, size_t n, Container &C, bool verify)
     const uint64_t row_bits = (uint64_t)I.width * samples * d;
     const uint64_t row_bytes = (row_bits + 7u) / 8u;
     I.bpp = samples * d >= 8u ? samples * d / 8u : 1u;
+    I.pixel_bits = samples * d;
     uint32_t channels = 0;
     switch (I.color_type) {
     case 0: channels = I.has_trns ? 2u : 1u; break;
@@ -164,8 +166,9 @@ int walk(const uint8_t *data, size_t n, Container &C, bool verify)
     case 4: channels = 2u; break;
     case 6: channels = 4u; break;
     }
-    I.supported = d <= 8 && !I.interlaced;
-    const uint64_t scan = (uint64_t)I.height * (1u + row_bytes), decoded = (uint64_t)I.width * I.height * channels;
+    I.supported = d <= 8 && (!I.interlaced || adam7);
+    const uint64_t scan = I.interlaced ? adam7_scan_bytes(I.width, I.height, I.pixel_bits) : (uint64_t)I.height * (1u + row_bytes);
+    const uint64_t decoded = (uint64_t)I.width * I.height * channels;
     if (scan >= kPngMaxDecoded || decoded >= kPngMaxDecoded) I.supported = 0;
     I.row_bytes = row_bytes <= 0xffffffffu ? (uint32_t)row_bytes : 0u;
     I.channels = I.supported ? channels : 0u;
@@ -425,18 +428,18 @@ int inflate(BitReader &br, uint8_t *out, size_t cap, size_t *produced)
 
 } // namespace
 
-int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc)
+int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc, bool adam7)
 {
     Container C;
-    const int rc = walk(data, n, C, verify_crc);
+    const int rc = walk(data, n, C, verify_crc, adam7);
     info = C.info;
     return rc;
 }
 
-int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr)
+int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr, bool adam7)
 {
     Container C;
-    int rc = walk(data, n, C, true);
+    int rc = walk(data, n, C, true, adam7);
     if (rc) return rc;
     const PngInfo &I = C.info;
     if (!I.supported) return kPngUnsupported;
@@ -447,9 +450,14 @@ int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t ca
     rc = inflate(br, scan, want, &produced);
     if (rc) return rc;
     if (produced != want) return kPngParse; // too few bytes for the picture
-    const size_t stride = 1u + (size_t)I.row_bytes;
-    for (uint32_t y = 0; y < I.height; ++y)
-        if (scan[(size_t)y * stride] > 4u) return kPngParse; // the kernel never sees another filter type
+    // the kernel never sees another filter type than 0..4: every row's filter byte, for an interlaced file every pass row's
+    for (uint32_t p = 0; p < (I.interlaced ? kAdam7Passes : 1u); ++p) {
+        const Adam7Pass P = I.interlaced ? adam7_pass(I.width, I.height, I.pixel_bits, p) : Adam7Pass{I.width, I.height, I.row_bytes, 0, 0};
+        if (!P.w || !P.h) continue;
+        const size_t stride = 1u + (size_t)P.row_bytes;
+        for (uint32_t y = 0; y < P.h; ++y)
+            if (scan[(size_t)P.scan_off + (size_t)y * stride] > 4u) return kPngParse;
+    }
     if (hdr) {
         memset(hdr, 0, sizeof(*hdr));
         hdr->magic = kPngMagic;
@@ -457,7 +465,9 @@ int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t ca
         hdr->color_type = I.color_type; hdr->bit_depth = I.bit_depth;
         hdr->channels = I.channels; hdr->bpp = I.bpp; hdr->row_bytes = I.row_bytes;
         hdr->has_trns = I.has_trns;
-        hdr->direct = (I.bit_depth == 8 && I.color_type != 3 && !I.has_trns) ? 1u : 0u;
+        hdr->interlaced = I.interlaced;
+        // (an interlaced picture's rows are never its pixels: the de-interlace kernel puts them together)
+        hdr->direct = (I.bit_depth == 8 && I.color_type != 3 && !I.has_trns && !I.interlaced) ? 1u : 0u;
         hdr->scan_off = (uint32_t)sizeof(PngBlobHeader);
         hdr->total_bytes = (uint32_t)(sizeof(PngBlobHeader) + want);
         // the key is compared on the raw sample (its low byte: samples have at most 8 bits here)

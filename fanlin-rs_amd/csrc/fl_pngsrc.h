@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fl_png_adam7.h"
+
 namespace fl {
 
 struct PngInfo {
@@ -15,10 +17,11 @@ struct PngInfo {
     uint32_t channels = 0;     // of the picture the pipeline sees (1 Luma8, 2 LumaA8, 3 Rgb8, 4 Rgba8); 0 if unsupported
     uint32_t interlaced = 0;   // Adam7
     uint32_t has_trns = 0;
-    uint32_t supported = 0;    // 1 = FLGPU_IMG_PNG_SOURCE decodes it: depth <= 8, no interlace
+    uint32_t supported = 0;    // 1 = FLGPU_IMG_PNG_SOURCE decodes it: depth <= 8, no interlace (or, asked with adam7 = true, Adam7)
     uint32_t row_bytes = 0;    // ceil(width * samples * depth / 8): a scanline without its filter byte
     uint32_t bpp = 0;          // the filters' pixel distance in bytes: max(1, samples * depth / 8)
     uint32_t plte_entries = 0;
+    uint32_t pixel_bits = 0;   // samples * depth
     uint64_t idat_bytes = 0;   // summed IDAT payloads
 };
 
@@ -42,9 +45,9 @@ struct alignas(16) PngBlobHeader {
     uint32_t has_trns;
     uint32_t key[3];          // tRNS of colour types 0 (key[0]) and 2: the raw sample values, compared before scaling
     uint32_t direct;          // 1 = the unfiltered rows ARE the pixels (8-bit colour type 0 / 2 / 4 / 6 without tRNS)
-    uint32_t scan_off;        // byte offset of the scanlines: height x (1 + row_bytes)
+    uint32_t scan_off;        // byte offset of the scanlines: height x (1 + row_bytes), or the seven passes' (adam7_pass of width, height, depth)
     uint32_t total_bytes;     // header + scanlines
-    uint32_t pad;
+    uint32_t interlaced;      // 1 = Adam7: the scanlines are those of the passes, back to back (fl_png_adam7.h)
     uint32_t palette[256];    // r | g << 8 | b << 16 | a << 24
 };
 
@@ -52,14 +55,23 @@ struct alignas(16) PngBlobHeader {
 // interpreted: IHDR, PLTE, tRNS, IDAT, IEND).
 // verify_crc = false: layout and lengths only, for a caller that sizes its buffers from the header and then calls
 // png_decode_scanlines, which verifies every CRC itself: the file is summed once per request.
-int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc = true);
+// adam7 = true: an Adam7-interlaced file of depth <= 8 is supported too, its size bounds taken on the seven passes' scanlines.
+int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc = true, bool adam7 = false);
+
+// Bits per pixel of the blob's samples as stored (pixel_bits of PngInfo)
+FL_A7_HD uint32_t png_pixel_bits(const PngBlobHeader &h) { return h.bit_depth < 8u ? h.bit_depth : 8u * h.bpp; }
 
 // Bytes of the scanlines / of the whole blob for `info`.
-inline size_t png_scan_bytes(const PngInfo &info) { return (size_t)info.height * (1u + (size_t)info.row_bytes); }
+inline size_t png_scan_bytes(const PngInfo &info)
+{
+    if (info.interlaced) return (size_t)adam7_scan_bytes(info.width, info.height, info.pixel_bits);
+    return (size_t)info.height * (1u + (size_t)info.row_bytes);
+}
 inline size_t png_blob_bytes(const PngInfo &info) { return sizeof(PngBlobHeader) + png_scan_bytes(info); }
 
 // Inflates the IDAT stream of a supported file into scan[0 .. png_scan_bytes) and checks Adler-32 and the filter bytes;
 // hdr (optional) receives the header of the blob.  `scan` is the inflate window: nothing else is allocated.
-int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr);
+// adam7 = true: as for png_parse_info; the stream of an interlaced file is left as it is stored, pass after pass.
+int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr, bool adam7 = false);
 
 } // namespace fl

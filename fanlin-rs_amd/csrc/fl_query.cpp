@@ -426,30 +426,33 @@ try {
 
 /* ---- PNG sources ---------------------------------------------------------------------------------------------------- */
 
-int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info)
+int flgpu_png_info_of_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_png_info *info)
 try {
     if (!png || !info) return FLGPU_ERR_INVALID_ARG;
     fl::PngInfo I;
-    if (fl::png_parse_info(png, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    if (fl::png_parse_info(png, (size_t)n, I, true, (src_flags & FLGPU_IMG_PNG_ADAM7) != 0) != 0) return FLGPU_ERR_PARSE;
     memset(info, 0, sizeof(*info));
     info->width = I.width; info->height = I.height; info->color_type = I.color_type; info->bit_depth = I.bit_depth;
     info->channels = I.channels; info->interlaced = I.interlaced; info->has_trns = I.has_trns; info->supported = I.supported;
     return FLGPU_OK;
 } FL_ABI_CATCH
 
+int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info) { return flgpu_png_info_of_flags(png, n, 0, info); }
+
 static int plan_png(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
                     flgpu_plan *plan, int *kind, int *out_format)
 {
     // (layout only here: flgpu_transform verifies the CRCs once, under the decode bound; as_is serves the file unread, as the reference does)
     if (!png) return FLGPU_ERR_INVALID_ARG;
+    const bool adam7 = (accept_flags & FLGPU_DECODE_PNG_ADAM7) != 0;
     fl::PngInfo info;
-    if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
+    if (fl::png_parse_info(png, (size_t)n, info, false, adam7) != 0) return FLGPU_ERR_PARSE;
     memset(src, 0, sizeof(*src));
     src->data = const_cast<uint8_t *>(png);
     src->capacity = n;
     /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
     src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
-    src->flags = FLGPU_IMG_PNG_SOURCE;
+    src->flags = FLGPU_IMG_PNG_SOURCE | (adam7 ? FLGPU_IMG_PNG_ADAM7 : 0u);
     if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
     /* the PNG decoder reports no orientation (handler.rs:206 sees none): 1 */
     return plan_request(src, 1, query_string, accept_flags, FLGPU_IN_PNG, p, plan, kind, out_format);
@@ -474,28 +477,37 @@ try {
     return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
 } FL_ABI_CATCH
 
-int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst)
+int flgpu_decode_png_flags(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_image *dst)
 try {
     if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
     if (!png) return FLGPU_ERR_INVALID_ARG;
+    const uint32_t adam7 = src_flags & FLGPU_IMG_PNG_ADAM7;
     fl::PngInfo info;
-    if (fl::png_parse_info(png, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE; // (CRCs: once, in flgpu_transform)
+    if (fl::png_parse_info(png, (size_t)n, info, false, adam7 != 0) != 0) return FLGPU_ERR_PARSE; // (CRCs: once, in flgpu_transform)
     if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    return decode_file(ctx, png, n, info.width, info.height, info.channels, FLGPU_IMG_PNG_SOURCE, dst);
+    return decode_file(ctx, png, n, info.width, info.height, info.channels, FLGPU_IMG_PNG_SOURCE | adam7, dst);
 } FL_ABI_CATCH
 
-int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst) { return flgpu_decode_png_flags(ctx, png, n, 0, dst); }
+
+int flgpu_debug_png_scanlines_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used)
 try {
     if (!png || !used) return FLGPU_ERR_INVALID_ARG;
+    const bool adam7 = (src_flags & FLGPU_IMG_PNG_ADAM7) != 0;
     fl::PngInfo I;
-    if (fl::png_parse_info(png, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
+    if (fl::png_parse_info(png, (size_t)n, I, true, adam7) != 0) return FLGPU_ERR_PARSE;
     if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
     *used = fl::png_scan_bytes(I);
     if (!out) return FLGPU_OK;
     if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    const int rc = fl::png_decode_scanlines(png, (size_t)n, out, (size_t)capacity, nullptr);
+    const int rc = fl::png_decode_scanlines(png, (size_t)n, out, (size_t)capacity, nullptr, adam7);
     return fl::png_status(rc);
 } FL_ABI_CATCH
+
+int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
+{
+    return flgpu_debug_png_scanlines_flags(png, n, 0, out, capacity, used);
+}
 
 /* ---- lossless WebP sources -------------------------------------------------------------------------------------------- */
 

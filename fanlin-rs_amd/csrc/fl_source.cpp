@@ -216,8 +216,13 @@ static int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
 static int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info)
 {
     // (layout only: png_source_to_blob verifies the CRCs, so the file is summed once per request)
-    if (png_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error("PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)"); return FLGPU_ERR_UNSUPPORTED; }
+    const bool adam7 = (src->flags & FLGPU_IMG_PNG_ADAM7) != 0;
+    if (png_parse_info(src->data, (size_t)src->capacity, info, false, adam7) != 0) { c->set_error("malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)"); return FLGPU_ERR_PARSE; }
+    if (!info.supported) {
+        c->set_error(adam7 ? "PNG file not covered by the device decoder (16-bit samples, or 2^31 bytes and more)"
+                           : "PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)");
+        return FLGPU_ERR_UNSUPPORTED;
+    }
     if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
         c->set_error("FLGPU_IMG_PNG_SOURCE: width / height / channels do not match the file (see flgpu_png_info_of)");
         return FLGPU_ERR_INVALID_ARG;
@@ -228,7 +233,8 @@ static int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info)
 static int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used)
 {
     if (cap < sizeof(PngBlobHeader)) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    const int rc = png_decode_scanlines(src->data, (size_t)src->capacity, blob + sizeof(PngBlobHeader), cap - sizeof(PngBlobHeader), hdr);
+    const int rc = png_decode_scanlines(src->data, (size_t)src->capacity, blob + sizeof(PngBlobHeader), cap - sizeof(PngBlobHeader), hdr,
+                                        (src->flags & FLGPU_IMG_PNG_ADAM7) != 0);
     if (rc == kPngParse) c->set_error("malformed PNG file (chunk CRC, Huffman code, distance, length, Adler-32 or filter byte)");
     if (rc == kPngUnsupported) c->set_error("PNG stream holds more scanline data than its IHDR implies");
     if (rc) return png_status(rc);
@@ -239,49 +245,79 @@ static int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blo
 
 static int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource *const *srcs, hipStream_t st)
 {
-    size_t np = 0, scratch = 0;
+    // np pictures; nu unfilter jobs (one per picture, one per non-empty pass of an Adam7 picture), nx_all expand and na_all de-interlace jobs
+    size_t np = 0, nu = 0, nx_all = 0, na_all = 0, scratch = 0;
     for (size_t i = 0; i < n; ++i) {
         if (srcs[i]->kind != SRC_PNG) continue;
         const PngBlobHeader *H = &srcs[i]->png;
         ++np;
         scratch += align_up((size_t)H->width * H->height * H->channels + 64, 256);
-        if (!H->direct) scratch += align_up((size_t)H->height * H->row_bytes + 64, 256);
+        if (H->interlaced) {
+            scratch += align_up((size_t)adam7_rows_bytes(H->width, H->height, png_pixel_bits(*H)) + 64, 256);
+            for (uint32_t p = 0; p < kAdam7Passes; ++p) {
+                const Adam7Pass P = adam7_pass(H->width, H->height, png_pixel_bits(*H), p);
+                if (P.w && P.h) ++nu;
+            }
+            ++na_all;
+            continue;
+        }
+        ++nu;
+        if (!H->direct) { scratch += align_up((size_t)H->height * H->row_bytes + 64, 256); ++nx_all; }
     }
     if (!np) return FLGPU_OK;
     FL_HIP(c, c->d_pngdec.reserve(scratch), "PNG decode scratch");
-    FL_HIP(c, c->h_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
-    FL_HIP(c, c->d_pngjobs.reserve(2 * np * sizeof(PngDecJob)), "PNG decode descriptors");
-    // jobs ordered by bpp (one launch per pixel size), behind them once more the ones the expand kernel takes
-    PngDecJob *jobs = static_cast<PngDecJob *>(c->h_pngjobs.p), *xjobs = jobs + np;
-    uint32_t per_bpp[4] = {0, 0, 0, 0}, nx = 0, max_px = 0;
-    size_t off = 0, k = 0;
+    FL_HIP(c, c->h_pngjobs.reserve((nu + nx_all + na_all) * sizeof(PngDecJob)), "PNG decode descriptors");
+    FL_HIP(c, c->d_pngjobs.reserve((nu + nx_all + na_all) * sizeof(PngDecJob)), "PNG decode descriptors");
+    // unfilter jobs ordered by bpp (one launch per pixel size), behind them once more the pictures the expand kernel takes, then the Adam7 pictures
+    PngDecJob *jobs = static_cast<PngDecJob *>(c->h_pngjobs.p), *xjobs = jobs + nu, *ajobs = xjobs + nx_all;
+    uint32_t per_bpp[4] = {0, 0, 0, 0}, nx = 0, na = 0, max_px = 0, max_apx = 0;
+    size_t off = 0, k = 0, seen = 0;
     for (uint32_t bpp = 1; bpp <= 4; ++bpp)
         for (size_t i = 0; i < n; ++i) {
             if (srcs[i]->kind != SRC_PNG || srcs[i]->png.bpp != bpp) continue;
             const PngBlobHeader &H = srcs[i]->png;
-            PngDecJob &j = jobs[k++];
+            PngDecJob j;
             memset(&j, 0, sizeof(j));
             j.blob = dsrc[i].data;
             j.width = H.width; j.height = H.height; j.row_bytes = H.row_bytes; j.bpp = H.bpp;
             j.pixels = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.width * H.height * H.channels + 64, 256);
             j.rows = j.pixels;
-            if (!H.direct) {
-                j.rows = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.height * H.row_bytes + 64, 256);
-                xjobs[nx++] = j;
-                max_px = std::max(max_px, H.width * H.height);
+            if (H.interlaced) {
+                // every non-empty pass is a picture of its own to the unfilter kernel; the de-interlace kernel takes the whole one
+                j.rows = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)adam7_rows_bytes(H.width, H.height, png_pixel_bits(H)) + 64, 256);
+                for (uint32_t p = 0; p < kAdam7Passes; ++p) {
+                    const Adam7Pass P = adam7_pass(H.width, H.height, png_pixel_bits(H), p);
+                    if (!P.w || !P.h) continue;
+                    PngDecJob &u = jobs[k++];
+                    u = j;
+                    u.width = P.w; u.height = P.h; u.row_bytes = P.row_bytes;
+                    u.scan_off = (uint32_t)P.scan_off; u.rows = j.rows + P.rows_off;
+                    per_bpp[bpp - 1]++;
+                }
+                ajobs[na++] = j;
+                max_apx = std::max(max_apx, H.width * H.height);
+            } else {
+                if (!H.direct) {
+                    j.rows = static_cast<uint8_t *>(c->d_pngdec.p) + off; off += align_up((size_t)H.height * H.row_bytes + 64, 256);
+                    xjobs[nx++] = j;
+                    max_px = std::max(max_px, H.width * H.height);
+                }
+                jobs[k++] = j;
+                per_bpp[bpp - 1]++;
             }
-            per_bpp[bpp - 1]++;
+            ++seen;
             if (!tl_force_host_huffman) { c->png_sources++; c->png_upload_bytes += H.total_bytes; } // (not twice when a batch is run again with the host Huffman decoder)
             dsrc[i].data = j.pixels;
             dsrc[i].channels = H.channels;
             dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
-            dsrc[i].flags &= ~FLGPU_IMG_PNG_SOURCE;
+            dsrc[i].flags &= ~(FLGPU_IMG_PNG_SOURCE | FLGPU_IMG_PNG_ADAM7);
         }
-    if (k != np) { c->set_error("PNG source: pixel size outside 1..4 bytes"); return FLGPU_ERR_INVALID_ARG; }
-    FL_HIP(c, hipMemcpyAsync(c->d_pngjobs.p, jobs, (np + nx) * sizeof(PngDecJob), hipMemcpyHostToDevice, st), "PNG decode descriptors");
+    if (seen != np) { c->set_error("PNG source: pixel size outside 1..4 bytes"); return FLGPU_ERR_INVALID_ARG; }
+    FL_HIP(c, hipMemcpyAsync(c->d_pngjobs.p, jobs, (nu + nx + na) * sizeof(PngDecJob), hipMemcpyHostToDevice, st), "PNG decode descriptors");
     const PngDecJob *d_jobs = static_cast<const PngDecJob *>(c->d_pngjobs.p);
     FL_HIP(c, launch_png_unfilter(d_jobs, per_bpp, st), "PNG unfilter kernel");
-    if (nx) FL_HIP(c, launch_png_expand(d_jobs + np, nx, max_px, st), "PNG expand kernel");
+    if (nx) FL_HIP(c, launch_png_expand(d_jobs + nu, nx, max_px, st), "PNG expand kernel");
+    if (na) FL_HIP(c, launch_png_adam7(d_jobs + nu + nx, na, max_apx, st), "PNG Adam7 kernel");
     return FLGPU_OK;
 }
 
@@ -549,6 +585,10 @@ int debug_vp8_planes(flgpu_ctx *c, const uint8_t *file, size_t n, int filter, ui
 int source_probe(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
 {
     out.kind = source_kind(src->flags);
+    if ((src->flags & FLGPU_IMG_PNG_ADAM7) && !(src->flags & FLGPU_IMG_PNG_SOURCE)) {
+        c->set_error("FLGPU_IMG_PNG_ADAM7 without FLGPU_IMG_PNG_SOURCE");
+        return FLGPU_ERR_INVALID_ARG;
+    }
     switch (out.kind) {
     case SRC_JPEG:
         if (jpeg_parse_info(src->data, (size_t)src->capacity, out.jpeg) != 0) return FLGPU_ERR_INVALID_ARG;

@@ -97,8 +97,15 @@ typedef struct flgpu_image {
                                          chunk CRCs and inflate on the calling thread, the row filters and the expansion of palette / sub-byte /
                                          tRNS pictures on the device -- replacing DynamicImage::from_decoder for PNG inputs (src/handler.rs:218-220).
                                          The filtered scanlines cross PCIe: the pixel bytes + height for 8-bit RGB, 3-24 x less for palette and
-                                         sub-byte pictures.  Files it does not cover (16-bit samples, Adam7): FLGPU_ERR_UNSUPPORTED (decode on the
-                                         host); damaged files: FLGPU_ERR_PARSE. */
+                                         sub-byte pictures.  Files it does not cover (16-bit samples; Adam7 unless FLGPU_IMG_PNG_ADAM7 is set too):
+                                         FLGPU_ERR_UNSUPPORTED (decode on the host); damaged files: FLGPU_ERR_PARSE. */
+#define FLGPU_IMG_PNG_ADAM7       256u /* in, beside FLGPU_IMG_PNG_SOURCE (without it: FLGPU_ERR_INVALID_ARG): the caller also hands in Adam7-
+                                         interlaced files of up to 8 bits per sample (flgpu_png_info_of_flags says which).  The inflated
+                                         stream -- the seven passes' filtered scanlines back to back -- crosses PCIe as it is stored; the
+                                         device undoes the row filters pass by pass and puts the passes together while it expands the
+                                         samples.  Opt-in, because without it an interlaced file keeps its answer of before
+                                         (FLGPU_ERR_UNSUPPORTED) for callers that route on it.  Nothing changes for a non-interlaced file.
+                                         16-bit samples stay FLGPU_ERR_UNSUPPORTED; the PNG encoder never writes interlaced files. */
 #define FLGPU_IMG_WEBP_SOURCE     64u /* in (src of flgpu_transform / flgpu_transform_batch): data holds a lossless WebP FILE of `capacity` bytes instead
                                          of pixels, width / height / channels say what it decodes to (flgpu_webp_info_of): the library decodes it
                                          itself -- container, prefix codes, LZ77 and colour cache on the calling thread, the predictor, cross-colour,
@@ -178,6 +185,10 @@ typedef enum flgpu_front_end {
 /* Not a content::Format bit: the caller wants the library to finish image/png bodies (FLGPU_FE_PNG,
  * FLGPU_RESULT_PNG_STREAM) for PNG inputs that stay PNG.  Without it such requests return pixels, as before. */
 #define FLGPU_ENCODE_PNG 0x100u
+/* Not a content::Format bit: flgpu_process_png / flgpu_process_png_plan also take Adam7-interlaced files (they hand the file on
+ * with FLGPU_IMG_PNG_ADAM7).  Without it such a file is FLGPU_ERR_UNSUPPORTED (as_is aside), as before.  Every other entry point
+ * ignores the bit. */
+#define FLGPU_DECODE_PNG_ADAM7 0x10000u
 /* Not a content::Format bit: the caller wants the library to finish lossless image/webp bodies (FLGPU_FE_WEBP_LOSSLESS,
  * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs at quality 100 (src/handler.rs:286-292).  Without it such requests
  * return pixels, as before. */
@@ -474,18 +485,26 @@ typedef struct flgpu_png_info {
                                    x17), 0 + tRNS -> 2 (LumaA8), 2 -> 3, 2 + tRNS -> 4, 3 -> 3, 3 + tRNS -> 4, 4 -> 2, 6 -> 4 */
     uint32_t interlaced;        /* Adam7 */
     uint32_t has_trns;
-    uint32_t supported;         /* 1 = FLGPU_IMG_PNG_SOURCE decodes it; 0: 16-bit samples, Adam7 interlace, 2^31 bytes or more */
+    uint32_t supported;         /* 1 = FLGPU_IMG_PNG_SOURCE decodes it; 0: 16-bit samples, Adam7 interlace (but see
+                                   flgpu_png_info_of_flags), 2^31 bytes or more */
 } flgpu_png_info;
 /* Header and chunk inspection only (no device needed): signature, IHDR, PLTE, tRNS, IDAT..., IEND with their CRCs; other ancillary
  * chunks are skipped.  FLGPU_ERR_PARSE if the bytes are not an intact PNG container.  PNG has no orientation (the image crate
  * reports none): the pipeline runs with orientation 1. */
 int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info);
+/* flgpu_png_info_of for a source that will carry src_flags: with FLGPU_IMG_PNG_ADAM7 among them an Adam7 file of up to 8 bits per
+ * sample whose seven passes' scanlines and whose pixels stay below 2^31 bytes reports supported = 1 and its channels (interlaced = 1
+ * says which kind it is).  Without that flag: flgpu_png_info_of. */
+int flgpu_png_info_of_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_png_info *info);
 /* Decodes a supported PNG to interleaved pixels in HOST memory at dst->data (capacity >= width*height*channels). */
 int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst);
+/* flgpu_decode_png (which is this with src_flags 0) for a file handed over with src_flags: FLGPU_IMG_PNG_ADAM7 admits Adam7 files. */
+int flgpu_decode_png_flags(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_image *dst);
 /* State::process_image for a PNG input from the file bytes on, input_format FLGPU_IN_PNG: query parsing, size gate, as_is, container
  * negotiation, then inflate + unfilter + pixel pipeline (+ PNG encode with FLGPU_ENCODE_PNG) in one pass.  Same outcomes as
  * flgpu_process_image; additionally FLGPU_ERR_UNSUPPORTED for files the decoder does not cover (the host then decodes with its own
- * decoder and calls flgpu_process_image) and FLGPU_ERR_PARSE for damaged ones. */
+ * decoder and calls flgpu_process_image) and FLGPU_ERR_PARSE for damaged ones.  With FLGPU_DECODE_PNG_ADAM7 in accept_flags the
+ * decoder covers Adam7-interlaced files too. */
 int flgpu_process_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags,
                       flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format);
 int flgpu_process_png_plan(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan,
@@ -688,7 +707,8 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base" (see flgpu_debug_vp8_filter_costs); "reset" restores every default.
  * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
  * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
- * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines);
+ * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines;
+ * for an Adam7 picture the header + the sum over its non-empty passes of pass height x (1 + pass row bytes));
  * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
  * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
@@ -730,6 +750,10 @@ int flgpu_debug_jpeg_blob(const uint8_t *jpeg, uint64_t n, uint8_t *blob, uint64
  * FLGPU_IMG_PNG_SOURCE, height x (1 + row bytes) -- the inflated IDAT stream, Adler-32 and filter bytes checked.
  * out == NULL: *used = capacity to provide. */
 int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used);
+/* The same for a source that carries src_flags (flgpu_debug_png_scanlines is this with 0).  With FLGPU_IMG_PNG_ADAM7, for an
+ * interlaced file: the seven passes' filtered scanlines back to back, for each non-empty pass its height x (1 + its row bytes) -- the
+ * inflated IDAT stream as it is stored, Adler-32 and every pass row's filter byte checked. */
+int flgpu_debug_png_scanlines_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used);
 
 /* The host half of the lossless WebP decode front end alone (csrc/fl_webpsrc.h): the blob flgpu_transform uploads for a
  * FLGPU_IMG_WEBP_SOURCE -- WebpBlobHeader, the mode / cross-colour images, the palette, the entropy-decoded residual picture.

@@ -80,6 +80,7 @@ const IMG_HAS_ALPHA: u32 = 2;
 const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the JPEG FILE (capacity = its length), not pixels
 #[allow(dead_code)]
 const IMG_PNG_SOURCE: u32 = 32;  // ... `data` holds the PNG FILE (flgpu_process_png sets it itself)
+const IMG_PNG_ADAM7: u32 = 256;  // ... beside IMG_PNG_SOURCE: the file may be Adam7-interlaced (flgpu_process_png sets it for DECODE_PNG_ADAM7)
 #[allow(dead_code)]
 const IMG_WEBP_SOURCE: u32 = 64; // ... `data` holds the lossless WebP FILE (flgpu_process_webp sets it itself)
 #[allow(dead_code)]
@@ -88,6 +89,8 @@ pub const ACCEPT_WEBP: u32 = 1;   // content::Format bits (src/content.rs:12-48)
 pub const ACCEPT_AVIF: u32 = 2;
 // not a content::Format bit: finish image/png bodies on the device for PNG inputs that stay PNG (RESULT_PNG_STREAM)
 pub const ENCODE_PNG: u32 = 0x100;
+// not a content::Format bit: process_png also takes Adam7-interlaced PNG files (up to 8 bits per sample); without it they are None
+pub const DECODE_PNG_ADAM7: u32 = 0x10000;
 // not a content::Format bit: finish lossless image/webp bodies on the device, the WebP arm at quality 100 (RESULT_WEBP_STREAM)
 pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
 // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours (RESULT_GIF_STREAM)
@@ -124,6 +127,7 @@ extern "C" {
     fn flgpu_process_jpeg(ctx: *mut c_void, jpeg: *const u8, n: u64, query: *const c_char, accept: u32,
                           dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
     fn flgpu_png_info_of(png: *const u8, n: u64, info: *mut FlPngInfo) -> c_int;
+    fn flgpu_png_info_of_flags(png: *const u8, n: u64, src_flags: u32, info: *mut FlPngInfo) -> c_int;
     fn flgpu_process_png_plan(png: *const u8, n: u64, query: *const c_char, accept: u32, plan: *mut FlPlan, kind: *mut c_int) -> c_int;
     fn flgpu_process_png(ctx: *mut c_void, png: *const u8, n: u64, query: *const c_char, accept: u32,
                          dst: *mut FlImage, plan: *mut FlPlan, kind: *mut c_int, out_format: *mut c_int) -> c_int;
@@ -272,9 +276,16 @@ impl Gpu {
         if unsafe { flgpu_png_info_of(original.as_ptr(), original.len() as u64, &mut info) } == 0 { Some(info) } else { None }
     }
 
+    /// `png_info` for a caller that passes DECODE_PNG_ADAM7: `supported` is 1 for Adam7-interlaced files of up to 8 bits per sample too.
+    pub fn png_info_adam7(original: &[u8]) -> Option<FlPngInfo> {
+        let mut info = FlPngInfo::default();
+        if unsafe { flgpu_png_info_of_flags(original.as_ptr(), original.len() as u64, IMG_PNG_ADAM7, &mut info) } == 0 { Some(info) } else { None }
+    }
+
     /// `process_image` for a PNG input FROM THE FILE BYTES ON (src/handler.rs:198-308 in one call, input format PNG, orientation 1):
     /// chunk CRCs + inflate on this thread, row filters + palette / tRNS expansion + pixel pipeline (+ the PNG encoder with ENCODE_PNG
-    /// in `accept`) in one device pass.  Ok(None): a file the decoder does not cover (16-bit samples, Adam7) or cannot read --
+    /// in `accept`) in one device pass.  Ok(None): a file the decoder does not cover (16-bit samples; Adam7 unless `accept` has
+    /// DECODE_PNG_ADAM7, with which the device puts the seven passes together) or cannot read --
     /// decode with the reference's own decoder, which also words the error, and use `transform`.  Otherwise as `process_jpeg`:
     /// RESULT_AS_IS, RESULT_PNG_STREAM (the finished image/png body), RESULT_WEBP_PLANES, RESULT_WEBP_STREAM or RESULT_PIXELS.
     pub fn process_png(&self, original: &[u8], query: &str, accept: u32)
@@ -282,7 +293,8 @@ impl Gpu {
     {
         let q = std::ffi::CString::new(query)?;
         let (mut plan, mut kind, mut fmt) = (FlPlan::default(), 0 as c_int, 0 as c_int);
-        if Self::png_info(original).map_or(true, |i| i.supported == 0) { return Ok(None); }
+        let info = if accept & DECODE_PNG_ADAM7 != 0 { Self::png_info_adam7(original) } else { Self::png_info(original) };
+        if info.map_or(true, |i| i.supported == 0) { return Ok(None); }
         check(unsafe { flgpu_process_png_plan(original.as_ptr(), original.len() as u64, q.as_ptr(), accept, &mut plan, &mut kind) })?;
         if kind == RESULT_AS_IS { return Ok(Some((kind, 0, plan, Vec::new()))); }
         let mut out = vec![0u8; plan.max_out_bytes as usize];
@@ -447,7 +459,8 @@ fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(
 //         }
 //     }
 //
-// PNG inputs the same way (src/handler.rs:218-220 + everything below them; `accept | gpu::ENCODE_PNG` to get finished image/png bodies):
+// PNG inputs the same way (src/handler.rs:218-220 + everything below them; `accept | gpu::ENCODE_PNG` to get finished image/png bodies;
+// with `| gpu::DECODE_PNG_ADAM7` there and `png_info_adam7` here, Adam7-interlaced files go the same way instead of to the decoder below):
 //     if gpu::Gpu::png_info(original).map_or(false, |i| i.supported != 0) {
 //         if let Some((kind, out_format, plan, bytes)) = self.gpu.process_png(original, raw_query, accept | gpu::ENCODE_PNG)? {
 //             match kind {
