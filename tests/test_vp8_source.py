@@ -2,7 +2,9 @@
 (tests/test_vp8_source_host.py), dequantisation, inverse transforms, intra prediction, loop filter, ALPH filters, up-sampling and
 YUV -> RGB on the device (csrc/fl_vp8dec.hip).  The arbiter is libwebp -- WebPDecodeYUV for the planes, WebPDecodeRGB / RGBA for the
 pixels -- and, for the files of tests/vp8_model.py, the model's own reconstruction; the decode is bit-exact, so every request on a
-file is held to equality with the same request on the decoded pixels."""
+file is held to equality with the same request on the decoded pixels.  How lanes, waves, rounds and bands share a picture is
+in the .hip file alone, out of the host twin's reach: the corpus holds the sizes around every such seam (cases.SCHEDULING;
+tests/test_vp8_source_host.py asserts that it does), and they are decoded here."""
 import io
 import threading
 
@@ -148,6 +150,26 @@ def test_mixed_batch_equals_each_request_alone_and_counters(gpu_state, fl):
     assert webp_after["webp_sources"] - webp_before["webp_sources"] == 1   # the one lossless file: lossy ones do not move it
     with pytest.raises(fl.FanlinError):
         gpu_state.debug_set("vp8_sources", 0)
+
+
+@needs_libwebp
+def test_one_launch_of_pictures_five_orders_of_magnitude_apart(gpu_state, fl):
+    """One launch of each kernel over jobs from 1 to 549,120 pixels: with and without a loop filter, with and without an ALPH plane, the
+    plane at stride 1 and at stride 4, past a round, a chunk and a band or far short of one.  Every kernel's early return for a job
+    that is not its business, and every loop bound taken from the job's own size, leaves the jobs beside it alone."""
+    names = ["lib_rounds_1040x528", "model_1x1", "model_alpha_3x1030_filter3", "lib_alpha_1100x3_filter2", "lib_alpha_200x70_filter3", "model_48x32"]
+    files = [cases.get(n)["data"] for n in names]
+    infos = [fl.vp8_info(d) for d in files]
+    assert [(i["width"], i["height"]) for i in infos] == [(1040, 528), (1, 1), (3, 1030), (1100, 3), (200, 70), (48, 32)]
+    assert [(i["channels"], i["alpha_compression"], i["alpha_filter"]) for i in infos[2:5]] == [(4, 0, 3), (4, 1, 2), (4, 1, 3)]
+    assert {bool(i["filter_level"]) for i in infos} == {False, True} and {i["channels"] for i in infos} == {3, 4}
+    each = [gpu_state.process_vp8_pixels(d, fl.make_params()) for d in files]
+    before = gpu_state.vp8_counters()["vp8_sources"]
+    got = gpu_state.process_batch([fl.LossyWebp(d) for d in files], [fl.make_params()] * len(files))
+    assert gpu_state.vp8_counters()["vp8_sources"] - before == len(files)
+    for n, a, b in zip(names, got, each):
+        assert a.shape == b.shape and np.array_equal(a, b), n
+        assert np.array_equal(a, cases.get(n)["pixels"]), n   # (an identity request is the decoded picture itself)
 
 
 def test_the_same_requests_through_the_queue_from_eight_threads(gpu_state, fl):

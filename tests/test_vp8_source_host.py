@@ -1,7 +1,8 @@
 """Host half of the lossy WebP decode front end (csrc/fl_vp8src.cpp) and the host twin of its device half (tests/vp8_src_host.cpp:
 the functions of csrc/fl_vp8dec_core.h in plain loops).  No GPU.  Host half plus twin must give exactly the planes and the pixels
 libwebp decodes -- the model's own reconstruction for the model's files -- for the whole corpus of tests/vp8_src_cases.py; the
-corpus itself is held to the coverage the decoder's tests rely on, read from flgpu_vp8_info_of's fields."""
+corpus itself is held to the coverage the decoder's tests rely on, read from flgpu_vp8_info_of's fields: every branch of the
+arithmetic, and every size at which the device's scheduling (csrc/fl_vp8dec.hip) starts a second chunk, round or band."""
 import ctypes
 import os
 import re
@@ -148,6 +149,79 @@ def test_the_corpus_covers_what_the_decoder_has(fl):
     assert {i["alpha_compression"] for i in infos.values() if i["channels"] == 4} == {0, 1}   # both decoded, both checked against WebPDecodeRGBA
 
 
+def fullest_diagonal(mbw, mbh):
+    """the most macroblocks on one anti-diagonal d = x + 2 y (diagonal() of csrc/fl_vp8dec.hip)"""
+    def count(d):
+        lo = (d - mbw + 2) >> 1 if d >= mbw else 0
+        return max(min(mbh - 1, d >> 1) - lo + 1, 0)
+    return max(count(d) for d in range(mbw + 2 * (mbh - 1)))
+
+
+@needs_libwebp
+def test_the_corpus_reaches_every_seam_of_the_device_schedule(fl):
+    """A condition on the corpus, like the one above, for what only csrc/fl_vp8dec.hip knows: how lanes, waves, rounds and bands
+    share a picture.  Every place where that scheduling has a second iteration is reached by a file whose decode is checked.  The
+    sizes are restated here and compared with the headers: whoever retunes the kernels moves the corpus with them."""
+    WAVES, LANES, THREADS, FILTER_SLOTS = 16, 64, 1024, 32
+    h_text, core_text = open(os.path.join(CSRC, "fl_vp8dec.h")).read(), open(os.path.join(CSRC, "fl_vp8dec_core.h")).read()
+    waves, per_wave = map(int, re.search(r"constexpr uint32_t kVp8dWaves = (\d+), kVp8dThreads = kVp8dWaves \* (\d+)u;", h_text).groups())
+    lanes = int(re.search(r"\bkVp8dLanes = (\d+)\b", core_text).group(1))
+    filter_lanes = int(re.search(r"\bkVp8dFilterLanes = (\d+)\b", core_text).group(1))
+    assert (waves, lanes, per_wave, waves * per_wave, waves * per_wave // filter_lanes) == (WAVES, LANES, LANES, THREADS, FILTER_SLOTS), \
+        "the kernels' shape changed: move the sizes of cases.SCHEDULING with it"
+    assert fullest_diagonal(35, 18) == 18 and fullest_diagonal(65, 33) == 33 and fullest_diagonal(1, 1) == 1
+
+    infos = {n: fl.vp8_info(cases.get(n)["data"]) for n in cases.names()}
+    assert set(cases.SCHEDULING) <= set(infos) and len(cases.SCHEDULING) == 26
+
+    # -- rounds of vp8dec_recon_kernel (WAVES macroblocks each) and vp8dec_filter_kernel (FILTER_SLOTS each)
+    def rounds(i):
+        mbw, mbh = (i["width"] + 15) // 16, (i["height"] + 15) // 16
+        assert mbw * mbh == i["macroblocks"]
+        return fullest_diagonal(mbw, mbh)
+    mixed = {n: (rounds(i), i["filter_type"]) for n, i in infos.items() if i["filter_level"] and 0 < i["bpred_macroblocks"] < i["macroblocks"]}
+    for filter_type, what in ((0, "normal"), (1, "simple")):
+        fullest = {f for f, t in mixed.values() if t == filter_type}
+        assert any(f > 2 * WAVES for f in fullest), f"no third reconstruction round under the {what} filter"
+        assert any(f % FILTER_SLOTS == 1 and f > FILTER_SLOTS for f in fullest), f"no second filter round with one slot active under the {what} filter"
+    assert any(f == FILTER_SLOTS and f % WAVES == 0 for f, t in mixed.values()), "no file whose fullest diagonal is whole rounds only"
+    for n in ("lib_rounds_1040x528", "lib_rounds_simple_1040x528", "lib_rounds_1040x512"):
+        assert n in mixed, f"{n}: B_PRED and one-mode macroblocks together behind a loop filter"
+        # ... and together in every round of the fullest diagonals but a one-wave one (Vp8MbRecord::ymode: csrc/fl_vp8src.h), so
+        # the rounds behind the first take the sixteen sub-steps with one-step waves waiting beside sixteen-step ones
+        blob = fl.debug_vp8_blob(cases.get(n)["data"])
+        mbw, mbh, rec_off = (int.from_bytes(blob[k:k + 4], "little") for k in (16, 20, 36))
+        ymode = np.frombuffer(blob, np.uint8, mbw * mbh * 48, rec_off).reshape(mbh, mbw, 48)[..., 4]
+        for d in range(mbw + 2 * (mbh - 1)):
+            ys = [y for y in range(mbh) if 0 <= d - 2 * y < mbw]
+            if len(ys) == mixed[n][0]:
+                for base in range(0, len(ys), WAVES):
+                    kinds = {int(ymode[y, d - 2 * y]) == 4 for y in ys[base:base + WAVES]}
+                    assert kinds == {False, True} or len(ys) - base == 1, (n, d, base)
+    assert infos["lib_rounds_1040x528"]["segmentation"] == 1 and infos["lib_rounds_1040x528"]["update_map"] == 1
+
+    # -- vp8dec_alpha_kernel: (compression, filter) -> the sizes it is decoded at; compression 0 is read at stride 1, 1 at stride 4
+    sizes = {}
+    for i in infos.values():
+        if i["channels"] == 4:
+            sizes.setdefault((i["alpha_compression"], i["alpha_filter"]), set()).add((i["width"], i["height"]))
+
+    def reached(compression, method, seam, what):
+        assert any(seam(w, h) for w, h in sizes.get((compression, method), ())), f"ALPH compression {compression}, filter {method}: {what}"
+    for m in (1, 2, 3):   # stride 1: each filter at every seam
+        reached(0, m, lambda w, h: w == LANES and h > 1, "a row of exactly one chunk")
+        reached(0, m, lambda w, h: w == LANES + 1 and h > 1, "a row one sample into the second chunk")
+        reached(0, m, lambda w, h: w > 2 * LANES and w % LANES and h > WAVES, "three chunks with a ragged end, more rows than waves")
+        reached(0, m, lambda w, h: h > THREADS + 1 and w > 1, "a second gradient band behind a row; 17 passes of the column sum; columns longer than a band")
+        reached(0, m, lambda w, h: w > THREADS and h > 1, "columns beyond the last thread; more chunks than waves")
+    reached(0, 0, lambda w, h: w * h > THREADS, "a second pass of the copy loop")
+    for m in (0, 1, 2, 3):   # stride 4: every filter past a chunk and past the waves
+        reached(1, m, lambda w, h: w > LANES and w % LANES and h > WAVES, "several chunks a row, more rows than waves")
+    reached(1, 3, lambda w, h: h > THREADS + 1 and w > LANES, "a second gradient band")
+    for m in (1, 2):
+        reached(1, m, lambda w, h: w > THREADS and h > 1, "columns beyond the last thread; more chunks than waves")
+
+
 # ---- damaged and refused files ---------------------------------------------------------------------------------------------------------
 
 def resized(data):
@@ -230,8 +304,8 @@ def test_mutated_files_under_address_and_ub_sanitizers(fl, tmp_path):
                     os.path.join(ROOT, "tests", "vp8_src_fuzz.cpp"), os.path.join(CSRC, "fl_vp8src.cpp"), os.path.join(CSRC, "fl_webpsrc.cpp"), "-o", exe], check=True)
     paths = []
     for name in cases.names(libwebp_too=cases.have_libwebp()):
-        if name in ("lib_560x288", "lib_300x200"):
-            continue   # (the large ones: the same code paths, ten times the time)
+        if name in ("lib_560x288", "lib_300x200") or name in cases.SCHEDULING:
+            continue   # (the large ones, and the sizes chosen for the device's scheduling: the same code paths, ten times the time)
         p = str(tmp_path / (name + ".webp"))
         open(p, "wb").write(cases.get(name)["data"])
         paths.append(p)

@@ -6,11 +6,13 @@ Two sources of files:
     the plane filtered here in numpy and spliced in, ALPH filters 1, 2 and 3 (libwebp picks the filter itself);
   * libwebp through ctypes (tests/vp8_dec_lib.py) writes what the model does not: B_PRED macroblocks, segments, both loop filters,
     sharpness, probability updates.  Expected planes: WebPDecodeYUV; expected pixels: WebPDecodeRGB / WebPDecodeRGBA.
+Both also hold the sizes at which the device's scheduling (csrc/fl_vp8dec.hip) takes a second chunk, round or band: SCHEDULING.
 
 get(name) -> dict(data, yuv, pixels, channels): yuv = the expected (y, u, v), pixels = the expected Rgb8 / Rgba8 picture or None
 where libwebp is not there to say (a model file's planes are the model's own).  Contents and seeds are fixed: the coverage the
 decoder's tests rely on is asserted there on flgpu_vp8_info_of's fields, not hoped for."""
 import functools
+import re
 
 import numpy as np
 
@@ -34,6 +36,17 @@ def textured(h, w, seed, alpha=None):
     img = synth.photo(h, w, 3, index=seed).astype(np.int32) + rng.integers(-40, 40, (h, w, 3))
     a = np.full((h, w), 255, np.uint8) if alpha is None else alpha
     return np.dstack([np.clip(img, 0, 255).astype(np.uint8), a])
+
+
+def quilt(h, w, seed):
+    """textured() with every other macroblock flat, as a chequerboard: at 1040 x 528 libwebp codes textured() itself with B_PRED
+    in every macroblock; here half are one-mode ones, and along an anti-diagonal (x - 2, y + 1) the two kinds alternate"""
+    img = textured(h, w, seed)
+    y, x = np.mgrid[0:h, 0:w]
+    flat = (x // 16 + y // 16) % 2 == 1
+    for k, v in enumerate(((x // 16) * 37 % 256, (y // 16) * 53 % 256, (x // 16 + y // 16) * 29 % 256)):
+        img[..., k][flat] = v[flat]
+    return img
 
 
 def bars(h, w, seed):
@@ -64,6 +77,31 @@ def quiet_and_noise(h, w, seed, gradient):
 def ramp_alpha(h, w):
     y, x = np.mgrid[0:h, 0:w]
     return ((x * 5 + y * 3) % 256).astype(np.uint8)
+
+
+def ramp(a, b):
+    """the plane (a x + b y) % 256 as a function of (h, w); ramp_alpha is ramp(5, 3)"""
+    def plane(h, w):
+        y, x = np.mgrid[0:h, 0:w]
+        return ((x * a + y * b) % 256).astype(np.uint8)
+    return plane
+
+
+def slope_alpha(h, w):
+    """a slow ramp: runs of equal samples along both axes"""
+    y, x = np.mgrid[0:h, 0:w]
+    return ((2 * x + 3 * y) // 4 % 256).astype(np.uint8)
+
+
+def bowl_alpha(h, w):
+    """second-order in x and y: the gradient predictor's kind of plane"""
+    y, x = np.mgrid[0:h, 0:w]
+    return ((x * x // 50 + y * y // 40 + x * y // 30) % 256).astype(np.uint8)
+
+
+def random_alpha(seed):
+    """seeded random bytes: arbitrary residuals under every filter, so a dropped or doubled carry changes what follows it"""
+    return lambda h, w: np.random.default_rng(seed).integers(0, 256, (h, w), dtype=np.uint8)
 
 
 def planes(h, w, seed):
@@ -156,10 +194,11 @@ REFUSED_FEATURES = {"color_space": "colour-space", "clamp": "clamping", "segment
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------
 
-def model(name, w, h, quality, seed, alpha=False, alpha_method=0):
+def model(name, w, h, quality, seed, alpha=None, alpha_method=0):
+    """alpha: None for an opaque picture, or the plane as a function of (h, w)"""
     def make():
         y, u, v = planes(h, w, seed)
-        a = ramp_alpha(h, w) if alpha else None
+        a = alpha(h, w) if alpha else None
         data, rec, stats = vp8_model.encode(y, u, v, quality, a=a)
         if alpha_method:
             data = splice_alpha(data, a, alpha_method)
@@ -173,10 +212,20 @@ for _h, _n in ((16, 1), (32, 2), (64, 4), (128, 8)):
     model(f"model_partitions{_n}", 16, _h, 60, 310 + _n)
 for _q in (1, 30, 75, 99):
     model(f"model_quality{_q}", 32, 32, _q, 320 + _q)
-model("model_alpha_raw", 33, 17, 75, 330, alpha=True)
+model("model_alpha_raw", 33, 17, 75, 330, alpha=ramp_alpha)
 for _m in (1, 2, 3):
-    model(f"model_alpha_filter{_m}", 33, 17, 75, 330, alpha=True, alpha_method=_m)
-model("model_alpha_filter3_tall", 5, 70, 75, 331, alpha=True, alpha_method=3)
+    model(f"model_alpha_filter{_m}", 33, 17, 75, 330, alpha=ramp_alpha, alpha_method=_m)
+model("model_alpha_filter3_tall", 5, 70, 75, 331, alpha=ramp_alpha, alpha_method=3)
+# The seams of vp8dec_alpha_kernel's scheduling at stride 1 (csrc/fl_vp8dec.hip: 64-sample chunks of a row with a carry between them,
+# rows dealt over 16 waves, the first column summed 64 rows a pass, columns dealt over 1,024 threads, gradient bands of 1,024 rows):
+#   64 x 2     a row is exactly one chunk                 3 x 1030   17 passes of the column sum, columns 1,030 long, a second
+#   65 x 2     one sample into the second chunk                      gradient band of 6 rows (which reads the first band's last row)
+#   129 x 17   three chunks, more rows than waves         1100 x 3   18 chunks, columns beyond thread 1,023, w + 1,023 gradient steps
+ALPHA_SEAM_SIZES = ((64, 2), (65, 2), (129, 17), (3, 1030), (1100, 3))
+for _k, (_w, _h) in enumerate(ALPHA_SEAM_SIZES):
+    for _m in (1, 2, 3):
+        model(f"model_alpha_{_w}x{_h}_filter{_m}", _w, _h, 75, 340 + _k, alpha=random_alpha(350 + 4 * _k + _m), alpha_method=_m)
+model("model_alpha_1100x3_filter0", 1100, 3, 75, 344, alpha=random_alpha(366))   # the copy loop, 1,024 samples a pass
 
 
 def libwebp(name, picture, quality, **settings):
@@ -203,6 +252,44 @@ libwebp("lib_alpha_raw_filtered", lambda: textured(41, 57, 441, ramp_alpha(41, 5
 libwebp("lib_alpha_compressed", lambda: textured(40, 56, 440, ramp_alpha(40, 56)), 75)   # a compressed (VP8L-coded) ALPH
 
 libwebp("lib_alpha_compressed_filtered", lambda: textured(41, 57, 441, ramp_alpha(41, 57)), 75, alpha_filtering=2, alpha_quality=60)
+
+
+def libwebp_alpha(name, w, h, method, candidates):
+    """A VP8L-coded ALPH plane (read at stride 4: the green bytes) under filter `method`.  libwebp picks the filter itself, so the case
+    is the first of `candidates` -- (plane, alpha_filtering, alpha_quality) -- whose ALPH header says compression 1 and `method`; with
+    none, building the case fails, and so does every test that asks for it."""
+    def make():
+        seen = []
+        for plane, filtering, quality in candidates:
+            data = vp8_dec_lib.encode(textured(h, w, 6, plane(h, w)), 75, alpha_filtering=filtering, alpha_quality=quality)
+            head = data[data.index(b"ALPH") + 8]
+            if (head & 3, head >> 2 & 3) == (1, method):
+                return dict(data=data)
+            seen.append((head & 3, head >> 2 & 3))
+        raise AssertionError(f"{name}: no candidate gave a compressed ALPH plane under filter {method}; (compression, filter) were {seen}")
+    LIBWEBP[name] = make
+
+
+# 200 x 70: four chunks a row and more rows than waves, under every method; 70 x 1030: the second gradient band; 1100 x 3: 18 chunks and
+# columns beyond thread 1,023
+libwebp_alpha("lib_alpha_200x70_filter0", 200, 70, 0, ((slope_alpha, 1, 100), (ramp_alpha, 0, 100), (bowl_alpha, 0, 100)))
+libwebp_alpha("lib_alpha_200x70_filter1", 200, 70, 1, ((slope_alpha, 2, 60), (ramp_alpha, 1, 100), (slope_alpha, 2, 30)))
+libwebp_alpha("lib_alpha_200x70_filter2", 200, 70, 2, ((slope_alpha, 2, 100), (ramp_alpha, 2, 100), (ramp(11, 1), 2, 100)))
+libwebp_alpha("lib_alpha_200x70_filter3", 200, 70, 3, ((bowl_alpha, 2, 100), (ramp_alpha, 2, 30), (ramp(7, 1), 2, 60)))
+libwebp_alpha("lib_alpha_70x1030_filter3", 70, 1030, 3, ((slope_alpha, 2, 60), (slope_alpha, 2, 30), (ramp(5, 1), 2, 60)))
+libwebp_alpha("lib_alpha_1100x3_filter1", 1100, 3, 1, ((slope_alpha, 2, 100), (slope_alpha, 2, 60), (bowl_alpha, 2, 100)))
+libwebp_alpha("lib_alpha_1100x3_filter2", 1100, 3, 2, ((ramp_alpha, 2, 100), (ramp(7, 2), 2, 100), (ramp(11, 1), 2, 100)))
+
+# Rounds of the macroblock schedule: 16 macroblocks of a diagonal a round in vp8dec_recon_kernel, 32 in vp8dec_filter_kernel.  65 x 33
+# macroblocks: the fullest diagonals hold 33 (a second filter round with one slot active, a third reconstruction round with one wave);
+# 65 x 32: 32, whole rounds only.  B_PRED and one-mode macroblocks alternate, so every round takes the sixteen sub-steps with waves
+# of both kinds in it
+libwebp("lib_rounds_1040x528", lambda: quilt(528, 1040, 450), 60)
+libwebp("lib_rounds_simple_1040x528", lambda: quilt(528, 1040, 450), 60, filter_type=0)
+libwebp("lib_rounds_1040x512", lambda: quilt(512, 1040, 451), 60)
+# the cases above that exist for the device's scheduling alone: to the host half they are more of what the others hold
+SCHEDULING = sorted(n for n in list(MODEL) + list(LIBWEBP) if re.search(r"_(alpha|rounds\w*)_\d+x\d+", n))
+
 REFUSED = ()
 NAMES = sorted(MODEL) + sorted(LIBWEBP)
 
