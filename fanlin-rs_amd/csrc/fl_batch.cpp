@@ -110,9 +110,11 @@ struct Batch {
     std::vector<JpegJob> jjobs;
     std::vector<PngJob> pjobs;
     std::vector<WebpJob> wjobs;
+    std::vector<WebpJob> ajobs; // the alpha-mode jobs of the lossy WebP pictures that carry FLGPU_FEO_ALPHA_VP8L, in the order of vjobs
+    uint32_t wjob_tiles = 0, ajob_tiles = 0; // tiles of each list: a launch numbers its own
     std::vector<Vp8Job> vjobs;
     uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
-    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
+    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, ajob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
     uint32_t jpeg_max_blocks = 0;
     size_t mid_floats_max = 0;
     bool has_results = false, has_err_word = false;
@@ -121,7 +123,7 @@ struct Batch {
     uint32_t *status_dev = nullptr;
     struct {
         const Job *jobs; const StreamItem *items; const FrontendJob *fjobs; const JpegJob *jjobs; const MfmaItem *mitems;
-        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs; const Vp8Job *vjobs;
+        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs; const WebpJob *ajobs; const Vp8Job *vjobs;
     } d{}; // the arrays' device copies
     Batch(flgpu_ctx *c, size_t n_, flgpu_image *dsts_) : n(n_), dsts(dsts_), dbg(*c->dbg), work(n_) {}
 };
@@ -429,6 +431,8 @@ bool vp8_fe_lf(uint32_t fe) { return fe >= FLGPU_FE_WEBP_LOSSY_LF && fe <= FLGPU
 bool vp8_fe_i4(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
 bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_AP_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
 bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe) || vp8_fe_lf(fe); }
+// FLGPU_FEO_ALPHA_VP8L, which only these front ends know: the picture also gets the lossless coder's scratch, for its alpha plane
+bool vp8_alpha_vp8l(const flgpu_params &p) { return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_ALPHA_VP8L); }
 int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
 {
     const bool i4 = vp8_fe_i4(fe), ap = vp8_fe_ap(fe);
@@ -497,6 +501,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
         if (vp8_fe(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, w.p->front_end);
+        if (!rc && vp8_alpha_vp8l(*w.p)) rc = webpll_scratch(pl, B.scratch);
         if (rc) return rc;
     }
     return FLGPU_OK;
@@ -893,17 +898,30 @@ int add_png_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
     return png_scratch(pl, at);
 }
 
-int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
+// alpha: the alpha-mode job of lossy WebP job `vj`, which reads the plane that job's planes launch writes and leaves its result in
+// front of the stream scratch (the stream itself kWebpllAlphaHead bytes in: webpll_max_out_bytes counts 40 header bits that an ALPH
+// payload does not have, and the tail of the scratch is alignment)
+int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, Vp8Job *vj = nullptr)
 {
-    WebpJob &j = encoder_job(B, B.wjobs, B.wjob_img, i);
+    WebpJob &j = vj ? encoder_job(B, B.ajobs, B.ajob_img, i) : encoder_job(B, B.wjobs, B.wjob_img, i);
     const flgpu_plan &pl = B.work[i].plan;
+    uint32_t &tiles = vj ? B.ajob_tiles : B.wjob_tiles;
     j.res = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_res.p) + at.wll_res);
     j.tok = reinterpret_cast<uint16_t *>(static_cast<char *>(c->d_webpll_tok.p) + at.wll_tok);
     j.tiles = static_cast<WebpllTile *>(c->d_webpll_tiles.p) + at.wll_tiles;
     j.pic = static_cast<uint32_t *>(c->d_webpll_pic.p) + (size_t)at.wll_pics * kWebpllPicWords;
     j.stream = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_stream.p) + at.wll_stream);
-    j.tile0 = at.wll_tiles; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
+    j.tile0 = tiles; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
     j.stream_words = (uint32_t)(align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256) / 4u);
+    tiles += j.ntiles;
+    if (vj) {
+        j.mode = kWebpllModeAlpha;
+        j.src = vj->src + (size_t)pl.out_w * pl.out_h + 2u * (size_t)((pl.out_w + 1u) / 2u) * ((pl.out_h + 1u) / 2u); // behind Y, U, V
+        j.dst = reinterpret_cast<uint8_t *>(j.stream);
+        j.dst_cap = 0; j.c = 1;
+        j.stream += kWebpllAlphaHead / 4u; j.stream_words -= kWebpllAlphaHead / 4u;
+        vj->alpha = reinterpret_cast<const uint32_t *>(j.dst);
+    }
     return webpll_scratch(pl, at);
 }
 
@@ -997,6 +1015,7 @@ int build_launches(flgpu_ctx *c, Batch &B)
     B.has_results = !fe_groups.empty();
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
     ScratchSizes vp8_at; // (the lossy WebP front ends are up to eight groups that share the lossy WebP scratch, in the families' order)
+    ScratchSizes wll_at; // (the lossless WebP files and the alpha planes of those groups share the lossless coder's scratch)
     static_assert(FLGPU_FE_WEBP_LOSSY < FLGPU_FE_WEBP_LOSSY_I4 && FLGPU_FE_WEBP_LOSSY_I4 < FLGPU_FE_WEBP_LOSSY_AP && FLGPU_FE_WEBP_LOSSY_AP < FLGPU_FE_WEBP_LOSSY_I4_AP,
                   "launch_vp8_encode takes one range of jobs per family, in this order");
     static_assert(vp8_family(FLGPU_FE_WEBP_LOSSY) == 0 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4) == 1 && vp8_family(FLGPU_FE_WEBP_LOSSY_AP) == 2 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP) == 3, "vp8_family");
@@ -1009,8 +1028,9 @@ int build_launches(flgpu_ctx *c, Batch &B)
             int rc = FLGPU_OK;
             if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
             if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
-            if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, at);
+            if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, wll_at);
             if (vp8_fe(g.first)) { rc = add_vp8_job(c, B, i, vp8_at, g.first); B.vjobs_fam[vp8_family(g.first)]++; }
+            if (!rc && vp8_alpha_vp8l(*B.work[i].p)) rc = add_webpll_job(c, B, i, wll_at, &B.vjobs.back());
             assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
             (void)rc;
         }
@@ -1036,6 +1056,7 @@ template <class F> void desc_regions(Batch &B, F &&f)
     f(B.mwg, B.d.mwg);
     f(B.pjobs, B.d.pjobs);
     f(B.wjobs, B.d.wjobs);
+    f(B.ajobs, B.d.ajobs);
     f(B.vjobs, B.d.vjobs);
 }
 
@@ -1083,6 +1104,7 @@ int stage_descriptors(flgpu_ctx *c, Batch &B, hipStream_t st)
         point_results(B.fjobs, B.fjob_img, &FrontendJob::status, B.status_dev);
         point_results(B.pjobs, B.pjob_img, &PngJob::result, B.status_dev);
         point_results(B.wjobs, B.wjob_img, &WebpJob::result, B.status_dev);
+        point_results(B.ajobs, B.ajob_img, &WebpJob::result, B.status_dev);
         point_results(B.vjobs, B.vjob_img, &Vp8Job::result, B.status_dev);
     }
     size_t off = 0;
@@ -1216,11 +1238,13 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
     }
     if (!B.wjobs.empty()) {
         ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_webpll_encode(B.d.wjobs, (uint32_t)B.wjobs.size(), B.scratch.wll_tiles, st), "lossless WebP encode");
+        FL_HIP(c, launch_webpll_encode(B.d.wjobs, (uint32_t)B.wjobs.size(), B.wjob_tiles, st), "lossless WebP encode");
         c->stats.frontend_launches++;
     }
     if (!B.vjobs.empty()) {
         ProfileScope ps(c, st, 7);
+        // the alpha planes' streams: after the planes launch that wrote the planes and the translucency bits, before any frame kernel
+        FL_HIP(c, launch_webpll_encode(B.d.ajobs, (uint32_t)B.ajobs.size(), B.ajob_tiles, st, kWebpllModeAlpha), "lossy WebP alpha plane encode");
         FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_fam, st), "lossy WebP encode");
         c->stats.frontend_launches++;
     }
@@ -1298,6 +1322,7 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st)
     int rc = FLGPU_OK;
     for (size_t i = 0; i < n; ++i) {
         if (c->last_fe[i] == FLGPU_FE_WEBP420 && (r[2 * i] & 1u)) dsts[i].flags |= FLGPU_IMG_HAS_ALPHA;
+        if (vp8_fe(c->last_fe[i]) && r[2 * i + 1] && (r[2 * i] & kVp8ResultAlphaVp8l)) c->webp_alpha_vp8l++;
         if (fe_encoded(c->last_fe[i])) {
             dsts[i].bytes = r[2 * i + 1];
             if (!r[2 * i + 1]) { c->set_error("encoded stream does not fit the destination"); rc = FLGPU_ERR_BUFFER_TOO_SMALL; }

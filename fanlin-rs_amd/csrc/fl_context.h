@@ -226,6 +226,7 @@ struct flgpu_ctx {
     fl::DeviceBuf d_vp8dec, d_vp8jobs;                 // lossy WebP decode (fl_vp8dec.hip): planes, alpha planes and pixels of a batch, job descriptors
     fl::PinnedBuf h_vp8jobs;
     uint64_t vp8_sources = 0, vp8_file_bytes = 0, vp8_upload_bytes = 0, vp8_decode_ns = 0;
+    uint64_t webp_alpha_vp8l = 0;                        // lossy WebP pictures whose ALPH chunk went out as a VP8L stream (FLGPU_FEO_ALPHA_VP8L; from the result words)
     uint64_t webp_lossy_ns = 0;                          // HIP-event time of the lossy WebP encoder's launches (fl_vp8.hip; profile = 1)
     uint64_t webp_predict_ns = 0, webp_pointwise_ns = 0; // HIP-event time of the two kernels' launches (profile = 1; resolved by flgpu_get_stats)
     fl::DeviceBuf d_gifdec;                            // GIF decode (fl_gifdec.hip): the composited frames of one animation

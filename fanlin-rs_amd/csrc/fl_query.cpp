@@ -222,6 +222,10 @@ try {
     if (fmt == FLGPU_OUT_WEBP) p->front_end = (qc == 100) ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
     else if (fmt == FLGPU_OUT_KEEP && input_is_jpeg) p->front_end = input_is_jpeg == 2 ? FLGPU_FE_JPEG : FLGPU_FE_JFIF444;
     else p->front_end = FLGPU_FE_NONE;
+    /* the lossy WebP arm with both bits: whichever lossy front end the caller (or plan_request below) puts in place of the planes
+       compresses the alpha plane; every other front end ignores the option */
+    if (p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY) && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA))
+        p->options |= FLGPU_FEO_ALPHA_VP8L;
     return FLGPU_OK;
 } FL_ABI_CATCH
 
@@ -279,6 +283,8 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
         if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_FILTER)
             p->front_end = p->front_end == FLGPU_FE_WEBP_LOSSY ? FLGPU_FE_WEBP_LOSSY_LF : p->front_end == FLGPU_FE_WEBP_LOSSY_I4 ? FLGPU_FE_WEBP_LOSSY_I4_LF
                            : p->front_end == FLGPU_FE_WEBP_LOSSY_AP ? FLGPU_FE_WEBP_LOSSY_AP_LF : FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
+        // _ALPHA: the option on whichever front end that is (a WebP source that stays WebP got its front end after the mapping above)
+        if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA) p->options |= FLGPU_FEO_ALPHA_VP8L;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
     if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {

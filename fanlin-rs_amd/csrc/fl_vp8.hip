@@ -11,7 +11,9 @@
 //                       codes): the boolean coder runs without storing and leaves the partition's size.  The probability table is
 //                       staged in LDS, a block's 16 levels are fetched whole.  The batch is the parallelism.
 //   vp8_frame_kernel    one workgroup per picture: the layout from the sizes; RIFF / VP8X / ALPH / VP8 framing, the raw alpha
-//                       plane where the planes kernel flagged a translucent pixel, the result word (0 if dst is too small).
+//                       plane where the planes kernel flagged a translucent pixel, the result word (0 if dst is too small).  With
+//                       FLGPU_FEO_ALPHA_VP8L the alpha coder (fl_webpll.hip, alpha mode) has left the plane's VP8L stream: that goes
+//                       into the chunk instead wherever it is strictly smaller (vp8_alph_size).
 //   vp8_write_kernel    one lane per partition again: the same coder, storing at the partition's place in the file.
 // The I4 variant (FLGPU_FE_WEBP_LOSSY_I4, fl_vp8_i4_core.h) has kernels of its own, so that the ones above stay as they are:
 //   vp8_analyse_i4_kernel  the same walk; after the mode pick a macroblock whose I16 error exceeds the penalty tries its luma as
@@ -302,10 +304,12 @@ template <bool I4, bool AP = false, bool LF = false> __global__ __launch_bounds_
     jb.sizes[part] = bw.pos;
 }
 
+// (the frame kernel and the coders both lay the file out: the rule for the ALPH payload is vp8_alph_size on the same words)
 __device__ __forceinline__ Vp8Layout layout_of(const Vp8Job &jb, uint32_t nparts, uint32_t *size)
 {
     for (uint32_t k = 0; k < 9u; ++k) size[k] = jb.sizes[k];
-    return vp8_layout(jb.w, jb.h, (jb.result[0] & 1u) != 0u, nparts, size);
+    const bool alpha = (jb.result[0] & 1u) != 0u;
+    return vp8_layout(jb.w, jb.h, alpha, nparts, size, alpha && jb.alpha ? vp8_alph_size(jb.w, jb.h, jb.alpha[0]) : 0u);
 }
 
 __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *__restrict__ jobs)
@@ -322,8 +326,10 @@ __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *
     }
     if (alpha) {
         const uint32_t npix = jb.w * jb.h;
-        const uint8_t *a = jb.src + npix + 2u * ((jb.w + 1u) / 2u) * ((jb.h + 1u) / 2u);
-        for (uint32_t i = threadIdx.x; i < npix; i += kFrameThreads) jb.dst[L.alph + 9u + i] = a[i];
+        const bool vp8l = L.alph_size != 1u + npix; // (only with FLGPU_FEO_ALPHA_VP8L: the stream is strictly smaller than the plane)
+        const uint8_t *a = vp8l ? reinterpret_cast<const uint8_t *>(jb.alpha) + kWebpllAlphaHead : jb.src + npix + 2u * ((jb.w + 1u) / 2u) * ((jb.h + 1u) / 2u);
+        for (uint32_t i = threadIdx.x; i < L.alph_size - 1u; i += kFrameThreads) jb.dst[L.alph + 9u + i] = a[i];
+        if (vp8l && threadIdx.x == 0u) jb.result[0] |= kVp8ResultAlphaVp8l; // (no other workgroup writes the word after the planes launch)
     }
 }
 

@@ -727,18 +727,25 @@ template <bool I4 = false, bool AP = false, bool LF = false> FL_VP8_HD void vp8_
 // Offsets of the file's parts from the partitions' sizes (size[0] = partition 0, size[1 + k] = token partition k).
 struct Vp8Layout {
     uint32_t alph;      // offset of the ALPH chunk header (0: none)
+    uint32_t alph_size; // payload of the ALPH chunk: its header byte and the plane, raw (1 + w h) or as a VP8L stream (less)
     uint32_t vp8;       // offset of the "VP8 " chunk header
     uint32_t part[9];   // offset of every partition
     uint32_t vp8_size;  // payload of the VP8 chunk
     uint32_t total;     // file bytes
 };
 
-FL_VP8_HD Vp8Layout vp8_layout(uint32_t w, uint32_t h, bool alpha, uint32_t nparts, const uint32_t *size)
+// The ALPH payload of a plane whose VP8L stream has `stream_bytes` bytes (0: there is none): the stream behind its header byte iff
+// that is strictly smaller than the raw plane behind its, else the raw one.  A file is never larger than with the raw plane.
+FL_VP8_HD uint32_t vp8_alph_size(uint32_t w, uint32_t h, uint32_t stream_bytes) { return stream_bytes && stream_bytes < w * h ? 1u + stream_bytes : 1u + w * h; }
+
+// alph_size: vp8_alph_size of a translucent picture (0: the raw plane)
+FL_VP8_HD Vp8Layout vp8_layout(uint32_t w, uint32_t h, bool alpha, uint32_t nparts, const uint32_t *size, uint32_t alph_size = 0u)
 {
     Vp8Layout L;
     uint32_t o = 12u;
     L.alph = 0u;
-    if (alpha) { o += 18u; L.alph = o; o += 8u + 1u + w * h; o += o & 1u; }
+    L.alph_size = alpha ? (alph_size ? alph_size : 1u + w * h) : 0u;
+    if (alpha) { o += 18u; L.alph = o; o += 8u + L.alph_size; o += o & 1u; }
     L.vp8 = o;
     o += 8u + 10u;
     L.part[0] = o;                       // partition 0, then the sizes of all token partitions but the last, then those partitions
@@ -754,7 +761,8 @@ FL_VP8_HD void vp8_put_le(uint8_t *d, uint32_t v, int bytes) { for (int i = 0; i
 FL_VP8_HD void vp8_put_tag(uint8_t *d, const char *t) { for (int i = 0; i < 4; ++i) d[i] = (uint8_t)t[i]; }
 
 // Everything of the file that is not a partition or the alpha plane's bytes: RIFF header, VP8X and ALPH headers where the picture
-// is translucent, the VP8 chunk header, frame tag, start code, dimensions, partition sizes, pad bytes.
+// is translucent (the ALPH header byte says raw, or lossless without filter or pre-processing, by the payload's size), the VP8 chunk
+// header, frame tag, start code, dimensions, partition sizes, pad bytes.
 FL_VP8_HD void vp8_put_framing(uint8_t *d, const Vp8Layout &L, uint32_t w, uint32_t h, bool alpha, uint32_t nparts, const uint32_t *size)
 {
     vp8_put_tag(d, "RIFF"); vp8_put_le(d + 4, L.total - 8u, 4); vp8_put_tag(d + 8, "WEBP");
@@ -762,9 +770,9 @@ FL_VP8_HD void vp8_put_framing(uint8_t *d, const Vp8Layout &L, uint32_t w, uint3
         vp8_put_tag(d + 12, "VP8X"); vp8_put_le(d + 16, 10u, 4);
         vp8_put_le(d + 20, 0x10u, 4);                               // flags: alpha
         vp8_put_le(d + 24, w - 1u, 3); vp8_put_le(d + 27, h - 1u, 3);
-        vp8_put_tag(d + L.alph, "ALPH"); vp8_put_le(d + L.alph + 4, 1u + w * h, 4);
-        d[L.alph + 8u] = 0;                                          // no compression, no filter, no pre-processing
-        if ((1u + w * h) & 1u) d[L.vp8 - 1u] = 0;
+        vp8_put_tag(d + L.alph, "ALPH"); vp8_put_le(d + L.alph + 4, L.alph_size, 4);
+        d[L.alph + 8u] = L.alph_size != 1u + w * h ? 1 : 0;         // compression (VP8L or none), no filter, no pre-processing
+        if (L.alph_size & 1u) d[L.vp8 - 1u] = 0;
     }
     uint8_t *f = d + L.vp8;
     vp8_put_tag(f, "VP8 "); vp8_put_le(f + 4, L.vp8_size, 4);

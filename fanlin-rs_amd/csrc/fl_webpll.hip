@@ -25,6 +25,10 @@
 //                         words out (the two it may share with its neighbours by atomicOr).
 //   webpll_frame_kernel   per picture: RIFF and chunk headers, the stream, the pad byte; the length (or 0 if the file does not
 //                         fit dst_cap) into the result word.
+// Every kernel is a template on the job mode (fl_webpll.h).  The alpha-plane instantiations code the alpha plane of a lossy WebP
+// picture for its ALPH chunk (fl_vp8.hip): one byte per pixel read as ARGB (255, 0, a, 0), no VP8L header and no subtract-green in
+// front of the predictor transform, no framing -- webpll_frame_kernel leaves the stream's byte count in front of the stream.  They
+// return at once for a picture the planes launch found opaque.  The file-mode instantiations are the kernels as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -141,9 +145,13 @@ __device__ __forceinline__ void load16(const WebpJob &jb, uint32_t p0, uint32_t 
 
 // ---------------------------------------------------------------- kernel 1: residuals --
 
-// into_rgba8, then subtract green: ARGB with r - g and b - g
-__device__ __forceinline__ uint32_t load_argb(const WebpJob &jb, uint32_t x, uint32_t y)
+// an alpha-mode job of an opaque picture: nothing to code (uniform over the workgroup; read before any barrier)
+template <bool ALPHA> __device__ __forceinline__ bool idle(const WebpJob &jb) { return ALPHA && (jb.result[0] & 1u) == 0u; }
+
+// into_rgba8, then subtract green: ARGB with r - g and b - g.  ALPHA: the plane's sample as green, nothing subtracted.
+template <bool ALPHA> __device__ __forceinline__ uint32_t load_argb(const WebpJob &jb, uint32_t x, uint32_t y)
 {
+    if (ALPHA) return 0xff000000u | ((uint32_t)jb.src[(size_t)y * jb.w + x] << 8);
     const uint8_t *p = jb.src + ((size_t)y * jb.w + x) * jb.c;
     uint32_t r, g, b, a;
     if (jb.c <= 2u) { r = g = b = p[0]; a = jb.c == 2u ? p[1] : 255u; }
@@ -160,25 +168,26 @@ __device__ __forceinline__ uint32_t sub_pixels(uint32_t a, uint32_t b)
 }
 
 // the predictor transform with mode T everywhere: black for the first pixel, L on row 0, T below
-__device__ __forceinline__ uint32_t residual(const WebpJob &jb, uint32_t i)
+template <bool ALPHA> __device__ __forceinline__ uint32_t residual(const WebpJob &jb, uint32_t i)
 {
     const uint32_t y = i / jb.w, x = i - y * jb.w;
-    const uint32_t p = load_argb(jb, x, y);
-    if (y) return sub_pixels(p, load_argb(jb, x, y - 1u));
-    return sub_pixels(p, x ? load_argb(jb, x - 1u, 0u) : 0xff000000u);
+    const uint32_t p = load_argb<ALPHA>(jb, x, y);
+    if (y) return sub_pixels(p, load_argb<ALPHA>(jb, x, y - 1u));
+    return sub_pixels(p, x ? load_argb<ALPHA>(jb, x - 1u, 0u) : 0xff000000u);
 }
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_resid_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_resid_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint32_t s_res[kWebpllTile + 1u]; // [k] = residual of pixel base + k - 1
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
     const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t k = tid; k <= kWebpllTile; k += kWebpllThreads) {
         const uint32_t i = base + k - 1u;
         if (base + k >= 1u && i < npix) {
-            const uint32_t r = residual(jb, i);
+            const uint32_t r = residual<ALPHA>(jb, i);
             s_res[k] = r;
             if (k) jb.res[i] = r;
         }
@@ -197,10 +206,11 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_resid_kernel(const Webp
 
 // ---------------------------------------------------------------- kernel 2: run starts carried across tiles --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_carry_kernel(const WebpJob *__restrict__ jobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_carry_kernel(const WebpJob *__restrict__ jobs)
 {
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const WebpJob &jb = jobs[blockIdx.x];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) jb.pic[kPicHist + i] = 0u;
     uint32_t run = 0;
@@ -215,7 +225,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_carry_kernel(const Webp
 
 // ---------------------------------------------------------------- kernel 3: tokens and histograms --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_token_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_token_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint32_t s_hist[kAlph];
     __shared__ uint32_t s_first[kWebpllThreads], s_last[kWebpllThreads];
@@ -223,6 +233,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_token_kernel(const Webp
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
     const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) s_hist[i] = 0u;
     const uint32_t p0 = base + tid * kPx;
@@ -283,7 +294,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_token_kernel(const Webp
 
 // ---------------------------------------------------------------- kernel 4: codes and header --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_code_kernel(const WebpJob *__restrict__ jobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_code_kernel(const WebpJob *__restrict__ jobs)
 {
     __shared__ uint32_t s_hist[kAlph], s_key[kAlph], s_sym[kAlph], s_code[kAlph];
     __shared__ uint32_t s_num[4][64];
@@ -292,6 +303,7 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_code_kernel(const WebpJ
     __shared__ uint32_t s_secbits[4];
     __shared__ uint32_t s_hdr[kPicHdrWords];
     const WebpJob &jb = jobs[blockIdx.x];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) { s_hist[i] = jb.pic[kPicHist + i]; s_code[i] = 0u; }
     __syncthreads();
@@ -338,11 +350,13 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_code_kernel(const WebpJ
     __syncthreads();
     if (tid == 0u) {
         BitSink o(s_hdr, 0u, false);
-        o.put(0x2fu, 8u);
-        o.put(jb.w - 1u, 14u); o.put(jb.h - 1u, 14u);
-        o.put(1u, 1u);  // alpha is used (the encoder is handed Rgba8)
-        o.put(0u, 3u);  // version
-        o.put(5u, 3u);  // transform: subtract green
+        if (!ALPHA) { // (an ALPH payload starts at the transform bits, and its red and blue stay zero without subtract-green)
+            o.put(0x2fu, 8u);
+            o.put(jb.w - 1u, 14u); o.put(jb.h - 1u, 14u);
+            o.put(1u, 1u);  // alpha is used (the encoder is handed Rgba8)
+            o.put(0u, 3u);  // version
+            o.put(5u, 3u);  // transform: subtract green
+        }
         o.put(57u, 6u); // transform: predictor, 2^9 blocks
         o.put(0u, 1u);  // its sub-image: no colour cache, five one-symbol codes (mode 2 = T), 0 bits per block
         put_simple(o, 2u);
@@ -364,12 +378,13 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_code_kernel(const WebpJ
 
 // ---------------------------------------------------------------- kernel 5: bits per tile --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_bits_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_bits_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint32_t s_code[kAlph];
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
     const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     for (uint32_t i = tid; i < kAlph; i += kWebpllThreads) s_code[i] = jb.pic[kPicCodes + i];
     __syncthreads();
@@ -389,10 +404,11 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_bits_kernel(const WebpJ
 
 // ---------------------------------------------------------------- kernel 6: tile offsets, header into the stream --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_scan_kernel(const WebpJob *__restrict__ jobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_scan_kernel(const WebpJob *__restrict__ jobs)
 {
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const WebpJob &jb = jobs[blockIdx.x];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t tid = threadIdx.x;
     const uint32_t hb = jb.pic[kPicMeta];
     uint64_t run = hb;
@@ -410,13 +426,14 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_scan_kernel(const WebpJ
 
 // ---------------------------------------------------------------- kernel 7: bits placed --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_place_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_place_kernel(const WebpJob *__restrict__ jobs, uint32_t njobs)
 {
     __shared__ uint32_t s_code[kAlph];
     __shared__ uint32_t s_buf[kTileWords];
     __shared__ uint32_t s_w[kWebpllThreads / 64u];
     const uint32_t tid = threadIdx.x, t = blockIdx.x;
     const WebpJob &jb = jobs[find_first_le(jobs, njobs, t, &WebpJob::tile0)];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t lt = t - jb.tile0, npix = jb.w * jb.h, base = lt * kWebpllTile;
     const uint64_t off = jb.tiles[lt].off;
     const uint32_t tbits = jb.tiles[lt].bits;
@@ -470,12 +487,17 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_place_kernel(const Webp
 
 // ---------------------------------------------------------------- kernel 8: the file --
 
-__global__ __launch_bounds__(kWebpllThreads) void webpll_frame_kernel(const WebpJob *__restrict__ jobs)
+template <bool ALPHA> __global__ __launch_bounds__(kWebpllThreads) void webpll_frame_kernel(const WebpJob *__restrict__ jobs)
 {
     const WebpJob &jb = jobs[blockIdx.x];
+    if (idle<ALPHA>(jb)) return;
     const uint32_t tid = threadIdx.x;
     const uint64_t bits = (uint64_t)jb.pic[kPicMeta + 2] | ((uint64_t)jb.pic[kPicMeta + 3] << 32);
     const uint64_t n = (bits + 7u) / 8u, file = 20u + n + (n & 1u);
+    if (ALPHA) { // the stream stays where it is (its last byte's spare bits are zero); its length in front of it
+        if (tid == 0u) *reinterpret_cast<uint32_t *>(jb.dst) = n > 4ull * jb.stream_words ? 0u : (uint32_t)n;
+        return;
+    }
     if (file > jb.dst_cap || n > 4ull * jb.stream_words) {
         if (tid == 0u) jb.result[1] = 0u;
         return;
@@ -501,27 +523,32 @@ __global__ __launch_bounds__(kWebpllThreads) void webpll_frame_kernel(const Webp
 
 } // namespace
 
-hipError_t launch_webpll_encode(const WebpJob *jobs, uint32_t njobs, uint32_t total_tiles, hipStream_t st)
+template <bool ALPHA> static hipError_t launch_mode(const WebpJob *jobs, uint32_t njobs, uint32_t total_tiles, hipStream_t st)
 {
-    if (!njobs || !total_tiles) return hipSuccess;
     const dim3 blk(kWebpllThreads);
-    hipLaunchKernelGGL(webpll_resid_kernel, dim3(total_tiles), blk, 0, st, jobs, njobs);
+    hipLaunchKernelGGL(webpll_resid_kernel<ALPHA>, dim3(total_tiles), blk, 0, st, jobs, njobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_carry_kernel, dim3(njobs), blk, 0, st, jobs);
+    hipLaunchKernelGGL(webpll_carry_kernel<ALPHA>, dim3(njobs), blk, 0, st, jobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_token_kernel, dim3(total_tiles), blk, 0, st, jobs, njobs);
+    hipLaunchKernelGGL(webpll_token_kernel<ALPHA>, dim3(total_tiles), blk, 0, st, jobs, njobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_code_kernel, dim3(njobs), blk, 0, st, jobs);
+    hipLaunchKernelGGL(webpll_code_kernel<ALPHA>, dim3(njobs), blk, 0, st, jobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_bits_kernel, dim3(total_tiles), blk, 0, st, jobs, njobs);
+    hipLaunchKernelGGL(webpll_bits_kernel<ALPHA>, dim3(total_tiles), blk, 0, st, jobs, njobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_scan_kernel, dim3(njobs), blk, 0, st, jobs);
+    hipLaunchKernelGGL(webpll_scan_kernel<ALPHA>, dim3(njobs), blk, 0, st, jobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_place_kernel, dim3(total_tiles), blk, 0, st, jobs, njobs);
+    hipLaunchKernelGGL(webpll_place_kernel<ALPHA>, dim3(total_tiles), blk, 0, st, jobs, njobs);
     FL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(webpll_frame_kernel, dim3(njobs), blk, 0, st, jobs);
+    hipLaunchKernelGGL(webpll_frame_kernel<ALPHA>, dim3(njobs), blk, 0, st, jobs);
     FL_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+hipError_t launch_webpll_encode(const WebpJob *jobs, uint32_t njobs, uint32_t total_tiles, hipStream_t st, uint32_t mode)
+{
+    if (!njobs || !total_tiles) return hipSuccess;
+    return mode == kWebpllModeAlpha ? launch_mode<true>(jobs, njobs, total_tiles, st) : launch_mode<false>(jobs, njobs, total_tiles, st);
 }
 
 } // namespace fl

@@ -146,9 +146,11 @@ typedef enum flgpu_front_end {
     FLGPU_FE_WEBP_LOSSY = 9, /* dst = a finished lossy WebP file (RIFF / VP8, or RIFF / VP8X + ALPH + VP8 where a pixel is not
                               opaque) for the WebP arm below quality 100 (src/handler.rs:293-297): the FLGPU_FE_WEBP420 planes
                               coded as one VP8 key frame -- every macroblock I16, modes by least SSE, one segment, loop filter
-                              level 0, default probabilities, quantiser from quality; the alpha plane uncompressed.  A valid file
-                              that decodes to exactly the coder's reconstruction; its bytes are not libwebp's.  out_w, out_h
-                              <= 16383 and at most about 21 000 macroblocks (see max_out_bytes); dst->bytes long */
+                              level 0, default probabilities, quantiser from quality; the alpha plane uncompressed, or with
+                              FLGPU_FEO_ALPHA_VP8L in flgpu_params::options (this front end and the seven below) as a VP8L stream
+                              wherever that is smaller.  A valid file that decodes to exactly the coder's reconstruction; its
+                              bytes are not libwebp's.  out_w, out_h <= 16383 and at most about 21 000 macroblocks (see
+                              max_out_bytes); dst->bytes long */
     FLGPU_FE_WEBP_LOSSY_I4 = 10, /* FLGPU_FE_WEBP_LOSSY where a macroblock's luma may also be B_PRED: sixteen 4x4 sub-blocks, each with
                               the one of the ten sub-block predictors that has the least SSE, tried against the macroblock's I16
                               coding and taken when its prediction error plus a penalty from the quantiser is the smaller.
@@ -213,6 +215,11 @@ typedef enum flgpu_front_end {
  * (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF) of whichever front end the other bits select, fall-backs included.  Alone, or
  * without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_FILTER 0x4000u
+/* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies of translucent pictures carry their
+ * alpha plane as a VP8L stream wherever that is smaller than the raw plane (FLGPU_FEO_ALPHA_VP8L on whichever lossy front end the
+ * other bits select, fall-backs included): the same pixels from every decoder, a file that is never larger.  Opaque pictures keep
+ * their bytes.  Alone, or without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
+#define FLGPU_ENCODE_WEBP_LOSSY_ALPHA 0x20000u
 /* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
  * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
  * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
@@ -246,8 +253,16 @@ typedef struct flgpu_params {
     uint8_t front_end;                 /* flgpu_front_end */
     uint8_t orientation;               /* EXIF orientation 1..8 from decoder.orientation() (src/handler.rs:206,221-223); 0 or 1 = none */
     uint8_t filter;                    /* flgpu_filter: Lanczos3 for stills (handler.rs:233,235), Nearest for GIF frames (handler.rs:338,340) */
-    uint8_t reserved[2];
+    uint8_t options;                   /* FLGPU_FEO_* bits (0 = every front end as before); a bit that the front end does not know,
+                                          or that is not defined, is ignored */
+    uint8_t reserved;
 } flgpu_params;
+
+/* flgpu_params::options, the byte that used to be the first of two reserved ones (the struct's size and layout are unchanged).
+ * FLGPU_FEO_ALPHA_VP8L: the lossy WebP front ends (FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP and their _LF twins) write the ALPH chunk
+ * of a translucent picture as header byte 0x01 and a VP8L stream -- lossless, no filter, no pre-processing -- iff that payload is
+ * strictly smaller than the raw one, which is used otherwise; decided on the device.  Every other front end ignores the bit. */
+#define FLGPU_FEO_ALPHA_VP8L 1u
 
 /* Geometry decided on the host before any pixel is touched. */
 typedef struct flgpu_plan {
@@ -285,6 +300,8 @@ typedef struct flgpu_plan {
                                           stands beside plus 7392 bytes, 1056 updates of 8 booleans: 9574 where 1126 stands above.
                                           FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF: the twin's (the bound is per boolean; the
                                           level's six were counted all along).
+                                          All eight with FLGPU_FEO_ALPHA_VP8L: unchanged (w h stands for the raw alpha plane, and a
+                                          compressed one is only written where it is smaller).
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 

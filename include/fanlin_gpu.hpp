@@ -99,6 +99,9 @@ public:
     void encode_webp_lossy_probs() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_PROBS; }
     // ... with a loop filter level picked on the device: the _LF twin of whichever front end the calls above select
     void encode_webp_lossy_filter() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_FILTER; }
+    // ... with the alpha plane of a translucent picture as a VP8L stream wherever that is smaller: FLGPU_FEO_ALPHA_VP8L on
+    // whichever front end the calls above select
+    void encode_webp_lossy_alpha() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_ALPHA; }
     uint32_t flags() const { return flags_; }
 
 private:

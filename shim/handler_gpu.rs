@@ -102,6 +102,8 @@ pub const ENCODE_GIF_QUANTIZE: u32 = 0x8000;
 pub const ENCODE_WEBP_LOSSY: u32 = 0x800;
 pub const ENCODE_WEBP_LOSSY_I4: u32 = 0x1000; // with ENCODE_WEBP_LOSSY: the bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
 pub const ENCODE_WEBP_LOSSY_FILTER: u32 = 0x4000; // with ENCODE_WEBP_LOSSY: the loop-filtered twin of whatever the other bits select; alone, or without it, it does nothing
+pub const ENCODE_WEBP_LOSSY_ALPHA: u32 = 0x20000; // with ENCODE_WEBP_LOSSY: the alpha plane of a translucent picture as a VP8L stream wherever that is smaller (FEO_ALPHA_VP8L); alone, or without it, it does nothing
+pub const FEO_ALPHA_VP8L: u8 = 1; // flgpu_params.reserved[0], the options byte: honoured by the lossy WebP front ends, ignored by every other
 pub const ENCODE_WEBP_LOSSY_PROBS: u32 = 0x2000; // with ENCODE_WEBP_LOSSY (and _I4): FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, it does nothing
 pub const RESULT_AS_IS: c_int = 0;        // flgpu_result_kind
 pub const RESULT_JPEG_STREAM: c_int = 1;
@@ -436,7 +438,7 @@ impl Drop for Gpu { fn drop(&mut self) { unsafe { flgpu_destroy(self.0) } } }
 
 fn p_clone(p: &FlParams) -> FlParams {
     FlParams { has_dims: p.has_dims, w: p.w, h: p.h, fill_r: p.fill_r, fill_g: p.fill_g, fill_b: p.fill_b, crop: p.crop, blur_sigma: p.blur_sigma,
-               grayscale: p.grayscale, inverse: p.inverse, quality: p.quality, front_end: p.front_end, orientation: p.orientation, filter: p.filter, reserved: [0; 2] }
+               grayscale: p.grayscale, inverse: p.inverse, quality: p.quality, front_end: p.front_end, orientation: p.orientation, filter: p.filter, reserved: [p.reserved[0], 0] /* [0]: the options byte (FEO_*) */ }
 }
 fn err(st: c_int) -> String { unsafe { std::ffi::CStr::from_ptr(flgpu_strerror(st)) }.to_string_lossy().into_owned() }
 fn check(st: c_int) -> Result<(), Box<dyn std::error::Error>> { if st == 0 { Ok(()) } else { Err(err(st).into()) } }

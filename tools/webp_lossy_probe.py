@@ -5,11 +5,16 @@ planes, and the bytes that cross PCIe.  Prints plain text; under `rocprofv3 --ke
 --timing-only) the kernel statistics attribute device time to the four vp8_* kernels, the planes kernel and the resample kernel.
 
     python tools/webp_lossy_probe.py [--batch 1024] [--iters 5] [--host-threads 16] [--timing-only] [--i4] [--probs] [--filter] [--events]
-                                     [--quality 75]
+                                     [--quality 75] [--alpha]
 --filter: in the quality part, per loop-filtered front end the chosen level, the file against its twin's, the Y-PSNR gain and a
 block-edge measure (mean absolute luma step across macroblock edges over the mean absolute step elsewhere) of the twin's file, the
 filtered file and libwebp's own file on the same planes; in the timing part each loop-filtered family right after its twin, and the
 histogram of the levels the batch's files carry.
+--alpha: instead of the above, FLGPU_FEO_ALPHA_VP8L: the ALPH chunk bytes of a disc, a soft falloff and a ramp without and with the
+option beside libwebp's own ALPH for the same plane; then, in interleaved rounds, the time per flagship batch (opaque) and per
+translucent twin of it (a disc alpha plane over the same pictures) without and with the option, for FLGPU_FE_WEBP_LOSSY and
+FLGPU_FE_WEBP_LOSSY_AP, with the mean file bytes.  With --timing-only as well: only the translucent FLGPU_FE_WEBP_LOSSY batch with the
+option, 1 + --iters times (the run to put under `rocprofv3 --kernel-trace --stats`).
 """
 import argparse
 import math
@@ -166,6 +171,63 @@ def timing(fl, st, batch, iters, host_threads, i4=False, events=False, probs=Fal
           f"({np.mean(nb_l) / np.mean(nb_p):.3f} x)")
 
 
+def alpha(fl, st, batch, iters, q=75, rounds=3, profile=False):
+    import torch
+    import synth
+    import vp8_alpha_cases as ac
+    import vp8_alpha_model as am
+    import vp8_cases
+    import webp_lib
+    print("# ALPH chunk payload of a translucent 300 x 200 picture: raw | FLGPU_FEO_ALPHA_VP8L | libwebp's own (WebPEncode of the same planes)")
+    rgb = synth.photo(200, 300, 3, index=61)
+    for name, a in () if profile else (("disc", ac.disc()), ("falloff", ac.falloff()), ("alpha_ramp", vp8_cases.alpha_ramp(300, 200))):
+        img = vp8_cases._rgba(rgb, a)
+        pl = st.process_pixels(img, fl.make_params(quality=q, front_end=fl.FE_WEBP420))
+        raw = st.process_pixels(img, fl.make_params(quality=q, front_end=fl.FE_WEBP_LOSSY))
+        new = st.process_pixels(img, fl.make_params(quality=q, front_end=fl.FE_WEBP_LOSSY, alpha_vp8l=True))
+        theirs = am.alph_of(webp_lib.encode_planes(pl.y, pl.u, pl.v, q, pl.a))
+        ours = am.alph_of(new)
+        print(f"{name}: ALPH {len(am.alph_of(raw))} | {len(ours)} (header byte {ours[0]}) | {len(theirs)} bytes ({len(ours) / len(theirs):.2f} x libwebp's); "
+              f"file {len(raw)} -> {len(new)} bytes; equals the model: {new == am.with_alpha(raw, pl.a)}")
+    nsrc = 16
+    d = ac.disc(1920, 1080, 500.0)
+    photos = [synth.photo(1080, 1920, 3, index=40 + i) for i in range(nsrc)]
+    sets = {"opaque": ([torch.from_numpy(p).cuda() for p in photos], 3),
+            "translucent": ([torch.from_numpy(vp8_cases._rgba(p, d)).cuda() for p in photos], 4)}
+    stream = torch.cuda.current_stream().cuda_stream
+    runs = {}
+    if profile:  # a run under rocprofv3: the translucent batch with the option alone, so that the kernel statistics are its own
+        sets, rounds = {"translucent": sets["translucent"]}, 1
+    for kind, (srcs, c) in sets.items():
+        for name, fe in (("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY), ("FE_WEBP_LOSSY_AP", fl.FE_WEBP_LOSSY_AP))[:1 if profile else 2]:
+            for opt in (True,) if profile else (False, True):
+                p = fl.make_params(300, 200, quality=q, front_end=fe, alpha_vp8l=opt)
+                cap = (int(fl.plan_output(p, 1920, 1080, c).max_out_bytes) + 255) // 256 * 256
+                dst = torch.empty(batch * cap, dtype=torch.uint8, device="cuda")
+                run = st.prepared_batch([srcs[i % nsrc].data_ptr() for i in range(batch)], [(1080, 1920, c)] * batch, p,
+                                        [dst.data_ptr() + i * cap for i in range(batch)], [cap] * batch)
+                run(stream)
+                torch.cuda.synchronize()
+                runs[(kind, name, opt)] = (run, dst, [r[1] for r in st.batch_results()])
+    times = {k: [] for k in runs}
+    for _ in range(rounds):  # interleaved, so that a drift of the clocks falls on every variant alike
+        for k, (run, dst, nbytes) in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                run(stream)
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / iters * 1e3)
+    for (kind, name, opt), ts in times.items():
+        nbytes = runs[(kind, name, opt)][2]
+        print(f"{kind} {name} option {int(opt)}: {batch} x 1080p -> w=300&h=200&webp=true&quality={q}: ms per batch {' '.join(f'{t:.2f}' for t in ts)} "
+              f"(median {float(np.median(ts)):.2f}), mean file {np.mean(nbytes):.0f} bytes")
+    try:
+        print("webp_alpha_vp8l:", st.debug_get("webp_alpha_vp8l"))
+    except fl.FanlinError:  # (FLGPU_LIB points at a library from before the option: an A/B run)
+        print("webp_alpha_vp8l: not in this library")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -177,10 +239,14 @@ def main():
     ap.add_argument("--probs", action="store_true", help="also FLGPU_FE_WEBP_LOSSY_AP (and, with --i4, FLGPU_FE_WEBP_LOSSY_I4_AP)")
     ap.add_argument("--filter", action="store_true", help="also the loop-filtered twin (FLGPU_FE_WEBP_LOSSY_LF, ...) of every front end selected")
     ap.add_argument("--quality", type=int, default=75, help="the timing part's quality")
+    ap.add_argument("--alpha", action="store_true", help="FLGPU_FEO_ALPHA_VP8L: ALPH chunk bytes and batch times without and with the option (instead of the rest)")
     a = ap.parse_args()
     import __graft_entry__ as g
     fl = g._load_package()
     with fl.State(device=0, profile=a.events) as st:
+        if a.alpha:
+            alpha(fl, st, a.batch, a.iters, a.quality, profile=a.timing_only)
+            return
         if not a.timing_only:
             quality(fl, st, a.i4, a.probs, a.filter)
         timing(fl, st, a.batch, a.iters, a.host_threads, a.i4, a.events, a.probs, a.filter, a.quality)
