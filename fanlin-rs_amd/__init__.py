@@ -45,6 +45,8 @@ ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q
 ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those bodies come from FE_WEBP_LOSSY_I4; alone it does nothing
 ENCODE_WEBP_LOSSY_FILTER = 0x4000  # accept_flags bit: with ENCODE_WEBP_LOSSY, the loop-filtered twin of whatever the other bits select; alone, or without it, nothing
 ENCODE_WEBP_LOSSY_ALPHA = 0x20000  # accept_flags bit: with ENCODE_WEBP_LOSSY, a translucent picture's alpha plane goes out as a VP8L stream wherever that is smaller (FEO_ALPHA_VP8L); alone, or without it, nothing
+ENCODE_WEBP_LOSSY_SEGMENTS = 0x40000  # accept_flags bit: with ENCODE_WEBP_LOSSY, segment-adaptive quantisers -- up to four classes of macroblocks by activity (FEO_SEGMENTS); alone, or without it, nothing
+FEO_SEGMENTS = 2  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_SEGMENTS
 FEO_ALPHA_VP8L = 1  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_ALPHA
 ENCODE_WEBP_LOSSY_PROBS = 0x2000  # accept_flags bit: with ENCODE_WEBP_LOSSY (and _I4), FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, nothing
 OUT_KEEP, OUT_WEBP, OUT_AVIF = 0, 1, 2
@@ -436,7 +438,7 @@ CMYK_GRID, CMYK_INPUT_YCCK = 17, 1
 
 def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 32), crop=False, blur_sigma=0.0,
                 grayscale=False, inverse=False, quality=75, front_end=FE_NONE, orientation=1, filter=FILTER_LANCZOS3,
-                alpha_vp8l=False) -> flgpu_params:
+                alpha_vp8l=False, segments=False) -> flgpu_params:
     p = flgpu_params()
     p.has_dims = 1 if (w is not None and h is not None) else 0
     p.w, p.h = (w or 0), (h or 0)
@@ -447,7 +449,7 @@ def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 
     p.quality, p.front_end = quality, front_end
     p.orientation = orientation
     p.filter = filter
-    p.reserved[0] = FEO_ALPHA_VP8L if alpha_vp8l else 0  # the options byte
+    p.reserved[0] = (FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0)  # the options byte
     return p
 
 

@@ -85,7 +85,7 @@ struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
 struct ScratchSizes {
     size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
     size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
-    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0, vp8_lf = 0;
+    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0, vp8_lf = 0, vp8_seg = 0;
     uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
 };
 
@@ -114,6 +114,7 @@ struct Batch {
     uint32_t wjob_tiles = 0, ajob_tiles = 0; // tiles of each list: a launch numbers its own
     std::vector<Vp8Job> vjobs;
     uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
+    uint32_t vjobs_seg = 0; // how many of them carry FLGPU_FEO_SEGMENTS (and fit its limits): vp8_segment_kernel launches iff any does
     std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, ajob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
     uint32_t jpeg_max_blocks = 0;
     size_t mid_floats_max = 0;
@@ -433,7 +434,13 @@ bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU
 bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe) || vp8_fe_lf(fe); }
 // FLGPU_FEO_ALPHA_VP8L, which only these front ends know: the picture also gets the lossless coder's scratch, for its alpha plane
 bool vp8_alpha_vp8l(const flgpu_params &p) { return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_ALPHA_VP8L); }
-int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
+// FLGPU_FEO_SEGMENTS, on the same front ends: the picture gets a record and a class map, unless it fits the front end's limits but
+// not the segmented partition 0's -- then it is coded without the option
+bool vp8_segments(const flgpu_params &p, const flgpu_plan &pl)
+{
+    return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_SEGMENTS) && vp8_seg_fits(pl.out_w, pl.out_h, vp8_fe_i4(p.front_end), vp8_fe_ap(p.front_end));
+}
+int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe, bool seg)
 {
     const bool i4 = vp8_fe_i4(fe), ap = vp8_fe_ap(fe);
     const bool fits = ap ? (i4 ? vp8_i4_ap_fits(pl.out_w, pl.out_h) : vp8_ap_fits(pl.out_w, pl.out_h)) : i4 ? vp8_i4_fits(pl.out_w, pl.out_h) : vp8_fits(pl.out_w, pl.out_h);
@@ -442,6 +449,7 @@ int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe)
     if (i4) s.vp8_i4_mbs += mbs;
     if (ap) s.vp8_ap_pics++;
     if (vp8_fe_lf(fe)) s.vp8_lf += vp8_lf_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h));
+    if (seg) s.vp8_seg += vp8_seg_bytes(mbs);
     s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
     s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
     s.vp8_mbs += mbs;
@@ -500,7 +508,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
-        if (vp8_fe(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, w.p->front_end);
+        if (vp8_fe(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, w.p->front_end, vp8_segments(*w.p, pl));
         if (!rc && vp8_alpha_vp8l(*w.p)) rc = webpll_scratch(pl, B.scratch);
         if (rc) return rc;
     }
@@ -531,6 +539,7 @@ int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
     FL_HIP(c, c->d_vp8_bm.reserve(sz.vp8_i4_mbs * 2u * sizeof(uint32_t)), "lossy WebP sub-block mode records");
     FL_HIP(c, c->d_vp8_tab.reserve((size_t)sz.vp8_ap_pics * kVp8TabBytes), "lossy WebP probability tables");
     FL_HIP(c, c->d_vp8_lf.reserve(sz.vp8_lf), "lossy WebP loop filter scratch");
+    FL_HIP(c, c->d_vp8_seg.reserve(sz.vp8_seg), "lossy WebP segment scratch");
     FL_HIP(c, c->d_vp8_sizes.reserve((size_t)sz.vp8_pics * kVp8SizeWords * sizeof(uint32_t)), "lossy WebP partition sizes");
     FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
     FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
@@ -942,7 +951,10 @@ int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, uint32_t fe)
     j.lf_base = (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, B.dbg.get(DBG_VP8_FILTER_BASE)));
     const uint32_t q = B.work[i].p->quality;
     j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
-    return vp8_scratch(pl, at, fe);
+    const bool seg = vp8_segments(*B.work[i].p, pl);
+    j.seg = seg ? static_cast<uint8_t *>(c->d_vp8_seg.p) + at.vp8_seg : nullptr;
+    B.vjobs_seg += seg;
+    return vp8_scratch(pl, at, fe, seg);
 }
 
 // The planar front ends (JFIF444, WebP420): one launch per kind.  to_vp8: the pictures are lossy WebP jobs (B.vjobs from `vjob0`
@@ -1245,7 +1257,7 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
         ProfileScope ps(c, st, 7);
         // the alpha planes' streams: after the planes launch that wrote the planes and the translucency bits, before any frame kernel
         FL_HIP(c, launch_webpll_encode(B.d.ajobs, (uint32_t)B.ajobs.size(), B.ajob_tiles, st, kWebpllModeAlpha), "lossy WebP alpha plane encode");
-        FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_fam, st), "lossy WebP encode");
+        FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_fam, st, B.vjobs_seg), "lossy WebP encode");
         c->stats.frontend_launches++;
     }
     // plain copies for requests that change nothing
@@ -1323,6 +1335,7 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st)
     for (size_t i = 0; i < n; ++i) {
         if (c->last_fe[i] == FLGPU_FE_WEBP420 && (r[2 * i] & 1u)) dsts[i].flags |= FLGPU_IMG_HAS_ALPHA;
         if (vp8_fe(c->last_fe[i]) && r[2 * i + 1] && (r[2 * i] & kVp8ResultAlphaVp8l)) c->webp_alpha_vp8l++;
+        if (vp8_fe(c->last_fe[i]) && r[2 * i + 1] && (r[2 * i] & kVp8ResultSegments)) c->webp_lossy_segments++;
         if (fe_encoded(c->last_fe[i])) {
             dsts[i].bytes = r[2 * i + 1];
             if (!r[2 * i + 1]) { c->set_error("encoded stream does not fit the destination"); rc = FLGPU_ERR_BUFFER_TOO_SMALL; }

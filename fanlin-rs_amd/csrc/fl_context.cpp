@@ -517,7 +517,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->d_mid.release(); c->d_tmp_a.release(); c->d_tmp_b.release(); c->d_tmp_o.release(); c->d_tmp_al.release(); c->d_in.release(); c->d_out.release();
     c->d_jpeg_coef.release(); c->d_jpeg_off.release(); c->d_jpeg_raw.release();
     c->d_png_filt.release(); c->d_png_chunks.release(); c->d_png_syms.release(); c->d_png_recs.release();
-    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release(); c->d_vp8_bm.release(); c->d_vp8_tab.release(); c->d_vp8_lf.release();
+    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release(); c->d_vp8_bm.release(); c->d_vp8_tab.release(); c->d_vp8_lf.release(); c->d_vp8_seg.release();
     c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
@@ -671,7 +671,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
-        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l},
+        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments},
         {"vp8_sources", &flgpu_ctx::vp8_sources}, {"vp8_file_bytes", &flgpu_ctx::vp8_file_bytes}, {"vp8_upload_bytes", &flgpu_ctx::vp8_upload_bytes},
         {"vp8_decode_ns", &flgpu_ctx::vp8_decode_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},

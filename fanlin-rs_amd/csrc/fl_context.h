@@ -226,6 +226,7 @@ struct flgpu_ctx {
     fl::DeviceBuf d_vp8dec, d_vp8jobs;                 // lossy WebP decode (fl_vp8dec.hip): planes, alpha planes and pixels of a batch, job descriptors
     fl::PinnedBuf h_vp8jobs;
     uint64_t vp8_sources = 0, vp8_file_bytes = 0, vp8_upload_bytes = 0, vp8_decode_ns = 0;
+    uint64_t webp_lossy_segments = 0;                    // lossy WebP pictures whose frame went out segmented (FLGPU_FEO_SEGMENTS; from the result words)
     uint64_t webp_alpha_vp8l = 0;                        // lossy WebP pictures whose ALPH chunk went out as a VP8L stream (FLGPU_FEO_ALPHA_VP8L; from the result words)
     uint64_t webp_lossy_ns = 0;                          // HIP-event time of the lossy WebP encoder's launches (fl_vp8.hip; profile = 1)
     uint64_t webp_predict_ns = 0, webp_pointwise_ns = 0; // HIP-event time of the two kernels' launches (profile = 1; resolved by flgpu_get_stats)
@@ -241,7 +242,7 @@ struct flgpu_ctx {
     uint32_t last_jh_n = 0;
     fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): unit records, bit offsets, AC bits past a record
     fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
-    fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes, d_vp8_bm, d_vp8_tab, d_vp8_lf; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables, the loop-filtered variants' cost words and working copies
+    fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes, d_vp8_bm, d_vp8_tab, d_vp8_lf, d_vp8_seg; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables, the loop-filtered variants' cost words and working copies, the segmented pictures' records and class maps
     fl::DeviceBuf d_webpll_res, d_webpll_tok, d_webpll_tiles, d_webpll_pic, d_webpll_stream; // lossless WebP scratch (fl_webpll.hip): residuals, tokens, tile records, per-picture words, bit streams
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front

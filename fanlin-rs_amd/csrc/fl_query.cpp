@@ -226,6 +226,8 @@ try {
        compresses the alpha plane; every other front end ignores the option */
     if (p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY) && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA))
         p->options |= FLGPU_FEO_ALPHA_VP8L;
+    if (p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY) && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS))
+        p->options |= FLGPU_FEO_SEGMENTS;
     return FLGPU_OK;
 } FL_ABI_CATCH
 
@@ -285,6 +287,8 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
                            : p->front_end == FLGPU_FE_WEBP_LOSSY_AP ? FLGPU_FE_WEBP_LOSSY_AP_LF : FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
         // _ALPHA: the option on whichever front end that is (a WebP source that stays WebP got its front end after the mapping above)
         if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA) p->options |= FLGPU_FEO_ALPHA_VP8L;
+        // _SEGMENTS likewise: segment-adaptive quantisers on whichever front end that is
+        if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS) p->options |= FLGPU_FEO_SEGMENTS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
     if (rc == FLGPU_OK && webp_lossless && plan->out_w <= fl::kWebpllMaxSide && plan->out_h <= fl::kWebpllMaxSide) {
@@ -928,6 +932,10 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
         plan->max_out_bytes = ap ? (i4 ? fl::vp8_i4_ap_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_ap_max_out_bytes(plan->out_w, plan->out_h))
                                  : (i4 ? fl::vp8_i4_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_max_out_bytes(plan->out_w, plan->out_h));
+        // FLGPU_FEO_SEGMENTS: the segment header and two booleans of id per macroblock more in partition 0 (a picture over the
+        // segmented limits is coded without the option and keeps the bound above)
+        if ((p->options & FLGPU_FEO_SEGMENTS) && fl::vp8_seg_fits(plan->out_w, plan->out_h, i4, ap))
+            plan->max_out_bytes = fl::vp8_seg_max_out_bytes(plan->out_w, plan->out_h, i4, ap);
         break;
     }
     case FLGPU_FE_WEBP420:

@@ -42,6 +42,17 @@
 //                       samples in 64 bits and one thread stores the candidate's word.
 //   vp8_size_kernel<I4, AP, true>, vp8_write_kernel<I4, AP, true>  the coders; the partition-0 lane derives the level from the
 //                       picture's four words (vp8_lf_choice) and writes it into the frame header.
+// FLGPU_FEO_SEGMENTS (fl_vp8_seg_core.h; a bit of flgpu_params::options on any of the eight front ends) adds one launch in front of
+// everything, only when some job of the batch carries the option:
+//   vp8_segment_kernel  one 256-thread workgroup per picture (it returns at once for a job without the option).  Waves stride over
+//                       the macroblocks: 64 lanes x 4 luma samples, two wave reductions (mean, then activity), lane 0 stores the
+//                       macroblock's bin and adds to a 256-word LDS histogram.  After a barrier the classification runs one
+//                       thread per bin (class sums by LDS atomics, four threads move the centres), one thread derives the indices
+//                       and the tree's probabilities and stores the picture's record, and all threads turn the stored bins into
+//                       classes.  Batch-parallel, no chain between macroblocks.
+// The analysis kernels then take each macroblock's steps from its class (vp8_seg_pick: one uniform branch and table look-up per
+// macroblock), vp8_lf_inner dequantises a Y2 block with them, and the partition-0 lane of the coders writes the segment header and
+// the ids (at run time, not a template axis).  Integer atomics only: the result does not depend on their order.
 // A batch's pictures are grouped by front end in the job list, so each of the eight families is one range of it.
 // No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
 // A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
@@ -52,6 +63,7 @@
 #include "fl_vp8_ap_core.h"
 #include "fl_vp8_i4_core.h"
 #include "fl_vp8_lf_core.h"
+#include "fl_vp8_seg_core.h"
 #include "fl_wave.h"
 
 namespace fl {
@@ -66,6 +78,8 @@ constexpr uint32_t kCoderThreads = 256;
 constexpr uint32_t kFrameThreads = 256;
 constexpr uint32_t kStatsThreads = 256;
 constexpr uint32_t kLfThreads = 256;
+constexpr uint32_t kSegThreads = 256;
+static_assert(kSegThreads == kVp8SegBins, "the classification runs one thread per bin");
 // the adaptive coders stage one table per workgroup: a workgroup's slots must be exactly one picture's
 static_assert(kCoderThreads / kLaneStride == kLaneSlots && kCoderThreads % kLaneStride == 0, "a coder workgroup is one picture");
 
@@ -76,17 +90,87 @@ __device__ __forceinline__ Vp8Pic pic_of(const Vp8Job &j, const uint8_t *prob = 
     p.prob = prob;
     p.src = j.src; p.rec = j.rec; p.lev = j.lev; p.info = j.info; p.bm = j.bm;
     p.q = vp8_quant(j.qi);
+    if (j.seg) { p.seg = reinterpret_cast<const Vp8SegRec *>(j.seg); p.segmap = j.seg + kVp8SegHead; } // (uniform over the picture)
     return p;
+}
+
+// The picture's classes and their quantiser indices (fl_vp8_seg_core.h states the rule).  Every barrier is in control flow uniform
+// over the workgroup; no workgroup waits on another.
+__global__ __launch_bounds__(kSegThreads) void vp8_segment_kernel(const Vp8Job *__restrict__ jobs)
+{
+    __shared__ uint32_t s_hist[kVp8SegBins];
+    __shared__ uint32_t s_n[4], s_sum[4], s_lo, s_hi;
+    __shared__ int32_t s_c[4];
+    __shared__ uint8_t s_cls[kVp8SegBins];
+    __shared__ Vp8SegRec s_rec;
+    const Vp8Job &jb = jobs[blockIdx.x];
+    if (!jb.seg) return; // (uniform) the job does not carry the option
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t mbw = vp8_mbs(jb.w), mbh = vp8_mbs(jb.h), mbs = mbw * mbh;
+    uint8_t *map = jb.seg + kVp8SegHead;
+    s_hist[tid] = 0u; s_cls[tid] = 0;
+    if (tid < 4u) { s_n[tid] = 0u; s_sum[tid] = 0u; s_c[tid] = 0; }
+    if (tid == 0u) { s_lo = kVp8SegBins; s_hi = 0u; }
+    __syncthreads();
+    // phase A: the activity of every macroblock; the bound is the wave's, all 64 lanes take part in both reductions
+    for (uint32_t mb = wave; mb < mbs; mb += kSegThreads / 64u) {
+        const uint32_t mbx = mb % mbw, mby = mb / mbw;
+        uint32_t y[4], sum = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) { y[i] = vp8_seg_sample(jb.src, jb.w, jb.h, mbx, mby, lane * 4u + i); sum += y[i]; }
+        const uint32_t m = vp8_seg_mean(wave_sum<uint32_t>(sum));
+        uint32_t dev = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) dev += vp8_seg_dev(y[i], m);
+        const uint32_t bin = vp8_seg_bin(wave_sum<uint32_t>(dev));
+        if (lane == 0u) {
+            map[mb] = (uint8_t)bin;
+            atomicAdd(&s_hist[bin], 1u);
+            if (bin) { atomicMin(&s_lo, bin); atomicMax(&s_hi, bin); }
+        }
+    }
+    __syncthreads();
+    // phase B: thread a is bin a
+    const uint32_t lo = s_lo, hi = s_hi, mine = s_hist[tid];
+    const bool ranged = lo < hi; // (uniform) else: no non-flat macroblock, or one occupied bin
+    if (ranged) {
+        if (tid < 4u) s_c[tid] = vp8_seg_centre0(lo, hi, tid);
+        __syncthreads();
+        for (uint32_t round = 0; round <= kVp8SegRounds; ++round) {
+            if (tid >= lo && tid <= hi) {
+                int32_t c[4] = {s_c[0], s_c[1], s_c[2], s_c[3]};
+                const uint32_t k = vp8_seg_nearest((int32_t)tid, c);
+                s_cls[tid] = (uint8_t)k;
+                if (mine) { atomicAdd(&s_n[k], mine); atomicAdd(&s_sum[k], tid * mine); } // (below 2^32: 255 x the macroblock limit)
+            }
+            __syncthreads();
+            if (round < kVp8SegRounds && tid < 4u) { s_c[tid] = vp8_seg_centre(s_sum[tid], s_n[tid], s_c[tid]); s_n[tid] = 0u; s_sum[tid] = 0u; }
+            __syncthreads();
+        }
+    }
+    if (tid == 0u) {
+        const int32_t c[4] = {s_c[0], s_c[1], s_c[2], s_c[3]};
+        const uint32_t n[4] = {s_n[0], s_n[1], s_n[2], s_n[3]};
+        Vp8SegRec r;
+        vp8_seg_finish(r, c, n, ranged ? s_hist[0] : 0u, jb.qi); // (not ranged: n = 0, not segmented)
+        s_rec = r;
+        *reinterpret_cast<Vp8SegRec *>(jb.seg) = r;
+    }
+    __syncthreads();
+    // phase C: the bins become classes
+    const bool on = s_rec.on != 0;
+    for (uint32_t mb = tid; mb < mbs; mb += kSegThreads) map[mb] = on ? s_cls[map[mb]] : (uint8_t)0;
 }
 
 __global__ __launch_bounds__(64) void vp8_analyse_kernel(const Vp8Job *__restrict__ jobs)
 {
     __shared__ Vp8Mb m;
     const Vp8Job &jb = jobs[blockIdx.x];
-    const Vp8Pic p = pic_of(jb);
+    Vp8Pic p = pic_of(jb);
     const uint32_t lane = threadIdx.x;
     for (uint32_t mby = 0; mby < p.mbh; ++mby)
         for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) {
+            vp8_seg_pick(p, (uint64_t)mby * p.mbw + mbx); // (uniform) FLGPU_FEO_SEGMENTS: the steps of the macroblock's class
             for (uint32_t k = lane; k < kVp8LoadItems; k += 64u) vp8_phase_load(p, m, mbx, mby, k);
             __syncthreads();
             if (lane < 3u) vp8_phase_dc(m, mbx, mby, lane);
@@ -143,10 +227,11 @@ __global__ __launch_bounds__(64) void vp8_analyse_i4_kernel(const Vp8Job *__rest
     __shared__ Vp8Mb m;
     __shared__ Vp8I4 t;
     const Vp8Job &jb = jobs[blockIdx.x];
-    const Vp8Pic p = pic_of(jb);
+    Vp8Pic p = pic_of(jb);
     const uint32_t lane = threadIdx.x;
     for (uint32_t mby = 0; mby < p.mbh; ++mby)
         for (uint32_t mbx = 0; mbx < p.mbw; ++mbx) {
+            vp8_seg_pick(p, (uint64_t)mby * p.mbw + mbx); // (uniform) FLGPU_FEO_SEGMENTS: the steps of the macroblock's class
             for (uint32_t k = lane; k < kVp8LoadItems; k += 64u) vp8_phase_load(p, m, mbx, mby, k);
             if (lane < kVp8I4BeginItems) vp8_i4_phase_begin(p, t, mbx, mby, lane);
             __syncthreads();
@@ -323,6 +408,7 @@ __global__ __launch_bounds__(kFrameThreads) void vp8_frame_kernel(const Vp8Job *
     if (threadIdx.x == 0u) {
         vp8_put_framing(jb.dst, L, jb.w, jb.h, alpha, nparts, size);
         jb.result[1] = L.total;
+        if (jb.seg && reinterpret_cast<const Vp8SegRec *>(jb.seg)->on) jb.result[0] |= kVp8ResultSegments; // (this thread alone writes the word in this launch)
     }
     if (alpha) {
         const uint32_t npix = jb.w * jb.h;
@@ -377,8 +463,14 @@ template <bool I4, bool AP, bool LF> static hipError_t launch_family(const Vp8Jo
     return hipGetLastError();
 }
 
-hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st)
+hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families], hipStream_t st, uint32_t segmented)
 {
+    if (segmented) {
+        uint32_t all = 0;
+        for (uint32_t f = 0; f < kVp8Families; ++f) all += n[f];
+        hipLaunchKernelGGL(vp8_segment_kernel, dim3(all), dim3(kSegThreads), 0, st, jobs);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
     if (hipError_t e = launch_family<false, false, false>(jobs, n[0], st)) return e;
     jobs += n[0];
     if (hipError_t e = launch_family<true, false, false>(jobs, n[1], st)) return e;

@@ -35,6 +35,12 @@
 // The loop-filtered variants (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF; fl_vp8_lf_core.h states the rule,
 // tests/vp8_lf_model.py restates it): the same again, but the frame header's loop filter level is the one of four candidates whose
 // filtered reconstruction is nearest to the source; what a decoder shows is that filtered picture.
+//
+// Segment-adaptive quantisers (FLGPU_FEO_SEGMENTS, a bit of flgpu_params::options on any of the eight front ends; fl_vp8_seg_core.h
+// states the rule, tests/vp8_seg_model.py restates it): the macroblocks are sorted into up to four classes by luma activity and
+// each class is coded at a quantiser index of its own around the picture's; the frame header carries the segment header (absolute
+// values, the frame's filter level in every segment) and every macroblock its id in front of its skip flag.  Where the rule finds
+// nothing to separate, the stream is the one above ("one segment"), byte for byte.
 #pragma once
 #include <stdint.h>
 
@@ -91,6 +97,24 @@ static_assert(kVp8MaxMbsI4Ap == 5039, "the B_PRED variant with updates: 72 macro
 // (the 1056 literals are whole bytes of worst case: the partition-0 term grows by exactly 7 x 8448 / 8 = 7392)
 static_assert(kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) % 8u == 0 && kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) / 8u == 7392, "the updates' worst case");
 
+// With FLGPU_FEO_SEGMENTS (fl_vp8_seg_core.h) partition 0 also holds the segment header -- update_mb_segmentation_map,
+// update_segment_feature_data and segment_feature_mode (3), four quantisers of flag + 7 bits + sign (36), four filter strengths of
+// flag + 6 bits + sign (32), three tree probabilities of flag + 8 bits (27): 98 -- and two booleans of segment id per macroblock.
+constexpr uint64_t kVp8Part0SegBools = 3 + 4 * 9 + 4 * 8 + 3 * 9, kVp8Part0MbSegBools = 2;
+static_assert(kVp8Part0SegBools == 98, "the segment header");
+FL_VP8_HD uint64_t vp8_seg_part0_max_bytes(uint64_t mbs, bool i4, bool ap)
+{
+    return (kVp8BoolBits * ((ap ? kVp8Part0BoolsAp : kVp8Part0Bools) + kVp8Part0SegBools + ((i4 ? kVp8Part0MbBoolsI4 : kVp8Part0MbBools) + kVp8Part0MbSegBools) * mbs) + 7u) / 8u;
+}
+constexpr uint64_t vp8_seg_max_mbs(uint64_t fixed_bools, uint64_t mb_bools) { return (((1ull << 19) - 1u) * 8u / kVp8BoolBits - fixed_bools - kVp8Part0SegBools) / (mb_bools + kVp8Part0MbSegBools); }
+constexpr uint64_t kVp8MaxMbsSeg = vp8_seg_max_mbs(kVp8Part0Bools, kVp8Part0MbBools), kVp8MaxMbsI4Seg = vp8_seg_max_mbs(kVp8Part0Bools, kVp8Part0MbBoolsI4);
+constexpr uint64_t kVp8MaxMbsApSeg = vp8_seg_max_mbs(kVp8Part0BoolsAp, kVp8Part0MbBools), kVp8MaxMbsI4ApSeg = vp8_seg_max_mbs(kVp8Part0BoolsAp, kVp8Part0MbBoolsI4);
+static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0SegBools + (kVp8Part0MbBools + kVp8Part0MbSegBools) * kVp8MaxMbsSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0SegBools + (kVp8Part0MbBoolsI4 + kVp8Part0MbSegBools) * kVp8MaxMbsI4Seg) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0SegBools + (kVp8Part0MbBools + kVp8Part0MbSegBools) * kVp8MaxMbsApSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0SegBools + (kVp8Part0MbBoolsI4 + kVp8Part0MbSegBools) * kVp8MaxMbsI4ApSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
+static_assert(kVp8MaxMbsI4Seg == 5024 && kVp8MaxMbsI4ApSeg == 4953, "the B_PRED variants with segments: 87 and 86 macroblocks fewer than without");
+
 FL_VP8_HD uint32_t vp8_mbs(uint32_t px) { return (px + 15u) >> 4; }
 // token partitions: the largest of 1 / 2 / 4 / 8 that is not above the number of macroblock rows; row r goes to partition r mod n
 FL_VP8_HD uint32_t vp8_partitions(uint32_t mb_rows) { return mb_rows >= 8 ? 8u : mb_rows >= 4 ? 4u : mb_rows >= 2 ? 2u : 1u; }
@@ -137,6 +161,19 @@ FL_VP8_HD uint64_t vp8_i4_ap_max_out_bytes(uint64_t w, uint64_t h)
 {
     const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
     return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_ap_part0_max_bytes(mbs);
+}
+
+// with FLGPU_FEO_SEGMENTS: the front end's limits with the segmented partition 0 (a picture that fits the front end but not these
+// is coded without the option)
+FL_VP8_HD bool vp8_seg_fits(uint64_t w, uint64_t h, bool i4, bool ap)
+{
+    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
+    return vp8_fits(w, h) && mbs <= (ap ? (i4 ? kVp8MaxMbsI4ApSeg : kVp8MaxMbsApSeg) : (i4 ? kVp8MaxMbsI4Seg : kVp8MaxMbsSeg));
+}
+FL_VP8_HD uint64_t vp8_seg_max_out_bytes(uint64_t w, uint64_t h, bool i4, bool ap)
+{
+    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
+    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_seg_part0_max_bytes(mbs, i4, ap);
 }
 
 // ---- quantiser --------------------------------------------------------------------------------------------------------------------
@@ -284,8 +321,21 @@ struct Vp8Pic {
     uint32_t *bm = nullptr;
     const uint8_t *prob;   // kVp8CoefProb or, in the adaptive-probability variants, the picture's table; the kernels keep a copy in LDS
     uint32_t w, h, cw, ch, mbw, mbh;
-    Vp8Quant q;
+    Vp8Quant q;            // the picture's steps; with FLGPU_FEO_SEGMENTS the current macroblock's (vp8_seg_pick)
+    const struct Vp8SegRec *seg = nullptr; // FLGPU_FEO_SEGMENTS only: the picture's record and, per macroblock, its class
+    const uint8_t *segmap = nullptr;
 };
+
+// What the segment rule (fl_vp8_seg_core.h) leaves of a picture: the quantiser index of each class, the probabilities of the
+// segment tree, and whether the file is segmented at all (else the four indices are the picture's and every macroblock is class 0).
+struct Vp8SegRec { uint8_t qi[4], prob[3], on; };
+static_assert(sizeof(Vp8SegRec) == 8, "the record in scratch");
+constexpr uint32_t kVp8SegHead = 16; // bytes of scratch in front of the class map
+FL_VP8_HD uint64_t vp8_seg_bytes(uint64_t mbs) { return (kVp8SegHead + mbs + 15u) & ~(uint64_t)15u; }
+// the steps of macroblock mb
+FL_VP8_HD Vp8Quant vp8_mb_quant(const Vp8Pic &p, uint64_t mb) { return p.seg ? vp8_quant(p.seg->qi[p.segmap[mb] & 3u]) : p.q; }
+// before the phases of macroblock mb: its class's steps become p.q (one branch, uniform over the picture)
+FL_VP8_HD void vp8_seg_pick(Vp8Pic &p, uint64_t mb) { if (p.seg) p.q = vp8_quant(p.seg->qi[p.segmap[mb] & 3u]); }
 
 FL_VP8_HD void vp8_pic_dims(Vp8Pic &p, uint32_t w, uint32_t h)
 {
@@ -684,6 +734,7 @@ FL_VP8_HD uint32_t vp8_skip_prob(uint32_t mbs, uint32_t skipped)
 // partition 0: the frame header and every macroblock's skip flag and modes.  AP (the adaptive-probability variants): p.prob is the
 // picture's table, and entry i is updated exactly where it differs from the default one (the rule never picks an equal value)
 // LF (the loop-filtered variants, fl_vp8_lf_core.h): `level` is the loop filter level of the frame header; else it is 0
+// p.seg (FLGPU_FEO_SEGMENTS, at run time): a segmented picture's header and, per macroblock, its id in front of the skip flag
 template <bool I4 = false, bool AP = false, bool LF = false> FL_VP8_HD void vp8_put_first_partition(Vp8Bool &bw, const Vp8Pic &p, uint32_t qi, uint32_t nparts, uint32_t level = 0u)
 {
     const uint32_t mbs = p.mbw * p.mbh;
@@ -692,7 +743,15 @@ template <bool I4 = false, bool AP = false, bool LF = false> FL_VP8_HD void vp8_
     const uint32_t ps = vp8_skip_prob(mbs, skipped);
     bw.literal(0, 1);                       // colour space
     bw.literal(0, 1);                       // clamping is needed
-    bw.literal(0, 1);                       // no segments
+    const bool seg = p.seg && p.seg->on;    // FLGPU_FEO_SEGMENTS and the rule found classes that differ
+    bw.literal(seg, 1);                     // segmentation_enabled
+    if (seg) {
+        bw.literal(1, 1); bw.literal(1, 1); bw.literal(1, 1); // update the map, update the data, absolute values
+        for (int k = 0; k < 4; ++k) { bw.literal(1, 1); bw.literal(p.seg->qi[k], 7); bw.literal(0, 1); }
+        // (under absolute values a decoder takes a macroblock's filter level from its segment: the frame's, four times)
+        for (int k = 0; k < 4; ++k) { bw.literal(LF && level, 1); if (LF && level) { bw.literal(level, 6); bw.literal(0, 1); } }
+        for (int k = 0; k < 3; ++k) { bw.literal(p.seg->prob[k] != 255u, 1); if (p.seg->prob[k] != 255u) bw.literal(p.seg->prob[k], 8); }
+    }
     bw.literal(0, 1); bw.literal(LF ? level : 0u, 6); bw.literal(0, 3); // normal filter, its level, sharpness 0
     bw.literal(0, 1);                       // no filter deltas
     bw.literal(nparts == 8u ? 3u : nparts == 4u ? 2u : nparts == 2u ? 1u : 0u, 2);
@@ -708,6 +767,11 @@ template <bool I4 = false, bool AP = false, bool LF = false> FL_VP8_HD void vp8_
     bw.literal(ps, 8);
     for (uint32_t mb = 0; mb < mbs; ++mb) {
         const uint32_t info = p.info[mb], ym = info & 3u, uvm = (info >> 2) & 3u;
+        if (seg) {
+            const uint32_t s = p.segmap[mb];
+            bw.put(s >= 2u, p.seg->prob[0]);
+            bw.put(s & 1u, s >= 2u ? p.seg->prob[2] : p.seg->prob[1]);
+        }
         bw.put(vp8_coded<I4>(p, mb) == 0u, ps);
         if (I4 && vp8_is_i4(p, mb)) {
             bw.put(0, kVp8YModeProb[0]);

@@ -63,7 +63,8 @@ template <bool I4> FL_VP8_HD bool vp8_lf_inner(const Vp8Pic &p, uint64_t mb)
     // only Y2 levels: the luma DCs the decoder will see
     const int16_t *l = p.lev + mb * kVp8MbLevels + 24u * 16u;
     int in[16], dc[16];
-    for (int k = 0; k < 16; ++k) in[kVp8Zigzag[k]] = (int16_t)(l[k] * (int)(k ? p.q.y2_ac : p.q.y2_dc));
+    const Vp8Quant q = vp8_mb_quant(p, mb); // (with FLGPU_FEO_SEGMENTS: the steps a decoder takes for this macroblock's segment)
+    for (int k = 0; k < 16; ++k) in[kVp8Zigzag[k]] = (int16_t)(l[k] * (int)(k ? q.y2_ac : q.y2_dc));
     vp8_iwht(in, dc);
     bool any = false;
     for (int b = 0; b < 16; ++b) any |= (int16_t)dc[b] != 0;

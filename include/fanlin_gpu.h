@@ -220,6 +220,12 @@ typedef enum flgpu_front_end {
  * other bits select, fall-backs included): the same pixels from every decoder, a file that is never larger.  Opaque pictures keep
  * their bytes.  Alone, or without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_ALPHA 0x20000u
+/* Not a content::Format bit: together with FLGPU_ENCODE_WEBP_LOSSY, the lossy image/webp bodies are coded with segment-adaptive
+ * quantisers (FLGPU_FEO_SEGMENTS on whichever lossy front end the other bits select, fall-backs included): up to four classes of
+ * macroblocks by activity, flat regions at a finer step than texture, as libwebp's own default (four segments) does.  A picture
+ * whose classes all come out at the picture's index keeps its file byte for byte.  max_out_bytes grows by the segment header and
+ * the ids.  Alone, or without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
+#define FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS 0x40000u
 /* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
  * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
  * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
@@ -263,6 +269,14 @@ typedef struct flgpu_params {
  * of a translucent picture as header byte 0x01 and a VP8L stream -- lossless, no filter, no pre-processing -- iff that payload is
  * strictly smaller than the raw one, which is used otherwise; decided on the device.  Every other front end ignores the bit. */
 #define FLGPU_FEO_ALPHA_VP8L 1u
+/* FLGPU_FEO_SEGMENTS: the same eight front ends sort the picture's macroblocks into up to four classes by luma activity on the device
+ * and code each class at a quantiser index of its own around the one from `quality` (DESIGN.md section 4 states the integer rule):
+ * the frame header carries the segment header (absolute values, the frame's filter level in every segment), every macroblock its
+ * segment id.  Where the rule finds nothing to separate -- one macroblock, a flat picture, one activity bin, every used class at the
+ * picture's index -- the file is the one without the bit, byte for byte.  A picture that fits the front end's limits but not the
+ * segmented ones (see max_out_bytes) is coded without the bit.  Every other front end ignores it; alone or with
+ * FLGPU_FEO_ALPHA_VP8L. */
+#define FLGPU_FEO_SEGMENTS 2u
 
 /* Geometry decided on the host before any pixel is touched. */
 typedef struct flgpu_plan {
@@ -302,6 +316,10 @@ typedef struct flgpu_plan {
                                           level's six were counted all along).
                                           All eight with FLGPU_FEO_ALPHA_VP8L: unchanged (w h stands for the raw alpha plane, and a
                                           compressed one is only written where it is smaller).
+                                          All eight with FLGPU_FEO_SEGMENTS: 98 booleans of segment header and 2 per macroblock more
+                                          in the first partition (1224 + 9 per macroblock where 1126 + 7 stands above); at most
+                                          5024 macroblocks with B_PRED, 4953 with B_PRED and updates -- a picture over that is
+                                          coded without the bit and keeps the bound without it.
                                           Otherwise equal to out_bytes. */
 } flgpu_plan;
 

@@ -102,6 +102,9 @@ public:
     // ... with the alpha plane of a translucent picture as a VP8L stream wherever that is smaller: FLGPU_FEO_ALPHA_VP8L on
     // whichever front end the calls above select
     void encode_webp_lossy_alpha() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_ALPHA; }
+    // ... with segment-adaptive quantisers (up to four classes of macroblocks by activity): FLGPU_FEO_SEGMENTS on whichever front
+    // end the calls above select
+    void encode_webp_lossy_segments() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS; }
     uint32_t flags() const { return flags_; }
 
 private:

@@ -15,6 +15,12 @@ option beside libwebp's own ALPH for the same plane; then, in interleaved rounds
 translucent twin of it (a disc alpha plane over the same pictures) without and with the option, for FLGPU_FE_WEBP_LOSSY and
 FLGPU_FE_WEBP_LOSSY_AP, with the mean file bytes.  With --timing-only as well: only the translucent FLGPU_FE_WEBP_LOSSY batch with the
 option, 1 + --iters times (the run to put under `rocprofv3 --kernel-trace --stats`).
+--segments: instead of the above, FLGPU_FEO_SEGMENTS: per quality the flagship request's file without and with the option beside
+libwebp's on the same planes (bytes, Y-PSNR, Y-PSNR over the lower-activity and the upper-activity half of the macroblocks, the class
+indices); then, in interleaved rounds, the time per flagship batch without and with the option, for FLGPU_FE_WEBP_LOSSY and
+FLGPU_FE_WEBP_LOSSY_AP: the host's clock around synchronised batches and, with --events, the HIP events the library records around the
+encoder's own launches (webp_lossy_ns: the segment kernel is inside, the resample and planes launches are not).  With --timing-only as well: only the FLGPU_FE_WEBP_LOSSY batch, 1 + --iters times, with
+the option -- or with --no-option without it (the runs to put under `rocprofv3 --kernel-trace --stats`).
 """
 import argparse
 import math
@@ -228,6 +234,63 @@ def alpha(fl, st, batch, iters, q=75, rounds=3, profile=False):
         print("webp_alpha_vp8l: not in this library")
 
 
+def segments(fl, st, batch, iters, q=75, rounds=3, profile=False, option=True, events=False):
+    import torch
+    import synth
+    import vp8_lib
+    import vp8_seg_model as sm
+    import webp_lib
+    big = synth.photo(1080, 1920, 3, index=3)
+    for qq in () if profile else (1, 30, 75, 99):
+        pl = st.process_pixels(big, fl.make_params(300, 200, quality=qq, front_end=fl.FE_WEBP420))
+        act = sm.activity(pl.y)
+        low = np.zeros(act.size, bool)
+        low[np.argsort(act.reshape(-1), kind="stable")[:act.size // 2]] = True
+        mask = np.repeat(np.repeat(low.reshape(act.shape), 16, axis=0), 16, axis=1)[:200, :300]
+        files = {"twin": st.process_pixels(big, fl.make_params(300, 200, quality=qq, front_end=fl.FE_WEBP_LOSSY)),
+                 "segments": st.process_pixels(big, fl.make_params(300, 200, quality=qq, front_end=fl.FE_WEBP_LOSSY, segments=True)),
+                 "libwebp": webp_lib.encode_planes(pl.y, pl.u, pl.v, qq)}
+        rule = sm.rule(pl.y, sm.vm.QUALITY_TO_INDEX[qq])
+        for who, data in files.items():
+            y = vp8_lib.decode_yuv(data)[0]
+            print(f"quality {qq}: {who} {len(data)} bytes, Y-PSNR {_psnr(y, pl.y):.2f} dB (lower-activity half {_psnr(y[mask], pl.y[mask]):.2f}, upper {_psnr(y[~mask], pl.y[~mask]):.2f})")
+        print(f"quality {qq}: classes {rule['qi']} around {sm.vm.QUALITY_TO_INDEX[qq]}, macroblocks per class {rule['counts']}, tree probabilities {rule['prob']}")
+    nsrc = 16
+    srcs = [torch.from_numpy(synth.photo(1080, 1920, 3, index=40 + i)).cuda() for i in range(nsrc)]
+    stream = torch.cuda.current_stream().cuda_stream
+    runs = {}
+    kinds = (("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY, option),) if profile else tuple((n, fe, o) for n, fe in (("FE_WEBP_LOSSY", fl.FE_WEBP_LOSSY), ("FE_WEBP_LOSSY_AP", fl.FE_WEBP_LOSSY_AP)) for o in (False, True))
+    for name, fe, opt in kinds:
+        p = fl.make_params(300, 200, quality=q, front_end=fe, segments=opt)
+        cap = (int(fl.plan_output(p, 1920, 1080, 3).max_out_bytes) + 255) // 256 * 256
+        dst = torch.empty(batch * cap, dtype=torch.uint8, device="cuda")
+        run = st.prepared_batch([srcs[i % nsrc].data_ptr() for i in range(batch)], [(1080, 1920, 3)] * batch, p,
+                                [dst.data_ptr() + i * cap for i in range(batch)], [cap] * batch)
+        run(stream)
+        torch.cuda.synchronize()
+        runs[(name, opt)] = (run, dst, [r[1] for r in st.batch_results()])
+    times, dev = {k: [] for k in runs}, {k: [] for k in runs}
+    for _ in range(1 if profile else rounds):  # interleaved, so that a drift of the clocks falls on every variant alike
+        for k, (run, dst, nbytes) in runs.items():
+            torch.cuda.synchronize()
+            ns0 = (st.stats(), st.debug_get("webp_lossy_ns"))[1] if events else 0  # (flgpu_get_stats resolves the pending events)
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                run(stream)
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / iters * 1e3)
+            if events:
+                dev[k].append(((st.stats(), st.debug_get("webp_lossy_ns"))[1] - ns0) / iters / 1e6)
+    for (name, opt), ts in times.items():
+        print(f"{name} option {int(opt)}: {batch} x 1080p -> w=300&h=200&webp=true&quality={q}: ms per batch {' '.join(f'{t:.2f}' for t in ts)} "
+              f"(median {float(np.median(ts)):.2f})" + (f", of which the encoder's launches by device events {' '.join(f'{t:.2f}' for t in dev[(name, opt)])} "
+              f"(median {float(np.median(dev[(name, opt)])):.2f})" if events else "") + f", mean file {np.mean(runs[(name, opt)][2]):.0f} bytes")
+    try:
+        print("webp_lossy_segments:", st.debug_get("webp_lossy_segments"))
+    except fl.FanlinError:  # (FLGPU_LIB points at a library from before the option: an A/B run)
+        print("webp_lossy_segments: not in this library")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -240,10 +303,15 @@ def main():
     ap.add_argument("--filter", action="store_true", help="also the loop-filtered twin (FLGPU_FE_WEBP_LOSSY_LF, ...) of every front end selected")
     ap.add_argument("--quality", type=int, default=75, help="the timing part's quality")
     ap.add_argument("--alpha", action="store_true", help="FLGPU_FEO_ALPHA_VP8L: ALPH chunk bytes and batch times without and with the option (instead of the rest)")
+    ap.add_argument("--segments", action="store_true", help="FLGPU_FEO_SEGMENTS: files and batch times without and with the option (instead of the rest)")
+    ap.add_argument("--no-option", action="store_true", help="with --segments --timing-only: the batch without the option")
     a = ap.parse_args()
     import __graft_entry__ as g
     fl = g._load_package()
     with fl.State(device=0, profile=a.events) as st:
+        if a.segments:
+            segments(fl, st, a.batch, a.iters, a.quality, profile=a.timing_only, option=not a.no_option, events=a.events)
+            return
         if a.alpha:
             alpha(fl, st, a.batch, a.iters, a.quality, profile=a.timing_only)
             return
