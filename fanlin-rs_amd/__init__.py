@@ -35,7 +35,6 @@ FE_WEBP_LOSSY_AP = 12  # FE_WEBP_LOSSY with per-picture coefficient probabilitie
 FE_WEBP_LOSSY_I4_AP = 13  # FE_WEBP_LOSSY_I4 with per-picture coefficient probabilities
 # the loop-filtered twin of each of the four: the frame header's loop filter level is picked on the device (14 and 15 are not front ends)
 FE_WEBP_LOSSY_LF, FE_WEBP_LOSSY_I4_LF, FE_WEBP_LOSSY_AP_LF, FE_WEBP_LOSSY_I4_AP_LF = 16, 17, 18, 19
-VP8_LF_TWIN = {9: 16, 10: 17, 12: 18, 13: 19}  # front end -> its loop-filtered twin
 FE_WEBP_LOSSY_ALL = (9, 10, 12, 13, 16, 17, 18, 19)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
@@ -686,50 +685,52 @@ def _as_image_array(a: np.ndarray) -> np.ndarray:
     return a
 
 
+def vp8_front_end(i4: bool = False, ap: bool = False, lf: bool = False) -> int:
+    """csrc/fl_vp8_variant.h vp8_front_end: the lossy WebP front end of a variant -- i4: macroblocks may be B_PRED, ap: per-picture
+    coefficient probabilities, lf: a loop filter level picked on the device."""
+    return (FE_WEBP_LOSSY_LF + (2 if ap else 0) if lf else FE_WEBP_LOSSY_AP if ap else FE_WEBP_LOSSY) + (1 if i4 else 0)
+
+
+def vp8_variant(front_end: int) -> Optional[Tuple[bool, bool, bool]]:
+    """csrc/fl_vp8_variant.h vp8_variant_of: (i4, ap, lf) of a lossy WebP front end, None for anything else."""
+    for f in range(8):
+        v = (bool(f & 1), bool(f & 2), bool(f & 4))
+        if vp8_front_end(*v) == front_end:
+            return v
+    return None
+
+
+def _vp8_part0_bools(i4: bool, ap: bool, seg: bool) -> Tuple[int, int]:
+    """csrc/fl_vp8_core.h vp8_part0_fixed_bools, vp8_part0_mb_bools: the first partition's worst case in booleans, fixed (1126; 9574
+    with ap, each of the 1056 update flags may carry 8 bits; 98 more with seg) and per macroblock (7; 117 with i4; 2 more with seg)."""
+    return (29 + 1056 * 9 + 9 + 32 if ap else 29 + 1056 + 9 + 32) + (98 if seg else 0), (1 + 1 + 16 * 7 + 3 if i4 else 7) + (2 if seg else 0)
+
+
+def vp8_max_mbs(i4: bool = False, ap: bool = False, seg: bool = False) -> int:
+    """csrc/fl_vp8_core.h vp8_max_mbs: the most macroblocks whose worst-case first partition (7 bits a boolean) fits its 19-bit size
+    field."""
+    fixed, per_mb = _vp8_part0_bools(i4, ap, seg)
+    return (((1 << 19) - 1) * 8 // 7 - fixed) // per_mb
+
+
+def vp8_max_out_bytes(w: int, h: int, i4: bool = False, ap: bool = False, seg: bool = False) -> int:
+    """csrc/fl_vp8_core.h vp8_max_out_bytes: the worst case of a lossy WebP file of that variant (the loop filter adds nothing)."""
+    mbs = ((w + 15) // 16) * ((h + 15) // 16)
+    fixed, per_mb = _vp8_part0_bools(i4, ap, seg)
+    return 80 + w * h + (7 * (fixed + per_mb * mbs) + 7) // 8 + (7 * (384 * 19 * mbs + 256) + 7) // 8
+
+
 def result_front_end(kind: int, quality: int = 100, accept_flags: int = 0, w: int = 1, h: int = 1) -> int:
     """The front end behind a result kind.  RESULT_WEBP_STREAM is the lossless coder's at (clamped) quality 100 and the lossy
-    coder's below it: FE_WEBP_LOSSY_I4 where accept_flags has ENCODE_WEBP_LOSSY_I4 and the w x h output is within its limits; with
-    ENCODE_WEBP_LOSSY_PROBS the adaptive-probability variant of either (FE_WEBP_LOSSY_AP where the output is over FE_WEBP_LOSSY_I4_AP's
-    limits); with ENCODE_WEBP_LOSSY_FILTER the loop-filtered twin of that."""
+    coder's below it: B_PRED macroblocks where accept_flags has ENCODE_WEBP_LOSSY_I4 and the w x h output is within that variant's
+    limits; per-picture probabilities with ENCODE_WEBP_LOSSY_PROBS (without B_PRED where the output is over the limits of both
+    together); the loop filter with ENCODE_WEBP_LOSSY_FILTER."""
     if kind == RESULT_WEBP_STREAM and min(max(int(quality), 1), 100) < 100:
         mbs = ((w + 15) // 16) * ((h + 15) // 16)
-        if accept_flags & ENCODE_WEBP_LOSSY_PROBS:
-            fe = FE_WEBP_LOSSY_I4_AP if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_AP_MAX_MBS else FE_WEBP_LOSSY_AP
-        else:
-            fe = FE_WEBP_LOSSY_I4 if accept_flags & ENCODE_WEBP_LOSSY_I4 and mbs <= VP8_I4_MAX_MBS else FE_WEBP_LOSSY
-        return VP8_LF_TWIN[fe] if accept_flags & ENCODE_WEBP_LOSSY_FILTER else fe
+        ap = bool(accept_flags & ENCODE_WEBP_LOSSY_PROBS)
+        i4 = bool(accept_flags & ENCODE_WEBP_LOSSY_I4) and mbs <= vp8_max_mbs(True, ap)
+        return vp8_front_end(i4, ap, bool(accept_flags & ENCODE_WEBP_LOSSY_FILTER))
     return _RESULT_FE[kind]
-
-
-def vp8_max_out_bytes(w: int, h: int) -> int:
-    """csrc/fl_vp8_core.h vp8_max_out_bytes: the worst case of a FE_WEBP_LOSSY file."""
-    mbs = ((w + 15) // 16) * ((h + 15) // 16)
-    return 80 + w * h + (7 * (1126 + 7 * mbs) + 7) // 8 + (7 * (384 * 19 * mbs + 256) + 7) // 8
-
-
-VP8_I4_PART0_MB_BOOLS = 1 + 1 + 16 * 7 + 3  # csrc/fl_vp8_core.h kVp8Part0MbBoolsI4
-VP8_I4_MAX_MBS = (((1 << 19) - 1) * 8 // 7 - 1126) // VP8_I4_PART0_MB_BOOLS  # kVp8MaxMbsI4
-
-
-def vp8_i4_max_out_bytes(w: int, h: int) -> int:
-    """csrc/fl_vp8_core.h vp8_i4_max_out_bytes: the worst case of a FE_WEBP_LOSSY_I4 file (117 booleans per macroblock in the
-    first partition where FE_WEBP_LOSSY has 7)."""
-    mbs = ((w + 15) // 16) * ((h + 15) // 16)
-    return 80 + w * h + (7 * (1126 + VP8_I4_PART0_MB_BOOLS * mbs) + 7) // 8 + (7 * (384 * 19 * mbs + 256) + 7) // 8
-
-
-VP8_AP_PART0_BOOLS = 29 + 1056 * 9 + 9 + 32  # csrc/fl_vp8_core.h kVp8Part0BoolsAp: every update flag may carry 8 bits
-VP8_I4_AP_MAX_MBS = (((1 << 19) - 1) * 8 // 7 - VP8_AP_PART0_BOOLS) // VP8_I4_PART0_MB_BOOLS  # kVp8MaxMbsI4Ap
-
-
-def vp8_ap_max_out_bytes(w: int, h: int) -> int:
-    """csrc/fl_vp8_core.h vp8_ap_max_out_bytes: the worst case of a FE_WEBP_LOSSY_AP file (FE_WEBP_LOSSY's plus 1056 literals)."""
-    return vp8_max_out_bytes(w, h) + 7 * (VP8_AP_PART0_BOOLS - 1126) // 8
-
-
-def vp8_i4_ap_max_out_bytes(w: int, h: int) -> int:
-    """csrc/fl_vp8_core.h vp8_i4_ap_max_out_bytes: the worst case of a FE_WEBP_LOSSY_I4_AP file."""
-    return vp8_i4_max_out_bytes(w, h) + 7 * (VP8_AP_PART0_BOOLS - 1126) // 8
 
 
 def _split_output(buf: np.ndarray, plan: flgpu_plan, front_end: int, flags: int, nbytes: int = 0):

@@ -428,27 +428,23 @@ int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
 // Lossy WebP: the front end's planes, the reconstruction (whole macroblocks), 400 levels and one record per macroblock, the sizes;
 // the I4 variants' pictures also two words of sub-block modes per macroblock, the adaptive-probability variants' a table, the
 // loop-filtered variants' four cost words and three working copies of the reconstruction.
-bool vp8_fe_lf(uint32_t fe) { return fe >= FLGPU_FE_WEBP_LOSSY_LF && fe <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
-bool vp8_fe_i4(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
-bool vp8_fe_ap(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP || fe == FLGPU_FE_WEBP_LOSSY_AP_LF || fe == FLGPU_FE_WEBP_LOSSY_I4_AP_LF; }
-bool vp8_fe(uint32_t fe) { return fe == FLGPU_FE_WEBP_LOSSY || vp8_fe_i4(fe) || vp8_fe_ap(fe) || vp8_fe_lf(fe); }
+bool vp8_fe(uint32_t fe) { return vp8_variant_of(fe).has_value(); }
 // FLGPU_FEO_ALPHA_VP8L, which only these front ends know: the picture also gets the lossless coder's scratch, for its alpha plane
 bool vp8_alpha_vp8l(const flgpu_params &p) { return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_ALPHA_VP8L); }
 // FLGPU_FEO_SEGMENTS, on the same front ends: the picture gets a record and a class map, unless it fits the front end's limits but
 // not the segmented partition 0's -- then it is coded without the option
 bool vp8_segments(const flgpu_params &p, const flgpu_plan &pl)
 {
-    return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_SEGMENTS) && vp8_seg_fits(pl.out_w, pl.out_h, vp8_fe_i4(p.front_end), vp8_fe_ap(p.front_end));
+    const std::optional<Vp8Variant> v = vp8_variant_of(p.front_end);
+    return v && (p.options & FLGPU_FEO_SEGMENTS) && vp8_fits(pl.out_w, pl.out_h, v->i4, v->ap, true);
 }
-int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, uint32_t fe, bool seg)
+int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, Vp8Variant v, bool seg)
 {
-    const bool i4 = vp8_fe_i4(fe), ap = vp8_fe_ap(fe);
-    const bool fits = ap ? (i4 ? vp8_i4_ap_fits(pl.out_w, pl.out_h) : vp8_ap_fits(pl.out_w, pl.out_h)) : i4 ? vp8_i4_fits(pl.out_w, pl.out_h) : vp8_fits(pl.out_w, pl.out_h);
-    if (!fits) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
+    if (!vp8_fits(pl.out_w, pl.out_h, v.i4, v.ap)) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
     const uint64_t mbs = (uint64_t)vp8_mbs(pl.out_w) * vp8_mbs(pl.out_h);
-    if (i4) s.vp8_i4_mbs += mbs;
-    if (ap) s.vp8_ap_pics++;
-    if (vp8_fe_lf(fe)) s.vp8_lf += vp8_lf_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h));
+    if (v.i4) s.vp8_i4_mbs += mbs;
+    if (v.ap) s.vp8_ap_pics++;
+    if (v.lf) s.vp8_lf += vp8_lf_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h));
     if (seg) s.vp8_seg += vp8_seg_bytes(mbs);
     s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
     s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
@@ -508,7 +504,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
         if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
-        if (vp8_fe(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, w.p->front_end, vp8_segments(*w.p, pl));
+        if (const auto v = vp8_variant_of(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, *v, vp8_segments(*w.p, pl));
         if (!rc && vp8_alpha_vp8l(*w.p)) rc = webpll_scratch(pl, B.scratch);
         if (rc) return rc;
     }
@@ -935,26 +931,25 @@ int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, Vp8Job *v
 }
 
 // The lossy WebP job reads the planes its own WebP420 front-end job writes to scratch (add_planes_launch with to_vp8).
-int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, uint32_t fe)
+int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, Vp8Variant v)
 {
-    const bool i4 = vp8_fe_i4(fe);
     Vp8Job &j = encoder_job(B, B.vjobs, B.vjob_img, i);
     const flgpu_plan &pl = B.work[i].plan;
     j.src = static_cast<uint8_t *>(c->d_vp8_planes.p) + at.vp8_planes;
     j.rec = static_cast<uint8_t *>(c->d_vp8_rec.p) + at.vp8_rec;
     j.lev = static_cast<int16_t *>(c->d_vp8_lev.p) + at.vp8_mbs * kVp8MbLevels;
     j.info = static_cast<uint32_t *>(c->d_vp8_info.p) + at.vp8_mbs;
-    j.bm = i4 ? static_cast<uint32_t *>(c->d_vp8_bm.p) + at.vp8_i4_mbs * 2u : nullptr;
-    j.tab = vp8_fe_ap(fe) ? static_cast<uint8_t *>(c->d_vp8_tab.p) + (size_t)at.vp8_ap_pics * kVp8TabBytes : nullptr;
+    j.bm = v.i4 ? static_cast<uint32_t *>(c->d_vp8_bm.p) + at.vp8_i4_mbs * 2u : nullptr;
+    j.tab = v.ap ? static_cast<uint8_t *>(c->d_vp8_tab.p) + (size_t)at.vp8_ap_pics * kVp8TabBytes : nullptr;
     j.sizes = static_cast<uint32_t *>(c->d_vp8_sizes.p) + (size_t)at.vp8_pics * kVp8SizeWords;
-    j.lf = vp8_fe_lf(fe) ? static_cast<uint8_t *>(c->d_vp8_lf.p) + at.vp8_lf : nullptr;
+    j.lf = v.lf ? static_cast<uint8_t *>(c->d_vp8_lf.p) + at.vp8_lf : nullptr;
     j.lf_base = (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, B.dbg.get(DBG_VP8_FILTER_BASE)));
     const uint32_t q = B.work[i].p->quality;
     j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
     const bool seg = vp8_segments(*B.work[i].p, pl);
     j.seg = seg ? static_cast<uint8_t *>(c->d_vp8_seg.p) + at.vp8_seg : nullptr;
     B.vjobs_seg += seg;
-    return vp8_scratch(pl, at, fe, seg);
+    return vp8_scratch(pl, at, v, seg);
 }
 
 // The planar front ends (JFIF444, WebP420): one launch per kind.  to_vp8: the pictures are lossy WebP jobs (B.vjobs from `vjob0`
@@ -1028,26 +1023,22 @@ int build_launches(flgpu_ctx *c, Batch &B)
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
     ScratchSizes vp8_at; // (the lossy WebP front ends are up to eight groups that share the lossy WebP scratch, in the families' order)
     ScratchSizes wll_at; // (the lossless WebP files and the alpha planes of those groups share the lossless coder's scratch)
-    static_assert(FLGPU_FE_WEBP_LOSSY < FLGPU_FE_WEBP_LOSSY_I4 && FLGPU_FE_WEBP_LOSSY_I4 < FLGPU_FE_WEBP_LOSSY_AP && FLGPU_FE_WEBP_LOSSY_AP < FLGPU_FE_WEBP_LOSSY_I4_AP,
-                  "launch_vp8_encode takes one range of jobs per family, in this order");
-    static_assert(vp8_family(FLGPU_FE_WEBP_LOSSY) == 0 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4) == 1 && vp8_family(FLGPU_FE_WEBP_LOSSY_AP) == 2 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP) == 3, "vp8_family");
-    static_assert(FLGPU_FE_WEBP_LOSSY_I4_AP < FLGPU_FE_WEBP_LOSSY_LF && vp8_family(FLGPU_FE_WEBP_LOSSY_LF) == 4 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_LF) == 5 &&
-                  vp8_family(FLGPU_FE_WEBP_LOSSY_AP_LF) == 6 && vp8_family(FLGPU_FE_WEBP_LOSSY_I4_AP_LF) == 7, "the loop-filtered twins follow in the same order");
     for (auto &g : fe_groups) {
         ScratchSizes at;
         const size_t vjob0 = B.vjobs.size();
+        const std::optional<Vp8Variant> vp8 = vp8_variant_of(g.first);
         for (size_t i : g.second) {
             int rc = FLGPU_OK;
             if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
             if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
             if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, wll_at);
-            if (vp8_fe(g.first)) { rc = add_vp8_job(c, B, i, vp8_at, g.first); B.vjobs_fam[vp8_family(g.first)]++; }
+            if (vp8) { rc = add_vp8_job(c, B, i, vp8_at, *vp8); B.vjobs_fam[vp8_family(*vp8)]++; }
             if (!rc && vp8_alpha_vp8l(*B.work[i].p)) rc = add_webpll_job(c, B, i, wll_at, &B.vjobs.back());
             assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
             (void)rc;
         }
         if (g.first == FLGPU_FE_JFIF444 || g.first == FLGPU_FE_WEBP420) add_planes_launch(B, g.first, g.second);
-        if (vp8_fe(g.first)) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
+        if (vp8) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
     }
     FL_HIP(c, c->d_mid.reserve(B.mid_floats_max * 4), "f32 intermediate");
     return FLGPU_OK;
@@ -1428,7 +1419,7 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
 // left (the picture is the batch's only one, so its scratch is the start of d_vp8_lf) and what every consumer derives from them.
 extern "C" int flgpu_debug_vp8_filter_costs(flgpu_ctx *c, const flgpu_image *src, const flgpu_params *p, uint32_t *levels, uint64_t *costs, uint32_t *chosen)
 try {
-    if (!c || !src || !p || !levels || !costs || !chosen || !c->dbg || !vp8_fe_lf(p->front_end) || !c->shard_ctx.empty()) return FLGPU_ERR_INVALID_ARG;
+    if (!c || !src || !p || !levels || !costs || !chosen || !c->dbg || !vp8_variant_of(p->front_end).value_or(Vp8Variant{}).lf || !c->shard_ctx.empty()) return FLGPU_ERR_INVALID_ARG;
     flgpu_plan plan;
     if (int rc = flgpu_plan_output(p, src->width, src->height, src->channels, &plan)) return rc;
     std::vector<uint8_t> file(plan.max_out_bytes);

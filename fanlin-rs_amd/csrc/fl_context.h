@@ -41,6 +41,7 @@
 #include "fl_webpdec.h"
 #include "fl_webpll.h"
 #include "fl_vp8.h"
+#include "fl_vp8_variant.h"
 #include "fl_wtile.h"
 
 namespace fl {
@@ -370,8 +371,8 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
 int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
 // front ends whose output is an encoded stream: its length is a result word, known once the batch has run
-inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS || fe == FLGPU_FE_WEBP_LOSSY || fe == FLGPU_FE_WEBP_LOSSY_I4 || fe == FLGPU_FE_WEBP_LOSSY_AP || fe == FLGPU_FE_WEBP_LOSSY_I4_AP ||
-           (fe >= FLGPU_FE_WEBP_LOSSY_LF && fe <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF); }
+inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS || vp8_variant_of(fe); }
+static_assert(vp8_family({true, true, true}) + 1u == kVp8Families, "launch_vp8_encode takes one range of jobs per family");
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------
 // contiguous split of n weighted items into n_shards shards of about equal weight: shard_of[i] is non-decreasing

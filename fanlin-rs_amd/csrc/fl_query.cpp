@@ -21,6 +21,7 @@
 #include "fl_gif.h"
 #include "fl_webpll.h"
 #include "fl_vp8_core.h"
+#include "fl_vp8_variant.h"
 #include "fl_jpeg_tables.h"
 #include "fl_jpegdec.h"
 #include "fl_mfma.h"
@@ -277,14 +278,12 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
         // _I4 and _PROBS each select a variant where the output fits it; an output over the B_PRED variant's limit with _PROBS (5039
         // macroblocks, 72 fewer than without) takes the I16-only adaptive coder, never the non-adaptive B_PRED one
         const bool want_i4 = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_I4) != 0, want_ap = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_PROBS) != 0;
-        if (want_ap && fl::vp8_ap_fits(plan->out_w, plan->out_h))
-            p->front_end = want_i4 && fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4_AP : FLGPU_FE_WEBP_LOSSY_AP;
-        else
-            p->front_end = want_i4 && fl::vp8_i4_fits(plan->out_w, plan->out_h) ? FLGPU_FE_WEBP_LOSSY_I4 : FLGPU_FE_WEBP_LOSSY;
+        fl::Vp8Variant v{};
+        v.ap = want_ap && fl::vp8_fits(plan->out_w, plan->out_h, false, true);
+        v.i4 = want_i4 && fl::vp8_fits(plan->out_w, plan->out_h, true, v.ap);
         // _FILTER: the loop-filtered twin of whichever front end the other bits selected (the same limits)
-        if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_FILTER)
-            p->front_end = p->front_end == FLGPU_FE_WEBP_LOSSY ? FLGPU_FE_WEBP_LOSSY_LF : p->front_end == FLGPU_FE_WEBP_LOSSY_I4 ? FLGPU_FE_WEBP_LOSSY_I4_LF
-                           : p->front_end == FLGPU_FE_WEBP_LOSSY_AP ? FLGPU_FE_WEBP_LOSSY_AP_LF : FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
+        v.lf = (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_FILTER) != 0;
+        p->front_end = (uint8_t)fl::vp8_front_end(v);
         // _ALPHA: the option on whichever front end that is (a WebP source that stays WebP got its front end after the mapping above)
         if (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA) p->options |= FLGPU_FEO_ALPHA_VP8L;
         // _SEGMENTS likewise: segment-adaptive quantisers on whichever front end that is
@@ -295,7 +294,10 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
         p->front_end = FLGPU_FE_WEBP_LOSSLESS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
-    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || p->front_end == FLGPU_FE_WEBP_LOSSY || p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || (p->front_end >= FLGPU_FE_WEBP_LOSSY_LF && p->front_end <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF)) ? FLGPU_RESULT_WEBP_STREAM : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || fl::vp8_variant_of(p->front_end)) ? FLGPU_RESULT_WEBP_STREAM
+                   : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM
+                   : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM
+                   : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
     return rc;
 }
 
@@ -821,8 +823,8 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
     /* front ends 0-4, 6, 9, 10, 12, 13 and 16-19 (5, 7, 8, 11, 14 and 15 are not) */
-    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && p->front_end != FLGPU_FE_WEBP_LOSSY && p->front_end != FLGPU_FE_WEBP_LOSSY_I4 &&
-         p->front_end != FLGPU_FE_WEBP_LOSSY_AP && p->front_end != FLGPU_FE_WEBP_LOSSY_I4_AP && !(p->front_end >= FLGPU_FE_WEBP_LOSSY_LF && p->front_end <= FLGPU_FE_WEBP_LOSSY_I4_AP_LF)) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
+    const std::optional<fl::Vp8Variant> vp8 = fl::vp8_variant_of(p->front_end);
+    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && !vp8) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
         return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
@@ -908,36 +910,6 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->out_bytes = 4ull * plan->out_w * plan->out_h;
         plan->max_out_bytes = fl::webpll_max_out_bytes(plan->out_w, plan->out_h);
         break;
-    case FLGPU_FE_WEBP_LOSSY:
-    case FLGPU_FE_WEBP_LOSSY_I4:
-    case FLGPU_FE_WEBP_LOSSY_AP:
-    case FLGPU_FE_WEBP_LOSSY_I4_AP:
-    case FLGPU_FE_WEBP_LOSSY_LF:
-    case FLGPU_FE_WEBP_LOSSY_I4_LF:
-    case FLGPU_FE_WEBP_LOSSY_AP_LF:
-    case FLGPU_FE_WEBP_LOSSY_I4_AP_LF: {
-        // the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the planes' bytes.
-        // max_out_bytes: the worst case of this coder's files (fl_vp8_core.h), so a dst of this capacity is never too small.
-        // (the I4 variants' partition 0 is larger per macroblock, the adaptive-probability variants' by its 1056 literals: fewer
-        // macroblocks, a larger worst case; the loop-filtered variants have their twins' limits and worst case: the bound is per boolean)
-        const bool i4 = p->front_end == FLGPU_FE_WEBP_LOSSY_I4 || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_LF || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
-        const bool ap = p->front_end == FLGPU_FE_WEBP_LOSSY_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP || p->front_end == FLGPU_FE_WEBP_LOSSY_AP_LF || p->front_end == FLGPU_FE_WEBP_LOSSY_I4_AP_LF;
-        const bool fits = ap ? (i4 ? fl::vp8_i4_ap_fits(plan->out_w, plan->out_h) : fl::vp8_ap_fits(plan->out_w, plan->out_h))
-                             : (i4 ? fl::vp8_i4_fits(plan->out_w, plan->out_h) : fl::vp8_fits(plan->out_w, plan->out_h));
-        if (!fits) return FLGPU_ERR_UNSUPPORTED;
-        plan->plane_w = plan->out_w;
-        plan->plane_h = plan->out_h;
-        plan->chroma_w = (plan->out_w + 1u) >> 1;
-        plan->chroma_h = (plan->out_h + 1u) >> 1;
-        plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
-        plan->max_out_bytes = ap ? (i4 ? fl::vp8_i4_ap_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_ap_max_out_bytes(plan->out_w, plan->out_h))
-                                 : (i4 ? fl::vp8_i4_max_out_bytes(plan->out_w, plan->out_h) : fl::vp8_max_out_bytes(plan->out_w, plan->out_h));
-        // FLGPU_FEO_SEGMENTS: the segment header and two booleans of id per macroblock more in partition 0 (a picture over the
-        // segmented limits is coded without the option and keeps the bound above)
-        if ((p->options & FLGPU_FEO_SEGMENTS) && fl::vp8_seg_fits(plan->out_w, plan->out_h, i4, ap))
-            plan->max_out_bytes = fl::vp8_seg_max_out_bytes(plan->out_w, plan->out_h, i4, ap);
-        break;
-    }
     case FLGPU_FE_WEBP420:
         plan->plane_w = plan->out_w;
         plan->plane_h = plan->out_h;
@@ -947,7 +919,20 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
         break;
     default:
-        plan->out_bytes = plan->pixel_bytes;
+        if (!vp8) { plan->out_bytes = plan->pixel_bytes; break; }
+        // a lossy WebP front end: the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the
+        // planes' bytes.  max_out_bytes: the worst case of this coder's files (fl_vp8_core.h: one rule over i4, ap and seg; the loop
+        // filter adds nothing, the bound is per boolean), so a dst of this capacity is never too small.
+        if (!fl::vp8_fits(plan->out_w, plan->out_h, vp8->i4, vp8->ap)) return FLGPU_ERR_UNSUPPORTED;
+        plan->plane_w = plan->out_w;
+        plan->plane_h = plan->out_h;
+        plan->chroma_w = (plan->out_w + 1u) >> 1;
+        plan->chroma_h = (plan->out_h + 1u) >> 1;
+        plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
+        // FLGPU_FEO_SEGMENTS: the segment header and two booleans of id per macroblock more in partition 0 (a picture over the
+        // segmented limits is coded without the option and keeps the unsegmented bound)
+        plan->max_out_bytes = fl::vp8_max_out_bytes(plan->out_w, plan->out_h, vp8->i4, vp8->ap,
+                                                    (p->options & FLGPU_FEO_SEGMENTS) && fl::vp8_fits(plan->out_w, plan->out_h, vp8->i4, vp8->ap, true));
         break;
     }
     if (plan->max_out_bytes < plan->out_bytes) plan->max_out_bytes = plan->out_bytes;

@@ -1,5 +1,5 @@
-// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; opt-in FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP and their loop-filtered twins): job descriptor, scratch sizes and the launch.
-// The format's limits and worst case, and everything the kernels compute, are in fl_vp8_core.h.
+// fl_vp8.h -- the lossy WebP encoder (fl_vp8.hip; the opt-in front ends of fl_vp8_variant.h's Vp8Variant): job descriptor, scratch sizes and the launch.
+// The format's limits and worst case (one rule over i4, ap, seg), and everything the kernels compute, are in fl_vp8_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,7 +24,7 @@ struct alignas(16) Vp8Job {
     uint32_t *info;       // scratch: one record per macroblock
     uint32_t *sizes;      // scratch: [kVp8SizeWords]
     uint32_t *result;     // [0] bit 0: some pixel is not opaque, bit 1 (kVp8ResultAlphaVp8l): the ALPH chunk went out compressed, bit 2 (kVp8ResultSegments): the frame went out segmented; [1] = file bytes (0 if it did not fit dst_cap): the words and protocol of JpegJob
-    uint32_t *bm;         // scratch, FLGPU_FE_WEBP_LOSSY_I4 only (else nullptr): two words of sub-block modes per macroblock
+    uint32_t *bm;         // scratch, the I4 variants only (else nullptr): two words of sub-block modes per macroblock
     uint32_t w, h, c;
     uint32_t dst_cap;     // bytes available at dst
     uint32_t qi;          // quantiser index (vp8_quality_index of the clamped quality)
@@ -42,10 +42,9 @@ static_assert(sizeof(Vp8Job) == 128, "the job record: 96 bytes before the loop-f
 inline uint64_t vp8_planes_bytes(uint64_t w, uint64_t h) { return 2u * w * h + 2u * ((w + 1u) / 2u) * ((h + 1u) / 2u); }
 
 constexpr uint32_t kVp8TabBytes = 4 * 8 * 3 * 11; // the coefficient probability table of one picture
-// The families of a launch in the order of their front ends, which is the order of their jobs: FLGPU_FE_WEBP_LOSSY, _I4, _AP, _I4_AP,
-// then the loop-filtered twin of each in the same order (family f + 4: front end 16 + f).
+// The families of a launch: f = i4 | ap << 1 | lf << 2 (fl_vp8_variant.h vp8_family), which is the order of their front ends and
+// so of their jobs.
 constexpr uint32_t kVp8Families = 8;
-constexpr uint32_t vp8_family(uint32_t front_end) { return front_end >= 16u ? 4u + (front_end - 16u) : front_end == 9u ? 0u : front_end == 10u ? 1u : front_end == 12u ? 2u : 3u; }
 // scratch of one loop-filtered picture behind Vp8Job::lf
 inline uint64_t vp8_lf_bytes(uint32_t mbw, uint32_t mbh) { return kVp8LfCostBytes + (kVp8LfCandidates - 1u) * ((vp8_rec_bytes(mbw, mbh) + 255u) & ~(uint64_t)255u); }
 

@@ -1,8 +1,9 @@
 // fl_vp8.hip -- the lossy WebP encoder on gfx950, so that what leaves the GPU for `webp=true` below quality 100 is the finished
 // image/webp body (reference src/handler.rs:293-297, webp::Encoder::encode(q)) instead of the Y | U | V | A planes.  Opt-in
-// (FLGPU_FE_WEBP_LOSSY).  The stream is a VP8 key frame of this encoder's own choices -- it decodes to exactly the encoder's
-// reconstruction, its bytes are not libwebp's; fl_vp8_core.h states the stream and holds all of its arithmetic, shared with the
-// host twin (tests/vp8_host.cpp) and restated in tests/vp8_model.py.  This file is the choreography:
+// (FLGPU_FE_WEBP_LOSSY and its variants: three switches, i4 / ap / lf, which fl_vp8_variant.h maps to front ends).  The stream is
+// a VP8 key frame of this encoder's own choices -- it decodes to exactly the encoder's reconstruction, its bytes are not
+// libwebp's; fl_vp8_core.h states the stream and holds all of its arithmetic, shared with the host twin (tests/vp8_host.cpp) and
+// restated in tests/vp8_model.py.  This file is the choreography:
 //   vp8_analyse_kernel  one wave per picture, macroblocks in raster order (a macroblock predicts from the reconstruction to its
 //                       left and above).  Within a macroblock the work spreads over the lanes phase by phase: 495 loads, 96 block
 //                       SSEs (4 modes x 24 blocks), 24 forward DCTs, 24 quantise / inverse DCT / reconstruct, 401 stores; the mode
@@ -15,7 +16,7 @@
 //                       FLGPU_FEO_ALPHA_VP8L the alpha coder (fl_webpll.hip, alpha mode) has left the plane's VP8L stream: that goes
 //                       into the chunk instead wherever it is strictly smaller (vp8_alph_size).
 //   vp8_write_kernel    one lane per partition again: the same coder, storing at the partition's place in the file.
-// The I4 variant (FLGPU_FE_WEBP_LOSSY_I4, fl_vp8_i4_core.h) has kernels of its own, so that the ones above stay as they are:
+// i4 (fl_vp8_i4_core.h) has kernels of its own, so that the ones above stay as they are:
 //   vp8_analyse_i4_kernel  the same walk; after the mode pick a macroblock whose I16 error exceeds the penalty tries its luma as
 //                       sixteen sub-blocks, one after the other: 13 neighbour loads, 160 (mode, sample) errors over the 64 lanes
 //                       in three rounds, each mode's sixteen summed across its lanes, then the chosen mode's residual through
@@ -23,17 +24,15 @@
 //                       levels are in LDS; the winner of the two trials is committed.
 //   vp8_size_kernel<true>, vp8_write_kernel<true>  the coder's instantiation with the mode tree in partition 0 and the type-3 / no-Y2
 //                       path in the tokens, a branch per macroblock on its mode record.
-// The adaptive-probability variants (FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP; fl_vp8_ap_core.h) share the analysis kernels
-// and add one launch between the analysis and the size kernel:
+// ap (fl_vp8_ap_core.h) shares the analysis kernels and adds one launch between the analysis and the size kernel:
 //   vp8_stats_kernel<I4>  one workgroup per picture.  The (macroblock, block) pairs spread over its 256 threads; each fetches its
 //                       block's levels whole, takes its contexts from the macroblock records and runs the coder's own token walk
 //                       into a counting sink: 2 x 1056 counters in LDS (8448 B), LDS atomics.  After a barrier thread i < 1056
 //                       applies the rule to entry i and stores the picture's table (1056 B of scratch).
 //   vp8_size_kernel<I4, true>, vp8_write_kernel<I4, true>  the coders, staging the picture's table instead of the default one (a
 //                       coder workgroup is exactly one picture) and writing the updates into partition 0.
-// The loop-filtered variants (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF; fl_vp8_lf_core.h) share all of the above and add one
-// launch in front of the first that codes partition 0 (the stats kernel where there is one, else the size kernel): the level's six
-// bits move the boolean coder's state, so the sizes depend on it.
+// lf (fl_vp8_lf_core.h) shares all of the above and adds one launch in front of the first that codes partition 0 (the stats kernel
+// where there is one, else the size kernel): the level's six bits move the boolean coder's state, so the sizes depend on it.
 //   vp8_lf_kernel<I4>   one workgroup per (picture, candidate level).  Candidate 0 measures the reconstruction as it is.  The others
 //                       copy it to a working copy of their own in scratch (the filter cascades in place; `rec` stays unfiltered for
 //                       the coder's contexts) and run the decode front end's filter on it in vp8dec_filter_kernel's schedule:
@@ -42,7 +41,7 @@
 //                       samples in 64 bits and one thread stores the candidate's word.
 //   vp8_size_kernel<I4, AP, true>, vp8_write_kernel<I4, AP, true>  the coders; the partition-0 lane derives the level from the
 //                       picture's four words (vp8_lf_choice) and writes it into the frame header.
-// FLGPU_FEO_SEGMENTS (fl_vp8_seg_core.h; a bit of flgpu_params::options on any of the eight front ends) adds one launch in front of
+// FLGPU_FEO_SEGMENTS (fl_vp8_seg_core.h; a bit of flgpu_params::options on any of the front ends) adds one launch in front of
 // everything, only when some job of the batch carries the option:
 //   vp8_segment_kernel  one 256-thread workgroup per picture (it returns at once for a job without the option).  Waves stride over
 //                       the macroblocks: 64 lanes x 4 luma samples, two wave reductions (mean, then activity), lane 0 stores the
@@ -53,7 +52,8 @@
 // The analysis kernels then take each macroblock's steps from its class (vp8_seg_pick: one uniform branch and table look-up per
 // macroblock), vp8_lf_inner dequantises a Y2 block with them, and the partition-0 lane of the coders writes the segment header and
 // the ids (at run time, not a template axis).  Integer atomics only: the result does not depend on their order.
-// A batch's pictures are grouped by front end in the job list, so each of the eight families is one range of it.
+// A batch's pictures are grouped by front end in the job list, so each family (i4 | ap << 1 | lf << 2) is one range of it:
+// launch_vp8_encode walks a table of the eight launch_family<I4, AP, LF> by that index.
 // No kernel waits on another workgroup or wave, so there is no bounded wait and no use of the device error word.
 // A lone large picture is latency-bound: one wave walks its macroblocks, nine lanes code it.
 #include <hip/hip_runtime.h>
@@ -471,20 +471,15 @@ hipError_t launch_vp8_encode(const Vp8Job *jobs, const uint32_t n[kVp8Families],
         hipLaunchKernelGGL(vp8_segment_kernel, dim3(all), dim3(kSegThreads), 0, st, jobs);
         if (hipError_t e = hipGetLastError()) return e;
     }
-    if (hipError_t e = launch_family<false, false, false>(jobs, n[0], st)) return e;
-    jobs += n[0];
-    if (hipError_t e = launch_family<true, false, false>(jobs, n[1], st)) return e;
-    jobs += n[1];
-    if (hipError_t e = launch_family<false, true, false>(jobs, n[2], st)) return e;
-    jobs += n[2];
-    if (hipError_t e = launch_family<true, true, false>(jobs, n[3], st)) return e;
-    jobs += n[3];
-    if (hipError_t e = launch_family<false, false, true>(jobs, n[4], st)) return e;
-    jobs += n[4];
-    if (hipError_t e = launch_family<true, false, true>(jobs, n[5], st)) return e;
-    jobs += n[5];
-    if (hipError_t e = launch_family<false, true, true>(jobs, n[6], st)) return e;
-    return launch_family<true, true, true>(jobs + n[6], n[7], st);
+    // family f = i4 | ap << 1 | lf << 2 (fl_vp8_variant.h vp8_family): one range of jobs after the other
+    static hipError_t (*const family[kVp8Families])(const Vp8Job *, uint32_t, hipStream_t) = {
+        launch_family<false, false, false>, launch_family<true, false, false>, launch_family<false, true, false>, launch_family<true, true, false>,
+        launch_family<false, false, true>,  launch_family<true, false, true>,  launch_family<false, true, true>,  launch_family<true, true, true>};
+    for (uint32_t f = 0; f < kVp8Families; ++f) {
+        if (hipError_t e = family[f](jobs, n[f], st)) return e;
+        jobs += n[f];
+    }
+    return hipSuccess;
 }
 
 } // namespace fl

@@ -1,7 +1,7 @@
 // fl_vp8_ap_core.h -- the adaptive-probability variants of the lossy WebP encoder (FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP):
 // the counting sink of the token walk and the rule that turns a picture's counts into its coefficient probability table.  Host and
 // device code like fl_vp8_core.h, which holds the walk itself (vp8_put_block), the header's update flags
-// (vp8_put_first_partition<I4, true>) and the limits; tests/vp8_ap_model.py restates the rule, tests/vp8_ap_host.cpp runs it in
+// (vp8_put_first_partition<I4, true>) and the limits; tests/vp8_ap_model.py restates the rule, tests/vp8_host.cpp runs it in
 // plain loops.
 //
 // Counts.  For every coded macroblock (vp8_coded<I4> != 0) the walk that vp8_put_mb codes runs into a Vp8Count instead of a

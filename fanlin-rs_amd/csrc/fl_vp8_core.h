@@ -2,15 +2,17 @@
 // quantiser set-up, intra prediction, forward / inverse transforms, the per-macroblock phases, the token walk, the boolean coder
 // and the file layout.  fl_vp8.hip spreads the phases over the lanes of a wave; tests/vp8_host.cpp runs the same functions in
 // plain loops, planes to file, on the CPU.  No HIP header is needed to include this one.
+// The encoder's variants are three switches -- i4, ap, lf: fl_vp8_variant.h maps them to front ends -- and one option, seg; they are
+// template axes of the coder below, and (i4, ap, seg) are the parameters of the one worst-case rule.
 //
-// The stream (tests/vp8_model.py restates it in numpy): one key frame, every macroblock I16, luma and chroma mode each the one of
-// DC / V / H / TM with the least integer SSE of prediction against source (ties: the first in that order), one segment, loop
-// filter level 0, default coefficient probabilities, 1 / 2 / 4 / 8 token partitions, mb_no_coeff_skip with a per-picture
-// probability.  Forward transforms and quantiser rounding are this encoder's own (integer only); everything the decoder repeats
+// The stream with every switch off (tests/vp8_model.py restates it in numpy): one key frame, every macroblock I16, luma and chroma
+// mode each the one of DC / V / H / TM with the least integer SSE of prediction against source (ties: the first in that order),
+// one segment, loop filter level 0, default coefficient probabilities, 1 / 2 / 4 / 8 token partitions, mb_no_coeff_skip with a
+// per-picture probability.  Forward transforms and quantiser rounding are this encoder's own (integer only); everything the decoder repeats
 // -- dequantisation, inverse WHT, inverse DCT, prediction, clamping -- is the format's.
 //
-// The I4 variant (FLGPU_FE_WEBP_LOSSY_I4; tests/vp8_i4_model.py restates it, fl_vp8_i4_core.h holds its analysis phases): the same
-// stream, but a macroblock's luma may be B_PRED.  Per macroblock, in raster order:
+// i4 (tests/vp8_i4_model.py restates it, fl_vp8_i4_core.h holds its analysis phases): the same stream, but a macroblock's luma may
+// be B_PRED.  Per macroblock, in raster order:
 //   1. I16 trial: the phases above.  S16 = the prediction SSE of the chosen luma mode.  Chroma is as above whatever follows.
 //   2. I4 trial: the luma sub-blocks 0..15 in raster order.  Each forms the ten predictions B_DC, B_TM, B_VE, B_HE, B_LD, B_RD, B_VR,
 //      B_VL, B_HD, B_HU (the format's numbering) from the reconstruction -- the macroblock's own sub-blocks before it, the row
@@ -26,17 +28,15 @@
 // B_DC.  Its tokens have no Y2 block, its luma blocks are type 3 from coefficient 0, it leaves the Y2 context of its column and
 // row as it found them, and it is skipped when its 24 blocks are zero.
 //
-// The adaptive-probability variants (FLGPU_FE_WEBP_LOSSY_AP, FLGPU_FE_WEBP_LOSSY_I4_AP; fl_vp8_ap_core.h states the rule,
-// tests/vp8_ap_model.py restates it): the same macroblocks, levels and modes as the front end each stands beside, but the picture's
-// token-tree branches are counted first, a coefficient probability table is derived from the counts, partition 0 carries the
+// ap (fl_vp8_ap_core.h states the rule, tests/vp8_ap_model.py restates it): the same macroblocks, levels and modes, but the
+// picture's token-tree branches are counted first, a coefficient probability table is derived from the counts, partition 0 carries the
 // updates (flag i is 1 and followed by the 8-bit probability where the picture's table differs from the default), and the token
 // partitions are coded with that table.  The reconstruction does not change.
 //
-// The loop-filtered variants (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF; fl_vp8_lf_core.h states the rule,
-// tests/vp8_lf_model.py restates it): the same again, but the frame header's loop filter level is the one of four candidates whose
-// filtered reconstruction is nearest to the source; what a decoder shows is that filtered picture.
+// lf (fl_vp8_lf_core.h states the rule, tests/vp8_lf_model.py restates it): the same again, but the frame header's loop filter
+// level is the one of four candidates whose filtered reconstruction is nearest to the source; what a decoder shows is that filtered picture.
 //
-// Segment-adaptive quantisers (FLGPU_FEO_SEGMENTS, a bit of flgpu_params::options on any of the eight front ends; fl_vp8_seg_core.h
+// seg: segment-adaptive quantisers (FLGPU_FEO_SEGMENTS, a bit of flgpu_params::options on any of the front ends; fl_vp8_seg_core.h
 // states the rule, tests/vp8_seg_model.py restates it): the macroblocks are sorted into up to four classes by luma activity and
 // each class is coded at a quantiser index of its own around the picture's; the frame header carries the segment header (absolute
 // values, the frame's filter level in every segment) and every macroblock its id in front of its skip flag.  Where the rule finds
@@ -63,7 +63,9 @@ constexpr uint32_t kVp8I4PenaltyShift = 9;  // vp8_i4_penalty
 constexpr int kVp8MaxLevel = 2047;          // the largest magnitude cat6 (67 + 11 bits) is asked to carry here
 
 // ---- worst cases ----------------------------------------------------------------------------------------------------------------
-// A boolean costs at most 7 bits: the range is 128..255 before it and at least 1 after it, so renormalising shifts at most 7.
+// One rule for every variant (i4: macroblocks may be B_PRED; ap: per-picture probabilities; seg: FLGPU_FEO_SEGMENTS; the loop filter
+// adds nothing, its level's six literals are header bits below): a boolean costs at most 7 bits -- the range is 128..255 before it
+// and at least 1 after it, so renormalising shifts at most 7 --, and no size field of the format may overflow on the worst case.
 // Partition 0 holds 29 header bits, 1056 "no update" flags, the skip switch and its probability (1 + 8), per macroblock the skip
 // flag, 3 luma-mode and 3 chroma-mode booleans, and the 32 booleans of the flush: 1126 + 7 per macroblock.
 // A coefficient costs at most 7 tree booleans + 11 extra bits + the sign = 19; a macroblock has 16 (Y2) + 16 x 15 (Y) + 8 x 16
@@ -72,48 +74,42 @@ constexpr uint64_t kVp8BoolBits = 7;
 constexpr uint64_t kVp8Part0Bools = 29 + 1056 + 9 + 32, kVp8Part0MbBools = 7;
 constexpr uint64_t kVp8MbTokenBools = 384 * 19;
 constexpr uint64_t kVp8FlushBools = 32;
-FL_VP8_HD uint64_t vp8_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBools * mbs) + 7u) / 8u; }
-// the first partition's size is a 19-bit field of the frame tag: the largest macroblock count whose worst case still fits it
-constexpr uint64_t kVp8MaxMbs = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0Bools) / kVp8Part0MbBools;
-static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBools * kVp8MaxMbs) + 7u) / 8u < (1ull << 19), "first partition size field");
-
-// The I4 variant's partition 0: a B_PRED macroblock has the skip flag, one luma-tree boolean, sixteen sub-block modes of at most 7
-// tree booleans (B_HD, B_HU: nodes 0, 1, 2, 3, 6, 7, 8) and 3 chroma-mode booleans: 1 + 1 + 16 x 7 + 3 = 117, against an I16
-// macroblock's 7.  Its tokens do not grow: 24 blocks x 16 coefficients = 384, what 16 (Y2) + 16 x 15 + 8 x 16 comes to.
+// i4: a B_PRED macroblock has the skip flag, one luma-tree boolean, sixteen sub-block modes of at most 7 tree booleans (B_HD, B_HU:
+// nodes 0, 1, 2, 3, 6, 7, 8) and 3 chroma-mode booleans: 1 + 1 + 16 x 7 + 3 = 117, against an I16 macroblock's 7.  Its tokens do
+// not grow: 24 blocks x 16 coefficients = 384, what 16 (Y2) + 16 x 15 + 8 x 16 comes to.
 constexpr uint64_t kVp8Part0MbBoolsI4 = 1 + 1 + 16 * 7 + 3;
-FL_VP8_HD uint64_t vp8_i4_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBoolsI4 * mbs) + 7u) / 8u; }
-constexpr uint64_t kVp8MaxMbsI4 = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0Bools) / kVp8Part0MbBoolsI4; // 5111
-static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0MbBoolsI4 * kVp8MaxMbsI4) + 7u) / 8u < (1ull << 19), "first partition size field");
-
-// The adaptive-probability variants' partition 0: each of the 1056 flags may be followed by an 8-bit probability.
+// ap: each of the 1056 flags may be followed by an 8-bit probability.
 constexpr uint64_t kVp8Part0BoolsAp = 29 + 1056 * 9 + 9 + 32; // 9574
-FL_VP8_HD uint64_t vp8_ap_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBools * mbs) + 7u) / 8u; }
-FL_VP8_HD uint64_t vp8_i4_ap_part0_max_bytes(uint64_t mbs) { return (kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBoolsI4 * mbs) + 7u) / 8u; }
-constexpr uint64_t kVp8MaxMbsAp = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0BoolsAp) / kVp8Part0MbBools;
-constexpr uint64_t kVp8MaxMbsI4Ap = (((1ull << 19) - 1u) * 8u / kVp8BoolBits - kVp8Part0BoolsAp) / kVp8Part0MbBoolsI4; // 5039
-static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBools * kVp8MaxMbsAp) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0MbBoolsI4 * kVp8MaxMbsI4Ap) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert(kVp8MaxMbsI4Ap == 5039, "the B_PRED variant with updates: 72 macroblocks fewer than without");
-// (the 1056 literals are whole bytes of worst case: the partition-0 term grows by exactly 7 x 8448 / 8 = 7392)
-static_assert(kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) % 8u == 0 && kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) / 8u == 7392, "the updates' worst case");
-
-// With FLGPU_FEO_SEGMENTS (fl_vp8_seg_core.h) partition 0 also holds the segment header -- update_mb_segmentation_map,
-// update_segment_feature_data and segment_feature_mode (3), four quantisers of flag + 7 bits + sign (36), four filter strengths of
-// flag + 6 bits + sign (32), three tree probabilities of flag + 8 bits (27): 98 -- and two booleans of segment id per macroblock.
+// seg (fl_vp8_seg_core.h): partition 0 also holds the segment header -- update_mb_segmentation_map, update_segment_feature_data and
+// segment_feature_mode (3), four quantisers of flag + 7 bits + sign (36), four filter strengths of flag + 6 bits + sign (32), three
+// tree probabilities of flag + 8 bits (27): 98 -- and two booleans of segment id per macroblock.
 constexpr uint64_t kVp8Part0SegBools = 3 + 4 * 9 + 4 * 8 + 3 * 9, kVp8Part0MbSegBools = 2;
 static_assert(kVp8Part0SegBools == 98, "the segment header");
-FL_VP8_HD uint64_t vp8_seg_part0_max_bytes(uint64_t mbs, bool i4, bool ap)
+
+FL_VP8_HD constexpr uint64_t vp8_part0_fixed_bools(bool ap, bool seg) { return (ap ? kVp8Part0BoolsAp : kVp8Part0Bools) + (seg ? kVp8Part0SegBools : 0u); }
+FL_VP8_HD constexpr uint64_t vp8_part0_mb_bools(bool i4, bool seg) { return (i4 ? kVp8Part0MbBoolsI4 : kVp8Part0MbBools) + (seg ? kVp8Part0MbSegBools : 0u); }
+FL_VP8_HD constexpr uint64_t vp8_part0_max_bytes(uint64_t mbs, bool i4 = false, bool ap = false, bool seg = false)
 {
-    return (kVp8BoolBits * ((ap ? kVp8Part0BoolsAp : kVp8Part0Bools) + kVp8Part0SegBools + ((i4 ? kVp8Part0MbBoolsI4 : kVp8Part0MbBools) + kVp8Part0MbSegBools) * mbs) + 7u) / 8u;
+    return (kVp8BoolBits * (vp8_part0_fixed_bools(ap, seg) + vp8_part0_mb_bools(i4, seg) * mbs) + 7u) / 8u;
 }
-constexpr uint64_t vp8_seg_max_mbs(uint64_t fixed_bools, uint64_t mb_bools) { return (((1ull << 19) - 1u) * 8u / kVp8BoolBits - fixed_bools - kVp8Part0SegBools) / (mb_bools + kVp8Part0MbSegBools); }
-constexpr uint64_t kVp8MaxMbsSeg = vp8_seg_max_mbs(kVp8Part0Bools, kVp8Part0MbBools), kVp8MaxMbsI4Seg = vp8_seg_max_mbs(kVp8Part0Bools, kVp8Part0MbBoolsI4);
-constexpr uint64_t kVp8MaxMbsApSeg = vp8_seg_max_mbs(kVp8Part0BoolsAp, kVp8Part0MbBools), kVp8MaxMbsI4ApSeg = vp8_seg_max_mbs(kVp8Part0BoolsAp, kVp8Part0MbBoolsI4);
-static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0SegBools + (kVp8Part0MbBools + kVp8Part0MbSegBools) * kVp8MaxMbsSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert((kVp8BoolBits * (kVp8Part0Bools + kVp8Part0SegBools + (kVp8Part0MbBoolsI4 + kVp8Part0MbSegBools) * kVp8MaxMbsI4Seg) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0SegBools + (kVp8Part0MbBools + kVp8Part0MbSegBools) * kVp8MaxMbsApSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert((kVp8BoolBits * (kVp8Part0BoolsAp + kVp8Part0SegBools + (kVp8Part0MbBoolsI4 + kVp8Part0MbSegBools) * kVp8MaxMbsI4ApSeg) + 7u) / 8u < (1ull << 19), "first partition size field");
-static_assert(kVp8MaxMbsI4Seg == 5024 && kVp8MaxMbsI4ApSeg == 4953, "the B_PRED variants with segments: 87 and 86 macroblocks fewer than without");
+// the first partition's size is a 19-bit field of the frame tag: the largest macroblock count whose worst case still fits it
+FL_VP8_HD constexpr uint64_t vp8_max_mbs(bool i4 = false, bool ap = false, bool seg = false)
+{
+    return (((1ull << 19) - 1u) * 8u / kVp8BoolBits - vp8_part0_fixed_bools(ap, seg)) / vp8_part0_mb_bools(i4, seg);
+}
+constexpr bool vp8_part0_fits_its_field()
+{
+    for (int v = 0; v < 8; ++v) {
+        const bool i4 = (v & 1) != 0, ap = (v & 2) != 0, seg = (v & 4) != 0;
+        if (vp8_part0_max_bytes(vp8_max_mbs(i4, ap, seg), i4, ap, seg) >= (1ull << 19)) return false;
+    }
+    return true;
+}
+static_assert(vp8_part0_fits_its_field(), "first partition size field, every (i4, ap, seg)");
+// the known values: B_PRED alone; with updates 72 macroblocks fewer; with segments 87 and 86 fewer than without
+static_assert(vp8_max_mbs(true) == 5111 && vp8_max_mbs(true, true) == 5039 && vp8_max_mbs(true, false, true) == 5024 && vp8_max_mbs(true, true, true) == 4953, "the B_PRED variants' limits");
+// (the 1056 literals are whole bytes of worst case: the partition-0 term grows by exactly 7 x 8448 / 8 = 7392)
+static_assert(kVp8BoolBits * (kVp8Part0BoolsAp - kVp8Part0Bools) % 8u == 0 && vp8_part0_max_bytes(0, false, true) - vp8_part0_max_bytes(0) == 7392, "the updates' worst case");
 
 FL_VP8_HD uint32_t vp8_mbs(uint32_t px) { return (px + 15u) >> 4; }
 // token partitions: the largest of 1 / 2 / 4 / 8 that is not above the number of macroblock rows; row r goes to partition r mod n
@@ -124,56 +120,22 @@ FL_VP8_HD uint64_t vp8_token_partition_max_bytes(uint64_t mbw, uint64_t mbh)
     const uint64_t np = vp8_partitions((uint32_t)mbh), rows = (mbh + np - 1u) / np;
     return (kVp8BoolBits * (kVp8MbTokenBools * rows * mbw + kVp8FlushBools) + 7u) / 8u;
 }
-// The pictures the coder takes: sides of at most 14 bits, and no size field that its worst case could overflow.
-FL_VP8_HD bool vp8_fits(uint64_t w, uint64_t h)
+// The pictures a variant takes: sides of at most 14 bits, and no size field that its worst case could overflow.  (Without B_PRED
+// the 24-bit token partition field binds first, at about 21 000 macroblocks; with it, vp8_max_mbs.)  A picture that fits its front
+// end but not the same with seg is coded without the option.
+FL_VP8_HD bool vp8_fits(uint64_t w, uint64_t h, bool i4 = false, bool ap = false, bool seg = false)
 {
     if (w < 1u || h < 1u || w > kVp8MaxSide || h > kVp8MaxSide) return false;
     const uint64_t mbw = (w + 15u) >> 4, mbh = (h + 15u) >> 4;
-    return mbw * mbh <= kVp8MaxMbs && vp8_token_partition_max_bytes(mbw, mbh) < (1ull << 24);
+    return mbw * mbh <= vp8_max_mbs(i4, ap, seg) && vp8_token_partition_max_bytes(mbw, mbh) < (1ull << 24);
 }
 // The file's worst case: RIFF header (12), VP8X chunk (18), ALPH chunk (8 + 1 + w h + pad), VP8 chunk header (8), frame header (10),
 // partition 0, seven partition sizes (21), the token partitions, the pad byte.  (Under vp8_fits this stays far below 2^32.)
-FL_VP8_HD uint64_t vp8_max_out_bytes(uint64_t w, uint64_t h)
+FL_VP8_HD uint64_t vp8_max_out_bytes(uint64_t w, uint64_t h, bool i4 = false, bool ap = false, bool seg = false)
 {
     const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return 12u + 18u + (8u + 1u + w * h + 1u) + 8u + 10u + 21u + vp8_part0_max_bytes(mbs) +
+    return 12u + 18u + (8u + 1u + w * h + 1u) + 8u + 10u + 21u + vp8_part0_max_bytes(mbs, i4, ap, seg) +
            (kVp8BoolBits * (kVp8MbTokenBools * mbs + 8u * kVp8FlushBools) + 7u) / 8u + 1u;
-}
-
-// the I4 variant: the same, with its own partition 0
-FL_VP8_HD bool vp8_i4_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsI4; }
-FL_VP8_HD uint64_t vp8_i4_max_out_bytes(uint64_t w, uint64_t h)
-{
-    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_part0_max_bytes(mbs);
-}
-
-// the adaptive-probability variants: the same, with their own partition 0.  The I16-only one stays bound by the 24-bit token
-// partition field (about 21 000 macroblocks; kVp8MaxMbsAp is four times that), the B_PRED one by kVp8MaxMbsI4Ap.
-FL_VP8_HD bool vp8_ap_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsAp; }
-FL_VP8_HD bool vp8_i4_ap_fits(uint64_t w, uint64_t h) { return vp8_fits(w, h) && ((w + 15u) >> 4) * ((h + 15u) >> 4) <= kVp8MaxMbsI4Ap; }
-FL_VP8_HD uint64_t vp8_ap_max_out_bytes(uint64_t w, uint64_t h)
-{
-    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_ap_part0_max_bytes(mbs);
-}
-FL_VP8_HD uint64_t vp8_i4_ap_max_out_bytes(uint64_t w, uint64_t h)
-{
-    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_i4_ap_part0_max_bytes(mbs);
-}
-
-// with FLGPU_FEO_SEGMENTS: the front end's limits with the segmented partition 0 (a picture that fits the front end but not these
-// is coded without the option)
-FL_VP8_HD bool vp8_seg_fits(uint64_t w, uint64_t h, bool i4, bool ap)
-{
-    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return vp8_fits(w, h) && mbs <= (ap ? (i4 ? kVp8MaxMbsI4ApSeg : kVp8MaxMbsApSeg) : (i4 ? kVp8MaxMbsI4Seg : kVp8MaxMbsSeg));
-}
-FL_VP8_HD uint64_t vp8_seg_max_out_bytes(uint64_t w, uint64_t h, bool i4, bool ap)
-{
-    const uint64_t mbs = ((w + 15u) >> 4) * ((h + 15u) >> 4);
-    return vp8_max_out_bytes(w, h) - vp8_part0_max_bytes(mbs) + vp8_seg_part0_max_bytes(mbs, i4, ap);
 }
 
 // ---- quantiser --------------------------------------------------------------------------------------------------------------------

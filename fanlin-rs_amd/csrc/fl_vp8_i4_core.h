@@ -2,7 +2,7 @@
 // luma as sixteen 4x4 sub-blocks, decide between that and I16, and commit the winner.  fl_vp8_core.h states the rule and holds
 // everything else (bounds, penalty, transforms, the coder with its mode tree); the ten predictors are the decoder's
 // (fl_vp8dec_core.h vp8d_predict4), not a second copy.  Like fl_vp8_core.h this compiles for the host and the device: fl_vp8.hip
-// spreads the items of every phase over the lanes of a wave, tests/vp8_i4_host.cpp runs them in plain loops.
+// spreads the items of every phase over the lanes of a wave, tests/vp8_host.cpp runs them in plain loops.
 #pragma once
 #include <stdint.h>
 

@@ -1,7 +1,7 @@
 // fl_vp8_lf_core.h -- the loop-filtered variants of the lossy WebP encoder (FLGPU_FE_WEBP_LOSSY_LF, _I4_LF, _AP_LF, _I4_AP_LF): the
 // rule that picks the frame header's loop filter level, as code that compiles for the host and for the device.  Each variant codes
 // the macroblocks, modes, levels and probabilities of the front end it stands beside; only the 6-bit level literal differs (and with
-// it the bytes of partition 0).  tests/vp8_lf_model.py restates the rule, tests/vp8_lf_host.cpp runs it in plain loops.
+// it the bytes of partition 0).  tests/vp8_lf_model.py restates the rule, tests/vp8_host.cpp runs it in plain loops.
 //
 // The rule, integer only:
 //   * base level from the quantiser index: s = min(y1_ac(qi) >> 2, 63), f = s * 300 / 256, L0 = 0 if f < 2 else min(f, 63).

@@ -2,7 +2,7 @@
 // the rule that sorts a picture's macroblocks into up to four classes by activity and gives each class its quantiser index, as code
 // that compiles for the host and for the device.  fl_vp8_core.h holds the record the rule leaves (Vp8SegRec), the header and the ids
 // in partition 0 (vp8_put_first_partition) and the limits; the analysis takes each macroblock's steps from its class (vp8_seg_pick).
-// tests/vp8_seg_model.py restates the rule, tests/vp8_seg_host.cpp runs it in plain loops, fl_vp8.hip (vp8_segment_kernel) over a
+// tests/vp8_seg_model.py restates the rule, tests/vp8_host.cpp runs it in plain loops, fl_vp8.hip (vp8_segment_kernel) over a
 // workgroup.
 //
 // The rule, integer only.  Inputs: the luma plane padded to whole macroblocks by edge replication (as vp8_phase_load pads it) and the

@@ -23,13 +23,11 @@ IDS = ("i16", "b_pred", "i16_probs", "b_pred_probs")
 
 
 def _fe(fl, i4, adapt):
-    return {(False, False): fl.FE_WEBP_LOSSY_LF, (True, False): fl.FE_WEBP_LOSSY_I4_LF, (False, True): fl.FE_WEBP_LOSSY_AP_LF,
-            (True, True): fl.FE_WEBP_LOSSY_I4_AP_LF}[(i4, adapt)]
+    return fl.vp8_front_end(i4, adapt, lf=True)
 
 
 def _twin(fl, i4, adapt):
-    return {(False, False): fl.FE_WEBP_LOSSY, (True, False): fl.FE_WEBP_LOSSY_I4, (False, True): fl.FE_WEBP_LOSSY_AP,
-            (True, True): fl.FE_WEBP_LOSSY_I4_AP}[(i4, adapt)]
+    return fl.vp8_front_end(i4, adapt)
 
 
 def _max_out(w, h, i4, adapt):

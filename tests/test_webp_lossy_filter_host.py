@@ -1,17 +1,17 @@
 """FLGPU_FE_WEBP_LOSSY_LF / _I4_LF / _AP_LF / _I4_AP_LF, the host half: routing and sizing of the four front ends and their accept
 bit, the rule's known answers, the restated encoder (tests/vp8_lf_model.py) pinned to the model it restates and judged by libwebp's
 decoder -- every file decodes to exactly the model's FILTERED reconstruction, and never to a worse picture than the twin front
-end's file --, what the corpus reaches, and the host twin (tests/vp8_lf_host.cpp: the kernels' own functions in plain loops) byte
+end's file --, what the corpus reaches, and the host twin (tests/vp8_host.cpp --filter: the kernels' own functions in plain loops) byte
 for byte and cost word for cost word against the model, plain and under ASan + UBSan.  No GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import vp8_ap_cases
 import vp8_ap_model as ap
+import vp8_host_twin
 import vp8_i4_model as m4
 import vp8_lf_cases as cases_mod
 import vp8_lf_model as lf
@@ -25,13 +25,11 @@ VARIANTS = cases_mod.VARIANTS
 
 
 def _fe(fl, i4, adapt):
-    return {(False, False): fl.FE_WEBP_LOSSY_LF, (True, False): fl.FE_WEBP_LOSSY_I4_LF, (False, True): fl.FE_WEBP_LOSSY_AP_LF,
-            (True, True): fl.FE_WEBP_LOSSY_I4_AP_LF}[(i4, adapt)]
+    return fl.vp8_front_end(i4, adapt, lf=True)
 
 
 def _twin(fl, i4, adapt):
-    return {(False, False): fl.FE_WEBP_LOSSY, (True, False): fl.FE_WEBP_LOSSY_I4, (False, True): fl.FE_WEBP_LOSSY_AP,
-            (True, True): fl.FE_WEBP_LOSSY_I4_AP}[(i4, adapt)]
+    return fl.vp8_front_end(i4, adapt)
 
 
 def _max_out(w, h, i4, adapt):
@@ -220,29 +218,14 @@ def test_the_corpus_reaches_what_it_is_there_for(cases):
 
 # ------------------------------------------------------------------------------------------------------- the host twin --
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-std=c++17", *extra, os.path.join(ROOT, "tests", "vp8_lf_host.cpp"),
-                    "-I", CSRC, "-o", exe], check=True)
-    return exe
-
-
 @pytest.mark.parametrize("sanitised", (False, True), ids=("plain", "asan_ubsan"))
 def test_the_host_twin_writes_the_models_bytes_and_prints_its_costs(cases, tmp_path, sanitised):
     """The kernels' own functions in plain loops, as a program of its own; the second build runs them under ASan + UBSan."""
-    exe = _build(tmp_path, "vp8_lf_host", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitised else [])
+    exe = vp8_host_twin.build(tmp_path, sanitised)
     bad = []
     for (i4, adapt, name), (y, u, v, a, q, base, data, rec, shown, stats, twin) in cases.items():
-        h, w = y.shape
-        planes, out, filtered = (str(tmp_path / f) for f in ("planes.bin", "out.webp", "filtered.bin"))
-        with open(planes, "wb") as f:
-            f.write(y.tobytes() + u.tobytes() + v.tobytes() + (a if a is not None else np.full((h, w), 255, np.uint8)).tobytes())
-        r = subprocess.run([exe, str(w), str(h), str(q), str(int(a is not None)), str(int(i4)), str(int(adapt)), str(-1 if base is None else base),
-                            planes, out, filtered], capture_output=True, text=True)
-        assert r.returncode == 0 and "vp8 lf ok" in r.stdout and not r.stderr, (name, r.stderr)
-        f = r.stdout.split()
-        levels, costs, chosen = [int(x) for x in f[5:9]], [int(x) for x in f[10:14]], int(f[15])
-        if (open(out, "rb").read() != data or open(filtered, "rb").read() != b"".join(p.tobytes() for p in shown)
-                or levels != stats["levels"] or costs != stats["D"] or chosen != stats["chosen"]):
-            bad.append((i4, adapt, name, levels, costs, chosen))
+        got = vp8_host_twin.run(exe, tmp_path, y, u, v, a, q, i4=i4, adaptive=adapt, filt=True, filter_base=base, files=("shown",))
+        if (got["file"] != data or got["shown"] != b"".join(p.tobytes() for p in shown)
+                or got["levels"] != stats["levels"] or got["D"] != stats["D"] or got["chosen"] != stats["chosen"]):
+            bad.append((i4, adapt, name, got["levels"], got["D"], got["chosen"]))
     assert not bad, bad

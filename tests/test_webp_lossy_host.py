@@ -4,18 +4,16 @@ own functions in plain loops) byte for byte against the model, and the coder mea
 planes.  No GPU."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import vp8_cases
+import vp8_host_twin
 import vp8_lib
 import vp8_model as vm
 import webp_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANES_300x200 = 2 * 300 * 200 + 2 * 150 * 100
 
 # Measured on the four photo_300x200 pictures (q = 1, 30, 75, 99; a letterboxed synth.photo), this coder against libwebp's encoder
@@ -191,17 +189,10 @@ def test_measured_against_libwebps_encoder(cases):
 # ------------------------------------------------------------------------------------------------------- the host twin --
 
 def test_the_host_twin_writes_the_models_bytes(cases, tmp_path):
-    exe = str(tmp_path / "vp8_host")
-    subprocess.run(["g++", "-O1", "-Wall", "-Wextra", "-Werror", "-std=c++17", os.path.join(ROOT, "tests", "vp8_host.cpp"),
-                    "-I", os.path.join(ROOT, "fanlin-rs_amd", "csrc"), "-o", exe], check=True)
+    exe = vp8_host_twin.build(tmp_path)
     bad = []
     for name, (y, u, v, a, q, data, rec, stats) in cases.items():
-        h, w = y.shape
-        planes, out, recon = str(tmp_path / "planes.bin"), str(tmp_path / "out.webp"), str(tmp_path / "rec.bin")
-        with open(planes, "wb") as f:
-            f.write(y.tobytes() + u.tobytes() + v.tobytes() + (a if a is not None else np.full((h, w), 255, np.uint8)).tobytes())
-        r = subprocess.run([exe, str(w), str(h), str(q), str(int(a is not None)), planes, out, recon], capture_output=True, text=True)
-        assert r.returncode == 0 and "vp8 ok" in r.stdout, (name, r.stderr)
-        if open(out, "rb").read() != data or open(recon, "rb").read() != b"".join(p.tobytes() for p in rec):
+        got = vp8_host_twin.run(exe, tmp_path, y, u, v, a, q, files=("recon",))
+        if got["file"] != data or got["recon"] != b"".join(p.tobytes() for p in rec):
             bad.append(name)
     assert not bad, bad

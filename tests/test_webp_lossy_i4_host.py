@@ -1,14 +1,14 @@
 """FLGPU_FE_WEBP_LOSSY_I4, the host half: routing and sizing of the front end and its accept bit, the restated encoder
 (tests/vp8_i4_model.py) judged by libwebp's decoder -- every file decodes to exactly the model's reconstruction --, what the corpus
-reaches, read from the model's mode map, and the host twin (tests/vp8_i4_host.cpp: the kernels' own functions in plain loops) byte
+reaches, read from the model's mode map, and the host twin (tests/vp8_host.cpp --i4: the kernels' own functions in plain loops) byte
 for byte against the model, plain and under ASan + UBSan.  No GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import vp8_host_twin
 import vp8_i4_cases
 import vp8_i4_model as m4
 import vp8_lib
@@ -57,14 +57,14 @@ def test_both_bits_choose_the_i4_front_end_and_the_new_bit_alone_does_nothing(fl
 def test_the_limits_are_the_derived_ones(fl):
     lib = fl.load_library()
     # 117 booleans of at most 7 bits per macroblock in a first partition of at most 2^19 - 1 bytes
-    assert m4.PART0_MB_BOOLS == 117 and m4.MAX_MBS == fl.VP8_I4_MAX_MBS == 5111
+    assert m4.PART0_MB_BOOLS == 117 and m4.MAX_MBS == fl.vp8_max_mbs(i4=True) == 5111
     assert (7 * (1126 + 117 * 5111) + 7) // 8 < (1 << 19) <= (7 * (1126 + 117 * 5112) + 7) // 8
     for w, h, c in ((1, 1, 1), (300, 200, 4), (301, 7, 3), (5000, 1, 2), (1, 16383, 3), (1136, 1136, 3)):
         assert m4.fits(w, h)
         plan = fl.plan_output(fl.make_params(quality=75, front_end=fl.FE_WEBP_LOSSY_I4), w, h, c)
         assert (plan.out_w, plan.out_h, plan.out_c) == (w, h, c)
         assert plan.out_bytes == 2 * w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
-        assert plan.max_out_bytes == m4.max_out_bytes(w, h) == fl.vp8_i4_max_out_bytes(w, h)
+        assert plan.max_out_bytes == m4.max_out_bytes(w, h) == fl.vp8_max_out_bytes(w, h, i4=True)
         mbs = ((w + 15) // 16) * ((h + 15) // 16)
         assert plan.max_out_bytes - vm.max_out_bytes(w, h) in ((7 * 110 * mbs) // 8, (7 * 110 * mbs + 7) // 8)
     # over the limit: the front end is refused, and the accept bits fall back to FE_WEBP_LOSSY
@@ -168,28 +168,16 @@ def test_the_corpus_reaches_the_paths_it_is_there_for(cases):
 
 # ------------------------------------------------------------------------------------------------------- the host twin --
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-std=c++17", *extra, os.path.join(ROOT, "tests", "vp8_i4_host.cpp"),
-                    "-I", CSRC, "-o", exe], check=True)
-    return exe
-
-
 @pytest.mark.parametrize("sanitised", (False, True), ids=("plain", "asan_ubsan"))
 def test_the_host_twin_writes_the_models_bytes(cases, tmp_path, sanitised):
     """The kernels' own functions in plain loops, as a program of its own; the second build runs them under ASan + UBSan."""
-    exe = _build(tmp_path, "vp8_i4_host", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitised else [])
+    exe = vp8_host_twin.build(tmp_path, sanitised)
     bad = []
     for name, (y, u, v, a, q, data, rec, stats) in cases.items():
-        h, w = y.shape
-        planes, out, recon, modes = (str(tmp_path / f) for f in ("planes.bin", "out.webp", "rec.bin", "modes.bin"))
-        with open(planes, "wb") as f:
-            f.write(y.tobytes() + u.tobytes() + v.tobytes() + (a if a is not None else np.full((h, w), 255, np.uint8)).tobytes())
-        r = subprocess.run([exe, str(w), str(h), str(q), str(int(a is not None)), planes, out, recon, modes], capture_output=True, text=True)
-        assert r.returncode == 0 and "vp8 i4 ok" in r.stdout and not r.stderr, (name, r.stderr)
-        got = np.frombuffer(open(modes, "rb").read(), np.uint8).reshape(stats["i4"].shape + (17,))
+        twin = vp8_host_twin.run(exe, tmp_path, y, u, v, a, q, i4=True, files=("recon", "modes"))
+        got = np.frombuffer(twin["modes"], np.uint8).reshape(stats["i4"].shape + (17,))
         want = np.where(stats["i4"][..., None], np.array(m4.RFC_TO_TABLE)[np.maximum(stats["bmodes"], 0)], 0)
-        if (open(out, "rb").read() != data or open(recon, "rb").read() != b"".join(p.tobytes() for p in rec)
+        if (twin["file"] != data or twin["recon"] != b"".join(p.tobytes() for p in rec)
                 or not np.array_equal(got[..., 0], stats["i4"]) or not np.array_equal(got[..., 1:], want)):
             bad.append(name)
     assert not bad, bad

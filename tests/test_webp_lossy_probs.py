@@ -20,7 +20,7 @@ Q = "w=300&h=200&webp=true&quality=75"
 
 
 def _fe(fl, i4):
-    return fl.FE_WEBP_LOSSY_I4_AP if i4 else fl.FE_WEBP_LOSSY_AP
+    return fl.vp8_front_end(i4, ap=True)
 
 
 def _planes(fl, st, img, **kw):

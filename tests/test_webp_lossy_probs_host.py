@@ -1,12 +1,11 @@
 """FLGPU_FE_WEBP_LOSSY_AP / FLGPU_FE_WEBP_LOSSY_I4_AP, the host half: routing and sizing of the two front ends and their accept bit,
 the cost table against its formula, the restated encoder (tests/vp8_ap_model.py) pinned to the two models it restates and judged by
 libwebp's decoder -- every file decodes to exactly the reconstruction of the non-adaptive front end --, what the corpus reaches,
-the sizes, and the host twin (tests/vp8_ap_host.cpp: the kernels' own functions in plain loops) byte for byte against the model,
+the sizes, and the host twin (tests/vp8_host.cpp --adaptive: the kernels' own functions in plain loops) byte for byte against the model,
 plain and under ASan + UBSan.  No GPU."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import pytest
 import vp8_ap_cases
 import vp8_ap_model as ap
 import vp8_cases
+import vp8_host_twin
 import vp8_i4_cases
 import vp8_i4_model as m4
 import vp8_lib
@@ -76,17 +76,17 @@ def test_the_new_bit_selects_the_adaptive_front_ends_and_alone_does_nothing(fl):
 def test_the_limits_are_the_derived_ones_and_the_fall_backs_work(fl):
     lib = fl.load_library()
     # 9574 booleans in the fixed part of a first partition of at most 2^19 - 1 bytes
-    assert ap.PART0_BOOLS == fl.VP8_AP_PART0_BOOLS == 9574 and ap.I4_MAX_MBS == fl.VP8_I4_AP_MAX_MBS == 5039 == (599185 - 9574) // 117
+    assert ap.PART0_BOOLS == 9574 and ap.I4_MAX_MBS == fl.vp8_max_mbs(i4=True, ap=True) == 5039 == (599185 - 9574) // 117
     assert (7 * (9574 + 117 * 5039) + 7) // 8 < (1 << 19) <= (7 * (9574 + 117 * 5040) + 7) // 8
     src = open(os.path.join(CSRC, "fl_vp8_core.h")).read()
     assert "kVp8Part0BoolsAp = 29 + 1056 * 9 + 9 + 32;" in src
     for w, h, c in ((1, 1, 1), (300, 200, 4), (301, 7, 3), (5000, 1, 2), (1, 16383, 3), (1120, 1136, 3)):
-        for i4, fe, helper in ((False, fl.FE_WEBP_LOSSY_AP, fl.vp8_ap_max_out_bytes), (True, fl.FE_WEBP_LOSSY_I4_AP, fl.vp8_i4_ap_max_out_bytes)):
+        for i4, fe in ((False, fl.FE_WEBP_LOSSY_AP), (True, fl.FE_WEBP_LOSSY_I4_AP)):
             assert ap.fits(w, h, i4)
             plan = fl.plan_output(fl.make_params(quality=75, front_end=fe), w, h, c)
             assert (plan.out_w, plan.out_h, plan.out_c) == (w, h, c)
             assert plan.out_bytes == 2 * w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
-            assert plan.max_out_bytes == ap.max_out_bytes(w, h, i4) == helper(w, h)
+            assert plan.max_out_bytes == ap.max_out_bytes(w, h, i4) == fl.vp8_max_out_bytes(w, h, i4, ap=True)
             assert plan.max_out_bytes - (m4.max_out_bytes(w, h) if i4 else vm.max_out_bytes(w, h)) == (7 * 8448 + 7) // 8 == 7392
     # the I16-only variant stays bound by the token partitions' 24-bit field: exactly the pictures FE_WEBP_LOSSY takes
     for w, h in ((1920, 1080), (2304, 2304), (2320, 2320), (16383, 16), (16384, 1), (16383, 16383)):
@@ -246,28 +246,16 @@ def test_the_sizes(cases):
 
 # ------------------------------------------------------------------------------------------------------- the host twin --
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-std=c++17", *extra, os.path.join(ROOT, "tests", "vp8_ap_host.cpp"),
-                    "-I", CSRC, "-o", exe], check=True)
-    return exe
-
-
 @pytest.mark.parametrize("sanitised", (False, True), ids=("plain", "asan_ubsan"))
 def test_the_host_twin_writes_the_models_bytes(cases, tmp_path, sanitised):
     """The kernels' own functions in plain loops, as a program of its own; the second build runs them under ASan + UBSan."""
-    exe = _build(tmp_path, "vp8_ap_host", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitised else [])
+    exe = vp8_host_twin.build(tmp_path, sanitised)
     bad = []
     for (i4, name), (y, u, v, a, q, data, rec, stats, plain) in cases.items():
-        h, w = y.shape
-        planes, out, recon, st = (str(tmp_path / f) for f in ("planes.bin", "out.webp", "rec.bin", "stats.bin"))
-        with open(planes, "wb") as f:
-            f.write(y.tobytes() + u.tobytes() + v.tobytes() + (a if a is not None else np.full((h, w), 255, np.uint8)).tobytes())
-        r = subprocess.run([exe, str(w), str(h), str(q), str(int(a is not None)), str(int(i4)), planes, out, recon, st], capture_output=True, text=True)
-        assert r.returncode == 0 and "vp8 ap ok" in r.stdout and not r.stderr, (name, r.stderr)
-        blob = open(st, "rb").read()
+        twin = vp8_host_twin.run(exe, tmp_path, y, u, v, a, q, i4=i4, adaptive=True, files=("recon", "stats"))
+        blob = twin["stats"]
         counts = np.frombuffer(blob[:8 * ap.N], "<u4")
-        if (open(out, "rb").read() != data or open(recon, "rb").read() != b"".join(p.tobytes() for p in rec)
+        if (twin["file"] != data or twin["recon"] != b"".join(p.tobytes() for p in rec)
                 or counts[:ap.N].tolist() != stats["z"] or counts[ap.N:].tolist() != stats["o"] or list(blob[8 * ap.N:]) != stats["probs"]):
             bad.append((i4, name))
     assert not bad, bad

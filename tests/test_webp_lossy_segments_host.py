@@ -1,7 +1,7 @@
 """FLGPU_FEO_SEGMENTS / FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS, the host half: the constants and the unchanged struct, the mapping of the accept
 bit, the larger worst case and the fall-back limits, the rule's known answers, the restated encoder (tests/vp8_seg_model.py) pinned
 to the models it restates and judged by libwebp's decoder -- every corpus file decodes to exactly what the model says a decoder
-shows, loop-filtered families with a level above 0 included --, what the corpus reaches, the host twin (tests/vp8_seg_host.cpp: the
+shows, loop-filtered families with a level above 0 included --, what the corpus reaches, the host twin (tests/vp8_host.cpp --segments: the
 kernels' own functions in plain loops) byte for byte against the model, plain and under ASan + UBSan, and the recorded measurement
 against libwebp's encoder.  No GPU."""
 import ctypes as C
@@ -17,6 +17,7 @@ import synth
 import vp8_ap_cases
 import vp8_ap_model as ap
 import vp8_cases
+import vp8_host_twin
 import vp8_i4_model as m4
 import vp8_lf_cases
 import vp8_lib
@@ -39,12 +40,6 @@ MEASURED_SIZE_RATIO = {"letterbox": (1.160, 1.562, 1.680, 2.034), "flagship": (1
 MEASURED_PSNR_DEFICIT_DB = {"letterbox": (1.28, 0.15, 0.42, -0.07), "flagship": (0.43, -0.10, -0.06, -0.04)}
 SIZE_RATIO_BAR = 2.3
 PSNR_DEFICIT_BAR_DB = 1.5
-
-
-def _fe_traits(fl, fe):
-    i4 = fe in (fl.FE_WEBP_LOSSY_I4, fl.FE_WEBP_LOSSY_I4_AP, fl.FE_WEBP_LOSSY_I4_LF, fl.FE_WEBP_LOSSY_I4_AP_LF)
-    adapt = fe in (fl.FE_WEBP_LOSSY_AP, fl.FE_WEBP_LOSSY_I4_AP, fl.FE_WEBP_LOSSY_AP_LF, fl.FE_WEBP_LOSSY_I4_AP_LF)
-    return i4, adapt
 
 
 def _twin_max_out(w, h, i4, adapt):
@@ -132,9 +127,11 @@ def test_max_out_bytes_and_the_fall_back_limits(fl):
     lib = fl.load_library()
     assert sm.PART0_SEG_BOOLS == 98 and (sm.max_mbs(True, False), sm.max_mbs(True, True)) == (5024, 4953)
     core = open(os.path.join(CSRC, "fl_vp8_core.h")).read()
-    assert "kVp8MaxMbsI4Seg == 5024 && kVp8MaxMbsI4ApSeg == 4953" in core and "kVp8Part0SegBools == 98" in core
+    assert ("vp8_max_mbs(true) == 5111 && vp8_max_mbs(true, true) == 5039 && vp8_max_mbs(true, false, true) == 5024 && vp8_max_mbs(true, true, true) == 4953" in core
+            and "kVp8Part0SegBools == 98" in core)
+    assert [fl.vp8_max_mbs(True, adapt, seg) for seg in (False, True) for adapt in (False, True)] == [5111, 5039, 5024, 4953]
     for fe in fl.FE_WEBP_LOSSY_ALL:
-        i4, adapt = _fe_traits(fl, fe)
+        i4, adapt, _ = fl.vp8_variant(fe)
         for w, h, c in ((1, 1, 1), (300, 200, 4), (301, 7, 3), (1, 16383, 3), (1104, 1136, 3)):
             plain = fl.plan_output(fl.make_params(quality=75, front_end=fe), w, h, c)
             seg = fl.plan_output(fl.make_params(quality=75, front_end=fe, segments=True), w, h, c)
@@ -148,7 +145,7 @@ def test_max_out_bytes_and_the_fall_back_limits(fl):
     # a picture within the front end's limits but over the segmented ones is planned (and coded) without the option:
     # 5040 = 72 x 70 and 5025 = 75 x 67 macroblocks for B_PRED (5111 / 5024), 5035 = 95 x 53 and 4958 = 74 x 67 with updates (5039 / 4953)
     for fe, (mw, mh) in ((fl.FE_WEBP_LOSSY_I4, (72, 70)), (fl.FE_WEBP_LOSSY_I4_LF, (75, 67)), (fl.FE_WEBP_LOSSY_I4_AP, (95, 53)), (fl.FE_WEBP_LOSSY_I4_AP_LF, (74, 67))):
-        i4, adapt = _fe_traits(fl, fe)
+        i4, adapt, _ = fl.vp8_variant(fe)
         w, h = 16 * mw, 16 * mh
         assert mw * mh > sm.max_mbs(i4, adapt) and not sm.fits(w, h, i4, adapt) and (ap.fits(w, h, True) if adapt else m4.fits(w, h))
         assert fl.plan_output(fl.make_params(front_end=fe, segments=True), w, h, 3).max_out_bytes == _twin_max_out(w, h, i4, adapt)
@@ -372,33 +369,19 @@ def test_measured_against_libwebps_encoder(oracle):
 
 # ------------------------------------------------------------------------------------------------------- the host twin --
 
-def _build(tmp_path, name, extra):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-std=c++17", *extra, os.path.join(ROOT, "tests", "vp8_seg_host.cpp"),
-                    "-I", CSRC, "-o", exe], check=True)
-    return exe
-
-
 @pytest.mark.parametrize("sanitised", (False, True), ids=("plain", "asan_ubsan"))
 def test_the_host_twin_writes_the_models_bytes(cases, tmp_path, sanitised):
     """The kernels' own functions in plain loops, as a program of its own; the second build runs them under ASan + UBSan."""
-    exe = _build(tmp_path, "vp8_seg_host", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitised else [])
+    exe = vp8_host_twin.build(tmp_path, sanitised)
     bad = []
     for (family, name), (y, u, v, a, q, data, rec, shown, stats, twin) in cases.items():
         i4, adapt, filt = FAMILIES[family]
-        h, w = y.shape
-        planes, out, dec = (str(tmp_path / f) for f in ("planes.bin", "out.webp", "shown.bin"))
-        with open(planes, "wb") as f:
-            f.write(y.tobytes() + u.tobytes() + v.tobytes() + (a if a is not None else np.full((h, w), 255, np.uint8)).tobytes())
-        for segments, want in ((1, data), (0, twin)):
-            r = subprocess.run([exe, str(w), str(h), str(q), str(int(a is not None)), str(int(i4)), str(int(adapt)), str(int(filt)), str(segments),
-                                planes, out, dec], capture_output=True, text=True)
-            assert r.returncode == 0 and "vp8 seg ok" in r.stdout and not r.stderr, (name, r.stderr)
-            f = r.stdout.split()
+        for segments, want in ((True, data), (False, twin)):
+            got = vp8_host_twin.run(exe, tmp_path, y, u, v, a, q, i4=i4, adaptive=adapt, filt=filt, segments=segments, files=("shown",))
             seg = stats["seg"]
-            if open(out, "rb").read() != want:
+            if got["file"] != want:
                 bad.append((family, name, segments, "file"))
-            if segments and (open(dec, "rb").read() != b"".join(p.tobytes() for p in shown) or int(f[5]) != int(seg["on"])
-                             or [int(x) for x in f[7:11]] != seg["qi"] or [int(x) for x in f[12:15]] != seg["prob"] or int(f[16]) != stats["chosen"]):
-                bad.append((family, name, f))
+            if segments and (got["shown"] != b"".join(p.tobytes() for p in shown) or got["seg_on"] != int(seg["on"])
+                             or got["seg_qi"] != seg["qi"] or got["seg_prob"] != seg["prob"] or got["chosen"] != stats["chosen"]):
+                bad.append((family, name, got))
     assert not bad, bad
