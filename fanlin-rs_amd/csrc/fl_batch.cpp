@@ -1,11 +1,11 @@
 // fl_batch.cpp -- the batch planner and launcher: geometry, buffer chain, table lookups, descriptor staging and kernel
 // launches of one batch on ONE device context (reference order of operations: src/handler.rs:221-278), the read-back of
-// per-image result words, and the host-memory batch built on top of it.
+// per-image result words, and the host-memory batch built on top of it.  Resample and blur are planned here; a picture's
+// front end (planes, an encoded stream) is fl_encode.cpp's.
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
-#include <cassert>
 #include <memory>
 #include <optional>
 
@@ -79,14 +79,11 @@ template <class Key> struct Launch {
     LaunchGeneric g{};
     size_t lds = 0, mid_floats = 0;
 };
-struct FeLaunch { uint32_t kind, base, n, mw, mh; bool rgba; };
 
 // Bytes (or records) of every scratch buffer a batch needs; while pictures are added, the running totals are their offsets.
 struct ScratchSizes {
     size_t a = 0, b = 0, o = 0, al = 0; // stage 1's output, the blur's, oriented sources, aligned copies
-    size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
-    size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0, vp8_lf = 0, vp8_seg = 0;
-    uint32_t png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
+    EncodeScratch enc;
 };
 
 // What passes between the phases of run_batch_device.
@@ -100,32 +97,20 @@ struct Batch {
     std::vector<LaunchGeneric> orient_launches; // EXIF orientation pre-pass, one per channel count
     std::vector<Launch<ResampleKey>> s1_launches;
     std::vector<Launch<BlurKey>> blur_launches;
-    std::vector<FeLaunch> fe_launches;
     std::vector<Job> jobs;
     std::vector<StreamItem> items;
     std::vector<MfmaItem> mitems;
     std::vector<MfmaReq> mreqs;
     std::vector<uint32_t> mwg; // matrix-pipe launches with persistent workgroups: {first item, items} of every workgroup
-    std::vector<FrontendJob> fjobs;
-    std::vector<JpegJob> jjobs;
-    std::vector<PngJob> pjobs;
-    std::vector<WebpJob> wjobs;
-    std::vector<WebpJob> ajobs; // the alpha-mode jobs of the lossy WebP pictures that carry FLGPU_FEO_ALPHA_VP8L, in the order of vjobs
-    uint32_t wjob_tiles = 0, ajob_tiles = 0; // tiles of each list: a launch numbers its own
-    std::vector<Vp8Job> vjobs;
-    uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
-    uint32_t vjobs_seg = 0; // how many of them carry FLGPU_FEO_SEGMENTS (and fit its limits): vp8_segment_kernel launches iff any does
-    std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, ajob_img, vjob_img; // image of every front-end / encoder job: addresses its result words
-    uint32_t jpeg_max_blocks = 0;
+    EncodeJobs enc; // the front ends' jobs and launches (fl_encode.h)
     size_t mid_floats_max = 0;
     bool has_results = false, has_err_word = false;
     // the staged descriptor block
     DescSlot *slot = nullptr;
     uint32_t *status_dev = nullptr;
     struct {
-        const Job *jobs; const StreamItem *items; const FrontendJob *fjobs; const JpegJob *jjobs; const MfmaItem *mitems;
-        const MfmaReq *mreqs; const uint32_t *mwg; const PngJob *pjobs; const WebpJob *wjobs; const WebpJob *ajobs; const Vp8Job *vjobs;
-    } d{}; // the arrays' device copies
+        const Job *jobs; const StreamItem *items; const MfmaItem *mitems; const MfmaReq *mreqs; const uint32_t *mwg;
+    } d{}; // the arrays' device copies (the front ends': enc.d)
     Batch(flgpu_ctx *c, size_t n_, flgpu_image *dsts_) : n(n_), dsts(dsts_), dbg(*c->dbg), work(n_) {}
 };
 
@@ -389,70 +374,6 @@ void xcd_interleave(Item *first, uint32_t nitems, Len len_of)
 
 // ---- planning ------------------------------------------------------------------------------------------------------------------
 
-// Encoded-stream front ends: the scratch one picture needs, appended to s, and the format's limits.  The job-building pass calls
-// them again on a running copy of the totals, which gives every picture the offsets it got here.
-int jpeg_scratch(const flgpu_plan &pl, ScratchSizes &s)
-{
-    if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions
-    const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
-    if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
-    s.jpeg_coef += align_up(units * sizeof(JpegUnit), 256);
-    s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
-    s.jpeg_raw += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
-    return FLGPU_OK;
-}
-
-int png_scratch(const flgpu_plan &pl, ScratchSizes &s)
-{
-    const uint64_t fb = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
-    if ((uint64_t)s.png_rows + pl.out_h >= (1ull << 31) || (uint64_t)s.png_segs + png_segments(fb) >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    s.png_filt += align_up(fb, 256);
-    s.png_rows += pl.out_h;
-    s.png_segs += (uint32_t)png_segments(fb);
-    return FLGPU_OK;
-}
-
-int webpll_scratch(const flgpu_plan &pl, ScratchSizes &s)
-{
-    const uint64_t npix = (uint64_t)pl.out_w * pl.out_h;
-    if ((uint64_t)s.wll_tiles + webpll_tiles(npix) >= (1ull << 31) || webpll_max_out_bytes(pl.out_w, pl.out_h) / 4u >= (1ull << 32))
-        return FLGPU_ERR_UNSUPPORTED;
-    s.wll_res += align_up(npix * 4u, 256);
-    s.wll_tok += align_up(npix * 2u, 256);
-    s.wll_stream += align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256);
-    s.wll_tiles += (uint32_t)webpll_tiles(npix);
-    s.wll_pics++;
-    return FLGPU_OK;
-}
-
-// Lossy WebP: the front end's planes, the reconstruction (whole macroblocks), 400 levels and one record per macroblock, the sizes;
-// the I4 variants' pictures also two words of sub-block modes per macroblock, the adaptive-probability variants' a table, the
-// loop-filtered variants' four cost words and three working copies of the reconstruction.
-bool vp8_fe(uint32_t fe) { return vp8_variant_of(fe).has_value(); }
-// FLGPU_FEO_ALPHA_VP8L, which only these front ends know: the picture also gets the lossless coder's scratch, for its alpha plane
-bool vp8_alpha_vp8l(const flgpu_params &p) { return vp8_fe(p.front_end) && (p.options & FLGPU_FEO_ALPHA_VP8L); }
-// FLGPU_FEO_SEGMENTS, on the same front ends: the picture gets a record and a class map, unless it fits the front end's limits but
-// not the segmented partition 0's -- then it is coded without the option
-bool vp8_segments(const flgpu_params &p, const flgpu_plan &pl)
-{
-    const std::optional<Vp8Variant> v = vp8_variant_of(p.front_end);
-    return v && (p.options & FLGPU_FEO_SEGMENTS) && vp8_fits(pl.out_w, pl.out_h, v->i4, v->ap, true);
-}
-int vp8_scratch(const flgpu_plan &pl, ScratchSizes &s, Vp8Variant v, bool seg)
-{
-    if (!vp8_fits(pl.out_w, pl.out_h, v.i4, v.ap)) return FLGPU_ERR_UNSUPPORTED; // a size field of the format could overflow (fl_vp8_core.h)
-    const uint64_t mbs = (uint64_t)vp8_mbs(pl.out_w) * vp8_mbs(pl.out_h);
-    if (v.i4) s.vp8_i4_mbs += mbs;
-    if (v.ap) s.vp8_ap_pics++;
-    if (v.lf) s.vp8_lf += vp8_lf_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h));
-    if (seg) s.vp8_seg += vp8_seg_bytes(mbs);
-    s.vp8_planes += align_up(vp8_planes_bytes(pl.out_w, pl.out_h), 256);
-    s.vp8_rec += align_up(vp8_rec_bytes(vp8_mbs(pl.out_w), vp8_mbs(pl.out_h)), 256);
-    s.vp8_mbs += mbs;
-    s.vp8_pics++;
-    return FLGPU_OK;
-}
-
 // Validates and plans every picture of the batch and sizes its scratch.  Nothing is enqueued before all of them have passed.
 int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, bool same_params)
 {
@@ -501,12 +422,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
         else if (w.s1 != S1_NONE) { w.s1_off = B.scratch.a; B.scratch.a += align_up(pl.pixel_bytes, 256); }
         if (blur && !fe) w.blur_dst = w.final_dst;
         else if (blur) { w.blur_off = B.scratch.b; B.scratch.b += align_up(pl.pixel_bytes, 256); }
-        if (w.p->front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(pl, B.scratch);
-        if (w.p->front_end == FLGPU_FE_PNG) rc = png_scratch(pl, B.scratch);
-        if (w.p->front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(pl, B.scratch);
-        if (const auto v = vp8_variant_of(w.p->front_end)) rc = vp8_scratch(pl, B.scratch, *v, vp8_segments(*w.p, pl));
-        if (!rc && vp8_alpha_vp8l(*w.p)) rc = webpll_scratch(pl, B.scratch);
-        if (rc) return rc;
+        if ((rc = encode_plan_picture(*w.p, pl, B.scratch.enc))) return rc;
     }
     return FLGPU_OK;
 }
@@ -516,27 +432,7 @@ int plan_pictures(Batch &B, const flgpu_image *srcs, const flgpu_params *ps, boo
 int reserve_scratch(flgpu_ctx *c, Batch &B, hipStream_t st)
 {
     const ScratchSizes &sz = B.scratch;
-    FL_HIP(c, c->d_jpeg_coef.reserve(sz.jpeg_coef), "JPEG coefficient scratch");
-    FL_HIP(c, c->d_jpeg_off.reserve(sz.jpeg_off), "JPEG offset scratch");
-    FL_HIP(c, c->d_jpeg_raw.reserve(sz.jpeg_raw), "JPEG bit-stream scratch");
-    FL_HIP(c, c->d_png_filt.reserve(sz.png_filt), "PNG filtered-row scratch");
-    FL_HIP(c, c->d_png_chunks.reserve((size_t)sz.png_segs * kPngSegOutBytes), "PNG chunk scratch");
-    FL_HIP(c, c->d_png_syms.reserve((size_t)sz.png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
-    FL_HIP(c, c->d_png_recs.reserve((size_t)sz.png_segs * 4u * sizeof(uint32_t)), "PNG segment records");
-    FL_HIP(c, c->d_webpll_res.reserve(sz.wll_res), "WebP residual scratch");
-    FL_HIP(c, c->d_webpll_tok.reserve(sz.wll_tok), "WebP token scratch");
-    FL_HIP(c, c->d_webpll_tiles.reserve((size_t)sz.wll_tiles * sizeof(WebpllTile)), "WebP tile records");
-    FL_HIP(c, c->d_webpll_pic.reserve((size_t)sz.wll_pics * kWebpllPicWords * sizeof(uint32_t)), "WebP per-picture scratch");
-    FL_HIP(c, c->d_webpll_stream.reserve(sz.wll_stream), "WebP bit-stream scratch");
-    FL_HIP(c, c->d_vp8_planes.reserve(sz.vp8_planes), "lossy WebP plane scratch");
-    FL_HIP(c, c->d_vp8_rec.reserve(sz.vp8_rec), "lossy WebP reconstruction scratch");
-    FL_HIP(c, c->d_vp8_lev.reserve(sz.vp8_mbs * kVp8MbLevels * sizeof(int16_t)), "lossy WebP level scratch");
-    FL_HIP(c, c->d_vp8_info.reserve(sz.vp8_mbs * sizeof(uint32_t)), "lossy WebP macroblock records");
-    FL_HIP(c, c->d_vp8_bm.reserve(sz.vp8_i4_mbs * 2u * sizeof(uint32_t)), "lossy WebP sub-block mode records");
-    FL_HIP(c, c->d_vp8_tab.reserve((size_t)sz.vp8_ap_pics * kVp8TabBytes), "lossy WebP probability tables");
-    FL_HIP(c, c->d_vp8_lf.reserve(sz.vp8_lf), "lossy WebP loop filter scratch");
-    FL_HIP(c, c->d_vp8_seg.reserve(sz.vp8_seg), "lossy WebP segment scratch");
-    FL_HIP(c, c->d_vp8_sizes.reserve((size_t)sz.vp8_pics * kVp8SizeWords * sizeof(uint32_t)), "lossy WebP partition sizes");
+    if (int rc = encode_reserve(c, sz.enc)) return rc;
     FL_HIP(c, c->d_tmp_o.reserve(sz.o), "orientation scratch");
     FL_HIP(c, c->d_tmp_al.reserve(sz.al), "alignment scratch");
     for (auto &w : B.work)
@@ -703,7 +599,7 @@ bool plan_blur(flgpu_ctx *c, const DebugSwitches &dbg, Work &w)
 // The JPEG encoder's header and quantisation tables for picture w.  false = the table arena is full.
 bool plan_jpeg_tables(flgpu_ctx *c, Work &w)
 {
-    const uint32_t q = std::min<uint32_t>(std::max<uint32_t>(w.p->quality, 1u), 100u); // handler.rs:275 quality().clamp(1, 100)
+    const uint32_t q = clamp_quality(w.p->quality);
     w.jpeg_tab = cached_block(c, c->jpeg_tables, std::make_tuple(w.plan.out_w, w.plan.out_h, q), [&](std::vector<uint32_t> &blk) { build_jpeg_tables(w.plan.out_w, w.plan.out_h, q, blk); });
     return w.jpeg_tab != 0;
 }
@@ -859,127 +755,12 @@ void add_blur_launch(flgpu_ctx *c, Batch &B, const BlurKey &k, const std::vector
     B.blur_launches.push_back(L);
 }
 
-// The header every encoded-stream job starts with: the picture it reads (the blur's output, else stage 1's), where the stream goes
-// and how much of it fits, and the image whose result words it writes (addressed once the descriptor block has its place).
-template <class J> J &encoder_job(Batch &B, std::vector<J> &jobs, std::vector<size_t> &image_of, size_t i)
-{
-    const Work &w = B.work[i];
-    J &j = jobs.emplace_back();
-    memset(&j, 0, sizeof(j));
-    j.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-    j.dst = w.final_dst;
-    j.dst_cap = (uint32_t)std::min<uint64_t>(B.dsts[i].capacity, 0xffffffffull);
-    j.w = w.plan.out_w; j.h = w.plan.out_h; j.c = w.plan.out_c;
-    image_of.push_back(i);
-    return j;
-}
-
-// Each encoder's job.  `at` holds the scratch totals of the pictures before this one, i.e. its offsets; the format's *_scratch
-// moves it past this picture (its limits were checked on the same totals in plan_pictures: it returns FLGPU_OK again).
-int add_jpeg_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
-{
-    JpegJob &j = encoder_job(B, B.jjobs, B.jjob_img, i);
-    const flgpu_plan &pl = B.work[i].plan;
-    j.units = reinterpret_cast<JpegUnit *>(static_cast<char *>(c->d_jpeg_coef.p) + at.jpeg_coef);
-    j.unit_off = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_off.p) + at.jpeg_off);
-    j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_jpeg_raw.p) + at.jpeg_raw);
-    j.bx = pl.plane_w / 8u; j.by = pl.plane_h / 8u;
-    j.tab_off = B.work[i].jpeg_tab;
-    B.jpeg_max_blocks = std::max(B.jpeg_max_blocks, j.bx * j.by);
-    return jpeg_scratch(pl, at);
-}
-
-int add_png_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at)
-{
-    PngJob &j = encoder_job(B, B.pjobs, B.pjob_img, i);
-    const flgpu_plan &pl = B.work[i].plan;
-    j.fbytes = png_filtered_bytes(pl.out_w, pl.out_h, pl.out_c);
-    j.filt = static_cast<uint8_t *>(c->d_png_filt.p) + at.png_filt;
-    j.chunks = static_cast<uint8_t *>(c->d_png_chunks.p) + (size_t)at.png_segs * kPngSegOutBytes;
-    j.syms = static_cast<uint16_t *>(c->d_png_syms.p) + (size_t)at.png_segs * kPngSegBytes;
-    j.recs = static_cast<uint32_t *>(c->d_png_recs.p) + (size_t)at.png_segs * 4u;
-    j.row0 = at.png_rows; j.seg0 = at.png_segs; j.nseg = (uint32_t)png_segments(j.fbytes);
-    j.level = png_level(B.work[i].p->quality);
-    return png_scratch(pl, at);
-}
-
-// alpha: the alpha-mode job of lossy WebP job `vj`, which reads the plane that job's planes launch writes and leaves its result in
-// front of the stream scratch (the stream itself kWebpllAlphaHead bytes in: webpll_max_out_bytes counts 40 header bits that an ALPH
-// payload does not have, and the tail of the scratch is alignment)
-int add_webpll_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, Vp8Job *vj = nullptr)
-{
-    WebpJob &j = vj ? encoder_job(B, B.ajobs, B.ajob_img, i) : encoder_job(B, B.wjobs, B.wjob_img, i);
-    const flgpu_plan &pl = B.work[i].plan;
-    uint32_t &tiles = vj ? B.ajob_tiles : B.wjob_tiles;
-    j.res = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_res.p) + at.wll_res);
-    j.tok = reinterpret_cast<uint16_t *>(static_cast<char *>(c->d_webpll_tok.p) + at.wll_tok);
-    j.tiles = static_cast<WebpllTile *>(c->d_webpll_tiles.p) + at.wll_tiles;
-    j.pic = static_cast<uint32_t *>(c->d_webpll_pic.p) + (size_t)at.wll_pics * kWebpllPicWords;
-    j.stream = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_webpll_stream.p) + at.wll_stream);
-    j.tile0 = tiles; j.ntiles = (uint32_t)webpll_tiles((uint64_t)pl.out_w * pl.out_h);
-    j.stream_words = (uint32_t)(align_up(webpll_max_out_bytes(pl.out_w, pl.out_h), 256) / 4u);
-    tiles += j.ntiles;
-    if (vj) {
-        j.mode = kWebpllModeAlpha;
-        j.src = vj->src + (size_t)pl.out_w * pl.out_h + 2u * (size_t)((pl.out_w + 1u) / 2u) * ((pl.out_h + 1u) / 2u); // behind Y, U, V
-        j.dst = reinterpret_cast<uint8_t *>(j.stream);
-        j.dst_cap = 0; j.c = 1;
-        j.stream += kWebpllAlphaHead / 4u; j.stream_words -= kWebpllAlphaHead / 4u;
-        vj->alpha = reinterpret_cast<const uint32_t *>(j.dst);
-    }
-    return webpll_scratch(pl, at);
-}
-
-// The lossy WebP job reads the planes its own WebP420 front-end job writes to scratch (add_planes_launch with to_vp8).
-int add_vp8_job(flgpu_ctx *c, Batch &B, size_t i, ScratchSizes &at, Vp8Variant v)
-{
-    Vp8Job &j = encoder_job(B, B.vjobs, B.vjob_img, i);
-    const flgpu_plan &pl = B.work[i].plan;
-    j.src = static_cast<uint8_t *>(c->d_vp8_planes.p) + at.vp8_planes;
-    j.rec = static_cast<uint8_t *>(c->d_vp8_rec.p) + at.vp8_rec;
-    j.lev = static_cast<int16_t *>(c->d_vp8_lev.p) + at.vp8_mbs * kVp8MbLevels;
-    j.info = static_cast<uint32_t *>(c->d_vp8_info.p) + at.vp8_mbs;
-    j.bm = v.i4 ? static_cast<uint32_t *>(c->d_vp8_bm.p) + at.vp8_i4_mbs * 2u : nullptr;
-    j.tab = v.ap ? static_cast<uint8_t *>(c->d_vp8_tab.p) + (size_t)at.vp8_ap_pics * kVp8TabBytes : nullptr;
-    j.sizes = static_cast<uint32_t *>(c->d_vp8_sizes.p) + (size_t)at.vp8_pics * kVp8SizeWords;
-    j.lf = v.lf ? static_cast<uint8_t *>(c->d_vp8_lf.p) + at.vp8_lf : nullptr;
-    j.lf_base = (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, B.dbg.get(DBG_VP8_FILTER_BASE)));
-    const uint32_t q = B.work[i].p->quality;
-    j.qi = vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q);
-    const bool seg = vp8_segments(*B.work[i].p, pl);
-    j.seg = seg ? static_cast<uint8_t *>(c->d_vp8_seg.p) + at.vp8_seg : nullptr;
-    B.vjobs_seg += seg;
-    return vp8_scratch(pl, at, v, seg);
-}
-
-// The planar front ends (JFIF444, WebP420): one launch per kind.  to_vp8: the pictures are lossy WebP jobs (B.vjobs from `vjob0`
-// on, in the order of pics) and the planes go to the scratch those jobs read.
-void add_planes_launch(Batch &B, uint32_t kind, const std::vector<size_t> &pics, bool to_vp8 = false, size_t vjob0 = 0)
-{
-    FeLaunch F{kind, (uint32_t)B.fjobs.size(), 0, 0, 0, true};
-    for (size_t idx : pics) {
-        const Work &w = B.work[idx];
-        FrontendJob f; memset(&f, 0, sizeof(f));
-        f.src = w.blur_dst ? w.blur_dst : w.s1_dst;
-        f.dst = to_vp8 ? const_cast<uint8_t *>(B.vjobs[vjob0 + B.fjobs.size() - F.base].src) : w.final_dst;
-        f.w = w.plan.out_w; f.h = w.plan.out_h; f.c = w.plan.out_c;
-        f.plane_w = w.plan.plane_w; f.plane_h = w.plan.plane_h; f.chroma_w = w.plan.chroma_w; f.chroma_h = w.plan.chroma_h;
-        if (f.c != 4 || ((uintptr_t)f.src & 3u) || ((uintptr_t)f.dst & 3u)) F.rgba = false;
-        if (F.kind == FLGPU_FE_JFIF444) { F.mw = std::max(F.mw, f.plane_w); F.mh = std::max(F.mh, f.plane_h); }
-        else { F.mw = std::max(F.mw, f.chroma_w); F.mh = std::max(F.mh, f.chroma_h); }
-        B.fjobs.push_back(f);
-        B.fjob_img.push_back(idx);
-        F.n++;
-    }
-    B.fe_launches.push_back(F);
-}
-
 // Groups the pictures into launches (each group in key order) and builds the job and item arrays the kernels read.
 int build_launches(flgpu_ctx *c, Batch &B)
 {
     std::map<ResampleKey, std::vector<size_t>> s1_groups;
     std::map<BlurKey, std::vector<size_t>> blur_groups;
-    std::map<uint32_t, std::vector<size_t>> fe_groups; // by front end
+    std::vector<EncodeInput> fe_inputs; // the pictures that have a front end, in batch order
     for (size_t i = 0; i < B.n; ++i) {
         const Work &w = B.work[i];
         if (w.s1 != S1_NONE) {
@@ -997,7 +778,7 @@ int build_launches(flgpu_ctx *c, Batch &B)
             const bool tiled = get_axis(c, w.plan.out_w, w.plan.out_w, FILTER_GAUSSIAN, w.p->blur_sigma, &hk, &hh) && hh && blur_tile_supported(hh->max_taps);
             blur_groups[{false, 0u, tiled ? blur_lanes(w.plan.out_w, hh->max_taps) : 256u, w.plan.out_c, blur_channels(w), false}].push_back(i);
         }
-        if (w.p->front_end != FLGPU_FE_NONE) fe_groups[w.p->front_end].push_back(i);
+        if (w.p->front_end != FLGPU_FE_NONE) fe_inputs.push_back({w.blur_dst ? w.blur_dst : w.s1_dst, w.final_dst, B.dsts[i].capacity, &w.plan, w.p, w.jpeg_tab, i});
     }
     // EXIF orientation pre-pass jobs, one launch per channel count
     for (uint32_t cs = 1; cs <= 4; ++cs) {
@@ -1019,27 +800,9 @@ int build_launches(flgpu_ctx *c, Batch &B)
     // result words: two per image of the batch, see flgpu_ctx::last_fe
     // ... followed by the batch's device error word (fl_mfma.h FLGPU_DEVERR_*): kernels that wait on one another inside a
     // workgroup bound their waits and report an expired one here instead of delivering pixels that were never synchronised
-    B.has_results = !fe_groups.empty();
+    B.has_results = !fe_inputs.empty();
     for (auto &L : B.s1_launches) B.has_err_word |= L.k.s1 == S1_MFMA;
-    ScratchSizes vp8_at; // (the lossy WebP front ends are up to eight groups that share the lossy WebP scratch, in the families' order)
-    ScratchSizes wll_at; // (the lossless WebP files and the alpha planes of those groups share the lossless coder's scratch)
-    for (auto &g : fe_groups) {
-        ScratchSizes at;
-        const size_t vjob0 = B.vjobs.size();
-        const std::optional<Vp8Variant> vp8 = vp8_variant_of(g.first);
-        for (size_t i : g.second) {
-            int rc = FLGPU_OK;
-            if (g.first == FLGPU_FE_JPEG) rc = add_jpeg_job(c, B, i, at);
-            if (g.first == FLGPU_FE_PNG) rc = add_png_job(c, B, i, at);
-            if (g.first == FLGPU_FE_WEBP_LOSSLESS) rc = add_webpll_job(c, B, i, wll_at);
-            if (vp8) { rc = add_vp8_job(c, B, i, vp8_at, *vp8); B.vjobs_fam[vp8_family(*vp8)]++; }
-            if (!rc && vp8_alpha_vp8l(*B.work[i].p)) rc = add_webpll_job(c, B, i, wll_at, &B.vjobs.back());
-            assert(rc == FLGPU_OK); // (the limits hold on these totals: plan_pictures checked them on the same ones)
-            (void)rc;
-        }
-        if (g.first == FLGPU_FE_JFIF444 || g.first == FLGPU_FE_WEBP420) add_planes_launch(B, g.first, g.second);
-        if (vp8) add_planes_launch(B, FLGPU_FE_WEBP420, g.second, true, vjob0);
-    }
+    encode_build_jobs(c, fe_inputs, B.enc);
     FL_HIP(c, c->d_mid.reserve(B.mid_floats_max * 4), "f32 intermediate");
     return FLGPU_OK;
 }
@@ -1052,20 +815,11 @@ template <class F> void desc_regions(Batch &B, F &&f)
 {
     f(B.jobs, B.d.jobs);
     f(B.items, B.d.items);
-    f(B.fjobs, B.d.fjobs);
-    f(B.jjobs, B.d.jjobs);
+    B.enc.head_regions(f);
     f(B.mitems, B.d.mitems);
     f(B.mreqs, B.d.mreqs);
     f(B.mwg, B.d.mwg);
-    f(B.pjobs, B.d.pjobs);
-    f(B.wjobs, B.d.wjobs);
-    f(B.ajobs, B.d.ajobs);
-    f(B.vjobs, B.d.vjobs);
-}
-
-template <class J> void point_results(std::vector<J> &jobs, const std::vector<size_t> &image_of, uint32_t *J::*word, uint32_t *status)
-{
-    for (size_t k = 0; k < jobs.size(); ++k) jobs[k].*word = status + 2 * image_of[k];
+    B.enc.tail_regions(f);
 }
 
 // Lays the batch's arrays out in one descriptor block and sends it to the device.
@@ -1103,12 +857,7 @@ int stage_descriptors(flgpu_ctx *c, Batch &B, hipStream_t st)
     if (words_b) {
         B.status_dev = reinterpret_cast<uint32_t *>(dp + words_off);
         memset(hp + words_off, 0, words_b);
-        point_results(B.jjobs, B.jjob_img, &JpegJob::result, B.status_dev);
-        point_results(B.fjobs, B.fjob_img, &FrontendJob::status, B.status_dev);
-        point_results(B.pjobs, B.pjob_img, &PngJob::result, B.status_dev);
-        point_results(B.wjobs, B.wjob_img, &WebpJob::result, B.status_dev);
-        point_results(B.ajobs, B.ajob_img, &WebpJob::result, B.status_dev);
-        point_results(B.vjobs, B.vjob_img, &Vp8Job::result, B.status_dev);
+        B.enc.point_results(B.status_dev);
     }
     size_t off = 0;
     desc_regions(B, [&](const auto &v, auto &dev) {
@@ -1223,34 +972,7 @@ int enqueue_launches(flgpu_ctx *c, Batch &B, hipStream_t st)
         }
         c->stats.blur_launches++;
     }
-    for (auto &F : B.fe_launches) {
-        ProfileScope ps(c, st, 2);
-        if (F.kind == FLGPU_FE_JFIF444) FL_HIP(c, launch_jfif444(B.d.fjobs, F.base, F.n, F.mw, F.mh, F.rgba, st), "jfif front end");
-        else FL_HIP(c, launch_webp420(B.d.fjobs, c->d_arena, c->gamma_off, F.base, F.n, F.mw, F.mh, F.rgba, st), "webp front end");
-        c->stats.frontend_launches++;
-    }
-    if (!B.jjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_jpeg_encode(B.d.jjobs, c->d_arena, 0, (uint32_t)B.jjobs.size(), B.jpeg_max_blocks, st), "JPEG encode");
-        c->stats.frontend_launches++;
-    }
-    if (!B.pjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_png_encode(B.d.pjobs, (uint32_t)B.pjobs.size(), B.scratch.png_rows, B.scratch.png_segs, st), "PNG encode");
-        c->stats.frontend_launches++;
-    }
-    if (!B.wjobs.empty()) {
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_webpll_encode(B.d.wjobs, (uint32_t)B.wjobs.size(), B.wjob_tiles, st), "lossless WebP encode");
-        c->stats.frontend_launches++;
-    }
-    if (!B.vjobs.empty()) {
-        ProfileScope ps(c, st, 7);
-        // the alpha planes' streams: after the planes launch that wrote the planes and the translucency bits, before any frame kernel
-        FL_HIP(c, launch_webpll_encode(B.d.ajobs, (uint32_t)B.ajobs.size(), B.ajob_tiles, st, kWebpllModeAlpha), "lossy WebP alpha plane encode");
-        FL_HIP(c, launch_vp8_encode(B.d.vjobs, B.vjobs_fam, st, B.vjobs_seg), "lossy WebP encode");
-        c->stats.frontend_launches++;
-    }
+    if (int rc = encode_enqueue(c, B.enc, st)) return rc;
     // plain copies for requests that change nothing
     for (const Work &w : B.work)
         if (w.s1 == S1_NONE && !(w.p->blur_sigma > 0.0f) && w.p->front_end == FLGPU_FE_NONE)
@@ -1291,9 +1013,7 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
     for (size_t i = 0; i < n; ++i) {
         const flgpu_plan &pl = B.work[i].plan;
         dsts[i].width = pl.out_w; dsts[i].height = pl.out_h; dsts[i].channels = pl.out_c;
-        const uint32_t fe = B.work[i].p->front_end;
-        dsts[i].flags = fe_encoded(fe) ? FLGPU_IMG_ENCODED : (fe != FLGPU_FE_NONE ? FLGPU_IMG_FRONTEND_PLANES : 0u);
-        dsts[i].bytes = fe_encoded(fe) ? 0 : pl.out_bytes; // an encoded stream's length is a result word: flgpu_batch_results
+        encode_dst_header(B.work[i].p->front_end, pl, dsts[i]);
     }
     c->last_n = n;
     c->last_status_dev = B.status_dev;
@@ -1323,15 +1043,8 @@ int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st)
     }
     if (!c->last_has_results) return FLGPU_OK;
     int rc = FLGPU_OK;
-    for (size_t i = 0; i < n; ++i) {
-        if (c->last_fe[i] == FLGPU_FE_WEBP420 && (r[2 * i] & 1u)) dsts[i].flags |= FLGPU_IMG_HAS_ALPHA;
-        if (vp8_fe(c->last_fe[i]) && r[2 * i + 1] && (r[2 * i] & kVp8ResultAlphaVp8l)) c->webp_alpha_vp8l++;
-        if (vp8_fe(c->last_fe[i]) && r[2 * i + 1] && (r[2 * i] & kVp8ResultSegments)) c->webp_lossy_segments++;
-        if (fe_encoded(c->last_fe[i])) {
-            dsts[i].bytes = r[2 * i + 1];
-            if (!r[2 * i + 1]) { c->set_error("encoded stream does not fit the destination"); rc = FLGPU_ERR_BUFFER_TOO_SMALL; }
-        }
-    }
+    for (size_t i = 0; i < n; ++i)
+        if (int e = encode_collect(c, c->last_fe[i], r[2 * i], r[2 * i + 1], dsts[i])) rc = e;
     return rc;
 }
 
@@ -1415,26 +1128,6 @@ int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_
 } // namespace fl
 
 // ---- diagnostics -----------------------------------------------------------------------------------------------------------------
-// One picture through the ordinary launch sequence of a loop-filtered lossy WebP front end; then the cost words its filter launch
-// left (the picture is the batch's only one, so its scratch is the start of d_vp8_lf) and what every consumer derives from them.
-extern "C" int flgpu_debug_vp8_filter_costs(flgpu_ctx *c, const flgpu_image *src, const flgpu_params *p, uint32_t *levels, uint64_t *costs, uint32_t *chosen)
-try {
-    if (!c || !src || !p || !levels || !costs || !chosen || !c->dbg || !vp8_variant_of(p->front_end).value_or(Vp8Variant{}).lf || !c->shard_ctx.empty()) return FLGPU_ERR_INVALID_ARG;
-    flgpu_plan plan;
-    if (int rc = flgpu_plan_output(p, src->width, src->height, src->channels, &plan)) return rc;
-    std::vector<uint8_t> file(plan.max_out_bytes);
-    flgpu_image dst{};
-    dst.data = file.data(); dst.capacity = file.size();
-    std::lock_guard<std::mutex> g(c->mu);
-    if (int rc = run_batch_host(c, 1, src, p, &dst)) return rc;
-    FL_HIP(c, hipMemcpy(costs, c->d_vp8_lf.p, kVp8LfCandidates * sizeof(uint64_t), hipMemcpyDeviceToHost), "lossy WebP filter costs D2H");
-    const uint32_t q = p->quality;
-    const uint32_t base = vp8_lf_base_of(vp8_quality_index(q < 1u ? 1u : q > 100u ? 100u : q), (int32_t)std::max<int64_t>(-1, std::min<int64_t>(63, c->dbg->get(DBG_VP8_FILTER_BASE))));
-    for (uint32_t k = 0; k < kVp8LfCandidates; ++k) levels[k] = vp8_lf_candidate(base, k);
-    *chosen = vp8_lf_choice(base, costs);
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
 extern "C" int flgpu_debug_assign_items(uint32_t pictures, uint32_t strips, uint32_t tiles, uint32_t workgroups, uint32_t capacity, uint32_t *job_of, uint32_t *strip_of,
                                         uint32_t *tile0_of, uint32_t *tile1_of, uint32_t *lists, uint32_t *nitems)
 {

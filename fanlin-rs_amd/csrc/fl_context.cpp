@@ -515,10 +515,7 @@ void flgpu_destroy(flgpu_ctx *c)
     if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
     if (c->last_done) (void)hipEventDestroy(c->last_done);
     c->d_mid.release(); c->d_tmp_a.release(); c->d_tmp_b.release(); c->d_tmp_o.release(); c->d_tmp_al.release(); c->d_in.release(); c->d_out.release();
-    c->d_jpeg_coef.release(); c->d_jpeg_off.release(); c->d_jpeg_raw.release();
-    c->d_png_filt.release(); c->d_png_chunks.release(); c->d_png_syms.release(); c->d_png_recs.release();
-    c->d_vp8_planes.release(); c->d_vp8_rec.release(); c->d_vp8_lev.release(); c->d_vp8_info.release(); c->d_vp8_sizes.release(); c->d_vp8_bm.release(); c->d_vp8_tab.release(); c->d_vp8_lf.release(); c->d_vp8_seg.release();
-    c->d_webpll_res.release(); c->d_webpll_tok.release(); c->d_webpll_tiles.release(); c->d_webpll_pic.release(); c->d_webpll_stream.release();
+    c->enc.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
     c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();

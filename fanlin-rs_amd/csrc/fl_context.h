@@ -1,6 +1,7 @@
 // fl_context.h -- internals of the host runtime behind the C ABI, shared by its translation units:
 //   fl_context.cpp   context lifetime, table arena + caches, stats, table export / import
-//   fl_batch.cpp     batch planner + launcher (device batches, host batches)
+//   fl_batch.cpp     batch planner + launcher (device batches, host batches): geometry, resample and blur
+//   fl_encode.cpp    the front ends of a batch: planes and encoded streams (fl_encode.h)
 //   fl_source.cpp    JPEG / PNG / WebP files as sources of a batch; fl_gifrun.cpp  a GIF file as a batch of its own (both: fl_source.h)
 //   fl_queue.cpp     persistent request-batching queue, lanes, sharding of flushed batches across the devices of a node
 //   fl_cmyk_ctx.cpp  CMYK device-link tables and their distribution to the devices (RCCL broadcast)
@@ -177,14 +178,9 @@ extern const char *const kDebugKeyNames[DBG_COUNT];
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
-// Worst case of a baseline JPEG stream of the encoder in fl_jpeg.hip: header + 2 x 208 bytes per 8x8 block and
-// component (every byte stuffed).  No picture can exceed it, so a destination of this size never overflows.
-inline uint64_t jpeg_worst_bytes(uint32_t plane_w, uint32_t plane_h)
-{
-    return 1024ull + 2ull * kJpegMaxUnitBytes * 3ull * (plane_w / 8u) * (plane_h / 8u);
-}
-
 } // namespace fl
+
+#include "fl_encode.h" // (down here: its EncodeBuffers holds DeviceBufs)
 
 struct flgpu_ctx {
     int device = 0;
@@ -241,10 +237,7 @@ struct flgpu_ctx {
     uint64_t gif_encode_ns = 0;                        // HIP-event time of the encode kernels' launches (profile = 1)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
-    fl::DeviceBuf d_jpeg_coef, d_jpeg_off, d_jpeg_raw; // JPEG encode scratch (fl_jpeg.hip): unit records, bit offsets, AC bits past a record
-    fl::DeviceBuf d_png_filt, d_png_chunks, d_png_syms, d_png_recs; // PNG encode scratch (fl_png.hip): filtered rows, segment chunks, symbols, records
-    fl::DeviceBuf d_vp8_planes, d_vp8_rec, d_vp8_lev, d_vp8_info, d_vp8_sizes, d_vp8_bm, d_vp8_tab, d_vp8_lf, d_vp8_seg; // lossy WebP scratch (fl_vp8.hip): the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables, the loop-filtered variants' cost words and working copies, the segmented pictures' records and class maps
-    fl::DeviceBuf d_webpll_res, d_webpll_tok, d_webpll_tiles, d_webpll_pic, d_webpll_stream; // lossless WebP scratch (fl_webpll.hip): residuals, tokens, tile records, per-picture words, bit streams
+    fl::EncodeBuffers enc; // the encoders' scratch (fl_encode.h)
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front
     // end, FL_JPEG_RESULT_OVERFLOW), [2i + 1] bytes of an encoded stream
@@ -370,9 +363,6 @@ int run_batch_device(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgp
                      flgpu_image *dsts, hipStream_t st);
 int collect_results(flgpu_ctx *c, size_t n, flgpu_image *dsts, hipStream_t st);
 int run_batch_host(flgpu_ctx *c, size_t n, const flgpu_image *srcs, const flgpu_params *ps, flgpu_image *dsts);
-// front ends whose output is an encoded stream: its length is a result word, known once the batch has run
-inline bool fe_encoded(uint32_t fe) { return fe == FLGPU_FE_JPEG || fe == FLGPU_FE_PNG || fe == FLGPU_FE_WEBP_LOSSLESS || vp8_variant_of(fe); }
-static_assert(vp8_family({true, true, true}) + 1u == kVp8Families, "launch_vp8_encode takes one range of jobs per family");
 
 // ---- fl_queue.cpp ----------------------------------------------------------------------------------------------------
 // contiguous split of n weighted items into n_shards shards of about equal weight: shard_of[i] is non-decreasing

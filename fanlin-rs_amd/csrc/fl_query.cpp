@@ -12,21 +12,11 @@
 #include <memory>
 #include <vector>
 
-#include "../../include/fanlin_gpu.h"
-#include "fl_abi.h"
-#include "fl_png.h"
 #include "fl_pngsrc.h"
 #include "fl_webpsrc.h"
 #include "fl_gifsrc.h"
-#include "fl_gif.h"
-#include "fl_webpll.h"
 #include "fl_vp8_core.h"
-#include "fl_vp8_variant.h"
-#include "fl_jpeg_tables.h"
-#include "fl_jpegdec.h"
-#include "fl_mfma.h"
-#include "fl_source.h"
-#include "fl_tables.h"
+#include "fl_context.h" // (the runtime's other headers come with it)
 
 namespace {
 
@@ -219,7 +209,7 @@ try {
     if (out_format) *out_format = fmt;
     /* lossy WebP (quality < 100, handler.rs:288-297) and JPEG have a device colour front end;
        lossless WebP, AVIF, PNG, ... take interleaved pixels */
-    uint8_t qc = p->quality < 1 ? 1 : (p->quality > 100 ? 100 : p->quality);
+    const uint32_t qc = fl::clamp_quality(p->quality);
     if (fmt == FLGPU_OUT_WEBP) p->front_end = (qc == 100) ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
     else if (fmt == FLGPU_OUT_KEEP && input_is_jpeg) p->front_end = input_is_jpeg == 2 ? FLGPU_FE_JPEG : FLGPU_FE_JFIF444;
     else p->front_end = FLGPU_FE_NONE;
@@ -257,8 +247,7 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
         p->orientation = exif_orientation;
         /* a WebP source that stays WebP goes through the same arm as a negotiated one (handler.rs:286-305) */
         if (fmt == FLGPU_OUT_KEEP && input_format == FLGPU_IN_WEBP) {
-            const uint8_t qc = p->quality < 1 ? 1 : (p->quality > 100 ? 100 : p->quality);
-            p->front_end = qc == 100 ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
+            p->front_end = fl::clamp_quality(p->quality) == 100 ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
         }
     }
     /* a PNG that stays PNG: the finished image/png body (handler.rs:264-273) when the caller opts in */
@@ -294,10 +283,7 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
         p->front_end = FLGPU_FE_WEBP_LOSSLESS;
         rc = flgpu_plan_output(p, decoded->width, decoded->height, decoded->channels, plan);
     }
-    *result_kind = (p->front_end == FLGPU_FE_WEBP_LOSSLESS || fl::vp8_variant_of(p->front_end)) ? FLGPU_RESULT_WEBP_STREAM
-                   : p->front_end == FLGPU_FE_PNG ? FLGPU_RESULT_PNG_STREAM
-                   : p->front_end == FLGPU_FE_JPEG ? FLGPU_RESULT_JPEG_STREAM
-                   : p->front_end == FLGPU_FE_WEBP420 ? FLGPU_RESULT_WEBP_PLANES : FLGPU_RESULT_PIXELS;
+    *result_kind = fl::front_end_kind(p->front_end).result_kind;
     return rc;
 }
 
@@ -822,10 +808,7 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
     if (!p || !plan) return FLGPU_ERR_INVALID_ARG;
     if (sw == 0 || sh == 0 || sc < 1 || sc > 4) return FLGPU_ERR_INVALID_ARG;
     if ((uint64_t)sw * sh * sc >= (1ull << 31)) return FLGPU_ERR_UNSUPPORTED;
-    /* front ends 0-4, 6, 9, 10, 12, 13 and 16-19 (5, 7, 8, 11, 14 and 15 are not) */
-    const std::optional<fl::Vp8Variant> vp8 = fl::vp8_variant_of(p->front_end);
-    if ((p->front_end > FLGPU_FE_PNG && p->front_end != FLGPU_FE_WEBP_LOSSLESS && !vp8) || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST)
-        return FLGPU_ERR_INVALID_ARG;
+    if (!fl::front_end_kind(p->front_end).valid || p->orientation > 8 || p->filter > FLGPU_FILTER_NEAREST) return FLGPU_ERR_INVALID_ARG;
     memset(plan, 0, sizeof(*plan));
     /* handler.rs:221-223: EXIF orientations 5..8 contain a quarter turn: width and height swap */
     if (p->orientation >= 5) { const uint32_t t = sw; sw = sh; sh = t; }
@@ -876,67 +859,7 @@ int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t 
         plan->out_c = plan->mid_c;
     }
     plan->pixel_bytes = (uint64_t)plan->out_w * plan->out_h * plan->out_c;
-    switch (p->front_end) {
-    case FLGPU_FE_JFIF444:
-        plan->plane_w = (plan->out_w + 7u) & ~7u;
-        plan->plane_h = (plan->out_h + 7u) & ~7u;
-        plan->chroma_w = plan->plane_w;
-        plan->chroma_h = plan->plane_h;
-        plan->out_bytes = 3ull * plan->plane_w * plan->plane_h;
-        break;
-    case FLGPU_FE_JPEG:
-        // out_bytes: a planning bound of the stream, not its length: header + one byte per sample (quantised photographs
-        // stay far below).  max_out_bytes: the worst case of the format, 623 + 2 + 2 * 208 bytes per 8x8 block and
-        // component: the library's own staging uses it, so a request fails with FLGPU_ERR_BUFFER_TOO_SMALL only if the
-        // finished stream really exceeds the caller's dst->capacity.
-        plan->plane_w = (plan->out_w + 7u) & ~7u;
-        plan->plane_h = (plan->out_h + 7u) & ~7u;
-        plan->chroma_w = plan->plane_w;
-        plan->chroma_h = plan->plane_h;
-        plan->out_bytes = 3ull * plan->plane_w * plan->plane_h + 1024ull;
-        plan->max_out_bytes = 1024ull + 2ull * fl::kJpegMaxUnitBytes * 3ull * (plan->plane_w / 8u) * (plan->plane_h / 8u);
-        break;
-    case FLGPU_FE_PNG:
-        // out_bytes: a planning bound, the filtered rows (what an incompressible picture's stream comes close to).
-        // max_out_bytes: the format's worst case (fl_png.h): every segment falls back to stored blocks rather than grow, so a
-        // dst of this capacity is never too small.
-        plan->out_bytes = fl::png_filtered_bytes(plan->out_w, plan->out_h, plan->out_c);
-        plan->max_out_bytes = fl::png_max_out_bytes(plan->out_bytes);
-        break;
-    case FLGPU_FE_WEBP_LOSSLESS:
-        // the VP8L header holds 14 bits of width - 1 and of height - 1.  out_bytes: a planning bound, the Rgba8 bytes.
-        // max_out_bytes: the format's worst case (fl_webpll.h), so a dst of this capacity is never too small.
-        if (plan->out_w > fl::kWebpllMaxSide || plan->out_h > fl::kWebpllMaxSide) return FLGPU_ERR_UNSUPPORTED;
-        plan->out_bytes = 4ull * plan->out_w * plan->out_h;
-        plan->max_out_bytes = fl::webpll_max_out_bytes(plan->out_w, plan->out_h);
-        break;
-    case FLGPU_FE_WEBP420:
-        plan->plane_w = plan->out_w;
-        plan->plane_h = plan->out_h;
-        plan->chroma_w = (plan->out_w + 1u) >> 1;
-        plan->chroma_h = (plan->out_h + 1u) >> 1;
-        /* Y | U | V | A: the alpha plane (w x h) is always written; it matters when FLGPU_IMG_HAS_ALPHA comes back */
-        plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
-        break;
-    default:
-        if (!vp8) { plan->out_bytes = plan->pixel_bytes; break; }
-        // a lossy WebP front end: the planes of FLGPU_FE_WEBP420 (to scratch), then the VP8 coder.  out_bytes: a planning bound, the
-        // planes' bytes.  max_out_bytes: the worst case of this coder's files (fl_vp8_core.h: one rule over i4, ap and seg; the loop
-        // filter adds nothing, the bound is per boolean), so a dst of this capacity is never too small.
-        if (!fl::vp8_fits(plan->out_w, plan->out_h, vp8->i4, vp8->ap)) return FLGPU_ERR_UNSUPPORTED;
-        plan->plane_w = plan->out_w;
-        plan->plane_h = plan->out_h;
-        plan->chroma_w = (plan->out_w + 1u) >> 1;
-        plan->chroma_h = (plan->out_h + 1u) >> 1;
-        plan->out_bytes = 2ull * plan->plane_w * plan->plane_h + 2ull * plan->chroma_w * plan->chroma_h;
-        // FLGPU_FEO_SEGMENTS: the segment header and two booleans of id per macroblock more in partition 0 (a picture over the
-        // segmented limits is coded without the option and keeps the unsegmented bound)
-        plan->max_out_bytes = fl::vp8_max_out_bytes(plan->out_w, plan->out_h, vp8->i4, vp8->ap,
-                                                    (p->options & FLGPU_FEO_SEGMENTS) && fl::vp8_fits(plan->out_w, plan->out_h, vp8->i4, vp8->ap, true));
-        break;
-    }
-    if (plan->max_out_bytes < plan->out_bytes) plan->max_out_bytes = plan->out_bytes;
-    return FLGPU_OK;
+    return fl::encode_plan_bytes(*p, *plan);
 }
 
 int flgpu_debug_axis_table(uint32_t in_size, uint32_t out_size, int filter, float sigma, uint32_t *left, uint32_t *count,
