@@ -465,77 +465,6 @@ def rccl_selftest(device: int = 0) -> dict:
     return {"status": status, "rccl_version": info[0], "bytes_intact": info[1], "tail_untouched": bool(info[2]), "communicator_destroyed": bool(info[3])}
 
 
-def jpeg_info(data: bytes) -> dict:
-    """flgpu_jpeg_info_of: header fields of a JPEG file (pure host function); raises FanlinError(ERR_PARSE) if it is none."""
-    info = flgpu_jpeg_info()
-    _check(load_library().flgpu_jpeg_info_of(data, len(data), C.byref(info)))
-    return {n: getattr(info, n) for n, _ in flgpu_jpeg_info._fields_}
-
-
-def png_info(data: bytes, adam7: bool = False) -> dict:
-    """flgpu_png_info_of: header fields of a PNG file (pure host function); raises FanlinError(ERR_PARSE) if the container is damaged.
-    ``adam7``: flgpu_png_info_of_flags with IMG_PNG_ADAM7 -- an Adam7-interlaced file of up to 8 bits per sample is supported too."""
-    info = flgpu_png_info()
-    if adam7:
-        _check(load_library().flgpu_png_info_of_flags(data, len(data), IMG_PNG_ADAM7, C.byref(info)))
-    else:
-        _check(load_library().flgpu_png_info_of(data, len(data), C.byref(info)))
-    return {n: getattr(info, n) for n, _ in flgpu_png_info._fields_}
-
-
-def debug_png_scanlines(data: bytes, adam7: bool = False) -> bytes:
-    """Host half of the PNG decode front end alone: the inflated IDAT stream (filtered scanlines), Adler-32 and filter bytes checked.
-    ``adam7``: flgpu_debug_png_scanlines_flags with IMG_PNG_ADAM7 -- for an interlaced file the seven passes' scanlines back to back."""
-    lib = load_library()
-    used = C.c_uint64()
-    if adam7:
-        def call(out, cap):
-            return lib.flgpu_debug_png_scanlines_flags(data, len(data), IMG_PNG_ADAM7, out, cap, C.byref(used))
-    else:
-        def call(out, cap):
-            return lib.flgpu_debug_png_scanlines(data, len(data), out, cap, C.byref(used))
-    _check(call(None, 0))
-    out = np.zeros(max(used.value, 1), np.uint8)
-    _check(call(out.ctypes.data, used.value))
-    return out[: used.value].tobytes()
-
-
-def webp_info(data: bytes) -> dict:
-    """flgpu_webp_info_of: container, VP8L header, transforms and code groups of a WebP file (pure host function); raises
-    FanlinError(ERR_PARSE) if the container or the headers are damaged."""
-    info = flgpu_webp_info()
-    _check(load_library().flgpu_webp_info_of(data, len(data), C.byref(info)))
-    return {n: getattr(info, n) for n, _ in flgpu_webp_info._fields_}
-
-
-def debug_webp_residuals(data: bytes) -> bytes:
-    """Host half of the lossless WebP decode front end alone: the blob that is uploaded (header, sub-images, residual picture)."""
-    lib = load_library()
-    used = C.c_uint64()
-    _check(lib.flgpu_debug_webp_residuals(data, len(data), None, 0, C.byref(used)))
-    out = np.zeros(max(used.value, 1), np.uint8)
-    _check(lib.flgpu_debug_webp_residuals(data, len(data), out.ctypes.data, used.value, C.byref(used)))
-    return out[: used.value].tobytes()
-
-
-def vp8_info(data: bytes) -> dict:
-    """flgpu_vp8_info_of: container, frame header and -- for a supported file -- what the partitions of a lossy WebP file use (pure
-    host function); raises FanlinError(ERR_PARSE) if the file is damaged or is no lossy WebP."""
-    info = flgpu_vp8_info()
-    _check(load_library().flgpu_vp8_info_of(data, len(data), C.byref(info)))
-    return {n: getattr(info, n) for n, _ in flgpu_vp8_info._fields_ if n != "reserved"}
-
-
-def debug_vp8_blob(data: bytes) -> bytes:
-    """Host half of the lossy WebP decode front end alone: the blob that is uploaded (header, macroblock records, levels, ALPH plane)."""
-    lib = load_library()
-    used = C.c_uint64()
-    _check(lib.flgpu_debug_vp8_blob(data, len(data), None, 0, C.byref(used)))
-    out = np.zeros(max(used.value, 1), np.uint8)
-    _check(lib.flgpu_debug_vp8_blob(data, len(data), out.ctypes.data, out.nbytes, C.byref(used)))
-    return out[: used.value].tobytes()
-
-
 class Adam7Png(bytes):
     """A PNG file for State.process_batch that may be Adam7-interlaced: handed over as FLGPU_IMG_PNG_SOURCE | FLGPU_IMG_PNG_ADAM7.
     (Bare ``bytes`` holding a PNG file are a FLGPU_IMG_PNG_SOURCE alone, for which an interlaced file is ERR_UNSUPPORTED.)"""
@@ -546,35 +475,111 @@ class LossyWebp(bytes):
     FLGPU_IMG_WEBP_SOURCE, which takes lossless files only.)"""
 
 
+@dataclass(frozen=True)
+class _FileFormat:
+    """One row per format a file request can have: everything the public wrappers below differ in."""
+    name: str                      # flgpu_<name>_info_of
+    info: type                     # ... and the struct it fills
+    hidden: Tuple[str, ...] = ()   # fields of it that the info dict leaves out
+    flag: int = 0                  # what a flgpu_image of the file carries
+    decode: str = ""               # the decode call
+    process: str = ""              # flgpu_process_<X>, flgpu_process_<X>_plan (both WebP kinds: the library goes by the chunk type)
+    input_format: int = IN_OTHER   # MIME[input_format] is the MIME of a result that keeps its format
+    as_is_file: bool = True        # AS_IS hands the file itself back; a JPEG gives None, as process_image does
+
+
+_JPEG = _FileFormat("jpeg", flgpu_jpeg_info, (), IMG_JPEG_SOURCE, "flgpu_decode_jpeg", "flgpu_process_jpeg", IN_JPEG, as_is_file=False)
+_PNG = _FileFormat("png", flgpu_png_info, (), IMG_PNG_SOURCE, "flgpu_decode_png", "flgpu_process_png", IN_PNG)
+_WEBP = _FileFormat("webp", flgpu_webp_info, (), IMG_WEBP_SOURCE, "flgpu_decode_webp", "flgpu_process_webp", IN_WEBP)
+_VP8 = _FileFormat("vp8", flgpu_vp8_info, ("reserved",), IMG_VP8_SOURCE, "flgpu_decode_webp_lossy", "flgpu_process_webp", IN_WEBP)
+_GIF = _FileFormat("gif", flgpu_gif_info, ("reserved",), input_format=IN_GIF_FRAME)   # (no source of a batch: State.process_gif has a body of its own)
+
+
+def _file_call(entry: str, head: tuple, data: bytes, src_flags: int, *args) -> int:
+    """flgpu_<entry>(*head, data, len(data), *args), or -- where the source carries more than its format's flag (IMG_PNG_ADAM7) -- the
+    entry point's ``_flags`` twin with ``src_flags`` behind the length."""
+    lib = load_library()
+    if src_flags:
+        return getattr(lib, entry + "_flags")(*head, data, len(data), src_flags, *args)
+    return getattr(lib, entry)(*head, data, len(data), *args)
+
+
+def _file_info(fmt: _FileFormat, data: bytes, src_flags: int = 0) -> dict:
+    info = fmt.info()
+    _check(_file_call(f"flgpu_{fmt.name}_info_of", (), data, src_flags, C.byref(info)))
+    return {n: getattr(info, n) for n, _ in fmt.info._fields_ if n not in fmt.hidden}
+
+
+def _sized_call(entry: str, data: bytes, src_flags: int = 0) -> bytes:
+    """A host half alone: asked for the size first (for a GIF a bound), then for the bytes."""
+    used = C.c_uint64()
+    _check(_file_call(entry, (), data, src_flags, None, 0, C.byref(used)))
+    out = np.zeros(max(used.value, 1), np.uint8)
+    _check(_file_call(entry, (), data, src_flags, out.ctypes.data, out.nbytes, C.byref(used)))
+    return out[: used.value].tobytes()
+
+
+def jpeg_info(data: bytes) -> dict:
+    """flgpu_jpeg_info_of: header fields of a JPEG file (pure host function); raises FanlinError(ERR_PARSE) if it is none."""
+    return _file_info(_JPEG, data)
+
+
+def png_info(data: bytes, adam7: bool = False) -> dict:
+    """flgpu_png_info_of: header fields of a PNG file (pure host function); raises FanlinError(ERR_PARSE) if the container is damaged.
+    ``adam7``: flgpu_png_info_of_flags with IMG_PNG_ADAM7 -- an Adam7-interlaced file of up to 8 bits per sample is supported too."""
+    return _file_info(_PNG, data, IMG_PNG_ADAM7 if adam7 else 0)
+
+
+def debug_png_scanlines(data: bytes, adam7: bool = False) -> bytes:
+    """Host half of the PNG decode front end alone: the inflated IDAT stream (filtered scanlines), Adler-32 and filter bytes checked.
+    ``adam7``: flgpu_debug_png_scanlines_flags with IMG_PNG_ADAM7 -- for an interlaced file the seven passes' scanlines back to back."""
+    return _sized_call("flgpu_debug_png_scanlines", data, IMG_PNG_ADAM7 if adam7 else 0)
+
+
+def webp_info(data: bytes) -> dict:
+    """flgpu_webp_info_of: container, VP8L header, transforms and code groups of a WebP file (pure host function); raises
+    FanlinError(ERR_PARSE) if the container or the headers are damaged."""
+    return _file_info(_WEBP, data)
+
+
+def debug_webp_residuals(data: bytes) -> bytes:
+    """Host half of the lossless WebP decode front end alone: the blob that is uploaded (header, sub-images, residual picture)."""
+    return _sized_call("flgpu_debug_webp_residuals", data)
+
+
+def vp8_info(data: bytes) -> dict:
+    """flgpu_vp8_info_of: container, frame header and -- for a supported file -- what the partitions of a lossy WebP file use (pure
+    host function); raises FanlinError(ERR_PARSE) if the file is damaged or is no lossy WebP."""
+    return _file_info(_VP8, data)
+
+
+def debug_vp8_blob(data: bytes) -> bytes:
+    """Host half of the lossy WebP decode front end alone: the blob that is uploaded (header, macroblock records, levels, ALPH plane)."""
+    return _sized_call("flgpu_debug_vp8_blob", data)
+
+
 def gif_info(data: bytes) -> dict:
     """flgpu_gif_info_of: canvas, frames and what the frames use, from the container and the LZW stage of a GIF file (pure host
     function); raises FanlinError(ERR_PARSE) if the file is damaged."""
-    info = flgpu_gif_info()
-    _check(load_library().flgpu_gif_info_of(data, len(data), C.byref(info)))
-    return {n: getattr(info, n) for n, _ in flgpu_gif_info._fields_ if n != "reserved"}
+    return _file_info(_GIF, data)
 
 
 def debug_gif_blob(data: bytes) -> bytes:
     """Host half of the GIF decode front end alone: the blob that is uploaded (header, frame records, index bytes, palettes)."""
-    lib = load_library()
-    used = C.c_uint64()
-    _check(lib.flgpu_debug_gif_blob(data, len(data), None, 0, C.byref(used)))
-    out = np.zeros(max(used.value, 1), np.uint8)
-    _check(lib.flgpu_debug_gif_blob(data, len(data), out.ctypes.data, out.nbytes, C.byref(used)))
-    return out[: used.value].tobytes()
+    return _sized_call("flgpu_debug_gif_blob", data)
 
 
 def _source_info(data):
-    """(header dict, source flag) of a file handed over as a source: PNG and WebP by their signatures, else JPEG."""
+    """(header dict, source flags) of a file handed over as a source: LossyWebp and Adam7Png say what they are, PNG and WebP go by their
+    signatures, anything else is a JPEG."""
+    more = IMG_PNG_ADAM7 if isinstance(data, Adam7Png) else 0
     if isinstance(data, LossyWebp):
-        return vp8_info(bytes(data)), IMG_VP8_SOURCE
-    if isinstance(data, Adam7Png):
-        return png_info(bytes(data), adam7=True), IMG_PNG_SOURCE | IMG_PNG_ADAM7
-    if bytes(data[:8]) == PNG_SIGNATURE:
-        return png_info(bytes(data)), IMG_PNG_SOURCE
-    if bytes(data[:4]) == b"RIFF" and bytes(data[8:12]) == b"WEBP":
-        return webp_info(bytes(data)), IMG_WEBP_SOURCE
-    return jpeg_info(bytes(data)), IMG_JPEG_SOURCE
+        fmt = _VP8
+    elif more or bytes(data[:8]) == PNG_SIGNATURE:
+        fmt = _PNG
+    else:
+        fmt = _WEBP if bytes(data[:4]) == b"RIFF" and bytes(data[8:12]) == b"WEBP" else _JPEG
+    return _file_info(fmt, bytes(data), more), fmt.flag | more
 
 
 def debug_jpeg_blob(data: bytes):
@@ -808,6 +813,16 @@ class State:
         _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
         return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
 
+    def _finish(self, plan: flgpu_plan, kind, input_format: int, run):
+        """The tail of every process_* call that is no AS_IS: the buffer at the plan's worst case, ``run(dst, plan, kind, out_format)`` (the
+        ABI call, all four by reference), then (mime, kind, payload)."""
+        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
+        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
+        fmt = C.c_int()
+        _check(run(C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
+        mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else MIME.get(input_format, "application/octet-stream")
+        return mime, kind.value, _split_output(out, plan, _RESULT_FE[kind.value], dst.flags, dst.bytes)
+
     def process_image(self, decoded: np.ndarray, query_string: str, content: "Format" = None, input_format: int = IN_JPEG,
                       orientation: int = 1):
         """State::process_image after the decoder (reference src/handler.rs:198-308): returns (mime, kind, payload) where
@@ -818,160 +833,97 @@ class State:
         too, the file of the variant they select)."""
         img = _as_image_array(decoded)
         src = flgpu_image(img.ctypes.data, img.nbytes, img.shape[1], img.shape[0], img.shape[2], 0)
-        plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
+        plan, kind = flgpu_plan(), C.c_int()
         flags = content.flags if content else 0
         qs = query_string.encode()
         _check(self._lib.flgpu_process_image_plan(C.byref(src), orientation, qs, flags, input_format, C.byref(plan), C.byref(kind)))
         if kind.value == RESULT_AS_IS:
             return MIME.get(input_format, "application/octet-stream"), RESULT_AS_IS, None
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_process_image(self._ctx, C.byref(src), orientation, qs, flags, input_format, C.byref(dst), C.byref(plan),
-                                             C.byref(kind), C.byref(fmt)), self._ctx)
-        mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else MIME.get(input_format, "application/octet-stream")
-        fe = _RESULT_FE[kind.value]
-        return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+        return self._finish(plan, kind, input_format, lambda *out: self._lib.flgpu_process_image(self._ctx, C.byref(src), orientation, qs, flags, input_format, *out))
 
-    # -- JPEG sources: the decode front end (handler.rs:205-220) --------------------------------------------------
-    def decode_jpeg(self, data: bytes) -> np.ndarray:
-        """DynamicImage::from_decoder(JpegDecoder::new(..)) on the device: (h, w, 1 or 3) uint8."""
-        info = jpeg_info(data)
+    # -- file requests: one path for JPEG, PNG and both WebP kinds (the rows of _FileFormat); the public methods say what each is ----------
+    def _process_file(self, fmt: _FileFormat, data: bytes, query_string: str, content: "Format"):
+        plan, kind = flgpu_plan(), C.c_int()
+        flags = content.flags if content else 0
+        qs = query_string.encode()
+        _check(getattr(self._lib, fmt.process + "_plan")(data, len(data), qs, flags, C.byref(plan), C.byref(kind)))
+        if kind.value == RESULT_AS_IS:
+            return MIME[fmt.input_format], RESULT_AS_IS, data if fmt.as_is_file else None
+        return self._finish(plan, kind, fmt.input_format, lambda *out: getattr(self._lib, fmt.process)(self._ctx, data, len(data), qs, flags, *out))
+
+    def _decode_file(self, fmt: _FileFormat, data: bytes, src_flags: int = 0) -> np.ndarray:
+        info = _file_info(fmt, data, src_flags)
         out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_decode_jpeg(self._ctx, data, len(data), C.byref(dst)), self._ctx)
+        _check(_file_call(fmt.decode, (self._ctx,), data, src_flags, C.byref(dst)), self._ctx)
         return out
 
-    def process_jpeg_pixels(self, data: bytes, params: flgpu_params):
-        """process_pixels with a JPEG FILE as the source (FLGPU_IMG_JPEG_SOURCE): decode + pipeline in one device pass."""
-        info = jpeg_info(data)
-        plan = plan_output(params, info["width"], info["height"], max(info["channels"], 1))
+    def _process_file_pixels(self, fmt: _FileFormat, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None, src_flags: int = 0):
+        if shape is None:
+            info = _file_info(fmt, data, src_flags)
+            shape = (info["height"], info["width"], max(info["channels"], 1))
+        plan = plan_output(params, shape[1], shape[0], shape[2])
         out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
         buf = C.create_string_buffer(data, len(data))
-        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), info["width"], info["height"], max(info["channels"], 1), IMG_JPEG_SOURCE)
+        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], fmt.flag | src_flags)
         dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
         _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
         return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
 
+    # -- JPEG sources: the decode front end (handler.rs:205-220) --------------------------------------------------
+    def decode_jpeg(self, data: bytes) -> np.ndarray:
+        """DynamicImage::from_decoder(JpegDecoder::new(..)) on the device: (h, w, 1 or 3) uint8."""
+        return self._decode_file(_JPEG, data)
+
+    def process_jpeg_pixels(self, data: bytes, params: flgpu_params):
+        """process_pixels with a JPEG FILE as the source (FLGPU_IMG_JPEG_SOURCE): decode + pipeline in one device pass."""
+        return self._process_file_pixels(_JPEG, data, params)
+
     def process_jpeg(self, data: bytes, query_string: str, content: "Format" = None):
         """State::process_image for a JPEG input from the file bytes on: (mime, kind, payload) as process_image."""
-        plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
-        flags = content.flags if content else 0
-        qs = query_string.encode()
-        _check(self._lib.flgpu_process_jpeg_plan(data, len(data), qs, flags, C.byref(plan), C.byref(kind)))
-        if kind.value == RESULT_AS_IS:
-            return "image/jpeg", RESULT_AS_IS, None
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_process_jpeg(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
-        mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else "image/jpeg"
-        fe = _RESULT_FE[kind.value]
-        return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+        return self._process_file(_JPEG, data, query_string, content)
 
     # -- PNG sources: the decode front end (handler.rs:218-220) ----------------------------------------------------
     def decode_png(self, data: bytes, adam7: bool = False) -> np.ndarray:
         """DynamicImage::from_decoder(PngDecoder::new(..)) on the device: (h, w, 1..4) uint8.  ``adam7``: flgpu_decode_png_flags with
         IMG_PNG_ADAM7 -- Adam7-interlaced files are decoded too."""
-        info = png_info(data, adam7)
-        out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        if adam7:
-            _check(self._lib.flgpu_decode_png_flags(self._ctx, data, len(data), IMG_PNG_ADAM7, C.byref(dst)), self._ctx)
-        else:
-            _check(self._lib.flgpu_decode_png(self._ctx, data, len(data), C.byref(dst)), self._ctx)
-        return out
+        return self._decode_file(_PNG, data, IMG_PNG_ADAM7 if adam7 else 0)
 
     def process_png_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None, adam7: bool = False):
         """process_pixels with a PNG FILE as the source (FLGPU_IMG_PNG_SOURCE): inflate on this thread, the rest in one device pass.
         ``shape`` = (height, width, channels) to announce instead of what flgpu_png_info_of says (tests of rejected inputs).
         ``adam7``: the source carries FLGPU_IMG_PNG_ADAM7 as well -- it may be an Adam7-interlaced file."""
-        if shape is None:
-            info = png_info(data, adam7)
-            shape = (info["height"], info["width"], max(info["channels"], 1))
-        plan = plan_output(params, shape[1], shape[0], shape[2])
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        buf = C.create_string_buffer(data, len(data))
-        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_PNG_SOURCE | (IMG_PNG_ADAM7 if adam7 else 0))
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
-        return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
+        return self._process_file_pixels(_PNG, data, params, shape, IMG_PNG_ADAM7 if adam7 else 0)
 
     def process_png(self, data: bytes, query_string: str, content: "Format" = None):
         """State::process_image for a PNG input from the file bytes on: (mime, kind, payload) as process_image; AS_IS hands the
         file itself back.  With DECODE_PNG_ADAM7 in the content flags Adam7-interlaced files are taken too."""
-        plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
-        flags = content.flags if content else 0
-        qs = query_string.encode()
-        _check(self._lib.flgpu_process_png_plan(data, len(data), qs, flags, C.byref(plan), C.byref(kind)))
-        if kind.value == RESULT_AS_IS:
-            return "image/png", RESULT_AS_IS, data
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_process_png(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
-        mime = "image/webp" if fmt.value == OUT_WEBP else "image/avif" if fmt.value == OUT_AVIF else "image/png"
-        fe = _RESULT_FE[kind.value]
-        return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+        return self._process_file(_PNG, data, query_string, content)
 
     # -- lossless WebP sources: the decode front end (handler.rs:205-220) ------------------------------------------
     def decode_webp(self, data: bytes) -> np.ndarray:
         """DynamicImage::from_decoder(WebPDecoder::new(..)) on the device: (h, w, 3 or 4) uint8; the EXIF orientation is not applied."""
-        info = webp_info(data)
-        out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_decode_webp(self._ctx, data, len(data), C.byref(dst)), self._ctx)
-        return out
+        return self._decode_file(_WEBP, data)
 
     def process_webp_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None):
         """process_pixels with a lossless WebP FILE as the source (FLGPU_IMG_WEBP_SOURCE): entropy decode on this thread, the rest in
         one device pass.  ``shape`` = (height, width, channels) to announce instead of what flgpu_webp_info_of says."""
-        if shape is None:
-            info = webp_info(data)
-            shape = (info["height"], info["width"], max(info["channels"], 1))
-        plan = plan_output(params, shape[1], shape[0], shape[2])
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        buf = C.create_string_buffer(data, len(data))
-        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_WEBP_SOURCE)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
-        return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
+        return self._process_file_pixels(_WEBP, data, params, shape)
 
     def process_webp(self, data: bytes, query_string: str, content: "Format" = None):
         """State::process_image for a WebP input from the file bytes on: (mime, kind, payload) as process_image; AS_IS hands the
         file itself back."""
-        plan, kind, fmt = flgpu_plan(), C.c_int(), C.c_int()
-        flags = content.flags if content else 0
-        qs = query_string.encode()
-        _check(self._lib.flgpu_process_webp_plan(data, len(data), qs, flags, C.byref(plan), C.byref(kind)))
-        if kind.value == RESULT_AS_IS:
-            return "image/webp", RESULT_AS_IS, data
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_process_webp(self._ctx, data, len(data), qs, flags, C.byref(dst), C.byref(plan), C.byref(kind), C.byref(fmt)), self._ctx)
-        mime = "image/avif" if fmt.value == OUT_AVIF else "image/webp"
-        fe = _RESULT_FE[kind.value]
-        return mime, kind.value, _split_output(out, plan, fe, dst.flags, dst.bytes)
+        return self._process_file(_WEBP, data, query_string, content)
 
     # -- lossy WebP sources: the decode front end (handler.rs:205-220) -----------------------------------------------
     def decode_webp_lossy(self, data: bytes) -> np.ndarray:
         """flgpu_decode_webp_lossy: (h, w, 3 or 4) uint8, libwebp's WebPDecodeRGB / WebPDecodeRGBA; the EXIF orientation is not applied."""
-        info = vp8_info(data)
-        out = np.empty((info["height"], info["width"], max(info["channels"], 1)), np.uint8)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_decode_webp_lossy(self._ctx, data, len(data), C.byref(dst)), self._ctx)
-        return out
+        return self._decode_file(_VP8, data)
 
     def process_vp8_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None):
         """process_pixels with a lossy WebP FILE as the source (FLGPU_IMG_VP8_SOURCE): boolean decoding on this thread, the rest in
         one device pass.  ``shape`` = (height, width, channels) to announce instead of what flgpu_vp8_info_of says."""
-        if shape is None:
-            info = vp8_info(data)
-            shape = (info["height"], info["width"], max(info["channels"], 1))
-        plan = plan_output(params, shape[1], shape[0], shape[2])
-        out = np.empty(max(int(plan.max_out_bytes), 1), dtype=np.uint8)
-        buf = C.create_string_buffer(data, len(data))
-        src = flgpu_image(C.cast(buf, C.c_void_p).value, len(data), shape[1], shape[0], shape[2], IMG_VP8_SOURCE)
-        dst = flgpu_image(out.ctypes.data, out.nbytes, 0, 0, 0, 0)
-        _check(self._lib.flgpu_transform(self._ctx, C.byref(src), C.byref(params), C.byref(dst)), self._ctx)
-        return _split_output(out, plan, params.front_end, dst.flags, dst.bytes)
+        return self._process_file_pixels(_VP8, data, params, shape)
 
     def debug_vp8_planes(self, data: bytes, filtered: bool = True):
         """flgpu_debug_vp8_planes: the device's (y, u, v) of a lossy WebP file, cut to the picture, before or behind the loop filter."""

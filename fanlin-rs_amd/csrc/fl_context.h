@@ -2,7 +2,8 @@
 //   fl_context.cpp   context lifetime, table arena + caches, stats, table export / import
 //   fl_batch.cpp     batch planner + launcher (device batches, host batches): geometry, resample and blur
 //   fl_encode.cpp    the front ends of a batch: planes and encoded streams (fl_encode.h)
-//   fl_source.cpp    JPEG / PNG / WebP files as sources of a batch; fl_gifrun.cpp  a GIF file as a batch of its own (both: fl_source.h)
+//   fl_source.cpp    JPEG / PNG / WebP files as sources of a batch; fl_gifrun.cpp  a GIF file as a batch of its own; fl_request.cpp  a file
+//                    as a request (all three: fl_source.h)
 //   fl_queue.cpp     persistent request-batching queue, lanes, sharding of flushed batches across the devices of a node
 //   fl_cmyk_ctx.cpp  CMYK device-link tables and their distribution to the devices (RCCL broadcast)
 //

@@ -9,12 +9,8 @@
 
 #include <algorithm>
 #include <string>
-#include <memory>
 #include <vector>
 
-#include "fl_pngsrc.h"
-#include "fl_webpsrc.h"
-#include "fl_gifsrc.h"
 #include "fl_vp8_core.h"
 #include "fl_context.h" // (the runtime's other headers come with it)
 
@@ -222,9 +218,11 @@ try {
     return FLGPU_OK;
 } FL_ABI_CATCH
 
+} // extern "C"
+
 /* Everything State::process_image decides before it touches pixels (handler.rs:198-261). */
-static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags,
-                        int input_format, flgpu_params *p, flgpu_plan *plan, int *result_kind, int *out_format)
+int fl::plan_request(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags,
+                     int input_format, flgpu_params *p, flgpu_plan *plan, int *result_kind, int *out_format)
 {
     if (!decoded || !query_string || !plan || !result_kind) return FLGPU_ERR_INVALID_ARG;
     if (input_format < FLGPU_IN_OTHER || input_format > FLGPU_IN_GIF_FRAME || exif_orientation > 8) return FLGPU_ERR_INVALID_ARG;
@@ -288,29 +286,16 @@ static int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, co
 }
 
 /* The shared end of flgpu_process_{image,jpeg,png,webp}: rc and kind are the planner's verdict; as_is never reaches the device. */
-static int run_planned(flgpu_ctx *ctx, int rc, int kind, int *result_kind, const flgpu_image *src, const flgpu_params *p, flgpu_image *dst)
+int fl::run_planned(flgpu_ctx *ctx, int rc, int kind, int *result_kind, const flgpu_image *src, const flgpu_params *p, flgpu_image *dst)
 {
     if (result_kind) *result_kind = kind;
     if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
     return flgpu_transform(ctx, src, p, dst);
 }
 
-/* flgpu_decode_{jpeg,png,webp}: the file as a source of the identity request -- no dimensions, no operation (and no orientation applied):
-   the result is the decoded picture */
-static int decode_file(flgpu_ctx *ctx, const uint8_t *file, uint64_t n, uint32_t w, uint32_t h, uint32_t channels, uint32_t source_flag, flgpu_image *dst)
-{
-    flgpu_image src;
-    memset(&src, 0, sizeof(src));
-    src.data = const_cast<uint8_t *>(file); src.capacity = n;
-    src.width = w; src.height = h; src.channels = channels; src.flags = source_flag;
-    flgpu_params p;
-    memset(&p, 0, sizeof(p));
-    return flgpu_transform(ctx, &src, &p, dst);
-}
-
-/* A file the device decoder does not take (plan_png, plan_webp): only as_is, which never decodes, gets through.  Geometry the planner
-   cannot take (2^31 bytes and more) must not hide the query's own verdict: parse it first */
-static int plan_undecodable(const char *query_string, flgpu_plan *plan, int *kind, int *out_format)
+/* A file the device decoder does not take (fl_request.cpp plan_file, plan_gif): only as_is, which never decodes, gets through.  Geometry the
+   planner cannot take (2^31 bytes and more) must not hide the query's own verdict: parse it first */
+int fl::plan_undecodable(const char *query_string, flgpu_plan *plan, int *kind, int *out_format)
 {
     flgpu_query q;
     const int rc = flgpu_query_parse(query_string ? query_string : "", &q);
@@ -324,11 +309,13 @@ static int plan_undecodable(const char *query_string, flgpu_plan *plan, int *kin
     return FLGPU_OK;
 }
 
+extern "C" {
+
 int flgpu_process_image_plan(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags,
                              int input_format, flgpu_plan *plan, int *result_kind)
 try {
     flgpu_params p;
-    return plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan, result_kind, nullptr);
+    return fl::plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan, result_kind, nullptr);
 } FL_ABI_CATCH
 
 int flgpu_process_image(flgpu_ctx *ctx, const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string,
@@ -338,469 +325,8 @@ try {
     flgpu_params p;
     flgpu_plan local;
     int kind = 0;
-    const int rc = plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan ? plan : &local, &kind, out_format);
-    return run_planned(ctx, rc, kind, result_kind, decoded, &p, dst);
-} FL_ABI_CATCH
-
-int flgpu_jpeg_info_of(const uint8_t *jpeg, uint64_t n, flgpu_jpeg_info *info)
-try {
-    if (!jpeg || !info) return FLGPU_ERR_INVALID_ARG;
-    fl::JpegInfo I;
-    if (fl::jpeg_parse_info(jpeg, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
-    memset(info, 0, sizeof(*info));
-    info->width = I.width; info->height = I.height; info->components = I.components;
-    info->channels = I.supported ? (I.components == 1 ? 1u : 3u) : 0u;
-    info->adobe_transform = (uint32_t)(I.adobe_transform + 1);
-    info->has_icc_profile = I.icc.empty() ? 0u : 1u;
-    info->progressive = I.progressive; info->restart_interval = I.restart_interval;
-    info->h_max = I.hmax; info->v_max = I.vmax;
-    info->exif_orientation = I.exif_orientation; info->supported = I.supported;
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-static int plan_jpeg(const uint8_t *jpeg, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, uint8_t *orientation,
-                     flgpu_params *p, flgpu_plan *plan, int *kind, int *out_format)
-{
-    flgpu_jpeg_info info;
-    int rc = flgpu_jpeg_info_of(jpeg, n, &info);
-    if (rc) return rc;
-    memset(src, 0, sizeof(*src));
-    src->data = const_cast<uint8_t *>(jpeg);
-    src->capacity = n;
-    src->width = info.width; src->height = info.height; src->channels = info.components == 1 ? 1u : 3u;
-    src->flags = FLGPU_IMG_JPEG_SOURCE;
-    *orientation = (uint8_t)(info.exif_orientation ? info.exif_orientation : 1u);
-    rc = plan_request(src, *orientation, query_string, accept_flags, FLGPU_IN_JPEG, p, plan, kind, out_format);
-    if (rc) return rc;
-    if (*kind != FLGPU_RESULT_AS_IS && !info.supported) return FLGPU_ERR_UNSUPPORTED; /* as_is never decodes (handler.rs:202-204) */
-    return FLGPU_OK;
-}
-
-int flgpu_process_jpeg_plan(const uint8_t *jpeg, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, int *result_kind)
-try {
-    flgpu_image src;
-    flgpu_params p;
-    uint8_t o = 1;
-    return plan_jpeg(jpeg, n, query_string, accept_flags, &src, &o, &p, plan, result_kind, nullptr);
-} FL_ABI_CATCH
-
-int flgpu_process_jpeg(flgpu_ctx *ctx, const uint8_t *jpeg, uint64_t n, const char *query_string, uint32_t accept_flags,
-                       flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format)
-try {
-    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
-    flgpu_image src;
-    flgpu_params p;
-    flgpu_plan local;
-    uint8_t o = 1;
-    int kind = 0;
-    const int rc = plan_jpeg(jpeg, n, query_string, accept_flags, &src, &o, &p, plan ? plan : &local, &kind, out_format);
-    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
-} FL_ABI_CATCH
-
-int flgpu_debug_jpeg_blob(const uint8_t *jpeg, uint64_t n, uint8_t *blob, uint64_t capacity, uint64_t *used)
-try {
-    if (!jpeg || !used) return FLGPU_ERR_INVALID_ARG;
-    fl::JpegInfo I;
-    if (fl::jpeg_parse_info(jpeg, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
-    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
-    *used = fl::jpeg_blob_bound(I);
-    if (!blob) return FLGPU_OK;
-    if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    size_t u = 0;
-    const int rc = fl::jpeg_entropy_decode(jpeg, (size_t)n, blob, (size_t)capacity, &u);
-    *used = u;
-    return rc == 0 ? FLGPU_OK : rc == -2 ? FLGPU_ERR_UNSUPPORTED : FLGPU_ERR_INVALID_ARG;
-} FL_ABI_CATCH
-
-int flgpu_decode_jpeg(flgpu_ctx *ctx, const uint8_t *jpeg, uint64_t n, flgpu_image *dst)
-try {
-    if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
-    flgpu_jpeg_info info;
-    int rc = flgpu_jpeg_info_of(jpeg, n, &info);
-    if (rc) return rc;
-    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    return decode_file(ctx, jpeg, n, info.width, info.height, info.channels, FLGPU_IMG_JPEG_SOURCE, dst);
-} FL_ABI_CATCH
-
-/* ---- PNG sources ---------------------------------------------------------------------------------------------------- */
-
-int flgpu_png_info_of_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_png_info *info)
-try {
-    if (!png || !info) return FLGPU_ERR_INVALID_ARG;
-    fl::PngInfo I;
-    if (fl::png_parse_info(png, (size_t)n, I, true, (src_flags & FLGPU_IMG_PNG_ADAM7) != 0) != 0) return FLGPU_ERR_PARSE;
-    memset(info, 0, sizeof(*info));
-    info->width = I.width; info->height = I.height; info->color_type = I.color_type; info->bit_depth = I.bit_depth;
-    info->channels = I.channels; info->interlaced = I.interlaced; info->has_trns = I.has_trns; info->supported = I.supported;
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-int flgpu_png_info_of(const uint8_t *png, uint64_t n, flgpu_png_info *info) { return flgpu_png_info_of_flags(png, n, 0, info); }
-
-static int plan_png(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
-                    flgpu_plan *plan, int *kind, int *out_format)
-{
-    // (layout only here: flgpu_transform verifies the CRCs once, under the decode bound; as_is serves the file unread, as the reference does)
-    if (!png) return FLGPU_ERR_INVALID_ARG;
-    const bool adam7 = (accept_flags & FLGPU_DECODE_PNG_ADAM7) != 0;
-    fl::PngInfo info;
-    if (fl::png_parse_info(png, (size_t)n, info, false, adam7) != 0) return FLGPU_ERR_PARSE;
-    memset(src, 0, sizeof(*src));
-    src->data = const_cast<uint8_t *>(png);
-    src->capacity = n;
-    /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
-    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
-    src->flags = FLGPU_IMG_PNG_SOURCE | (adam7 ? FLGPU_IMG_PNG_ADAM7 : 0u);
-    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
-    /* the PNG decoder reports no orientation (handler.rs:206 sees none): 1 */
-    return plan_request(src, 1, query_string, accept_flags, FLGPU_IN_PNG, p, plan, kind, out_format);
-}
-
-int flgpu_process_png_plan(const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, int *result_kind)
-try {
-    flgpu_image src;
-    flgpu_params p;
-    return plan_png(png, n, query_string, accept_flags, &src, &p, plan, result_kind, nullptr);
-} FL_ABI_CATCH
-
-int flgpu_process_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, const char *query_string, uint32_t accept_flags,
-                      flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format)
-try {
-    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
-    flgpu_image src;
-    flgpu_params p;
-    flgpu_plan local;
-    int kind = 0;
-    const int rc = plan_png(png, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
-    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
-} FL_ABI_CATCH
-
-int flgpu_decode_png_flags(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, uint32_t src_flags, flgpu_image *dst)
-try {
-    if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
-    if (!png) return FLGPU_ERR_INVALID_ARG;
-    const uint32_t adam7 = src_flags & FLGPU_IMG_PNG_ADAM7;
-    fl::PngInfo info;
-    if (fl::png_parse_info(png, (size_t)n, info, false, adam7 != 0) != 0) return FLGPU_ERR_PARSE; // (CRCs: once, in flgpu_transform)
-    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    return decode_file(ctx, png, n, info.width, info.height, info.channels, FLGPU_IMG_PNG_SOURCE | adam7, dst);
-} FL_ABI_CATCH
-
-int flgpu_decode_png(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, flgpu_image *dst) { return flgpu_decode_png_flags(ctx, png, n, 0, dst); }
-
-int flgpu_debug_png_scanlines_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used)
-try {
-    if (!png || !used) return FLGPU_ERR_INVALID_ARG;
-    const bool adam7 = (src_flags & FLGPU_IMG_PNG_ADAM7) != 0;
-    fl::PngInfo I;
-    if (fl::png_parse_info(png, (size_t)n, I, true, adam7) != 0) return FLGPU_ERR_PARSE;
-    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
-    *used = fl::png_scan_bytes(I);
-    if (!out) return FLGPU_OK;
-    if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    const int rc = fl::png_decode_scanlines(png, (size_t)n, out, (size_t)capacity, nullptr, adam7);
-    return fl::png_status(rc);
-} FL_ABI_CATCH
-
-int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
-{
-    return flgpu_debug_png_scanlines_flags(png, n, 0, out, capacity, used);
-}
-
-/* ---- lossless WebP sources -------------------------------------------------------------------------------------------- */
-
-// the orientation ImageDecoder::orientation() reports for a WebP: from the EXIF chunk, whose payload usually starts at the TIFF
-// header, without the "Exif\0\0" a JPEG APP1 segment has; both forms are taken.  0 = no tag.
-static uint32_t webp_orientation(const uint8_t *file, const fl::WebpInfo &I)
-{
-    if (!I.exif_len) return 0;
-    const uint8_t *p = file + I.exif_off;
-    size_t n = I.exif_len;
-    if (n >= 6 && !memcmp(p, "Exif\0\0", 6)) { p += 6; n -= 6; }
-    return (uint32_t)fl::tiff_orientation(p, n);
-}
-
-int flgpu_webp_info_of(const uint8_t *webp, uint64_t n, flgpu_webp_info *info)
-try {
-    if (!webp || !info) return FLGPU_ERR_INVALID_ARG;
-    fl::WebpInfo I;
-    if (fl::webp_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE;
-    memset(info, 0, sizeof(*info));
-    info->width = I.width; info->height = I.height; info->channels = I.channels; info->has_alpha = I.has_alpha;
-    info->extended = I.extended; info->animated = I.animated; info->lossless = I.lossless;
-    info->exif_orientation = webp_orientation(webp, I);
-    info->transforms = I.transforms; info->color_cache_bits = I.color_cache_bits; info->prefix_groups = I.prefix_groups;
-    info->supported = I.supported;
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-// EXIF orientation of a lossy file: the same chunk, the same two forms
-static uint32_t vp8_orientation(const uint8_t *file, const fl::Vp8Info &I)
-{
-    fl::WebpInfo W;
-    W.exif_off = I.exif_off; W.exif_len = I.exif_len;
-    return webp_orientation(file, W);
-}
-
-// the picture of a WebP file is a `VP8 ` chunk (the first chunk, or the first image chunk behind VP8X)
-static bool webp_is_lossy(const uint8_t *d, uint64_t n)
-{
-    if (!d || n < 20 || memcmp(d, "RIFF", 4) || memcmp(d + 8, "WEBP", 4)) return false;
-    for (uint64_t pos = 12; n - pos >= 8;) {
-        if (!memcmp(d + pos, "VP8 ", 4)) return true;
-        if (!memcmp(d + pos, "VP8L", 4) || !memcmp(d + pos, "ANMF", 4)) return false;
-        const uint64_t len = (uint64_t)d[pos + 4] | (uint64_t)d[pos + 5] << 8 | (uint64_t)d[pos + 6] << 16 | (uint64_t)d[pos + 7] << 24;
-        if (len > n - pos - 8) return false;
-        pos += 8u + len + (len & 1u);
-        if (pos > n) return false;
-    }
-    return false;
-}
-
-int flgpu_vp8_info_of(const uint8_t *webp, uint64_t n, flgpu_vp8_info *info)
-try {
-    if (!webp || !info) return FLGPU_ERR_INVALID_ARG;
-    fl::Vp8Info I;
-    if (fl::vp8_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE;
-    memset(info, 0, sizeof(*info));
-    info->width = I.width; info->height = I.height; info->channels = I.channels; info->has_alpha = I.has_alpha;
-    info->extended = I.extended; info->animated = I.animated; info->exif_orientation = vp8_orientation(webp, I);
-    info->supported = I.supported; info->version = I.version; info->segmentation = I.segmentation; info->update_map = I.update_map;
-    info->filter_type = I.filter_simple; info->filter_level = I.filter_level; info->sharpness = I.sharpness; info->partitions = I.partitions;
-    info->alpha_compression = I.alpha_compression; info->alpha_filter = I.alpha_filter;
-    info->segment_quantizers = I.segment_quantizers; info->segment_filter_levels = I.segment_filter_levels;
-    info->coef_prob_updates = I.coef_prob_updates;
-    info->macroblocks = I.macroblocks; info->bpred_macroblocks = I.bpred_macroblocks; info->skipped_macroblocks = I.skipped_macroblocks;
-    info->skipped_bpred_macroblocks = I.skipped_bpred_macroblocks;
-    info->bmodes_mask = I.bmodes_mask; info->ymodes_mask = I.ymodes_mask; info->uvmodes_mask = I.uvmodes_mask;
-    info->cat6_tokens = I.cat6_tokens; info->blob_bytes = I.blob_bytes;
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-static int plan_vp8(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
-                    flgpu_plan *plan, int *kind, int *out_format)
-{
-    // (container and frame header only here: flgpu_transform reads the partitions once; as_is serves the file unread)
-    fl::Vp8Info info;
-    if (fl::vp8_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    memset(src, 0, sizeof(*src));
-    src->data = const_cast<uint8_t *>(webp);
-    src->capacity = n;
-    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
-    src->flags = FLGPU_IMG_VP8_SOURCE;
-    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
-    const uint32_t o = vp8_orientation(webp, info);
-    return plan_request(src, (uint8_t)(o ? o : 1u), query_string, accept_flags, FLGPU_IN_WEBP, p, plan, kind, out_format);
-}
-
-int flgpu_decode_webp_lossy(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst)
-try {
-    if (!ctx || !dst || !dst->data || !webp) return FLGPU_ERR_INVALID_ARG;
-    fl::Vp8Info info;
-    if (fl::vp8_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    return decode_file(ctx, webp, n, info.width, info.height, info.channels, FLGPU_IMG_VP8_SOURCE, dst);
-} FL_ABI_CATCH
-
-int flgpu_debug_vp8_blob(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
-try {
-    if (!webp || !used) return FLGPU_ERR_INVALID_ARG;
-    fl::Vp8Info I;
-    if (fl::vp8_parse_info(webp, (size_t)n, I, out == nullptr) != 0) return FLGPU_ERR_PARSE; // (the blob's size follows from the tokens)
-    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
-    if (!out) { *used = I.blob_bytes; return FLGPU_OK; }
-    // decoded into a buffer of the worst-case capacity, as flgpu_transform has it in its staging
-    const size_t cap = fl::vp8_blob_capacity(I);
-    std::unique_ptr<uint8_t[]> work(new uint8_t[cap + 16u]);
-    uint8_t *blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
-    fl::Vp8BlobHeader H;
-    const int rc = fl::vp8_decode_levels(webp, (size_t)n, blob, cap, &H);
-    if (rc) return fl::vp8_status(rc);
-    *used = H.total_bytes;
-    if (capacity < H.total_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    memcpy(out, blob, H.total_bytes);
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int filter, uint8_t *out, uint64_t capacity, uint64_t *used)
-try {
-    if (!ctx || !webp || !used) return FLGPU_ERR_INVALID_ARG;
-    size_t u = 0;
-    const int rc = fl::debug_vp8_planes(ctx, webp, (size_t)n, filter, out, (size_t)capacity, &u);
-    *used = u;
-    return rc;
-} FL_ABI_CATCH
-
-static int plan_webp(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *src, flgpu_params *p,
-                     flgpu_plan *plan, int *kind, int *out_format)
-{
-    // (container and VP8L header only here: flgpu_transform reads the stream once; as_is serves the file unread, as the reference does)
-    if (!webp) return FLGPU_ERR_INVALID_ARG;
-    if (webp_is_lossy(webp, n)) return plan_vp8(webp, n, query_string, accept_flags, src, p, plan, kind, out_format);
-    fl::WebpInfo info;
-    if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    memset(src, 0, sizeof(*src));
-    src->data = const_cast<uint8_t *>(webp);
-    src->capacity = n;
-    /* (an unsupported file is planned as one channel: only as_is, which never decodes, gets past the check below) */
-    src->width = info.width; src->height = info.height; src->channels = info.supported ? info.channels : 1u;
-    src->flags = FLGPU_IMG_WEBP_SOURCE;
-    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format);
-    /* ImageDecoder::orientation() falls back to exif_metadata(), which the WebP decoder implements (handler.rs:206) */
-    const uint32_t o = webp_orientation(webp, info);
-    return plan_request(src, (uint8_t)(o ? o : 1u), query_string, accept_flags, FLGPU_IN_WEBP, p, plan, kind, out_format);
-}
-
-int flgpu_process_webp_plan(const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, int *result_kind)
-try {
-    flgpu_image src;
-    flgpu_params p;
-    return plan_webp(webp, n, query_string, accept_flags, &src, &p, plan, result_kind, nullptr);
-} FL_ABI_CATCH
-
-int flgpu_process_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, const char *query_string, uint32_t accept_flags,
-                       flgpu_image *dst, flgpu_plan *plan, int *result_kind, int *out_format)
-try {
-    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
-    flgpu_image src;
-    flgpu_params p;
-    flgpu_plan local;
-    int kind = 0;
-    const int rc = plan_webp(webp, n, query_string, accept_flags, &src, &p, plan ? plan : &local, &kind, out_format);
-    return run_planned(ctx, rc, kind, result_kind, &src, &p, dst);
-} FL_ABI_CATCH
-
-int flgpu_decode_webp(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, flgpu_image *dst)
-try {
-    if (!ctx || !dst || !dst->data) return FLGPU_ERR_INVALID_ARG;
-    if (!webp) return FLGPU_ERR_INVALID_ARG;
-    fl::WebpInfo info;
-    if (fl::webp_parse_info(webp, (size_t)n, info, false) != 0) return FLGPU_ERR_PARSE;
-    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    return decode_file(ctx, webp, n, info.width, info.height, info.channels, FLGPU_IMG_WEBP_SOURCE, dst);
-} FL_ABI_CATCH
-
-int flgpu_debug_webp_residuals(const uint8_t *webp, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
-try {
-    if (!webp || !used) return FLGPU_ERR_INVALID_ARG;
-    fl::WebpInfo I;
-    if (fl::webp_parse_info(webp, (size_t)n, I, true) != 0) return FLGPU_ERR_PARSE; // (the blob's size follows from the transform headers)
-    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
-    *used = I.blob_bytes;
-    if (!out) return FLGPU_OK;
-    if (capacity < I.blob_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    // the blob in front, the decoder's work area behind it: one buffer, as flgpu_transform has it in its staging
-    const size_t cap = fl::webp_blob_capacity(I, (size_t)n);
-    std::unique_ptr<uint8_t[]> work(new uint8_t[cap + 16u]);
-    uint8_t *blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
-    fl::WebpBlobHeader H;
-    const int rc = fl::webp_decode_residuals(webp, (size_t)n, blob, cap, &H);
-    if (rc) return fl::webp_status(rc);
-    memcpy(out, blob, H.total_bytes);
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-/* ---- GIF files -------------------------------------------------------------------------------------------------------- */
-
-// the host half into a buffer of this call's own: the blob in `work`, its header in H
-static int gif_blob(const uint8_t *gif, uint64_t n, const fl::GifInfo &I, std::unique_ptr<uint8_t[]> &work, uint8_t *&blob, fl::GifBlobHeader &H)
-{
-    const size_t cap = fl::gif_blob_capacity(I);
-    work.reset(new uint8_t[cap + 16u]);
-    blob = work.get() + ((16u - (reinterpret_cast<uintptr_t>(work.get()) & 15u)) & 15u);
-    return fl::gif_status(fl::gif_decode_blob(gif, (size_t)n, blob, cap, &H));
-}
-
-int flgpu_gif_info_of(const uint8_t *gif, uint64_t n, flgpu_gif_info *info)
-try {
-    if (!gif || !info) return FLGPU_ERR_INVALID_ARG;
-    fl::GifInfo I;
-    if (fl::gif_parse_info(gif, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
-    memset(info, 0, sizeof(*info));
-    info->width = I.width; info->height = I.height; info->frames = I.frames; info->has_global_table = I.has_global_table;
-    info->interlaced_frames = I.interlaced_frames; info->transparent_frames = I.transparent_frames;
-    info->disposal_mask = I.disposal_mask; info->max_code_size = I.max_code_size; info->decoded_bytes = I.decoded_bytes;
-    info->supported = I.supported;
-    if (I.supported) { // whether the file is supported is known only behind the LZW stage (an index beyond its colour table)
-        std::unique_ptr<uint8_t[]> work;
-        uint8_t *blob = nullptr;
-        fl::GifBlobHeader H;
-        const int rc = gif_blob(gif, n, I, work, blob, H);
-        if (rc == FLGPU_ERR_UNSUPPORTED) info->supported = 0;
-        else if (rc) return rc;
-    }
-    return FLGPU_OK;
-} FL_ABI_CATCH
-
-static int plan_gif(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_params *p, flgpu_plan *plan,
-                    uint32_t *frames, int *kind, int *out_format)
-{
-    /* (the container only: flgpu_process_gif runs the LZW stage once; as_is serves the file unread, as the reference does) */
-    if (!gif) return FLGPU_ERR_INVALID_ARG;
-    fl::GifInfo info;
-    if (fl::gif_parse_info(gif, (size_t)n, info) != 0) return FLGPU_ERR_PARSE;
-    flgpu_image canvas;
-    memset(&canvas, 0, sizeof(canvas));
-    canvas.width = info.width; canvas.height = info.height; canvas.channels = 4; /* every frame is the Rgba8 canvas (handler.rs:327-333) */
-    if (frames) *frames = info.frames;
-    if (!info.supported) return plan_undecodable(query_string, plan, kind, out_format); /* (the canvas may be beyond what a plan can describe) */
-    const int rc = plan_request(&canvas, 1, query_string, accept_flags, FLGPU_IN_GIF_FRAME, p, plan, kind, out_format);
-    /* FLGPU_ENCODE_GIF: the finished file is what will be attempted (a frame above 256 colours turns it back into pixels, unless
-       FLGPU_ENCODE_GIF_QUANTIZE has it quantised -- the plan is the same either way); the per-frame parameters stay as they are,
-       one file comes from all the frames */
-    if (rc == FLGPU_OK && *kind == FLGPU_RESULT_PIXELS && (accept_flags & FLGPU_ENCODE_GIF) &&
-        fl::gif_encodable(plan->out_w, plan->out_h, plan->out_c, info.frames, plan->out_bytes)) {
-        *kind = FLGPU_RESULT_GIF_STREAM;
-        plan->max_out_bytes = std::max<uint64_t>(plan->out_bytes, fl::gif_max_frame_bytes((uint64_t)plan->out_w * plan->out_h));
-    }
-    return rc;
-}
-
-int flgpu_process_gif_plan(const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_plan *plan, uint32_t *frames,
-                           int *result_kind)
-try {
-    flgpu_params p;
-    return plan_gif(gif, n, query_string, accept_flags, &p, plan, frames, result_kind, nullptr);
-} FL_ABI_CATCH
-
-int flgpu_process_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, const char *query_string, uint32_t accept_flags, flgpu_image *dst,
-                      flgpu_plan *plan, uint32_t *frames, int *result_kind, int *out_format)
-try {
-    if (!ctx || !dst) return FLGPU_ERR_INVALID_ARG;
-    flgpu_params p;
-    flgpu_plan local;
-    int kind = 0;
-    int rc = plan_gif(gif, n, query_string, accept_flags, &p, plan ? plan : &local, frames, &kind, out_format);
-    if (result_kind) *result_kind = kind;
-    if (rc || kind == FLGPU_RESULT_AS_IS) return rc;
-    rc = fl::run_gif_host(ctx, gif, (size_t)n, &p, accept_flags, dst, frames, &kind);
-    if (result_kind) *result_kind = kind; /* what happened: the file, or the pixels */
-    return rc;
-} FL_ABI_CATCH
-
-int flgpu_decode_gif(flgpu_ctx *ctx, const uint8_t *gif, uint64_t n, flgpu_image *dst, uint32_t *frames)
-try {
-    if (!ctx || !dst || !dst->data || !gif) return FLGPU_ERR_INVALID_ARG;
-    return fl::run_gif_host(ctx, gif, (size_t)n, nullptr, 0, dst, frames, nullptr);
-} FL_ABI_CATCH
-
-int flgpu_debug_gif_blob(const uint8_t *gif, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used)
-try {
-    if (!gif || !used) return FLGPU_ERR_INVALID_ARG;
-    fl::GifInfo I;
-    if (fl::gif_parse_info(gif, (size_t)n, I) != 0) return FLGPU_ERR_PARSE;
-    if (!I.supported) return FLGPU_ERR_UNSUPPORTED;
-    *used = fl::gif_blob_capacity(I); // (a bound: the palettes the frames share are known only behind the decode)
-    if (!out) return FLGPU_OK;
-    std::unique_ptr<uint8_t[]> work;
-    uint8_t *blob = nullptr;
-    fl::GifBlobHeader H;
-    const int rc = gif_blob(gif, n, I, work, blob, H);
-    if (rc) return rc;
-    *used = H.total_bytes;
-    if (capacity < H.total_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    memcpy(out, blob, H.total_bytes);
-    return FLGPU_OK;
+    const int rc = fl::plan_request(decoded, exif_orientation, query_string, accept_flags, input_format, &p, plan ? plan : &local, &kind, out_format);
+    return fl::run_planned(ctx, rc, kind, result_kind, decoded, &p, dst);
 } FL_ABI_CATCH
 
 int flgpu_plan_output(const flgpu_params *p, uint32_t sw, uint32_t sh, uint32_t sc, flgpu_plan *plan)

@@ -209,26 +209,97 @@ static int decode_jpeg_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
     return FLGPU_OK;
 }
 
-// ---- PNG sources -----------------------------------------------------------------------------------------------------------------
+// ---- the header of a file, whatever its format ---------------------------------------------------------------------------------------
 
-// The container walk has bounded what the file may make the library reserve (png_parse_info: below 2^31 bytes, and no more than
-// 1032 x its IDAT payload); here the file is held against what the caller announced.
-static int png_source_info(flgpu_ctx *c, const flgpu_image *src, PngInfo &info)
+// the picture of a WebP file is a `VP8 ` chunk (the first chunk, or the first image chunk behind VP8X)
+static bool webp_is_lossy(const uint8_t *d, uint64_t n)
 {
-    // (layout only: png_source_to_blob verifies the CRCs, so the file is summed once per request)
-    const bool adam7 = (src->flags & FLGPU_IMG_PNG_ADAM7) != 0;
-    if (png_parse_info(src->data, (size_t)src->capacity, info, false, adam7) != 0) { c->set_error("malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) {
-        c->set_error(adam7 ? "PNG file not covered by the device decoder (16-bit samples, or 2^31 bytes and more)"
-                           : "PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)");
-        return FLGPU_ERR_UNSUPPORTED;
+    if (!d || n < 20 || memcmp(d, "RIFF", 4) || memcmp(d + 8, "WEBP", 4)) return false;
+    for (uint64_t pos = 12; n - pos >= 8;) {
+        if (!memcmp(d + pos, "VP8 ", 4)) return true;
+        if (!memcmp(d + pos, "VP8L", 4) || !memcmp(d + pos, "ANMF", 4)) return false;
+        const uint64_t len = (uint64_t)d[pos + 4] | (uint64_t)d[pos + 5] << 8 | (uint64_t)d[pos + 6] << 16 | (uint64_t)d[pos + 7] << 24;
+        if (len > n - pos - 8) return false;
+        pos += 8u + len + (len & 1u);
+        if (pos > n) return false;
     }
-    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
-        c->set_error("FLGPU_IMG_PNG_SOURCE: width / height / channels do not match the file (see flgpu_png_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
+    return false;
+}
+
+// the orientation ImageDecoder::orientation() reports for a WebP, lossless or lossy: from the EXIF chunk, whose payload usually starts at the
+// TIFF header, without the "Exif\0\0" a JPEG APP1 segment has; both forms are taken.  0 = no tag.
+static uint32_t webp_orientation(const uint8_t *file, size_t exif_off, size_t exif_len)
+{
+    if (!exif_len) return 0;
+    const uint8_t *p = file + exif_off;
+    size_t n = exif_len;
+    if (n >= 6 && !memcmp(p, "Exif\0\0", 6)) { p += 6; n -= 6; }
+    return (uint32_t)tiff_orientation(p, n);
+}
+
+int file_head(SourceKind kind, const uint8_t *file, size_t n, uint32_t opts, SourceProbe &out)
+{
+    const bool full = (opts & HEAD_FULL) != 0, adam7 = (opts & HEAD_ADAM7) != 0;
+    if (kind == SRC_WEBP && (opts & HEAD_SNIFF) && webp_is_lossy(file, n)) kind = SRC_VP8;
+    out.kind = kind;
+    FileHead &h = out.head;
+    h = FileHead();
+    auto fill = [&h](const auto &I, uint32_t channels, uint32_t flags, int input_format, uint32_t orientation) {
+        h.width = I.width; h.height = I.height; h.supported = I.supported;
+        h.channels = channels; h.flags = flags; h.input_format = input_format; h.orientation = orientation;
+    };
+    switch (kind) {
+    case SRC_JPEG: // (announces 1 or 3 channels whether supported or not: plan_file plans it before it refuses it)
+        if (jpeg_parse_info(file, n, out.jpeg) != 0) return FLGPU_ERR_PARSE;
+        fill(out.jpeg, out.jpeg.components == 1 ? 1u : 3u, FLGPU_IMG_JPEG_SOURCE, FLGPU_IN_JPEG, out.jpeg.exif_orientation);
+        break;
+    case SRC_PNG: // (the PNG decoder reports no orientation, handler.rs:206)
+        if (png_parse_info(file, n, out.png, full, adam7) != 0) return FLGPU_ERR_PARSE;
+        fill(out.png, out.png.channels, FLGPU_IMG_PNG_SOURCE | (adam7 ? FLGPU_IMG_PNG_ADAM7 : 0u), FLGPU_IN_PNG, 0);
+        break;
+    case SRC_WEBP:
+        if (webp_parse_info(file, n, out.webp, full) != 0) return FLGPU_ERR_PARSE;
+        fill(out.webp, out.webp.channels, FLGPU_IMG_WEBP_SOURCE, FLGPU_IN_WEBP, webp_orientation(file, out.webp.exif_off, out.webp.exif_len));
+        break;
+    case SRC_VP8:
+        if (vp8_parse_info(file, n, out.vp8, full) != 0) return FLGPU_ERR_PARSE;
+        fill(out.vp8, out.vp8.channels, FLGPU_IMG_VP8_SOURCE, FLGPU_IN_WEBP, webp_orientation(file, out.vp8.exif_off, out.vp8.exif_len));
+        break;
+    case SRC_PIXELS: return FLGPU_ERR_INVALID_ARG;
     }
     return FLGPU_OK;
 }
+
+// A PNG / WebP file as a source: the container walk has bounded what the file may make the library reserve (png_parse_info: below 2^31 bytes, and
+// no more than 1032 x its IDAT payload); here the file is held against what the caller announced.  (Layout only: *_source_to_blob verifies the
+// CRCs and reads the streams, so the file is summed once per request.)
+static int file_source_check(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
+{
+    static const struct { const char *malformed, *refused, *mismatch; } kTexts[] = { // [kind - SRC_PNG]
+        {"malformed PNG file (signature, chunk layout, CRC, IHDR or too few bytes)",
+         "PNG file not covered by the device decoder (16-bit samples, Adam7 interlace, or 2^31 bytes and more)",
+         "FLGPU_IMG_PNG_SOURCE: width / height / channels do not match the file (see flgpu_png_info_of)"},
+        {"malformed WebP file (RIFF size, chunk layout, VP8L signature or version)",
+         "WebP file not covered by the device decoder (lossy VP8, ALPH, animation)",
+         "FLGPU_IMG_WEBP_SOURCE: width / height / channels do not match the file (see flgpu_webp_info_of)"},
+        {"malformed lossy WebP file (RIFF size, chunk layout, frame tag, start code, partition sizes or too few bytes)",
+         "lossy WebP file not covered by the device decoder: ",
+         "FLGPU_IMG_VP8_SOURCE: width / height / channels do not match the file (see flgpu_vp8_info_of)"}};
+    const auto &t = kTexts[out.kind - SRC_PNG];
+    const bool adam7 = (src->flags & FLGPU_IMG_PNG_ADAM7) != 0;
+    if (file_head(out.kind, src->data, (size_t)src->capacity, adam7 ? HEAD_ADAM7 : 0u, out) != 0) { c->set_error(t.malformed); return FLGPU_ERR_PARSE; }
+    const FileHead &h = out.head;
+    if (!h.supported) {
+        // the two refusals with a text of their own: a lossy WebP names the feature, a PNG asked for with Adam7 does not list it
+        if (out.kind == SRC_VP8) c->set_error(std::string(t.refused) + (out.vp8.refused ? out.vp8.refused : "unknown feature"));
+        else c->set_error(adam7 ? "PNG file not covered by the device decoder (16-bit samples, or 2^31 bytes and more)" : t.refused);
+        return FLGPU_ERR_UNSUPPORTED;
+    }
+    if (h.width != src->width || h.height != src->height || h.channels != src->channels) { c->set_error(t.mismatch); return FLGPU_ERR_INVALID_ARG; }
+    return FLGPU_OK;
+}
+
+// ---- PNG sources -----------------------------------------------------------------------------------------------------------------
 
 static int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used)
 {
@@ -322,18 +393,6 @@ static int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const S
 }
 
 // ---- lossless WebP sources ---------------------------------------------------------------------------------------------------------
-
-static int webp_source_info(flgpu_ctx *c, const flgpu_image *src, WebpInfo &info)
-{
-    // (container and VP8L header only: webp_source_to_blob reads the stream itself, once per request)
-    if (webp_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed WebP file (RIFF size, chunk layout, VP8L signature or version)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error("WebP file not covered by the device decoder (lossy VP8, ALPH, animation)"); return FLGPU_ERR_UNSUPPORTED; }
-    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
-        c->set_error("FLGPU_IMG_WEBP_SOURCE: width / height / channels do not match the file (see flgpu_webp_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    return FLGPU_OK;
-}
 
 static int webp_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, WebpBlobHeader *hdr, size_t *used)
 {
@@ -438,18 +497,6 @@ static int decode_webp_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const 
 
 // ---- lossy WebP sources ------------------------------------------------------------------------------------------------------------
 
-static int vp8_source_info(flgpu_ctx *c, const flgpu_image *src, Vp8Info &info)
-{
-    // (container and frame header only: vp8_source_to_blob reads the partitions, once per request)
-    if (vp8_parse_info(src->data, (size_t)src->capacity, info, false) != 0) { c->set_error("malformed lossy WebP file (RIFF size, chunk layout, frame tag, start code, partition sizes or too few bytes)"); return FLGPU_ERR_PARSE; }
-    if (!info.supported) { c->set_error(std::string("lossy WebP file not covered by the device decoder: ") + (info.refused ? info.refused : "unknown feature")); return FLGPU_ERR_UNSUPPORTED; }
-    if (info.width != src->width || info.height != src->height || info.channels != src->channels) {
-        c->set_error("FLGPU_IMG_VP8_SOURCE: width / height / channels do not match the file (see flgpu_vp8_info_of)");
-        return FLGPU_ERR_INVALID_ARG;
-    }
-    return FLGPU_OK;
-}
-
 static int vp8_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, Vp8BlobHeader *hdr, size_t *used)
 {
     const int rc = vp8_decode_levels(src->data, (size_t)src->capacity, blob, cap, hdr);
@@ -550,16 +597,16 @@ static int decode_vp8_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const S
 
 int debug_vp8_planes(flgpu_ctx *c, const uint8_t *file, size_t n, int filter, uint8_t *out, size_t capacity, size_t *used)
 {
-    Vp8Info info;
-    if (vp8_parse_info(file, n, info, false) != 0) return FLGPU_ERR_PARSE;
-    if (!info.supported) return FLGPU_ERR_UNSUPPORTED;
-    const size_t planes = (size_t)vp8_rec_bytes(vp8_mbs(info.width), vp8_mbs(info.height));
+    SourceProbe probe;
+    if (int rc = file_head(SRC_VP8, file, n, 0, probe)) return rc;
+    if (!probe.head.supported) return FLGPU_ERR_UNSUPPORTED;
+    const size_t planes = (size_t)vp8_rec_bytes(vp8_mbs(probe.head.width), vp8_mbs(probe.head.height));
     *used = planes;
     if (!out) return FLGPU_OK;
     if (capacity < planes) return FLGPU_ERR_BUFFER_TOO_SMALL;
-    const size_t cap = vp8_blob_capacity(info);
-    std::vector<uint8_t> work(cap + 16u);
-    uint8_t *blob = work.data() + ((16u - (reinterpret_cast<uintptr_t>(work.data()) & 15u)) & 15u);
+    const size_t cap = vp8_blob_capacity(probe.vp8);
+    WorkBuf work(cap);
+    uint8_t *blob = work.p;
     Vp8BlobHeader H;
     if (int rc = vp8_decode_levels(file, n, blob, cap, &H)) return vp8_status(rc);
     std::lock_guard<std::mutex> g(c->mu);
@@ -590,23 +637,15 @@ int source_probe(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
         return FLGPU_ERR_INVALID_ARG;
     }
     switch (out.kind) {
-    case SRC_JPEG:
-        if (jpeg_parse_info(src->data, (size_t)src->capacity, out.jpeg) != 0) return FLGPU_ERR_INVALID_ARG;
-        if (!out.jpeg.supported) return FLGPU_ERR_UNSUPPORTED; // (no text from here: flgpu_transform adds its own, a host batch has none)
+    case SRC_JPEG: // its own statuses: FLGPU_ERR_INVALID_ARG, not _PARSE, for a file that does not parse; its own checks against the caller's announcement
+        if (file_head(SRC_JPEG, src->data, (size_t)src->capacity, 0, out) != 0) return FLGPU_ERR_INVALID_ARG;
+        if (!out.head.supported) return FLGPU_ERR_UNSUPPORTED; // (no text from here: flgpu_transform adds its own, a host batch has none)
         if (int rc = jpeg_source_precheck(c, src, out.jpeg)) return rc;
         out.capacity = jpeg_source_capacity(c, src, out.jpeg);
         break;
-    case SRC_PNG:
-        if (int rc = png_source_info(c, src, out.png)) return rc;
-        out.capacity = png_blob_bytes(out.png);
-        break;
-    case SRC_WEBP:
-        if (int rc = webp_source_info(c, src, out.webp)) return rc;
-        out.capacity = webp_blob_capacity(out.webp, (size_t)src->capacity);
-        break;
-    case SRC_VP8:
-        if (int rc = vp8_source_info(c, src, out.vp8)) return rc;
-        out.capacity = vp8_blob_capacity(out.vp8);
+    case SRC_PNG: case SRC_WEBP: case SRC_VP8:
+        if (int rc = file_source_check(c, src, out)) return rc;
+        out.capacity = out.kind == SRC_PNG ? png_blob_bytes(out.png) : out.kind == SRC_WEBP ? webp_blob_capacity(out.webp, (size_t)src->capacity) : vp8_blob_capacity(out.vp8);
         break;
     case SRC_PIXELS:
         out.capacity = (size_t)src->width * src->height * src->channels;

@@ -1,4 +1,6 @@
 // fl_source.h -- encoded files on the way into a batch:
+//   fl_request.cpp   a file + query string + accept flags as ONE request (the flgpu_process_* / flgpu_decode_* / flgpu_*_info_of entry points): head,
+//                    plan, run -- whatever the format
 //   fl_source.cpp    JPEG / PNG / lossless WebP / lossy WebP files as SOURCES of a batch: probe (header + what the caller announced), stage (the host
 //                    half, into the caller's staging), decode (the device half, in front of run_batch_device)
 //   fl_gifrun.cpp    a GIF file, which is no source of a batch but a batch of its own (a caller of run_batch_device)
@@ -8,6 +10,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <memory>
 #include <vector>
 
 #include "../../include/fanlin_gpu.h"
@@ -27,9 +30,20 @@ inline SourceKind source_kind(uint32_t flags)
            : (flags & FLGPU_IMG_VP8_SOURCE) ? SRC_VP8 : SRC_PIXELS;
 }
 
+// What a request needs of a file's header, whatever the format (file_head below fills it).
+struct FileHead {
+    uint32_t width = 0, height = 0;
+    uint32_t channels = 0;    // of the decoded picture; 0 if unsupported -- but a JPEG announces 1 (one component) or 3 either way: it is planned before it is refused
+    uint32_t flags = 0;       // what a flgpu_image of the file carries: FLGPU_IMG_*_SOURCE (| FLGPU_IMG_PNG_ADAM7)
+    int input_format = 0;     // FLGPU_IN_*; both WebP kinds are FLGPU_IN_WEBP
+    uint32_t orientation = 0; // EXIF, 1..8; 0 = no tag (a request then runs with 1).  The PNG decoder reports none (handler.rs:206): always 0
+    uint32_t supported = 0;   // 1 = the device decoder takes the file
+};
+
 // What source_probe learns from a source before anything is reserved for it.
 struct SourceProbe {
     SourceKind kind = SRC_PIXELS;
+    FileHead head;       // of a file (file_head)
     size_t capacity = 0; // of the buffer source_stage fills: jpeg_source_capacity / png_blob_bytes / webp_blob_capacity / vp8_blob_capacity, or W*H*C for pixels
     JpegInfo jpeg;       // the header of `kind`
     PngInfo png;
@@ -50,6 +64,29 @@ struct StagedSource {
     WebpBlobHeader vp8_alpha; // ... vp8.alpha == 2: the header of the lossless blob that holds the alpha plane
     uint64_t file_bytes = 0;  // of the file (the *_file_bytes counters)
     size_t used = 0;          // bytes of the staging to upload
+};
+
+// The header of a file of `kind`, into out.kind / out.head / that kind's *Info: the ONE place outside the per-format decoders that parses a header for a
+// request, a source or an info call.  0, or FLGPU_ERR_PARSE.  Depth: the layout alone (requests and sources: flgpu_transform verifies CRCs and reads
+// the streams once, under the decode bound; as_is serves the file unread) unless HEAD_FULL (the *_info_of calls: PNG CRCs, the WebP streams' contents).
+// HEAD_SNIFF: a SRC_WEBP file whose picture is a `VP8 ` chunk becomes SRC_VP8 (flgpu_process_webp goes by the chunk type; a source goes by its flag).
+enum : uint32_t { HEAD_ADAM7 = 1u, HEAD_FULL = 2u, HEAD_SNIFF = 4u };
+int file_head(SourceKind kind, const uint8_t *file, size_t n, uint32_t opts, SourceProbe &out);
+// the flgpu_image a file with that head is handed over as
+inline flgpu_image file_image(const uint8_t *file, uint64_t n, const FileHead &h)
+{
+    flgpu_image src;
+    memset(&src, 0, sizeof(src));
+    src.data = const_cast<uint8_t *>(file); src.capacity = n;
+    src.width = h.width; src.height = h.height; src.channels = h.channels; src.flags = h.flags;
+    return src;
+}
+
+// A host buffer of `cap` bytes that starts at a multiple of 16, as the staging flgpu_transform decodes a blob into does.
+struct WorkBuf {
+    std::unique_ptr<uint8_t[]> mem;
+    uint8_t *p;
+    explicit WorkBuf(size_t cap) : mem(new uint8_t[cap + 16u]), p(mem.get() + ((16u - (reinterpret_cast<uintptr_t>(mem.get()) & 15u)) & 15u)) {}
 };
 
 // Decides the kind and holds the file against what the caller announced: that format's header parse, width / height / channels, for JPEG
@@ -87,6 +124,15 @@ inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FL
 // The device's Y | U | V planes of a lossy WebP file (padded to whole macroblocks, vp8_rec_bytes), before (filter == 0) or behind
 // the loop filter: what flgpu_debug_vp8_planes hands out, so that a wrong pixel names its stage.  Buffers of its own, no batch.
 int debug_vp8_planes(flgpu_ctx *c, const uint8_t *file, size_t n, int filter, uint8_t *out, size_t capacity, size_t *used);
+
+// ---- fl_query.cpp: the planner behind every request -----------------------------------------------------------------------
+// Everything State::process_image decides before it touches pixels (handler.rs:198-261).
+int plan_request(const flgpu_image *decoded, uint8_t exif_orientation, const char *query_string, uint32_t accept_flags, int input_format,
+                 flgpu_params *p, flgpu_plan *plan, int *result_kind, int *out_format);
+// A file the device decoder does not take: only as_is, which never decodes, gets through (verdict order: query parse, size gate, as_is; the plan zeroed).
+int plan_undecodable(const char *query_string, flgpu_plan *plan, int *kind, int *out_format);
+// The shared end of flgpu_process_{image,jpeg,png,webp}: rc and kind are the planner's verdict; as_is never reaches the device.
+int run_planned(flgpu_ctx *ctx, int rc, int kind, int *result_kind, const flgpu_image *src, const flgpu_params *p, flgpu_image *dst);
 
 // ---- fl_gifrun.cpp ---------------------------------------------------------------------------------------------------
 // A GIF file (not a source of a batch: it IS one).  The LZW stage runs on the calling thread, outside the context's lock; then blob

@@ -161,19 +161,12 @@ public:
     Processed process_image(const Decoded &img, const query::Query &params, const content::Format &content)
     {
         const flgpu_image src{const_cast<uint8_t *>(img.pixels), (uint64_t)img.width * img.height * img.channels, img.width, img.height, img.channels, 0, 0};
-        Processed out{};
-        int kind = 0, fmt = 0;
-        check(flgpu_process_image_plan(&src, img.orientation, params.text().c_str(), content.flags(), img.format, &out.plan, &kind));
-        out.kind = static_cast<flgpu_result_kind>(kind);
-        if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
-        // a PNG or lossless WebP body is staged at the format's worst case, so that it never comes back too small
-        out.data.resize(out.kind == FLGPU_RESULT_PNG_STREAM || out.kind == FLGPU_RESULT_WEBP_STREAM ? out.plan.max_out_bytes : out.plan.out_bytes);
-        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
-        check(flgpu_process_image(ctx_, &src, img.orientation, params.text().c_str(), content.flags(), img.format, &dst, &out.plan, &kind, &fmt), ctx_);
-        out.negotiated = static_cast<flgpu_out_format>(fmt);
-        out.flags = dst.flags;
-        out.data.resize(dst.bytes);
-        return out;
+        const char *q = params.text().c_str();
+        return process(
+            [&](flgpu_plan *plan, int *kind) { return flgpu_process_image_plan(&src, img.orientation, q, content.flags(), img.format, plan, kind); },
+            // a PNG or lossless WebP body is staged at the format's worst case, so that it never comes back too small
+            [](const Processed &o) { return o.kind == FLGPU_RESULT_PNG_STREAM || o.kind == FLGPU_RESULT_WEBP_STREAM ? o.plan.max_out_bytes : o.plan.out_bytes; },
+            [&](flgpu_image *dst, flgpu_plan *plan, int *kind, int *fmt) { return flgpu_process_image(ctx_, &src, img.orientation, q, content.flags(), img.format, dst, plan, kind, fmt); });
     }
 
     // PngDecoder::new's view of a file (src/handler.rs:218-220): false if the bytes are no intact PNG container
@@ -184,18 +177,7 @@ public:
     // (FLGPU_ERR_UNSUPPORTED: 16-bit samples, Adam7) and on damaged ones (FLGPU_ERR_PARSE): the host then uses its own decoder.
     Processed process_png(const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
     {
-        Processed out{};
-        int kind = 0, fmt = 0;
-        check(flgpu_process_png_plan(file.data(), file.size(), params.text().c_str(), content.flags(), &out.plan, &kind));
-        out.kind = static_cast<flgpu_result_kind>(kind);
-        if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
-        out.data.resize(out.plan.max_out_bytes);
-        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
-        check(flgpu_process_png(ctx_, file.data(), file.size(), params.text().c_str(), content.flags(), &dst, &out.plan, &kind, &fmt), ctx_);
-        out.negotiated = static_cast<flgpu_out_format>(fmt);
-        out.flags = dst.flags;
-        out.data.resize(dst.bytes);
-        return out;
+        return process_file(flgpu_process_png_plan, flgpu_process_png, file, params, content);
     }
 
     // WebPDecoder::new's view of a file (src/handler.rs:205-220): false if the bytes are no intact WebP container
@@ -223,18 +205,7 @@ public:
     // ones (FLGPU_ERR_PARSE): the host then uses its own decoder.
     Processed process_webp(const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
     {
-        Processed out{};
-        int kind = 0, fmt = 0;
-        check(flgpu_process_webp_plan(file.data(), file.size(), params.text().c_str(), content.flags(), &out.plan, &kind));
-        out.kind = static_cast<flgpu_result_kind>(kind);
-        if (out.kind == FLGPU_RESULT_AS_IS) { out.negotiated = FLGPU_OUT_KEEP; return out; }
-        out.data.resize(out.plan.max_out_bytes);
-        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
-        check(flgpu_process_webp(ctx_, file.data(), file.size(), params.text().c_str(), content.flags(), &dst, &out.plan, &kind, &fmt), ctx_);
-        out.negotiated = static_cast<flgpu_out_format>(fmt);
-        out.flags = dst.flags;
-        out.data.resize(dst.bytes);
-        return out;
+        return process_file(flgpu_process_webp_plan, flgpu_process_webp, file, params, content);
     }
 
     // GifDecoder::new's view of a file (src/handler.rs:311-321), LZW stage included: false if the file is damaged
@@ -247,25 +218,49 @@ public:
     // (FLGPU_ERR_PARSE): the host then decodes the frames itself and hands them to flgpu_transform_batch.
     Processed process_gif(const std::vector<uint8_t> &file, const query::Query &params, uint32_t &frames, const content::Format &accepted = content::Format())
     {
-        Processed out{};
-        int kind = 0, fmt = 0;
-        check(flgpu_process_gif_plan(file.data(), file.size(), params.text().c_str(), accepted.flags(), &out.plan, &frames, &kind));
-        out.kind = static_cast<flgpu_result_kind>(kind);
-        out.negotiated = FLGPU_OUT_KEEP;
-        if (out.kind == FLGPU_RESULT_AS_IS) return out;
-        // (a planned stream may still come back as pixels: 64 + frames x max_out_bytes holds either)
-        out.data.resize(out.kind == FLGPU_RESULT_GIF_STREAM ? 64 + out.plan.max_out_bytes * frames : out.plan.out_bytes * frames);
-        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
-        check(flgpu_process_gif(ctx_, file.data(), file.size(), params.text().c_str(), accepted.flags(), &dst, &out.plan, &frames, &kind, &fmt), ctx_);
-        out.kind = static_cast<flgpu_result_kind>(kind); // what happened
-        out.flags = dst.flags;
-        out.data.resize(dst.bytes);
-        return out;
+        const char *q = params.text().c_str();
+        return process(
+            [&](flgpu_plan *plan, int *kind) { return flgpu_process_gif_plan(file.data(), file.size(), q, accepted.flags(), plan, &frames, kind); },
+            // (a planned stream may still come back as pixels: 64 + frames x max_out_bytes holds either)
+            [&](const Processed &o) { return o.kind == FLGPU_RESULT_GIF_STREAM ? 64 + o.plan.max_out_bytes * frames : o.plan.out_bytes * frames; },
+            [&](flgpu_image *dst, flgpu_plan *plan, int *kind, int *fmt) { return flgpu_process_gif(ctx_, file.data(), file.size(), q, accepted.flags(), dst, plan, &frames, kind, fmt); });
     }
 
     flgpu_ctx *raw() { return ctx_; }
 
 private:
+    // What the four process_* calls share: plan, size, run, shrink.  plan(plan, kind) and run(dst, plan, kind, fmt) are one format's two ABI calls,
+    // bytes(out) is what to reserve for the planned result.
+    template <class Plan, class Bytes, class Run>
+    Processed process(Plan plan, Bytes bytes, Run run)
+    {
+        Processed out{};
+        int kind = 0, fmt = FLGPU_OUT_KEEP;
+        check(plan(&out.plan, &kind));
+        out.kind = static_cast<flgpu_result_kind>(kind);
+        out.negotiated = FLGPU_OUT_KEEP;
+        if (out.kind == FLGPU_RESULT_AS_IS) return out;
+        out.data.resize(bytes(out));
+        flgpu_image dst{out.data.data(), out.data.size(), 0, 0, 0, 0, 0};
+        check(run(&dst, &out.plan, &kind, &fmt), ctx_);
+        out.kind = static_cast<flgpu_result_kind>(kind); // what happened: a GIF planned as a stream may come back as pixels (the others report the planned kind again)
+        out.negotiated = static_cast<flgpu_out_format>(fmt);
+        out.flags = dst.flags;
+        out.data.resize(dst.bytes);
+        return out;
+    }
+
+    // process_png / process_webp: a file staged at its format's worst case (max_out_bytes)
+    template <class PlanFn, class RunFn>
+    Processed process_file(PlanFn plan_fn, RunFn run_fn, const std::vector<uint8_t> &file, const query::Query &params, const content::Format &content)
+    {
+        const char *q = params.text().c_str();
+        return process(
+            [&](flgpu_plan *plan, int *kind) { return plan_fn(file.data(), file.size(), q, content.flags(), plan, kind); },
+            [](const Processed &o) { return o.plan.max_out_bytes; },
+            [&](flgpu_image *dst, flgpu_plan *plan, int *kind, int *fmt) { return run_fn(ctx_, file.data(), file.size(), q, content.flags(), dst, plan, kind, fmt); });
+    }
+
     flgpu_ctx *ctx_ = nullptr;
 };
 
