@@ -45,6 +45,8 @@ ENCODE_WEBP_LOSSY_I4 = 0x1000  # accept_flags bit: with ENCODE_WEBP_LOSSY, those
 ENCODE_WEBP_LOSSY_FILTER = 0x4000  # accept_flags bit: with ENCODE_WEBP_LOSSY, the loop-filtered twin of whatever the other bits select; alone, or without it, nothing
 ENCODE_WEBP_LOSSY_ALPHA = 0x20000  # accept_flags bit: with ENCODE_WEBP_LOSSY, a translucent picture's alpha plane goes out as a VP8L stream wherever that is smaller (FEO_ALPHA_VP8L); alone, or without it, nothing
 ENCODE_WEBP_LOSSY_SEGMENTS = 0x40000  # accept_flags bit: with ENCODE_WEBP_LOSSY, segment-adaptive quantisers -- up to four classes of macroblocks by activity (FEO_SEGMENTS); alone, or without it, nothing
+ENCODE_JPEG_OPTIMIZE = 0x80000  # accept_flags bit: a JPEG that stays JPEG is coded with Huffman tables from the picture's own symbol counts (FEO_JPEG_OPTIMIZE); never a larger file, nothing else changes
+FEO_JPEG_OPTIMIZE = 4  # flgpu_params.reserved[0] (the header's `options` byte), FE_JPEG only: see ENCODE_JPEG_OPTIMIZE
 FEO_SEGMENTS = 2  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_SEGMENTS
 FEO_ALPHA_VP8L = 1  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_ALPHA
 ENCODE_WEBP_LOSSY_PROBS = 0x2000  # accept_flags bit: with ENCODE_WEBP_LOSSY (and _I4), FE_WEBP_LOSSY_AP (FE_WEBP_LOSSY_I4_AP); alone, or with only _I4, nothing
@@ -169,7 +171,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
     "flgpu_png_info_of_flags", "flgpu_decode_png_flags", "flgpu_debug_png_scanlines_flags",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
-    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs",
+    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs", "flgpu_debug_jpeg_optimize_tables",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
@@ -437,7 +439,7 @@ CMYK_GRID, CMYK_INPUT_YCCK = 17, 1
 
 def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 32), crop=False, blur_sigma=0.0,
                 grayscale=False, inverse=False, quality=75, front_end=FE_NONE, orientation=1, filter=FILTER_LANCZOS3,
-                alpha_vp8l=False, segments=False) -> flgpu_params:
+                alpha_vp8l=False, segments=False, jpeg_optimize=False) -> flgpu_params:
     p = flgpu_params()
     p.has_dims = 1 if (w is not None and h is not None) else 0
     p.w, p.h = (w or 0), (h or 0)
@@ -448,7 +450,7 @@ def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 
     p.quality, p.front_end = quality, front_end
     p.orientation = orientation
     p.filter = filter
-    p.reserved[0] = (FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0)  # the options byte
+    p.reserved[0] = (FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0) | (FEO_JPEG_OPTIMIZE if jpeg_optimize else 0)  # the options byte
     return p
 
 
@@ -534,6 +536,19 @@ def debug_png_scanlines(data: bytes, adam7: bool = False) -> bytes:
     """Host half of the PNG decode front end alone: the inflated IDAT stream (filtered scanlines), Adler-32 and filter bytes checked.
     ``adam7``: flgpu_debug_png_scanlines_flags with IMG_PNG_ADAM7 -- for an interlaced file the seven passes' scanlines back to back."""
     return _sized_call("flgpu_debug_png_scanlines", data, IMG_PNG_ADAM7 if adam7 else 0)
+
+
+def debug_jpeg_optimize_tables(counts, fallback: bool = False) -> dict:
+    """flgpu_debug_jpeg_optimize_tables: the table rule of FEO_JPEG_OPTIMIZE on the host (the code the device runs) for counts[4][256] in
+    DHT order (DC luma, AC luma, DC chroma, AC chroma) -> dict(luts = uint32[4][256] of length << 16 | code, dht = the four DHT
+    segments, optimized = the never-larger decision for these counts)."""
+    lib = load_library()
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32).reshape(4, 256)
+    luts, dht = np.zeros((4, 256), np.uint32), np.zeros(1108, np.uint8)
+    n, on = C.c_uint32(), C.c_int()
+    lib.flgpu_debug_jpeg_optimize_tables.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    _check(lib.flgpu_debug_jpeg_optimize_tables(cnt.ctypes.data, int(bool(fallback)), luts.ctypes.data, dht.ctypes.data, C.byref(n), C.byref(on)))
+    return dict(luts=luts, dht=dht[:n.value].tobytes(), optimized=bool(on.value))
 
 
 def webp_info(data: bytes) -> dict:

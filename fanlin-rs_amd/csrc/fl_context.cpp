@@ -367,7 +367,7 @@ void resolve_pending(flgpu_ctx *c)
 
 const char *const kDebugKeyNames[DBG_COUNT] = {
     "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first", "mfma_arith", "force_bands", "no_tile", "no_place4",
-    "host_huffman", "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base",
+    "host_huffman", "device_huffman_always", "device_huffman_min_bytes", "mfma_spin_limit", "debug_mfma", "debug_jh", "jpeg_optimize_fallback", "vp8_filter_base",
 };
 
 DebugSwitches::DebugSwitches()
@@ -668,7 +668,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
-        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments},
+        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments}, {"jpeg_optimized", &flgpu_ctx::jpeg_optimized},
         {"vp8_sources", &flgpu_ctx::vp8_sources}, {"vp8_file_bytes", &flgpu_ctx::vp8_file_bytes}, {"vp8_upload_bytes", &flgpu_ctx::vp8_upload_bytes},
         {"vp8_decode_ns", &flgpu_ctx::vp8_decode_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},

@@ -164,6 +164,7 @@ enum DebugKey : uint32_t {
     DBG_MFMA_SPIN_LIMIT,          // bound of the matrix-pipe kernel's LDS-counter waits (default kMfmaDefaultSpinLimit; 0 = every wait expires)
     DBG_DEBUG_MFMA,               // print every matrix-pipe plan
     DBG_DEBUG_JH,                 // print why a staged file went back to the host decoder
+    DBG_JPEG_OPTIMIZE_FALLBACK,   // FLGPU_FEO_JPEG_OPTIMIZE: the size comparison always falls against the picture's tables (tests reach the fallback branch)
     DBG_VP8_FILTER_BASE,          // the lossy WebP encoder's loop-filtered variants: -1 (default) = the base level from the quantiser, 0..63 = forced
     DBG_COUNT
 };
@@ -224,6 +225,7 @@ struct flgpu_ctx {
     fl::DeviceBuf d_vp8dec, d_vp8jobs;                 // lossy WebP decode (fl_vp8dec.hip): planes, alpha planes and pixels of a batch, job descriptors
     fl::PinnedBuf h_vp8jobs;
     uint64_t vp8_sources = 0, vp8_file_bytes = 0, vp8_upload_bytes = 0, vp8_decode_ns = 0;
+    uint64_t jpeg_optimized = 0;                         // JPEG pictures whose file went out with their own Huffman tables (FLGPU_FEO_JPEG_OPTIMIZE; from the result words)
     uint64_t webp_lossy_segments = 0;                    // lossy WebP pictures whose frame went out segmented (FLGPU_FEO_SEGMENTS; from the result words)
     uint64_t webp_alpha_vp8l = 0;                        // lossy WebP pictures whose ALPH chunk went out as a VP8L stream (FLGPU_FEO_ALPHA_VP8L; from the result words)
     uint64_t webp_lossy_ns = 0;                          // HIP-event time of the lossy WebP encoder's launches (fl_vp8.hip; profile = 1)

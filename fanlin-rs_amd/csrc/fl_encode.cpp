@@ -3,6 +3,7 @@
 #include <cassert>
 
 #include "fl_context.h"
+#include "fl_jpeg_opt_core.h"
 
 namespace fl {
 
@@ -54,7 +55,7 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan)
 namespace {
 
 // The scratch one picture needs, appended to s, and the limits flgpu_plan_output does not hold a single picture against.
-int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s)
+int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize)
 {
     if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions (the plan of such a picture is valid: refused when it is run)
     const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
@@ -62,6 +63,11 @@ int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s)
     s.jpeg_coef += align_up(units * sizeof(JpegUnit), 256);
     s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
     s.jpeg_raw += align_up(units * kAcWordsPerUnit * sizeof(uint32_t), 256);
+    if (optimize) { // FLGPU_FEO_JPEG_OPTIMIZE: the picture's record and its counts; JpegJob::opt_off is a 32-bit word offset
+        if ((s.jpeg_opt + jpeg_opt_bytes(units)) / 4u >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED;
+        s.jpeg_opt += jpeg_opt_bytes(units);
+        s.jpeg_opt_pics++;
+    }
     return FLGPU_OK;
 }
 
@@ -131,7 +137,11 @@ void add_jpeg_job(flgpu_ctx *c, EncodeJobs &E, const EncodeInput &x, const Encod
     j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->enc.jpeg_raw.p) + at.jpeg_raw);
     j.bx = x.plan->plane_w / 8u; j.by = x.plan->plane_h / 8u;
     j.tab_off = x.jpeg_tab;
-    E.jpeg_max_blocks = std::max(E.jpeg_max_blocks, j.bx * j.by);
+    if (jpeg_optimize(*x.p)) {
+        j.opt_off = (uint32_t)(at.jpeg_opt / 4u);
+        E.jjobs_opt++;
+        E.jpeg_opt_max_blocks = std::max(E.jpeg_opt_max_blocks, j.bx * j.by);
+    } else E.jpeg_max_blocks = std::max(E.jpeg_max_blocks, j.bx * j.by);
 }
 
 void add_png_job(flgpu_ctx *c, EncodeJobs &E, const EncodeInput &x, const EncodeScratch &at)
@@ -219,7 +229,7 @@ void add_planes_launch(EncodeJobs &E, uint32_t kind, const std::vector<const Enc
 int encode_plan_picture(const flgpu_params &p, const flgpu_plan &plan, EncodeScratch &s)
 {
     int rc = FLGPU_OK;
-    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s);
+    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s, jpeg_optimize(p));
     if (p.front_end == FLGPU_FE_PNG) rc = png_scratch(plan, s);
     if (p.front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(plan, s);
     if (const auto v = vp8_variant_of(p.front_end)) vp8_scratch(plan, s, *v, vp8_segments(p, plan.out_w, plan.out_h)); // (its limits: encode_plan_bytes)
@@ -233,6 +243,8 @@ int encode_reserve(flgpu_ctx *c, const EncodeScratch &sz)
     FL_HIP(c, b.jpeg_coef.reserve(sz.jpeg_coef), "JPEG coefficient scratch");
     FL_HIP(c, b.jpeg_off.reserve(sz.jpeg_off), "JPEG offset scratch");
     FL_HIP(c, b.jpeg_raw.reserve(sz.jpeg_raw), "JPEG bit-stream scratch");
+    FL_HIP(c, b.jpeg_opt.reserve(sz.jpeg_opt), "JPEG per-picture table scratch");
+    FL_HIP(c, b.jpeg_hist.reserve((size_t)sz.jpeg_opt_pics * kJpegOptHistWords * sizeof(uint32_t)), "JPEG symbol counts");
     FL_HIP(c, b.png_filt.reserve(sz.png_filt), "PNG filtered-row scratch");
     FL_HIP(c, b.png_chunks.reserve((size_t)sz.png_segs * kPngSegOutBytes), "PNG chunk scratch");
     FL_HIP(c, b.png_syms.reserve((size_t)sz.png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
@@ -256,11 +268,12 @@ int encode_reserve(flgpu_ctx *c, const EncodeScratch &sz)
 
 void encode_build_jobs(flgpu_ctx *c, const std::vector<EncodeInput> &in, EncodeJobs &E)
 {
-    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end
-    for (const EncodeInput &x : in) groups[x.p->front_end].push_back(&x);
+    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end; FLGPU_FE_JPEG with FLGPU_FEO_JPEG_OPTIMIZE behind FLGPU_FE_JPEG without
+    for (const EncodeInput &x : in) groups[2u * x.p->front_end + jpeg_optimize(*x.p)].push_back(&x);
     // E.at runs over ALL the jobs in this order: the lossy WebP groups share the lossy WebP scratch, in the families' order, and the
     // lossless WebP files share the lossless coder's with those groups' alpha planes; no other two formats touch the same total
-    for (auto &g : groups) {
+    for (auto &gk : groups) {
+        const std::pair<uint32_t, std::vector<const EncodeInput *> &> g{gk.first / 2u, gk.second};
         const size_t vjob0 = E.vjobs.size();
         const std::optional<Vp8Variant> vp8 = vp8_variant_of(g.first);
         for (const EncodeInput *x : g.second) {
@@ -291,7 +304,7 @@ void EncodeJobs::point_results(uint32_t *status)
 
 void EncodeBuffers::release()
 {
-    for (DeviceBuf *b : {&jpeg_coef, &jpeg_off, &jpeg_raw, &png_filt, &png_chunks, &png_syms, &png_recs, &webpll_res, &webpll_tok, &webpll_tiles, &webpll_pic,
+    for (DeviceBuf *b : {&jpeg_coef, &jpeg_off, &jpeg_raw, &jpeg_opt, &jpeg_hist, &png_filt, &png_chunks, &png_syms, &png_recs, &webpll_res, &webpll_tok, &webpll_tiles, &webpll_pic,
                          &webpll_stream, &vp8_planes, &vp8_rec, &vp8_lev, &vp8_info, &vp8_sizes, &vp8_bm, &vp8_tab, &vp8_lf, &vp8_seg}) b->release();
 }
 
@@ -303,9 +316,16 @@ int encode_enqueue(flgpu_ctx *c, const EncodeJobs &E, hipStream_t st)
         else FL_HIP(c, launch_webp420(E.d.fjobs, c->d_arena, c->gamma_off, F.base, F.n, F.mw, F.mh, F.rgba, st), "webp front end");
         c->stats.frontend_launches++;
     }
-    if (!E.jjobs.empty()) {
+    const uint32_t jplain = (uint32_t)E.jjobs.size() - E.jjobs_opt;
+    if (jplain) {
         ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_jpeg_encode(E.d.jjobs, c->d_arena, 0, (uint32_t)E.jjobs.size(), E.jpeg_max_blocks, st), "JPEG encode");
+        FL_HIP(c, launch_jpeg_encode(E.d.jjobs, c->d_arena, 0, jplain, E.jpeg_max_blocks, st), "JPEG encode");
+        c->stats.frontend_launches++;
+    }
+    if (E.jjobs_opt) { // FLGPU_FEO_JPEG_OPTIMIZE: the jobs behind the plain ones, with their records and counts
+        ProfileScope ps(c, st, 2);
+        FL_HIP(c, launch_jpeg_encode_optimized(E.d.jjobs, c->d_arena, jplain, E.jjobs_opt, E.jpeg_opt_max_blocks, static_cast<uint32_t *>(c->enc.jpeg_opt.p),
+                                               static_cast<uint32_t *>(c->enc.jpeg_hist.p), c->dbg->on(DBG_JPEG_OPTIMIZE_FALLBACK), st), "JPEG encode with per-picture tables");
         c->stats.frontend_launches++;
     }
     if (!E.pjobs.empty()) {
@@ -335,6 +355,7 @@ int encode_collect(flgpu_ctx *c, uint32_t fe, uint32_t r0, uint32_t r1, flgpu_im
         c->webp_alpha_vp8l += (r0 & kVp8ResultAlphaVp8l) != 0;
         c->webp_lossy_segments += (r0 & kVp8ResultSegments) != 0;
     }
+    if (fe == FLGPU_FE_JPEG && r1 && (r0 & FL_JPEG_RESULT_OPTIMIZED)) c->jpeg_optimized++;
     if (!fe_encoded(fe)) return FLGPU_OK;
     dst.bytes = r1;
     if (r1) return FLGPU_OK;
@@ -345,6 +366,16 @@ int encode_collect(flgpu_ctx *c, uint32_t fe, uint32_t r0, uint32_t r1, flgpu_im
 } // namespace fl
 
 // ---- diagnostics -----------------------------------------------------------------------------------------------------------------
+// The rule of fl_jpeg_opt_core.h in plain loops (jpeg_opt_tables_serial): what jpeg_opt_tables_kernel computes over a workgroup.
+extern "C" int flgpu_debug_jpeg_optimize_tables(const uint32_t *counts, int fallback, uint32_t *luts, uint8_t *dht, uint32_t *dht_bytes, int *optimized)
+try {
+    if (!counts || !luts || !dht || !dht_bytes || !optimized) return FLGPU_ERR_INVALID_ARG;
+    const int on = fl::jpeg_opt_tables_serial(counts, fallback != 0, luts, dht, dht_bytes);
+    if (on < 0) return FLGPU_ERR_INVALID_ARG;
+    *optimized = on;
+    return FLGPU_OK;
+} FL_ABI_CATCH
+
 // One picture through the ordinary launch sequence of a loop-filtered lossy WebP front end; then the cost words its filter launch
 // left (the picture is the batch's only one, so its scratch is the start of the loop filter scratch) and what every consumer derives from them.
 extern "C" int flgpu_debug_vp8_filter_costs(flgpu_ctx *c, const flgpu_image *src, const flgpu_params *p, uint32_t *levels, uint64_t *costs, uint32_t *chosen)

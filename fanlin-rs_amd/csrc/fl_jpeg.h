@@ -7,6 +7,7 @@ namespace fl {
 
 // One image of a JPEG-encode launch (fl_jpeg.hip).
 #define FL_JPEG_RESULT_OVERFLOW 4u
+#define FL_JPEG_RESULT_OPTIMIZED 8u   // FLGPU_FEO_JPEG_OPTIMIZE: the file went out with the picture's own Huffman tables
 constexpr uint32_t kAcWordsPerUnit = 52; // 63 coefficients x (16-bit code + 10 value bits) = 1638 bits
 constexpr uint32_t kUnitAcWords = 3;     // AC code words a unit's record holds itself (96 bits: nearly every unit of a photograph)
 // What jpeg_dct_quant_kernel hands jpeg_pack_kernel per unit (unit = block * 3 + component): one 16-byte record, written and
@@ -26,13 +27,27 @@ struct alignas(16) JpegJob {
     uint32_t w, h, c;
     uint32_t bx, by;      // blocks per row / column
     uint32_t tab_off;     // arena word offset of the header + quantisation tables block (fl_jpeg_tables.h)
-    uint32_t pad0;
+    uint32_t opt_off;     // FLGPU_FEO_JPEG_OPTIMIZE only (else 0): word offset of the picture's record in the batch's optimise scratch
     uint32_t dst_cap;     // bytes available at dst
 };
+
+// FLGPU_FEO_JPEG_OPTIMIZE.  A picture's record in the optimise scratch, in words from JpegJob::opt_off: what jpeg_opt_tables_kernel
+// leaves for the coding and pack launches -- header length and decision, the two DC and the two AC code tables (length << 16 | code),
+// the header bytes (prefix, four DHT segments, SOS; Annex K's where the decision fell against the picture's tables) -- and behind them
+// the quantised DC terms, 2 bytes per unit, which jpeg_opt_stats_kernel leaves for the DC histograms.
+constexpr uint32_t kJpegOptHdrLen = 0, kJpegOptFlag = 1, kJpegOptDcLut = 4, kJpegOptAcLut = 32, kJpegOptHeader = 544, kJpegOptHeadWords = 704;
+constexpr uint32_t kJpegOptHistWords = 512; // per picture, in a scratch of its own (cleared per batch): the AC symbol counts, luma then chroma
+constexpr size_t jpeg_opt_bytes(size_t units) { return (kJpegOptHeadWords * 4u + units * 2u + 255u) & ~(size_t)255u; }
 
 // JPEG encode of njobs pictures: colour + FDCT + quantise + AC coding (one wave per 16 blocks), then offsets, assembly, stuffing
 // and framing (one workgroup per picture)
 hipError_t launch_jpeg_encode(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
                               hipStream_t st);
+// The same for pictures that carry FLGPU_FEO_JPEG_OPTIMIZE (jobs job_base .. job_base + njobs - 1, whose opt_off address `opt`; hist:
+// njobs x kJpegOptHistWords words): clear the counts, count the AC symbols (the transform phase again, LDS histograms), build the four
+// tables per picture and decide (one workgroup per picture), code with those tables, pack with the picture's header.
+// fallback: the decision always falls against the picture's tables (tests).
+hipError_t launch_jpeg_encode_optimized(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
+                                        uint32_t *opt, uint32_t *hist, bool fallback, hipStream_t st);
 
 } // namespace fl

@@ -209,6 +209,8 @@ try {
     if (fmt == FLGPU_OUT_WEBP) p->front_end = (qc == 100) ? FLGPU_FE_NONE : FLGPU_FE_WEBP420;
     else if (fmt == FLGPU_OUT_KEEP && input_is_jpeg) p->front_end = input_is_jpeg == 2 ? FLGPU_FE_JPEG : FLGPU_FE_JFIF444;
     else p->front_end = FLGPU_FE_NONE;
+    /* per-picture Huffman tables: only the finished JPEG stream knows the option */
+    if (p->front_end == FLGPU_FE_JPEG && (accept_flags & FLGPU_ENCODE_JPEG_OPTIMIZE)) p->options |= FLGPU_FEO_JPEG_OPTIMIZE;
     /* the lossy WebP arm with both bits: whichever lossy front end the caller (or plan_request below) puts in place of the planes
        compresses the alpha plane; every other front end ignores the option */
     if (p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY) && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA))

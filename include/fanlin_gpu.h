@@ -226,6 +226,12 @@ typedef enum flgpu_front_end {
  * whose classes all come out at the picture's index keeps its file byte for byte.  max_out_bytes grows by the segment header and
  * the ids.  Alone, or without FLGPU_ENCODE_WEBP_LOSSY, it does nothing. */
 #define FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS 0x40000u
+/* Not a content::Format bit: a JPEG source that stays JPEG (FLGPU_FE_JPEG, FLGPU_RESULT_JPEG_STREAM) is entropy-coded with Huffman
+ * tables built from the picture's own symbol counts on the device (FLGPU_FEO_JPEG_OPTIMIZE), as libjpeg's `optimize` switch does:
+ * the same quantised coefficients, so every decoder shows the same pixels, in a file that is smaller wherever the picture's tables
+ * pay -- and today's file byte for byte where they do not.  max_out_bytes is unchanged.  It does nothing for FLGPU_FE_JFIF444, a
+ * negotiated WebP or AVIF, PNG, GIF or as_is. */
+#define FLGPU_ENCODE_JPEG_OPTIMIZE 0x80000u
 /* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
  * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
  * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
@@ -277,6 +283,12 @@ typedef struct flgpu_params {
  * segmented ones (see max_out_bytes) is coded without the bit.  Every other front end ignores it; alone or with
  * FLGPU_FEO_ALPHA_VP8L. */
 #define FLGPU_FEO_SEGMENTS 2u
+/* FLGPU_FEO_JPEG_OPTIMIZE, which only FLGPU_FE_JPEG knows: the four DHT segments list only the symbols the picture's scan uses, with
+ * length-limited minimum-redundancy codes from their counts (DESIGN.md section 4 states the integer rule; no code is all ones, none
+ * longer than 16 bits); SOI, APP0, SOF0, DQT, SOS, the coefficients, their order, padding, stuffing and EOI are FLGPU_FE_JPEG's.  The
+ * device compares header + entropy-coded bytes of both codings and writes the picture's tables only if that is strictly smaller;
+ * otherwise the file is FLGPU_FE_JPEG's byte for byte.  Every other front end ignores the bit. */
+#define FLGPU_FEO_JPEG_OPTIMIZE 4u
 
 /* Geometry decided on the host before any pixel is touched. */
 typedef struct flgpu_plan {
@@ -739,7 +751,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * context, its queue lanes and its device shards.  Keys (csrc/fl_context.h DebugKey): "no_mfma", "force_generic", "no_wtile",
  * "no_luma_mid" (a grey picture on a grey frame is blurred as Rgba8, not as one channel), "wtile_first", "mfma_arith" (0 full width,
  * 1 packed), "force_bands", "no_tile", "no_place4", "host_huffman", "device_huffman_always", "device_huffman_min_bytes",
- * "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base" (see flgpu_debug_vp8_filter_costs); "reset" restores every default.
+ * "mfma_spin_limit", "debug_mfma", "debug_jh", "vp8_filter_base" (see flgpu_debug_vp8_filter_costs), "jpeg_optimize_fallback" (1: a
+ * FLGPU_FEO_JPEG_OPTIMIZE picture's size comparison always falls against its own tables -- tests reach the fallback branch with it);
+ * "reset" restores every default.
  * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
  * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
  * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines;
@@ -756,6 +770,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * "gif_encoded" = files FLGPU_ENCODE_GIF finished on the device, "gif_encoded_bytes" = their bytes, "gif_encode_fallbacks" = files
  * it handed back as pixels (a frame above 256 colours), "gif_quantized_frames" = frames above 256 colours that
  * FLGPU_ENCODE_GIF_QUANTIZE gave a table (their files count as "gif_encoded"), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
+ * "jpeg_optimized" = FLGPU_FEO_JPEG_OPTIMIZE pictures whose file went out with their own tables (not those that fell back to Annex K's);
  * "blur_wtile_launches", "blur_tile_launches", "blur_generic_launches" = the blur launches (flgpu_stats.blur_launches is their sum)
  * served by the window-tile matrix-pipe kernel, by the f32 LDS-tile kernel and by the generic two passes.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
@@ -812,6 +827,13 @@ int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int 
  * flgpu_debug_set(ctx, "vp8_filter_base", v): -1 (the default) takes the base level from the quantiser, 0..63 forces it; candidates
  * and choice are still made on the device; only these four front ends look at it.  Single-device contexts. */
 int flgpu_debug_vp8_filter_costs(flgpu_ctx *ctx, const flgpu_image *src, const flgpu_params *params, uint32_t *levels, uint64_t *costs, uint32_t *chosen);
+
+/* The table rule of FLGPU_FEO_JPEG_OPTIMIZE alone, on the host (csrc/fl_jpeg_opt_core.h, the code jpeg_opt_tables_kernel runs): counts[4][256]
+ * = the symbol counts of the four tables in DHT order (DC luma, AC luma, DC chroma, AC chroma; each table's sum below 2^32 - 1).  Out:
+ * luts[4][256] = length << 16 | code per symbol (0 = unused); dht[1108] / *dht_bytes = the four DHT segments; *optimized = the
+ * never-larger decision for these counts (fallback != 0: as with "jpeg_optimize_fallback"), 0 also where the segments would exceed
+ * Annex K's.  Needs no device. */
+int flgpu_debug_jpeg_optimize_tables(const uint32_t *counts, int fallback, uint32_t *luts, uint8_t *dht, uint32_t *dht_bytes, int *optimized);
 
 /* The host half of the GIF decode front end alone (csrc/fl_gifsrc.h): the blob flgpu_process_gif uploads, all fields little-endian
  * dwords, offsets in bytes from the blob's start:

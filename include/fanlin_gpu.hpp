@@ -105,6 +105,9 @@ public:
     // ... with segment-adaptive quantisers (up to four classes of macroblocks by activity): FLGPU_FEO_SEGMENTS on whichever front
     // end the calls above select
     void encode_webp_lossy_segments() { flags_ |= FLGPU_ENCODE_WEBP_LOSSY | FLGPU_ENCODE_WEBP_LOSSY_SEGMENTS; }
+    // a JPEG that stays JPEG is coded with Huffman tables from the picture's own symbol counts (FLGPU_FEO_JPEG_OPTIMIZE): the same
+    // pixels in a smaller file, today's file where the tables do not pay
+    void encode_jpeg_optimize() { flags_ |= FLGPU_ENCODE_JPEG_OPTIMIZE; }
     uint32_t flags() const { return flags_; }
 
 private:
