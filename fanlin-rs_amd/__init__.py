@@ -38,6 +38,7 @@ FE_WEBP_LOSSY_LF, FE_WEBP_LOSSY_I4_LF, FE_WEBP_LOSSY_AP_LF, FE_WEBP_LOSSY_I4_AP_
 FE_WEBP_LOSSY_ALL = (9, 10, 12, 13, 16, 17, 18, 19)
 ACCEPT_WEBP, ACCEPT_AVIF = 1, 2
 ENCODE_PNG = 0x100  # accept_flags bit, not a content::Format bit: finish image/png bodies on the device (FE_PNG)
+DECODE_PNG_INFLATE = 0x100000  # accept_flags bit, not a content::Format bit: State.process_png has the deflate stream inflated on the device
 DECODE_PNG_ADAM7 = 0x10000  # accept_flags bit, not a content::Format bit: State.process_png also takes Adam7-interlaced files
 ENCODE_WEBP_LOSSLESS = 0x200  # accept_flags bit: finish lossless image/webp bodies (q == 100) on the device (FE_WEBP_LOSSLESS)
 ENCODE_WEBP_LOSSY = 0x800  # accept_flags bit: finish lossy image/webp bodies (q < 100) on the device (FE_WEBP_LOSSY)
@@ -69,6 +70,7 @@ _RESULT_FE = {RESULT_JPEG_STREAM: FE_JPEG, RESULT_WEBP_PLANES: FE_WEBP420, RESUL
 MIME = {IN_JPEG: "image/jpeg", IN_PNG: "image/png", IN_WEBP: "image/webp", IN_GIF_FRAME: "image/gif"}
 IMG_FRONTEND_PLANES, IMG_HAS_ALPHA, IMG_ENCODED, IMG_PINNED, IMG_JPEG_SOURCE, IMG_PNG_SOURCE, IMG_WEBP_SOURCE = 1, 2, 4, 8, 16, 32, 64
 IMG_VP8_SOURCE = 128
+IMG_PNG_INFLATE = 512  # beside IMG_PNG_SOURCE: the deflate stream is inflated on the device, the compressed payload crosses PCIe
 IMG_PNG_ADAM7 = 256  # beside IMG_PNG_SOURCE: the caller also hands in Adam7-interlaced PNG files
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 BATCH_SAME_PARAMS = 1
@@ -169,7 +171,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_transform_batch", "flgpu_transform_batch_device", "flgpu_batch_results", "flgpu_plan_shards", "flgpu_devices",
     "flgpu_cmyk_distribution", "flgpu_rccl_selftest", "flgpu_jpeg_info_of", "flgpu_decode_jpeg", "flgpu_process_jpeg", "flgpu_process_jpeg_plan",
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
-    "flgpu_png_info_of_flags", "flgpu_decode_png_flags", "flgpu_debug_png_scanlines_flags",
+    "flgpu_png_info_of_flags", "flgpu_decode_png_flags", "flgpu_debug_png_scanlines_flags", "flgpu_debug_png_inflate_device", "flgpu_debug_png_inflate_model",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
     "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs", "flgpu_debug_jpeg_optimize_tables",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
@@ -249,6 +251,9 @@ def load_library() -> C.CDLL:
         lib.flgpu_png_info_of_flags.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(flgpu_png_info)]
         lib.flgpu_decode_png_flags.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(flgpu_image)]
         lib.flgpu_debug_png_scanlines_flags.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "flgpu_debug_png_inflate_model"):  # (PNG sources whose deflate stream the device inflates)
+        lib.flgpu_debug_png_inflate_device.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.flgpu_debug_png_inflate_model.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     if hasattr(lib, "flgpu_webp_info_of"):  # (the same for lossless WebP sources)
         lib.flgpu_webp_info_of.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(flgpu_webp_info)]
         lib.flgpu_decode_webp.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(flgpu_image)]
@@ -472,6 +477,17 @@ class Adam7Png(bytes):
     (Bare ``bytes`` holding a PNG file are a FLGPU_IMG_PNG_SOURCE alone, for which an interlaced file is ERR_UNSUPPORTED.)"""
 
 
+class InflatePng(bytes):
+    """A PNG file for State.process_batch whose deflate stream the device inflates: handed over as FLGPU_IMG_PNG_SOURCE |
+    FLGPU_IMG_PNG_INFLATE, and with ``adam7=True`` | FLGPU_IMG_PNG_ADAM7 as well."""
+    adam7 = False
+
+    def __new__(cls, data, adam7: bool = False):
+        self = super().__new__(cls, data)
+        self.adam7 = bool(adam7)
+        return self
+
+
 class LossyWebp(bytes):
     """A lossy WebP file for State.process_batch: handed over as FLGPU_IMG_VP8_SOURCE.  (Bare ``bytes`` holding a WebP file are a
     FLGPU_IMG_WEBP_SOURCE, which takes lossless files only.)"""
@@ -526,10 +542,27 @@ def jpeg_info(data: bytes) -> dict:
     return _file_info(_JPEG, data)
 
 
-def png_info(data: bytes, adam7: bool = False) -> dict:
+def _png_flags(adam7: bool, device_inflate: bool) -> int:
+    return (IMG_PNG_ADAM7 if adam7 else 0) | (IMG_PNG_INFLATE if device_inflate else 0)
+
+
+def png_info(data: bytes, adam7: bool = False, device_inflate: bool = False) -> dict:
     """flgpu_png_info_of: header fields of a PNG file (pure host function); raises FanlinError(ERR_PARSE) if the container is damaged.
-    ``adam7``: flgpu_png_info_of_flags with IMG_PNG_ADAM7 -- an Adam7-interlaced file of up to 8 bits per sample is supported too."""
-    return _file_info(_PNG, data, IMG_PNG_ADAM7 if adam7 else 0)
+    ``adam7``: flgpu_png_info_of_flags with IMG_PNG_ADAM7 -- an Adam7-interlaced file of up to 8 bits per sample is supported too.
+    ``device_inflate``: with IMG_PNG_INFLATE -- accepted, and reports what it reports without it."""
+    return _file_info(_PNG, data, _png_flags(adam7, device_inflate))
+
+
+def debug_png_inflate_model(data: bytes):
+    """flgpu_debug_png_inflate_model: the host twin of the inflate kernel on a PNG file -> (scanlines, stats); stats = dict(blocks, strips,
+    sync_rounds, resolve_rounds, tokens, tokens_again, max_sync_rounds, max_resolve_rounds).  FanlinError(ERR_PARSE) = the device's "no"."""
+    lib = load_library()
+    used, stats = C.c_uint64(), (C.c_uint32 * 8)()
+    _check(lib.flgpu_debug_png_inflate_model(data, len(data), None, 0, C.byref(used), stats))
+    out = np.zeros(max(used.value, 1), np.uint8)
+    _check(lib.flgpu_debug_png_inflate_model(data, len(data), out.ctypes.data, out.nbytes, C.byref(used), stats))
+    names = ("blocks", "strips", "sync_rounds", "resolve_rounds", "tokens", "tokens_again", "max_sync_rounds", "max_resolve_rounds")
+    return out[: used.value].tobytes(), dict(zip(names, (int(v) for v in stats)))
 
 
 def debug_png_scanlines(data: bytes, adam7: bool = False) -> bytes:
@@ -588,6 +621,8 @@ def _source_info(data):
     """(header dict, source flags) of a file handed over as a source: LossyWebp and Adam7Png say what they are, PNG and WebP go by their
     signatures, anything else is a JPEG."""
     more = IMG_PNG_ADAM7 if isinstance(data, Adam7Png) else 0
+    if isinstance(data, InflatePng):
+        more = IMG_PNG_INFLATE | (IMG_PNG_ADAM7 if data.adam7 else 0)
     if isinstance(data, LossyWebp):
         fmt = _VP8
     elif more or bytes(data[:8]) == PNG_SIGNATURE:
@@ -899,20 +934,34 @@ class State:
         return self._process_file(_JPEG, data, query_string, content)
 
     # -- PNG sources: the decode front end (handler.rs:218-220) ----------------------------------------------------
-    def decode_png(self, data: bytes, adam7: bool = False) -> np.ndarray:
+    def decode_png(self, data: bytes, adam7: bool = False, device_inflate: bool = False) -> np.ndarray:
         """DynamicImage::from_decoder(PngDecoder::new(..)) on the device: (h, w, 1..4) uint8.  ``adam7``: flgpu_decode_png_flags with
-        IMG_PNG_ADAM7 -- Adam7-interlaced files are decoded too."""
-        return self._decode_file(_PNG, data, IMG_PNG_ADAM7 if adam7 else 0)
+        IMG_PNG_ADAM7 -- Adam7-interlaced files are decoded too.  ``device_inflate``: with IMG_PNG_INFLATE -- the deflate stream is
+        inflated on the device."""
+        return self._decode_file(_PNG, data, _png_flags(adam7, device_inflate))
 
-    def process_png_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None, adam7: bool = False):
+    def process_png_pixels(self, data: bytes, params: flgpu_params, shape: Optional[Tuple[int, int, int]] = None, adam7: bool = False,
+                           device_inflate: bool = False):
         """process_pixels with a PNG FILE as the source (FLGPU_IMG_PNG_SOURCE): inflate on this thread, the rest in one device pass.
         ``shape`` = (height, width, channels) to announce instead of what flgpu_png_info_of says (tests of rejected inputs).
-        ``adam7``: the source carries FLGPU_IMG_PNG_ADAM7 as well -- it may be an Adam7-interlaced file."""
-        return self._process_file_pixels(_PNG, data, params, shape, IMG_PNG_ADAM7 if adam7 else 0)
+        ``adam7``: the source carries FLGPU_IMG_PNG_ADAM7 as well -- it may be an Adam7-interlaced file.
+        ``device_inflate``: the source carries FLGPU_IMG_PNG_INFLATE -- this thread only stages the file, the device inflates it."""
+        return self._process_file_pixels(_PNG, data, params, shape, _png_flags(adam7, device_inflate))
+
+    def debug_png_inflate_device(self, data: bytes, adam7: bool = False) -> bytes:
+        """flgpu_debug_png_inflate_device: the scanlines of a PNG file exactly as the inflate kernel leaves them (no host re-run: a device
+        "no" raises FanlinError(ERR_PARSE))."""
+        flags = _png_flags(adam7, True)
+        used = C.c_uint64()
+        _check(self._lib.flgpu_debug_png_inflate_device(self._ctx, data, len(data), flags, None, 0, C.byref(used)), self._ctx)
+        out = np.zeros(max(used.value, 1), np.uint8)
+        _check(self._lib.flgpu_debug_png_inflate_device(self._ctx, data, len(data), flags, out.ctypes.data, out.nbytes, C.byref(used)), self._ctx)
+        return out[: used.value].tobytes()
 
     def process_png(self, data: bytes, query_string: str, content: "Format" = None):
         """State::process_image for a PNG input from the file bytes on: (mime, kind, payload) as process_image; AS_IS hands the
-        file itself back.  With DECODE_PNG_ADAM7 in the content flags Adam7-interlaced files are taken too."""
+        file itself back.  With DECODE_PNG_ADAM7 in the content flags Adam7-interlaced files are taken too; with DECODE_PNG_INFLATE the
+        deflate stream is inflated on the device."""
         return self._process_file(_PNG, data, query_string, content)
 
     # -- lossless WebP sources: the decode front end (handler.rs:205-220) ------------------------------------------
@@ -1021,7 +1070,7 @@ class State:
         return {k: self.debug_get(k) for k in ("png_sources", "png_file_bytes", "png_upload_bytes")}
 
     def process_batch(self, images: Sequence, params: Sequence[flgpu_params]) -> List:
-        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file, or a LossyWebp, or an Adam7Png (decoded by the library)."""
+        """images[i]: an ndarray of pixels, or `bytes` holding a JPEG, a PNG or a lossless WebP file, or a LossyWebp, or an Adam7Png, or an InflatePng (decoded by the library)."""
         n = len(images)
         srcinfo = [_source_info(a) if isinstance(a, (bytes, bytearray)) else (None, 0) for a in images]
         infos = [s[0] for s in srcinfo]

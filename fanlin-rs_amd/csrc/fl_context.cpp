@@ -518,6 +518,7 @@ void flgpu_destroy(flgpu_ctx *c)
     c->enc.release();
     c->d_dec.release(); c->d_decjobs.release(); c->h_decjobs.release();
     c->d_pngdec.release(); c->d_pngjobs.release(); c->h_pngjobs.release();
+    c->d_inf.release(); c->d_infjobs.release(); c->d_inferr.release(); c->h_infjobs.release(); c->h_inferr.release();
     c->d_webpdec.release(); c->d_webpjobs.release(); c->h_webpjobs.release();
     c->d_vp8dec.release(); c->d_vp8jobs.release(); c->h_vp8jobs.release();
     c->d_gifdec.release();
@@ -635,7 +636,7 @@ int flgpu_reset_stats(flgpu_ctx *c)
         resolve_pending(c);
         c->stats = flgpu_stats{};
         c->blur_wtile_launches = c->blur_tile_launches = c->blur_generic_launches = 0;
-        c->png_sources = c->png_file_bytes = c->png_upload_bytes = 0;
+        c->png_sources = c->png_file_bytes = c->png_upload_bytes = c->png_device_inflates = c->png_inflate_retries = 0;
         c->webp_sources = c->webp_file_bytes = c->webp_upload_bytes = c->webp_predict_ns = c->webp_pointwise_ns = c->webp_lossy_ns = 0;
         c->vp8_sources = c->vp8_file_bytes = c->vp8_upload_bytes = c->vp8_decode_ns = 0;
         c->gif_sources = c->gif_frames = c->gif_file_bytes = c->gif_upload_bytes = c->gif_compose_ns = 0;
@@ -666,6 +667,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
     // read-only counters of the PNG, lossless WebP, lossy WebP and GIF decode front ends and of the blur's routes (flgpu_stats keeps its size): this context's and its lanes' / shards'
     static const struct { const char *name; uint64_t flgpu_ctx::*field; } counters[] = {
         {"png_sources", &flgpu_ctx::png_sources}, {"png_file_bytes", &flgpu_ctx::png_file_bytes}, {"png_upload_bytes", &flgpu_ctx::png_upload_bytes},
+        {"png_device_inflates", &flgpu_ctx::png_device_inflates}, {"png_inflate_retries", &flgpu_ctx::png_inflate_retries},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
         {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments}, {"jpeg_optimized", &flgpu_ctx::jpeg_optimized},

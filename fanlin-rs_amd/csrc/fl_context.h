@@ -218,6 +218,9 @@ struct flgpu_ctx {
     fl::PinnedBuf h_jhjobs, h_jherr;
     fl::DeviceBuf d_pngdec, d_pngjobs;                 // PNG decode (fl_pngdec.hip): unfiltered rows + pixels of a batch, job descriptors
     fl::PinnedBuf h_pngjobs;
+    fl::DeviceBuf d_inf, d_infjobs, d_inferr;          // device inflate of PNG sources (fl_inflate.hip): header + scanlines per picture, job descriptors, error words
+    fl::PinnedBuf h_infjobs, h_inferr;
+    uint64_t png_device_inflates = 0, png_inflate_retries = 0; // pictures the inflate kernel inflated / said no to (those are run again on the host)
     uint64_t png_sources = 0, png_file_bytes = 0, png_upload_bytes = 0; // counters behind flgpu_debug_get (guarded by mu)
     fl::DeviceBuf d_webpdec, d_webpjobs;               // lossless WebP decode (fl_webpdec.hip): intermediate pictures + pixels of a batch, job descriptors
     fl::PinnedBuf h_webpjobs;
@@ -240,6 +243,8 @@ struct flgpu_ctx {
     uint64_t gif_encode_ns = 0;                        // HIP-event time of the encode kernels' launches (profile = 1)
     std::vector<int32_t> last_jh_slot; // per image of the batch decoded last: index of its error word, -1 = not entropy-decoded on the device
     uint32_t last_jh_n = 0;
+    std::vector<int32_t> last_inf_slot; // the same for the device inflate of PNG sources
+    uint32_t last_inf_n = 0;
     fl::EncodeBuffers enc; // the encoders' scratch (fl_encode.h)
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front

@@ -4,6 +4,11 @@
 
 #include <string.h>
 
+#include <memory>
+#include <vector>
+
+#include "fl_inflate_core.h"
+
 namespace fl {
 namespace {
 
@@ -426,6 +431,34 @@ int inflate(BitReader &br, uint8_t *out, size_t cap, size_t *produced)
     return 0;
 }
 
+// the blob header of the picture `C` describes
+void fill_header(const Container &C, uint32_t magic, size_t total_bytes, PngBlobHeader *hdr)
+{
+    const PngInfo &I = C.info;
+    memset(hdr, 0, sizeof(*hdr));
+    hdr->magic = magic;
+    hdr->width = I.width; hdr->height = I.height;
+    hdr->color_type = I.color_type; hdr->bit_depth = I.bit_depth;
+    hdr->channels = I.channels; hdr->bpp = I.bpp; hdr->row_bytes = I.row_bytes;
+    hdr->has_trns = I.has_trns;
+    hdr->interlaced = I.interlaced;
+    // (an interlaced picture's rows are never its pixels: the de-interlace kernel puts them together)
+    hdr->direct = (I.bit_depth == 8 && I.color_type != 3 && !I.has_trns && !I.interlaced) ? 1u : 0u;
+    hdr->scan_off = (uint32_t)sizeof(PngBlobHeader);
+    hdr->total_bytes = (uint32_t)total_bytes;
+    // the key is compared on the raw sample (its low byte: samples have at most 8 bits here)
+    if (I.has_trns && I.color_type == 0) hdr->key[0] = C.trns[1];
+    if (I.has_trns && I.color_type == 2) { hdr->key[0] = C.trns[1]; hdr->key[1] = C.trns[3]; hdr->key[2] = C.trns[5]; }
+    for (uint32_t k = 0; k < 256; ++k) {
+        uint32_t e = 0xff000000u; // beyond PLTE: opaque black
+        if (I.color_type == 3) {
+            if (k < I.plte_entries) e |= (uint32_t)C.plte[3 * k] | (uint32_t)C.plte[3 * k + 1] << 8 | (uint32_t)C.plte[3 * k + 2] << 16;
+            if (I.has_trns && k < C.trns_len) e = (e & 0x00ffffffu) | (uint32_t)C.trns[k] << 24;
+        }
+        hdr->palette[k] = e;
+    }
+}
+
 } // namespace
 
 int png_parse_info(const uint8_t *data, size_t n, PngInfo &info, bool verify_crc, bool adam7)
@@ -458,29 +491,180 @@ int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t ca
         for (uint32_t y = 0; y < P.h; ++y)
             if (scan[(size_t)P.scan_off + (size_t)y * stride] > 4u) return kPngParse;
     }
-    if (hdr) {
-        memset(hdr, 0, sizeof(*hdr));
-        hdr->magic = kPngMagic;
-        hdr->width = I.width; hdr->height = I.height;
-        hdr->color_type = I.color_type; hdr->bit_depth = I.bit_depth;
-        hdr->channels = I.channels; hdr->bpp = I.bpp; hdr->row_bytes = I.row_bytes;
-        hdr->has_trns = I.has_trns;
-        hdr->interlaced = I.interlaced;
-        // (an interlaced picture's rows are never its pixels: the de-interlace kernel puts them together)
-        hdr->direct = (I.bit_depth == 8 && I.color_type != 3 && !I.has_trns && !I.interlaced) ? 1u : 0u;
-        hdr->scan_off = (uint32_t)sizeof(PngBlobHeader);
-        hdr->total_bytes = (uint32_t)(sizeof(PngBlobHeader) + want);
-        // the key is compared on the raw sample (its low byte: samples have at most 8 bits here)
-        if (I.has_trns && I.color_type == 0) hdr->key[0] = C.trns[1];
-        if (I.has_trns && I.color_type == 2) { hdr->key[0] = C.trns[1]; hdr->key[1] = C.trns[3]; hdr->key[2] = C.trns[5]; }
-        for (uint32_t k = 0; k < 256; ++k) {
-            uint32_t e = 0xff000000u; // beyond PLTE: opaque black
-            if (I.color_type == 3) {
-                if (k < I.plte_entries) e |= (uint32_t)C.plte[3 * k] | (uint32_t)C.plte[3 * k + 1] << 8 | (uint32_t)C.plte[3 * k + 2] << 16;
-                if (I.has_trns && k < C.trns_len) e = (e & 0x00ffffffu) | (uint32_t)C.trns[k] << 24;
-            }
-            hdr->palette[k] = e;
+    if (hdr) fill_header(C, kPngMagic, sizeof(PngBlobHeader) + want, hdr);
+    return 0;
+}
+
+// ---- sources whose deflate stream the device inflates ----------------------------------------------------------------------------
+
+int png_stage_compressed(const uint8_t *data, size_t n, uint8_t *blob, size_t cap, PngBlobHeader *hdr, bool adam7)
+{
+    Container C;
+    const int rc = walk(data, n, C, true, adam7);
+    if (rc) return rc;
+    const PngInfo &I = C.info;
+    if (!I.supported) return kPngUnsupported;
+    const size_t total = png_stage_bytes(I);
+    if (!blob || !hdr || cap < total || total > 0xffffffffu) return kPngSmall;
+    fill_header(C, kPngzMagic, total, hdr);
+    memcpy(blob, hdr, sizeof(*hdr));
+    uint8_t *to = blob + sizeof(PngBlobHeader);
+    size_t pos = C.first_idat, left = (size_t)I.idat_bytes;
+    Chunk c;
+    while (left && next_chunk(data, n, pos, c) == 0 && c.type == kIDAT) { // (consecutive, and their lengths sum to idat_bytes: the walk has seen to both)
+        if (c.len > left) return kPngParse;
+        memcpy(to, c.p, c.len);
+        to += c.len; left -= c.len;
+    }
+    if (left) return kPngParse;
+    memset(to, 0, kPngzPad);
+    return 0;
+}
+
+int png_inflate_model(const uint8_t *staged, size_t staged_bytes, uint8_t *out, size_t cap, uint32_t stats[8])
+{
+    uint32_t none[8];
+    if (!stats) stats = none;
+    memset(stats, 0, 8 * sizeof(uint32_t));
+    PngBlobHeader H;
+    if (!staged || staged_bytes < sizeof(H) + kPngzPad) return kPngParse;
+    memcpy(&H, staged, sizeof(H));
+    if (H.magic != kPngzMagic || H.total_bytes != staged_bytes) return kPngParse;
+    const uint32_t payload = (uint32_t)(staged_bytes - sizeof(H) - kPngzPad);
+    const size_t want = png_header_scan_bytes(H);
+    if (want >= kPngMaxDecoded) return kPngParse;
+    if (!out || cap < want) return kPngSmall;
+    const uint32_t expected = (uint32_t)want;
+    // the kernel's view of the payload: whole words, zero bits past them
+    const uint64_t nwords = ((uint64_t)payload + kPngzPad) / 4u, total_bits = (uint64_t)payload * 8u;
+    std::vector<uint32_t> words((size_t)nwords);
+    memcpy(words.data(), staged + sizeof(H), (size_t)nwords * 4u);
+    const uint8_t *bytes = staged + sizeof(H);
+    // the kernel's LDS, array by array
+    std::vector<uint32_t> window(kInfWindowWords), state(kInfSubs + 1u), seen(kInfSubs), cnt(kInfSubs), ntok(kInfSubs), in(kInfSubs), pos(kInfSubs), off(kInfSubs);
+    std::vector<uint8_t> lengths(320), fin(kInfSubs);
+    std::unique_ptr<InfTable> fixed_lit(new InfTable), fixed_dist(new InfTable), lit(new InfTable), dist(new InfTable), cl(new InfTable);
+
+    if (payload < 2u) return kPngParse;
+    {
+        const uint32_t cmf = bytes[0], flg = bytes[1];
+        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) return kPngParse;
+    }
+    inf_fixed_tables(*fixed_lit, *fixed_dist, lengths.data());
+    uint64_t P = 16;
+    uint32_t obase = 0, exact_total = 0;
+    for (bool last = false; !last;) {
+        if (total_bits - P < 3u) return kPngParse;
+        stats[0]++;
+        const uint64_t hw = P >> 5;
+        const uint32_t hb = (uint32_t)P & 31u;
+        for (uint32_t k = 0; k < kInfHeaderWords; ++k) window[k] = hw + k < nwords ? words[(size_t)(hw + k)] : 0u;
+        const uint64_t hv = inf_peek(window.data(), kInfHeaderWords, hb);
+        last = (hv & 1u) != 0;
+        const uint32_t type = (uint32_t)(hv >> 1) & 3u;
+        if (type == 3u) return kPngParse;
+        if (type == 0u) {
+            const uint64_t at = (P + 3u + 7u) >> 3;
+            if (at + 4u > payload) return kPngParse;
+            const uint32_t len = bytes[at] | (uint32_t)bytes[at + 1] << 8, nlen = bytes[at + 2] | (uint32_t)bytes[at + 3] << 8;
+            if ((len ^ nlen) != 0xffffu) return kPngParse;
+            if (len > payload - at - 4u) return kPngParse;
+            if (len > expected - obase) return kPngParse;
+            memcpy(out + obase, bytes + at + 4u, len);
+            obase += len;
+            P = (at + 4u + len) * 8u;
+            continue;
         }
+        const InfTable *L = fixed_lit.get(), *D = fixed_dist.get();
+        if (type == 2u) {
+            const uint64_t rem = total_bits - (hw << 5);
+            const uint32_t q = inf_dynamic_header(window.data(), kInfHeaderWords, hb + 3u, rem > (1u << 28) ? 1u << 28 : (uint32_t)rem, *cl, *lit, *dist, lengths.data());
+            if (!q) return kPngParse;
+            P = (hw << 5) + q;
+            L = lit.get(); D = dist.get();
+        } else {
+            P += 3u;
+        }
+        for (bool in_block = true; in_block;) {
+            stats[1]++;
+            const uint64_t wb = P >> 5;
+            const uint32_t base = (uint32_t)P & 31u;
+            for (uint32_t k = 0; k < kInfWindowWords; ++k) window[k] = wb + k < nwords ? words[(size_t)(wb + k)] : 0u;
+            const uint64_t rem = total_bits - (wb << 5);
+            const uint32_t limit = rem > (1u << 28) ? 1u << 28 : (uint32_t)rem;
+            for (uint32_t t = 0; t < kInfSubs; ++t) { state[t] = base + t * kInfSubBits; seen[t] = kInfNever; cnt[t] = ntok[t] = 0; }
+            // 1. synchronisation: every "thread" reads its state, then every thread whose state changed walks again
+            bool settled = false;
+            uint32_t rounds = 0;
+            for (uint32_t round = 0; round < kInfSubs + 2u; ++round) {
+                for (uint32_t t = 0; t < kInfSubs; ++t) in[t] = state[t];
+                bool changed = false;
+                for (uint32_t t = 0; t < kInfSubs; ++t) {
+                    if (in[t] == seen[t]) continue;
+                    seen[t] = in[t];
+                    uint32_t st = kInfDead;
+                    cnt[t] = ntok[t] = 0;
+                    if (!(in[t] & kInfFlags)) {
+                        st = inf_walk(*L, *D, window.data(), kInfWindowWords, in[t], base + (t + 1u) * kInfSubBits, limit, cnt[t], ntok[t]);
+                        stats[4] += ntok[t];
+                    }
+                    state[t + 1u] = st;
+                    changed = true;
+                }
+                if (!changed) { settled = true; break; }
+                ++rounds;
+            }
+            if (!settled) return kPngParse;
+            stats[2] += rounds;
+            if (rounds > stats[6]) stats[6] = rounds;
+            // 2. the block's end, the output offsets
+            uint32_t e = kInfNever, total = 0;
+            for (uint32_t t = 0; t < kInfSubs && e == kInfNever; ++t) if (state[t + 1u] & (kInfEob | kInfInvalid)) e = t;
+            if (e != kInfNever && (state[e + 1u] & kInfInvalid)) return kPngParse;
+            uint32_t exact = 0;
+            for (uint32_t t = 0; t < kInfSubs; ++t) { off[t] = total; total += cnt[t]; exact += ntok[t]; }
+            stats[5] = stats[4] - (exact_total += exact); // (stats[4] counts every walk: what is left once the exact tokens are taken off was decoded again)
+            if (total > expected - obase) return kPngParse;
+            // 3. write and resolve
+            for (uint32_t t = 0; t < kInfSubs; ++t) { pos[t] = seen[t]; off[t] += obase; fin[t] = (seen[t] & kInfFlags) != 0; }
+            uint32_t done = obase, rr = 0;
+            for (;; ++rr) {
+                if (rr > kInfStripBits + 1u) return kPngParse;
+                uint32_t next = kInfNever;
+                for (uint32_t t = 0; t < kInfSubs; ++t) {
+                    if (fin[t]) continue;
+                    const int r = inf_resolve(*L, *D, window.data(), kInfWindowWords, pos[t], base + (t + 1u) * kInfSubBits, off[t], done, out, expected);
+                    if (r == kInfFail) return kPngParse;
+                    if (r == kInfPending) { if (off[t] < next) next = off[t]; }
+                    else fin[t] = 1;
+                }
+                if (next == kInfNever) break;
+                done = next;
+            }
+            stats[3] += rr + 1u;
+            if (rr + 1u > stats[7]) stats[7] = rr + 1u;
+            obase += total;
+            if (e != kInfNever) { P = (wb << 5) + (state[e + 1u] & ~kInfFlags); in_block = false; }
+            else P = (wb << 5) + state[kInfSubs];
+        }
+    }
+    if (obase != expected) return kPngParse;
+    const uint64_t at = (P + 7u) >> 3;
+    if (at + 4u > payload) return kPngParse;
+    const uint32_t check = (uint32_t)bytes[at] << 24 | (uint32_t)bytes[at + 1] << 16 | (uint32_t)bytes[at + 2] << 8 | bytes[at + 3];
+    uint64_t s1 = 0, s2 = 0;
+    for (uint32_t j = 0; j < expected; j += 16u) {
+        const uint32_t k = expected - j < 16u ? expected - j : 16u;
+        inf_adler_piece(s1, s2, out + j, k, (expected - j) % kAdlerMod);
+        s1 %= kAdlerMod; s2 %= kAdlerMod;
+    }
+    if (inf_adler_finish(s1, s2, expected) != check) return kPngParse;
+    for (uint32_t p = 0; p < (H.interlaced ? kAdam7Passes : 1u); ++p) {
+        const Adam7Pass A = H.interlaced ? adam7_pass(H.width, H.height, png_pixel_bits(H), p) : Adam7Pass{H.width, H.height, H.row_bytes, 0, 0};
+        if (!A.w || !A.h) continue;
+        const size_t stride = 1u + (size_t)A.row_bytes;
+        for (uint32_t y = 0; y < A.h; ++y)
+            if (out[(size_t)A.scan_off + (size_t)y * stride] > 4u) return kPngParse;
     }
     return 0;
 }

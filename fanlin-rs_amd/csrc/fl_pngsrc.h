@@ -30,6 +30,10 @@ struct PngInfo {
 constexpr int kPngParse = -1, kPngUnsupported = -2, kPngSmall = -3;
 
 constexpr uint32_t kPngMagic = 0x31444e50u; // "PND1"
+// A source that carries FLGPU_IMG_PNG_INFLATE is staged compressed: the same header under this magic, then the IDAT payloads back to back
+// (total_bytes - header - kPngzPad bytes of them), then kPngzPad zero bytes so the kernel may read whole words past the end.
+constexpr uint32_t kPngzMagic = 0x5a444e50u; // "PNDZ"
+constexpr uint32_t kPngzPad = 16;
 // the decoded picture may not exceed what the reference's decoder runs under (image::Limits::default(): 512 MiB), and the
 // pipeline addresses pictures below 2^31 bytes
 constexpr uint64_t kPngMaxDecoded = 1ull << 31;
@@ -73,5 +77,23 @@ inline size_t png_blob_bytes(const PngInfo &info) { return sizeof(PngBlobHeader)
 // hdr (optional) receives the header of the blob.  `scan` is the inflate window: nothing else is allocated.
 // adam7 = true: as for png_parse_info; the stream of an interlaced file is left as it is stored, pass after pass.
 int png_decode_scanlines(const uint8_t *data, size_t n, uint8_t *scan, size_t cap, PngBlobHeader *hdr, bool adam7 = false);
+
+// Bytes of the staging of a source whose deflate stream the device inflates (fl_inflate.h): header + IDAT payloads + pad.
+inline size_t png_stage_bytes(const PngInfo &info) { return sizeof(PngBlobHeader) + (size_t)info.idat_bytes + kPngzPad; }
+// The host half of such a source: the same container walk with the same CRC checks as png_decode_scanlines, then the IDAT payloads
+// copied back to back behind the header (magic kPngzMagic).  Nothing is inflated here.  blob[0 .. png_stage_bytes) is written.
+int png_stage_compressed(const uint8_t *data, size_t n, uint8_t *blob, size_t cap, PngBlobHeader *hdr, bool adam7 = false);
+// Bytes of the scanlines a blob header stands for.
+inline size_t png_header_scan_bytes(const PngBlobHeader &h)
+{
+    if (h.interlaced) return (size_t)adam7_scan_bytes(h.width, h.height, png_pixel_bits(h));
+    return (size_t)h.height * (1u + (size_t)h.row_bytes);
+}
+// The host twin of the inflate kernel: the kernel's algorithm (fl_inflate_core.h) in plain loops over arrays of the kernel's LDS sizes,
+// on what png_stage_compressed left.  0 and scan[0 .. png_header_scan_bytes) = the scanlines, or kPngParse = the device's "no" (a
+// caller then runs png_decode_scanlines, whose verdict is final), or kPngSmall.  stats: [0] blocks, [1] strips, [2] synchronisation
+// rounds, [3] resolution rounds, [4] tokens decoded, [5] of those decoded more than once, [6] / [7] the most synchronisation / resolution
+// rounds of one strip.
+int png_inflate_model(const uint8_t *staged, size_t staged_bytes, uint8_t *scan, size_t cap, uint32_t stats[8]);
 
 } // namespace fl

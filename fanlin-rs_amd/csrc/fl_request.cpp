@@ -15,7 +15,8 @@ static int plan_file(SourceKind kind, const uint8_t *file, uint64_t n, const cha
 {
     if (!file) return FLGPU_ERR_INVALID_ARG;
     /* FLGPU_DECODE_PNG_ADAM7 in the accept flags becomes FLGPU_IMG_PNG_ADAM7 on the source */
-    const uint32_t adam7 = kind == fl::SRC_PNG && (accept_flags & FLGPU_DECODE_PNG_ADAM7) ? fl::HEAD_ADAM7 : 0u;
+    const uint32_t adam7 = kind != fl::SRC_PNG ? 0u : ((accept_flags & FLGPU_DECODE_PNG_ADAM7) ? fl::HEAD_ADAM7 : 0u) |
+                           ((accept_flags & FLGPU_DECODE_PNG_INFLATE) ? fl::HEAD_INFLATE : 0u); /* ... and FLGPU_DECODE_PNG_INFLATE becomes FLGPU_IMG_PNG_INFLATE */
     fl::SourceProbe probe;
     if (int rc = fl::file_head(kind, file, (size_t)n, fl::HEAD_SNIFF | adam7, probe)) return rc;
     const fl::FileHead &h = probe.head;
@@ -50,7 +51,7 @@ static int decode_file(flgpu_ctx *ctx, SourceKind kind, uint32_t src_flags, cons
 {
     if (!ctx || !dst || !dst->data || !file) return FLGPU_ERR_INVALID_ARG;
     fl::SourceProbe probe;
-    if (int rc = fl::file_head(kind, file, (size_t)n, (src_flags & FLGPU_IMG_PNG_ADAM7) ? fl::HEAD_ADAM7 : 0u, probe)) return rc;
+    if (int rc = fl::file_head(kind, file, (size_t)n, fl::png_head_opts(src_flags), probe)) return rc;
     if (!probe.head.supported) return FLGPU_ERR_UNSUPPORTED;
     const flgpu_image src = fl::file_image(file, n, probe.head);
     flgpu_params p;
@@ -238,6 +239,31 @@ try {
     if (capacity < H.total_bytes) return FLGPU_ERR_BUFFER_TOO_SMALL;
     memcpy(out, work.p, H.total_bytes);
     return FLGPU_OK;
+} FL_ABI_CATCH
+
+int flgpu_debug_png_inflate_device(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used)
+try {
+    if (!ctx || !png || !used) return FLGPU_ERR_INVALID_ARG;
+    size_t u = 0;
+    const int rc = fl::debug_png_inflate_device(ctx, png, (size_t)n, src_flags, out, (size_t)capacity, &u);
+    *used = u;
+    return rc;
+} FL_ABI_CATCH
+
+int flgpu_debug_png_inflate_model(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used, uint32_t stats[8])
+try {
+    if (!png || !used) return FLGPU_ERR_INVALID_ARG;
+    fl::SourceProbe probe;
+    if (int rc = fl::file_head(fl::SRC_PNG, png, (size_t)n, fl::HEAD_FULL | fl::HEAD_ADAM7, probe)) return rc; // (an interlaced stream is the same deflate stream)
+    if (!probe.head.supported) return FLGPU_ERR_UNSUPPORTED;
+    *used = fl::png_scan_bytes(probe.png);
+    if (!out) return FLGPU_OK;
+    if (capacity < *used) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const size_t cap = fl::png_stage_bytes(probe.png);
+    fl::WorkBuf work(cap);
+    fl::PngBlobHeader H;
+    if (int rc = fl::png_stage_compressed(png, (size_t)n, work.p, cap, &H, true)) return fl::png_status(rc);
+    return fl::png_status(fl::png_inflate_model(work.p, cap, out, (size_t)capacity, stats));
 } FL_ABI_CATCH
 
 int flgpu_debug_vp8_planes(flgpu_ctx *ctx, const uint8_t *webp, uint64_t n, int filter, uint8_t *out, uint64_t capacity, uint64_t *used)

@@ -239,7 +239,7 @@ static uint32_t webp_orientation(const uint8_t *file, size_t exif_off, size_t ex
 
 int file_head(SourceKind kind, const uint8_t *file, size_t n, uint32_t opts, SourceProbe &out)
 {
-    const bool full = (opts & HEAD_FULL) != 0, adam7 = (opts & HEAD_ADAM7) != 0;
+    const bool full = (opts & HEAD_FULL) != 0, adam7 = (opts & HEAD_ADAM7) != 0, inflate = (opts & HEAD_INFLATE) != 0;
     if (kind == SRC_WEBP && (opts & HEAD_SNIFF) && webp_is_lossy(file, n)) kind = SRC_VP8;
     out.kind = kind;
     FileHead &h = out.head;
@@ -255,7 +255,7 @@ int file_head(SourceKind kind, const uint8_t *file, size_t n, uint32_t opts, Sou
         break;
     case SRC_PNG: // (the PNG decoder reports no orientation, handler.rs:206)
         if (png_parse_info(file, n, out.png, full, adam7) != 0) return FLGPU_ERR_PARSE;
-        fill(out.png, out.png.channels, FLGPU_IMG_PNG_SOURCE | (adam7 ? FLGPU_IMG_PNG_ADAM7 : 0u), FLGPU_IN_PNG, 0);
+        fill(out.png, out.png.channels, FLGPU_IMG_PNG_SOURCE | (adam7 ? FLGPU_IMG_PNG_ADAM7 : 0u) | (inflate ? FLGPU_IMG_PNG_INFLATE : 0u), FLGPU_IN_PNG, 0);
         break;
     case SRC_WEBP:
         if (webp_parse_info(file, n, out.webp, full) != 0) return FLGPU_ERR_PARSE;
@@ -287,7 +287,7 @@ static int file_source_check(flgpu_ctx *c, const flgpu_image *src, SourceProbe &
          "FLGPU_IMG_VP8_SOURCE: width / height / channels do not match the file (see flgpu_vp8_info_of)"}};
     const auto &t = kTexts[out.kind - SRC_PNG];
     const bool adam7 = (src->flags & FLGPU_IMG_PNG_ADAM7) != 0;
-    if (file_head(out.kind, src->data, (size_t)src->capacity, adam7 ? HEAD_ADAM7 : 0u, out) != 0) { c->set_error(t.malformed); return FLGPU_ERR_PARSE; }
+    if (file_head(out.kind, src->data, (size_t)src->capacity, png_head_opts(src->flags), out) != 0) { c->set_error(t.malformed); return FLGPU_ERR_PARSE; }
     const FileHead &h = out.head;
     if (!h.supported) {
         // the two refusals with a text of their own: a lossy WebP names the feature, a PNG asked for with Adam7 does not list it
@@ -301,9 +301,20 @@ static int file_source_check(flgpu_ctx *c, const flgpu_image *src, SourceProbe &
 
 // ---- PNG sources -----------------------------------------------------------------------------------------------------------------
 
+// whether the deflate stream of a source with these flags goes to the device (not in the second run after the device said no)
+static bool png_device_inflate(uint32_t src_flags) { return (src_flags & FLGPU_IMG_PNG_INFLATE) != 0 && !tl_force_host_huffman; }
+
 static int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blob, size_t cap, PngBlobHeader *hdr, size_t *used)
 {
     if (cap < sizeof(PngBlobHeader)) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    if (png_device_inflate(src->flags)) {
+        // only the container walk (with its CRCs) and one copy here: the device inflates the stream, and whatever it says no to comes back for the host inflate
+        const int rc = png_stage_compressed(src->data, (size_t)src->capacity, blob, cap, hdr, (src->flags & FLGPU_IMG_PNG_ADAM7) != 0);
+        if (rc == kPngParse) c->set_error("malformed PNG file (chunk CRC, Huffman code, distance, length, Adler-32 or filter byte)");
+        if (rc) return png_status(rc);
+        *used = hdr->total_bytes;
+        return FLGPU_OK;
+    }
     const int rc = png_decode_scanlines(src->data, (size_t)src->capacity, blob + sizeof(PngBlobHeader), cap - sizeof(PngBlobHeader), hdr,
                                         (src->flags & FLGPU_IMG_PNG_ADAM7) != 0);
     if (rc == kPngParse) c->set_error("malformed PNG file (chunk CRC, Huffman code, distance, length, Adler-32 or filter byte)");
@@ -311,6 +322,42 @@ static int png_source_to_blob(flgpu_ctx *c, const flgpu_image *src, uint8_t *blo
     if (rc) return png_status(rc);
     memcpy(blob, hdr, sizeof(*hdr));
     *used = hdr->total_bytes;
+    return FLGPU_OK;
+}
+
+// The pictures staged compressed (kPngzMagic): one launch inflates them all, each into a scratch laid out like the blob of the host path, and
+// dsrc[i].data is pointed at it.  Without such a picture nothing is reserved and nothing launched.
+static int inflate_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource *const *srcs, hipStream_t st)
+{
+    size_t ni = 0, bytes = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (srcs[i]->kind == SRC_PNG && srcs[i]->png.magic == kPngzMagic) { ++ni; bytes += align_up(sizeof(PngBlobHeader) + png_header_scan_bytes(srcs[i]->png) + 64, 256); }
+    if (!ni) return FLGPU_OK;
+    FL_HIP(c, c->d_inf.reserve(bytes), "PNG inflate scratch");
+    FL_HIP(c, c->d_inferr.reserve(ni * 4), "PNG inflate error words");
+    FL_HIP(c, c->h_inferr.reserve(ni * 4), "PNG inflate error words");
+    FL_HIP(c, c->h_infjobs.reserve(ni * sizeof(InfJob)), "PNG inflate descriptors");
+    FL_HIP(c, c->d_infjobs.reserve(ni * sizeof(InfJob)), "PNG inflate descriptors");
+    InfJob *jobs = static_cast<InfJob *>(c->h_infjobs.p);
+    size_t off = 0, k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (srcs[i]->kind != SRC_PNG || srcs[i]->png.magic != kPngzMagic) continue;
+        const PngBlobHeader &H = srcs[i]->png;
+        const size_t scan = png_header_scan_bytes(H);
+        if (H.total_bytes < sizeof(PngBlobHeader) + kPngzPad || H.total_bytes > dsrc[i].capacity || scan >= kPngMaxDecoded) { c->set_error("PNG source: damaged blob header"); return FLGPU_ERR_INVALID_ARG; }
+        InfJob &j = jobs[k];
+        memset(&j, 0, sizeof(j));
+        j.stage = dsrc[i].data;
+        j.scratch = static_cast<uint8_t *>(c->d_inf.p) + off; off += align_up(sizeof(PngBlobHeader) + scan + 64, 256);
+        j.err = static_cast<uint32_t *>(c->d_inferr.p) + k;
+        j.payload_bytes = (uint32_t)(H.total_bytes - sizeof(PngBlobHeader) - kPngzPad);
+        j.expected = (uint32_t)scan;
+        dsrc[i].data = j.scratch; // what the unfilter, expand and Adam7 kernels read from here on
+        c->last_inf_slot[i] = (int32_t)k++;
+    }
+    FL_HIP(c, hipMemcpyAsync(c->d_infjobs.p, jobs, ni * sizeof(InfJob), hipMemcpyHostToDevice, st), "PNG inflate descriptors");
+    FL_HIP(c, launch_png_inflate(static_cast<const InfJob *>(c->d_infjobs.p), (uint32_t)ni, st), "PNG inflate kernel");
+    c->last_inf_n = (uint32_t)ni;
     return FLGPU_OK;
 }
 
@@ -335,7 +382,10 @@ static int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const S
         ++nu;
         if (!H->direct) { scratch += align_up((size_t)H->height * H->row_bytes + 64, 256); ++nx_all; }
     }
+    c->last_inf_slot.assign(n, -1);
+    c->last_inf_n = 0;
     if (!np) return FLGPU_OK;
+    if (int rc = inflate_png_sources(c, n, dsrc, srcs, st)) return rc;
     FL_HIP(c, c->d_pngdec.reserve(scratch), "PNG decode scratch");
     FL_HIP(c, c->h_pngjobs.reserve((nu + nx_all + na_all) * sizeof(PngDecJob)), "PNG decode descriptors");
     FL_HIP(c, c->d_pngjobs.reserve((nu + nx_all + na_all) * sizeof(PngDecJob)), "PNG decode descriptors");
@@ -381,7 +431,7 @@ static int decode_png_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const S
             dsrc[i].data = j.pixels;
             dsrc[i].channels = H.channels;
             dsrc[i].capacity = (uint64_t)H.width * H.height * H.channels;
-            dsrc[i].flags &= ~(FLGPU_IMG_PNG_SOURCE | FLGPU_IMG_PNG_ADAM7);
+            dsrc[i].flags &= ~(FLGPU_IMG_PNG_SOURCE | FLGPU_IMG_PNG_ADAM7 | FLGPU_IMG_PNG_INFLATE);
         }
     if (seen != np) { c->set_error("PNG source: pixel size outside 1..4 bytes"); return FLGPU_ERR_INVALID_ARG; }
     FL_HIP(c, hipMemcpyAsync(c->d_pngjobs.p, jobs, (nu + nx + na) * sizeof(PngDecJob), hipMemcpyHostToDevice, st), "PNG decode descriptors");
@@ -636,6 +686,10 @@ int source_probe(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
         c->set_error("FLGPU_IMG_PNG_ADAM7 without FLGPU_IMG_PNG_SOURCE");
         return FLGPU_ERR_INVALID_ARG;
     }
+    if ((src->flags & FLGPU_IMG_PNG_INFLATE) && !(src->flags & FLGPU_IMG_PNG_SOURCE)) {
+        c->set_error("FLGPU_IMG_PNG_INFLATE without FLGPU_IMG_PNG_SOURCE");
+        return FLGPU_ERR_INVALID_ARG;
+    }
     switch (out.kind) {
     case SRC_JPEG: // its own statuses: FLGPU_ERR_INVALID_ARG, not _PARSE, for a file that does not parse; its own checks against the caller's announcement
         if (file_head(SRC_JPEG, src->data, (size_t)src->capacity, 0, out) != 0) return FLGPU_ERR_INVALID_ARG;
@@ -645,7 +699,7 @@ int source_probe(flgpu_ctx *c, const flgpu_image *src, SourceProbe &out)
         break;
     case SRC_PNG: case SRC_WEBP: case SRC_VP8:
         if (int rc = file_source_check(c, src, out)) return rc;
-        out.capacity = out.kind == SRC_PNG ? png_blob_bytes(out.png) : out.kind == SRC_WEBP ? webp_blob_capacity(out.webp, (size_t)src->capacity) : vp8_blob_capacity(out.vp8);
+        out.capacity = out.kind == SRC_PNG ? (png_device_inflate(src->flags) ? png_stage_bytes(out.png) : png_blob_bytes(out.png)) : out.kind == SRC_WEBP ? webp_blob_capacity(out.webp, (size_t)src->capacity) : vp8_blob_capacity(out.vp8);
         break;
     case SRC_PIXELS:
         out.capacity = (size_t)src->width * src->height * src->channels;
@@ -695,30 +749,86 @@ int decode_sources(flgpu_ctx *c, size_t n, flgpu_image *dsrc, const StagedSource
     return decode_vp8_sources(c, n, dsrc, staged, st);
 }
 
-// Enqueues the copy of the device entropy decoder's error words (final once its kernels have run): a caller that waits for the stream anyway
-// asks for them in front of that wait and passes fetched = true below.
+// Enqueues the copy of the device entropy decoder's and the device inflate's error words (final once their kernels have run): a caller that
+// waits for the stream anyway asks for them in front of that wait and passes fetched = true below.
 int entropy_failures_fetch(flgpu_ctx *c, size_t n, hipStream_t st)
 {
-    if (!c->last_jh_n || c->last_jh_slot.size() != n) return FLGPU_OK;
-    FL_HIP(c, hipMemcpyAsync(c->h_jherr.p, c->d_jherr.p, (size_t)c->last_jh_n * 4, hipMemcpyDeviceToHost, st), "device entropy decode: error words D2H");
+    if (c->last_jh_n && c->last_jh_slot.size() == n)
+        FL_HIP(c, hipMemcpyAsync(c->h_jherr.p, c->d_jherr.p, (size_t)c->last_jh_n * 4, hipMemcpyDeviceToHost, st), "device entropy decode: error words D2H");
+    if (c->last_inf_n && c->last_inf_slot.size() == n)
+        FL_HIP(c, hipMemcpyAsync(c->h_inferr.p, c->d_inferr.p, (size_t)c->last_inf_n * 4, hipMemcpyDeviceToHost, st), "PNG inflate: error words D2H");
     return FLGPU_OK;
 }
 
 int entropy_failures(flgpu_ctx *c, size_t n, std::vector<uint8_t> &bad, hipStream_t st, bool fetched)
 {
     bad.assign(n, 0);
-    if (!c->last_jh_n || c->last_jh_slot.size() != n) return 0;
-    if (!fetched && (hipMemcpyAsync(c->h_jherr.p, c->d_jherr.p, (size_t)c->last_jh_n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+    const bool jh = c->last_jh_n && c->last_jh_slot.size() == n, inf = c->last_inf_n && c->last_inf_slot.size() == n;
+    if (!jh && !inf) return 0;
+    if (!fetched && (entropy_failures_fetch(c, n, st) != FLGPU_OK || hipStreamSynchronize(st) != hipSuccess)) {
         c->set_error("device entropy decode: error words D2H");
         return -FLGPU_ERR_DEVICE;
     }
     int nbad = 0;
-    const uint32_t *e = static_cast<const uint32_t *>(c->h_jherr.p);
-    if (c->dbg->on(DBG_DEBUG_JH)) for (uint32_t k = 0; k < c->last_jh_n; ++k) fprintf(stderr, "device entropy decode: picture %u error word %u\n", k, e[k]);
-    for (size_t i = 0; i < n; ++i)
-        if (c->last_jh_slot[i] >= 0 && e[c->last_jh_slot[i]]) { bad[i] = 1; ++nbad; }
-    c->stats.jpeg_device_huffman_retries += (uint64_t)nbad;
+    if (jh) {
+        const uint32_t *e = static_cast<const uint32_t *>(c->h_jherr.p);
+        if (c->dbg->on(DBG_DEBUG_JH)) for (uint32_t k = 0; k < c->last_jh_n; ++k) fprintf(stderr, "device entropy decode: picture %u error word %u\n", k, e[k]);
+        int nj = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (c->last_jh_slot[i] >= 0 && e[c->last_jh_slot[i]]) { bad[i] = 1; ++nj; }
+        c->stats.jpeg_device_huffman_retries += (uint64_t)nj;
+        nbad += nj;
+    }
+    if (inf) {
+        const uint32_t *e = static_cast<const uint32_t *>(c->h_inferr.p);
+        if (c->dbg->on(DBG_DEBUG_JH)) for (uint32_t k = 0; k < c->last_inf_n; ++k) fprintf(stderr, "PNG inflate: picture %u error word %u\n", k, e[k]);
+        int ni = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (c->last_inf_slot[i] >= 0 && e[c->last_inf_slot[i]]) { bad[i] = 1; ++ni; }
+        c->png_device_inflates += (uint64_t)c->last_inf_n - (uint64_t)ni;
+        c->png_inflate_retries += (uint64_t)ni;
+        nbad += ni;
+        c->last_inf_n = 0; // (counted once)
+    }
     return nbad;
+}
+
+// One picture through the inflate kernel alone.
+int debug_png_inflate_device(flgpu_ctx *c, const uint8_t *file, size_t n, uint32_t src_flags, uint8_t *out, size_t capacity, size_t *used)
+{
+    SourceProbe probe;
+    if (int rc = file_head(SRC_PNG, file, n, HEAD_FULL | png_head_opts(src_flags), probe)) return rc;
+    if (!probe.head.supported) return FLGPU_ERR_UNSUPPORTED;
+    const size_t scan = png_scan_bytes(probe.png);
+    *used = scan;
+    if (!out) return FLGPU_OK;
+    if (capacity < scan) return FLGPU_ERR_BUFFER_TOO_SMALL;
+    const size_t cap = png_stage_bytes(probe.png);
+    WorkBuf work(cap);
+    PngBlobHeader H;
+    if (int rc = png_stage_compressed(file, n, work.p, cap, &H, (src_flags & FLGPU_IMG_PNG_ADAM7) != 0)) return png_status(rc);
+    std::lock_guard<std::mutex> g(c->mu);
+    FL_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    DeviceBuf d_stage, d_scratch, d_job;
+    struct Release { DeviceBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release{d_stage, d_scratch, d_job};
+    FL_HIP(c, d_stage.reserve(cap), "PNG inflate staging");
+    FL_HIP(c, d_scratch.reserve(sizeof(PngBlobHeader) + scan + 64), "PNG inflate scratch");
+    FL_HIP(c, d_job.reserve(sizeof(InfJob) + 16), "PNG inflate descriptors");
+    InfJob job;
+    memset(&job, 0, sizeof(job));
+    job.stage = static_cast<const uint8_t *>(d_stage.p);
+    job.scratch = static_cast<uint8_t *>(d_scratch.p);
+    job.err = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_job.p) + sizeof(InfJob));
+    job.payload_bytes = (uint32_t)(H.total_bytes - sizeof(PngBlobHeader) - kPngzPad);
+    job.expected = (uint32_t)scan;
+    FL_HIP(c, hipMemcpy(d_stage.p, work.p, cap, hipMemcpyHostToDevice), "PNG inflate staging H2D");
+    FL_HIP(c, hipMemcpy(d_job.p, &job, sizeof(job), hipMemcpyHostToDevice), "PNG inflate descriptors");
+    FL_HIP(c, launch_png_inflate(static_cast<const InfJob *>(d_job.p), 1, nullptr), "PNG inflate kernel");
+    uint32_t err = 0;
+    FL_HIP(c, hipMemcpy(&err, job.err, 4, hipMemcpyDeviceToHost), "PNG inflate error word D2H");
+    if (err) { c->set_error("PNG inflate kernel: no (error word " + std::to_string(err) + ")"); return FLGPU_ERR_PARSE; }
+    FL_HIP(c, hipMemcpy(out, job.scratch + sizeof(PngBlobHeader), scan, hipMemcpyDeviceToHost), "PNG scanlines D2H");
+    return FLGPU_OK;
 }
 
 } // namespace fl

@@ -15,6 +15,7 @@
 
 #include "../../include/fanlin_gpu.h"
 #include "fl_gifdec.h"
+#include "fl_inflate.h"
 #include "fl_jpegdec.h"
 #include "fl_pngdec.h"
 #include "fl_vp8dec.h"
@@ -58,7 +59,7 @@ struct StagedSource {
     JpegBlobHeader jpeg;      // SRC_JPEG: the coefficient blob the staging thread decoded, or ...
     JpegHuffStage stage{};    // ... jpeg.magic == kJhMagic: the staged entropy-coded segment, decoded on the device (a host copy of its description)
     std::vector<uint8_t> icc; // four-component JPEG + use_embedded_profile: the file's own ICC profile
-    PngBlobHeader png;        // SRC_PNG: header + filtered scanlines the staging thread inflated
+    PngBlobHeader png;        // SRC_PNG: header + filtered scanlines the staging thread inflated, or (magic kPngzMagic) header + the deflate stream for the device
     WebpBlobHeader webp;      // SRC_WEBP: header + sub-images + residuals the staging thread entropy-decoded
     Vp8BlobHeader vp8;        // SRC_VP8: header + macroblock records + levels (+ ALPH payload) the staging thread decoded
     WebpBlobHeader vp8_alpha; // ... vp8.alpha == 2: the header of the lossless blob that holds the alpha plane
@@ -70,7 +71,10 @@ struct StagedSource {
 // request, a source or an info call.  0, or FLGPU_ERR_PARSE.  Depth: the layout alone (requests and sources: flgpu_transform verifies CRCs and reads
 // the streams once, under the decode bound; as_is serves the file unread) unless HEAD_FULL (the *_info_of calls: PNG CRCs, the WebP streams' contents).
 // HEAD_SNIFF: a SRC_WEBP file whose picture is a `VP8 ` chunk becomes SRC_VP8 (flgpu_process_webp goes by the chunk type; a source goes by its flag).
-enum : uint32_t { HEAD_ADAM7 = 1u, HEAD_FULL = 2u, HEAD_SNIFF = 4u };
+// HEAD_INFLATE: a PNG head carries FLGPU_IMG_PNG_INFLATE (the request asked for the device inflate); what the head reports is the same.
+enum : uint32_t { HEAD_ADAM7 = 1u, HEAD_FULL = 2u, HEAD_SNIFF = 4u, HEAD_INFLATE = 8u };
+// the HEAD_* options the flags of a PNG source stand for
+inline uint32_t png_head_opts(uint32_t src_flags) { return ((src_flags & FLGPU_IMG_PNG_ADAM7) ? HEAD_ADAM7 : 0u) | ((src_flags & FLGPU_IMG_PNG_INFLATE) ? HEAD_INFLATE : 0u); }
 int file_head(SourceKind kind, const uint8_t *file, size_t n, uint32_t opts, SourceProbe &out);
 // the flgpu_image a file with that head is handed over as
 inline flgpu_image file_image(const uint8_t *file, uint64_t n, const FileHead &h)
@@ -124,6 +128,9 @@ inline int png_status(int rc) { return rc == 0 ? FLGPU_OK : rc == kPngParse ? FL
 // The device's Y | U | V planes of a lossy WebP file (padded to whole macroblocks, vp8_rec_bytes), before (filter == 0) or behind
 // the loop filter: what flgpu_debug_vp8_planes hands out, so that a wrong pixel names its stage.  Buffers of its own, no batch.
 int debug_vp8_planes(flgpu_ctx *c, const uint8_t *file, size_t n, int filter, uint8_t *out, size_t capacity, size_t *used);
+// The scanlines of a PNG file exactly as the inflate kernel leaves them: buffers of its own, no batch, no host re-run (a device "no" is
+// FLGPU_ERR_PARSE).  What flgpu_debug_png_inflate_device hands out, so that a wrong pixel names its stage.
+int debug_png_inflate_device(flgpu_ctx *c, const uint8_t *file, size_t n, uint32_t src_flags, uint8_t *out, size_t capacity, size_t *used);
 
 // ---- fl_query.cpp: the planner behind every request -----------------------------------------------------------------------
 // Everything State::process_image decides before it touches pixels (handler.rs:198-261).

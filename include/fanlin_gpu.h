@@ -106,6 +106,12 @@ typedef struct flgpu_image {
                                          samples.  Opt-in, because without it an interlaced file keeps its answer of before
                                          (FLGPU_ERR_UNSUPPORTED) for callers that route on it.  Nothing changes for a non-interlaced file.
                                          16-bit samples stay FLGPU_ERR_UNSUPPORTED; the PNG encoder never writes interlaced files. */
+#define FLGPU_IMG_PNG_INFLATE     512u /* in, beside FLGPU_IMG_PNG_SOURCE (without it: FLGPU_ERR_INVALID_ARG), with or without FLGPU_IMG_PNG_ADAM7:
+                                         the file's deflate stream is inflated on the device (csrc/fl_inflate.hip).  The calling thread only walks the
+                                         container (same CRC checks) and copies the IDAT payloads: the compressed payload crosses PCIe, not the
+                                         scanlines.  The device answers "here are the scanlines" or "no"; every "no" is run again with the host
+                                         inflate, whose verdict is final, so pixels, status codes and error texts are those of a source without
+                                         the bit.  Counters: "png_device_inflates", "png_inflate_retries" (flgpu_debug_get). */
 #define FLGPU_IMG_WEBP_SOURCE     64u /* in (src of flgpu_transform / flgpu_transform_batch): data holds a lossless WebP FILE of `capacity` bytes instead
                                          of pixels, width / height / channels say what it decodes to (flgpu_webp_info_of): the library decodes it
                                          itself -- container, prefix codes, LZ77 and colour cache on the calling thread, the predictor, cross-colour,
@@ -191,6 +197,9 @@ typedef enum flgpu_front_end {
  * with FLGPU_IMG_PNG_ADAM7).  Without it such a file is FLGPU_ERR_UNSUPPORTED (as_is aside), as before.  Every other entry point
  * ignores the bit. */
 #define FLGPU_DECODE_PNG_ADAM7 0x10000u
+/* Not a content::Format bit: flgpu_process_png hands the file on with FLGPU_IMG_PNG_INFLATE (its deflate stream is inflated on the
+ * device).  flgpu_process_png_plan ignores it; as_is still never reads the file. */
+#define FLGPU_DECODE_PNG_INFLATE 0x100000u
 /* Not a content::Format bit: the caller wants the library to finish lossless image/webp bodies (FLGPU_FE_WEBP_LOSSLESS,
  * FLGPU_RESULT_WEBP_STREAM) where the WebP arm runs at quality 100 (src/handler.rs:286-292).  Without it such requests
  * return pixels, as before. */
@@ -757,7 +766,9 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * flgpu_debug_get also reads three counters of the context (its queue lanes and device shards included; flgpu_reset_stats clears
  * them; flgpu_debug_set refuses them): "png_sources" = FLGPU_IMG_PNG_SOURCE pictures decoded, "png_file_bytes" = their file bytes,
  * "png_upload_bytes" = what crossed PCIe for them (per picture a 1,088-byte header + height x (1 + row bytes) of filtered scanlines;
- * for an Adam7 picture the header + the sum over its non-empty passes of pass height x (1 + pass row bytes));
+ * for an Adam7 picture the header + the sum over its non-empty passes of pass height x (1 + pass row bytes); for a picture handed over
+ * with FLGPU_IMG_PNG_INFLATE the header + its IDAT payloads + 16 bytes of padding), "png_device_inflates" = pictures the inflate kernel
+ * inflated, "png_inflate_retries" = pictures it said no to, which were run again with the host inflate;
  * "webp_sources", "webp_file_bytes", "webp_upload_bytes" the same for FLGPU_IMG_WEBP_SOURCE pictures (per picture a 112-byte header,
  * the transforms' sub-images and 4 bytes per pixel of the packed width), and with flgpu_config.profile "webp_predict_ns" /
  * "webp_pointwise_ns" = the HIP-event time of the predictor and the pointwise kernels' launches (complete after flgpu_get_stats);
@@ -804,6 +815,14 @@ int flgpu_debug_png_scanlines(const uint8_t *png, uint64_t n, uint8_t *out, uint
  * interlaced file: the seven passes' filtered scanlines back to back, for each non-empty pass its height x (1 + its row bytes) -- the
  * inflated IDAT stream as it is stored, Adler-32 and every pass row's filter byte checked. */
 int flgpu_debug_png_scanlines_flags(const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used);
+/* The same scanlines exactly as the inflate kernel (FLGPU_IMG_PNG_INFLATE) leaves them, so that a wrong pixel can name its stage: buffers
+ * of its own, no batch and NO host re-run -- a device "no" is FLGPU_ERR_PARSE.  out == NULL: *used alone. */
+int flgpu_debug_png_inflate_device(flgpu_ctx *ctx, const uint8_t *png, uint64_t n, uint32_t src_flags, uint8_t *out, uint64_t capacity, uint64_t *used);
+/* The host twin of that kernel (csrc/fl_inflate_core.h in plain loops over arrays of the kernel's LDS sizes; not the host inflate): pure host,
+ * no context.  FLGPU_ERR_PARSE = the device's "no".  stats (optional): [0] deflate blocks, [1] strips, [2] synchronisation rounds,
+ * [3] resolution rounds, [4] tokens decoded, [5] of those decoded more than once, [6] / [7] the most synchronisation / resolution rounds of
+ * one strip. */
+int flgpu_debug_png_inflate_model(const uint8_t *png, uint64_t n, uint8_t *out, uint64_t capacity, uint64_t *used, uint32_t stats[8]);
 
 /* The host half of the lossless WebP decode front end alone (csrc/fl_webpsrc.h): the blob flgpu_transform uploads for a
  * FLGPU_IMG_WEBP_SOURCE -- WebpBlobHeader, the mode / cross-colour images, the palette, the entropy-decoded residual picture.

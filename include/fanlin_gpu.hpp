@@ -81,6 +81,8 @@ public:
     void encode_png() { flags_ |= FLGPU_ENCODE_PNG; }
     // not a content::Format bit: process_png also takes Adam7-interlaced files of up to 8 bits per sample
     void decode_png_adam7() { flags_ |= FLGPU_DECODE_PNG_ADAM7; }
+    // not a content::Format bit: process_png has the file's deflate stream inflated on the device (FLGPU_IMG_PNG_INFLATE)
+    void decode_png_inflate() { flags_ |= FLGPU_DECODE_PNG_INFLATE; }
     // not a content::Format bit: the library finishes lossless image/webp bodies, the WebP arm at quality 100
     // (FLGPU_RESULT_WEBP_STREAM)
     void encode_webp_lossless() { flags_ |= FLGPU_ENCODE_WEBP_LOSSLESS; }

@@ -82,6 +82,8 @@ const IMG_JPEG_SOURCE: u32 = 16; // FlImage.flags of a SOURCE: `data` holds the 
 const IMG_PNG_SOURCE: u32 = 32;  // ... `data` holds the PNG FILE (flgpu_process_png sets it itself)
 const IMG_PNG_ADAM7: u32 = 256;  // ... beside IMG_PNG_SOURCE: the file may be Adam7-interlaced (flgpu_process_png sets it for DECODE_PNG_ADAM7)
 #[allow(dead_code)]
+const IMG_PNG_INFLATE: u32 = 512; // ... beside IMG_PNG_SOURCE: the deflate stream is inflated on the device (flgpu_process_png sets it for DECODE_PNG_INFLATE)
+#[allow(dead_code)]
 const IMG_WEBP_SOURCE: u32 = 64; // ... `data` holds the lossless WebP FILE (flgpu_process_webp sets it itself)
 #[allow(dead_code)]
 const IMG_VP8_SOURCE: u32 = 128; // ... `data` holds the lossy WebP FILE (flgpu_process_webp sets it itself)
@@ -91,6 +93,9 @@ pub const ACCEPT_AVIF: u32 = 2;
 pub const ENCODE_PNG: u32 = 0x100;
 // not a content::Format bit: process_png also takes Adam7-interlaced PNG files (up to 8 bits per sample); without it they are None
 pub const DECODE_PNG_ADAM7: u32 = 0x10000;
+// not a content::Format bit: process_png has the PNG file's deflate stream inflated on the device, the compressed payload crosses PCIe
+#[allow(dead_code)]
+pub const DECODE_PNG_INFLATE: u32 = 0x100000;
 // not a content::Format bit: finish lossless image/webp bodies on the device, the WebP arm at quality 100 (RESULT_WEBP_STREAM)
 pub const ENCODE_WEBP_LOSSLESS: u32 = 0x200;
 // not a content::Format bit: process_gif finishes the image/gif body where no frame has more than 256 colours (RESULT_GIF_STREAM)
