@@ -47,6 +47,8 @@ ENCODE_WEBP_LOSSY_FILTER = 0x4000  # accept_flags bit: with ENCODE_WEBP_LOSSY, t
 ENCODE_WEBP_LOSSY_ALPHA = 0x20000  # accept_flags bit: with ENCODE_WEBP_LOSSY, a translucent picture's alpha plane goes out as a VP8L stream wherever that is smaller (FEO_ALPHA_VP8L); alone, or without it, nothing
 ENCODE_WEBP_LOSSY_SEGMENTS = 0x40000  # accept_flags bit: with ENCODE_WEBP_LOSSY, segment-adaptive quantisers -- up to four classes of macroblocks by activity (FEO_SEGMENTS); alone, or without it, nothing
 ENCODE_JPEG_OPTIMIZE = 0x80000  # accept_flags bit: a JPEG that stays JPEG is coded with Huffman tables from the picture's own symbol counts (FEO_JPEG_OPTIMIZE); never a larger file, nothing else changes
+ENCODE_JPEG_420 = 0x200000  # accept_flags bit: a JPEG that stays JPEG is coded with 4:2:0 chroma subsampling (FEO_JPEG_420); alone or with ENCODE_JPEG_OPTIMIZE
+FEO_JPEG_420 = 8  # the `options` byte, FE_JPEG only: see ENCODE_JPEG_420
 FEO_JPEG_OPTIMIZE = 4  # flgpu_params.reserved[0] (the header's `options` byte), FE_JPEG only: see ENCODE_JPEG_OPTIMIZE
 FEO_SEGMENTS = 2  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_SEGMENTS
 FEO_ALPHA_VP8L = 1  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_ALPHA
@@ -444,7 +446,7 @@ CMYK_GRID, CMYK_INPUT_YCCK = 17, 1
 
 def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 32), crop=False, blur_sigma=0.0,
                 grayscale=False, inverse=False, quality=75, front_end=FE_NONE, orientation=1, filter=FILTER_LANCZOS3,
-                alpha_vp8l=False, segments=False, jpeg_optimize=False) -> flgpu_params:
+                alpha_vp8l=False, segments=False, jpeg_optimize=False, jpeg_420=False) -> flgpu_params:
     p = flgpu_params()
     p.has_dims = 1 if (w is not None and h is not None) else 0
     p.w, p.h = (w or 0), (h or 0)
@@ -455,7 +457,8 @@ def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 
     p.quality, p.front_end = quality, front_end
     p.orientation = orientation
     p.filter = filter
-    p.reserved[0] = (FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0) | (FEO_JPEG_OPTIMIZE if jpeg_optimize else 0)  # the options byte
+    p.reserved[0] = ((FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0) | (FEO_JPEG_OPTIMIZE if jpeg_optimize else 0)
+                     | (FEO_JPEG_420 if jpeg_420 else 0))  # the options byte
     return p
 
 

@@ -600,7 +600,8 @@ bool plan_blur(flgpu_ctx *c, const DebugSwitches &dbg, Work &w)
 bool plan_jpeg_tables(flgpu_ctx *c, Work &w)
 {
     const uint32_t q = clamp_quality(w.p->quality);
-    w.jpeg_tab = cached_block(c, c->jpeg_tables, std::make_tuple(w.plan.out_w, w.plan.out_h, q), [&](std::vector<uint32_t> &blk) { build_jpeg_tables(w.plan.out_w, w.plan.out_h, q, blk); });
+    const bool s420 = jpeg_420(*w.p); // the one byte of SOF0 that differs: a block of its own
+    w.jpeg_tab = cached_block(c, c->jpeg_tables, std::make_tuple(w.plan.out_w, w.plan.out_h, q, s420), [&](std::vector<uint32_t> &blk) { build_jpeg_tables(w.plan.out_w, w.plan.out_h, q, s420, blk); });
     return w.jpeg_tab != 0;
 }
 

@@ -228,6 +228,7 @@ struct flgpu_ctx {
     fl::DeviceBuf d_vp8dec, d_vp8jobs;                 // lossy WebP decode (fl_vp8dec.hip): planes, alpha planes and pixels of a batch, job descriptors
     fl::PinnedBuf h_vp8jobs;
     uint64_t vp8_sources = 0, vp8_file_bytes = 0, vp8_upload_bytes = 0, vp8_decode_ns = 0;
+    uint64_t jpeg_420 = 0;                               // JPEG pictures coded with FLGPU_FEO_JPEG_420 (counted when their launches are enqueued)
     uint64_t jpeg_optimized = 0;                         // JPEG pictures whose file went out with their own Huffman tables (FLGPU_FEO_JPEG_OPTIMIZE; from the result words)
     uint64_t webp_lossy_segments = 0;                    // lossy WebP pictures whose frame went out segmented (FLGPU_FEO_SEGMENTS; from the result words)
     uint64_t webp_alpha_vp8l = 0;                        // lossy WebP pictures whose ALPH chunk went out as a VP8L stream (FLGPU_FEO_ALPHA_VP8L; from the result words)
@@ -246,7 +247,7 @@ struct flgpu_ctx {
     std::vector<int32_t> last_inf_slot; // the same for the device inflate of PNG sources
     uint32_t last_inf_n = 0;
     fl::EncodeBuffers enc; // the encoders' scratch (fl_encode.h)
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> jpeg_tables; // (w, h, quality) -> arena offset of header + q tables
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t, bool>, uint32_t> jpeg_tables; // (w, h, quality, FLGPU_FEO_JPEG_420) -> arena offset of header + q tables
     // per-image result words of the most recent device batch: [2i] flags (bit 0: non-opaque alpha seen by the WebP front
     // end, FL_JPEG_RESULT_OVERFLOW), [2i + 1] bytes of an encoded stream
     size_t last_n = 0;

@@ -14,6 +14,13 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan)
     switch (p.front_end) {
     case FLGPU_FE_JFIF444:
     case FLGPU_FE_JPEG:
+        if (jpeg_420(p)) { // FLGPU_FEO_JPEG_420: whole 16 x 16 MCUs of six units; a unit's longest code is what it was
+            plan.plane_w = (plan.out_w + 15u) & ~15u; plan.plane_h = (plan.out_h + 15u) & ~15u;
+            plan.chroma_w = plan.plane_w / 2u; plan.chroma_h = plan.plane_h / 2u;
+            plan.out_bytes = 1024ull + 3ull * plan.plane_w * plan.plane_h / 2u;
+            plan.max_out_bytes = 1024ull + 2ull * kJpegMaxUnitBytes * 6ull * (plan.plane_w / 16u) * (plan.plane_h / 16u);
+            break;
+        }
         plan.plane_w = plan.chroma_w = (plan.out_w + 7u) & ~7u;
         plan.plane_h = plan.chroma_h = (plan.out_h + 7u) & ~7u;
         plan.out_bytes = 3ull * plan.plane_w * plan.plane_h;
@@ -55,10 +62,10 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan)
 namespace {
 
 // The scratch one picture needs, appended to s, and the limits flgpu_plan_output does not hold a single picture against.
-int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize)
+int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize, bool s420)
 {
     if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions (the plan of such a picture is valid: refused when it is run)
-    const size_t units = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
+    const size_t units = s420 ? (size_t)(pl.plane_w / 16u) * (pl.plane_h / 16u) * 6u : (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
     if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
     s.jpeg_coef += align_up(units * sizeof(JpegUnit), 256);
     s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
@@ -135,13 +142,12 @@ void add_jpeg_job(flgpu_ctx *c, EncodeJobs &E, const EncodeInput &x, const Encod
     j.units = reinterpret_cast<JpegUnit *>(static_cast<char *>(c->enc.jpeg_coef.p) + at.jpeg_coef);
     j.unit_off = reinterpret_cast<uint32_t *>(static_cast<char *>(c->enc.jpeg_off.p) + at.jpeg_off);
     j.acbits = reinterpret_cast<uint32_t *>(static_cast<char *>(c->enc.jpeg_raw.p) + at.jpeg_raw);
-    j.bx = x.plan->plane_w / 8u; j.by = x.plan->plane_h / 8u;
+    const uint32_t side = jpeg_420(*x.p) ? 16u : 8u, v = jpeg_variant(*x.p);
+    j.bx = x.plan->plane_w / side; j.by = x.plan->plane_h / side;
     j.tab_off = x.jpeg_tab;
-    if (jpeg_optimize(*x.p)) {
-        j.opt_off = (uint32_t)(at.jpeg_opt / 4u);
-        E.jjobs_opt++;
-        E.jpeg_opt_max_blocks = std::max(E.jpeg_opt_max_blocks, j.bx * j.by);
-    } else E.jpeg_max_blocks = std::max(E.jpeg_max_blocks, j.bx * j.by);
+    if (jpeg_optimize(*x.p)) j.opt_off = (uint32_t)(at.jpeg_opt / 4u);
+    E.jjobs_of[v]++;
+    E.jpeg_max_of[v] = std::max(E.jpeg_max_of[v], j.bx * j.by);
 }
 
 void add_png_job(flgpu_ctx *c, EncodeJobs &E, const EncodeInput &x, const EncodeScratch &at)
@@ -229,7 +235,7 @@ void add_planes_launch(EncodeJobs &E, uint32_t kind, const std::vector<const Enc
 int encode_plan_picture(const flgpu_params &p, const flgpu_plan &plan, EncodeScratch &s)
 {
     int rc = FLGPU_OK;
-    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s, jpeg_optimize(p));
+    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s, jpeg_optimize(p), jpeg_420(p));
     if (p.front_end == FLGPU_FE_PNG) rc = png_scratch(plan, s);
     if (p.front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(plan, s);
     if (const auto v = vp8_variant_of(p.front_end)) vp8_scratch(plan, s, *v, vp8_segments(p, plan.out_w, plan.out_h)); // (its limits: encode_plan_bytes)
@@ -268,12 +274,12 @@ int encode_reserve(flgpu_ctx *c, const EncodeScratch &sz)
 
 void encode_build_jobs(flgpu_ctx *c, const std::vector<EncodeInput> &in, EncodeJobs &E)
 {
-    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end; FLGPU_FE_JPEG with FLGPU_FEO_JPEG_OPTIMIZE behind FLGPU_FE_JPEG without
-    for (const EncodeInput &x : in) groups[2u * x.p->front_end + jpeg_optimize(*x.p)].push_back(&x);
+    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end; FLGPU_FE_JPEG: its four variants in jpeg_variant's order
+    for (const EncodeInput &x : in) groups[kJpegVariants * x.p->front_end + jpeg_variant(*x.p)].push_back(&x);
     // E.at runs over ALL the jobs in this order: the lossy WebP groups share the lossy WebP scratch, in the families' order, and the
     // lossless WebP files share the lossless coder's with those groups' alpha planes; no other two formats touch the same total
     for (auto &gk : groups) {
-        const std::pair<uint32_t, std::vector<const EncodeInput *> &> g{gk.first / 2u, gk.second};
+        const std::pair<uint32_t, std::vector<const EncodeInput *> &> g{gk.first / kJpegVariants, gk.second};
         const size_t vjob0 = E.vjobs.size();
         const std::optional<Vp8Variant> vp8 = vp8_variant_of(g.first);
         for (const EncodeInput *x : g.second) {
@@ -316,16 +322,21 @@ int encode_enqueue(flgpu_ctx *c, const EncodeJobs &E, hipStream_t st)
         else FL_HIP(c, launch_webp420(E.d.fjobs, c->d_arena, c->gamma_off, F.base, F.n, F.mw, F.mh, F.rgba, st), "webp front end");
         c->stats.frontend_launches++;
     }
-    const uint32_t jplain = (uint32_t)E.jjobs.size() - E.jjobs_opt;
-    if (jplain) {
+    // FLGPU_FE_JPEG: one launch sequence per variant that has jobs.  The _OPTIMIZE variants' records are addressed by the jobs, their
+    // counts by the launch: the 4:2:0 pictures' behind the 4:4:4 ones'.
+    uint32_t *const jopt = static_cast<uint32_t *>(c->enc.jpeg_opt.p), *const jhist = static_cast<uint32_t *>(c->enc.jpeg_hist.p);
+    const bool fallback = c->dbg->on(DBG_JPEG_OPTIMIZE_FALLBACK);
+    uint32_t jbase = 0;
+    for (uint32_t v = 0; v < kJpegVariants; jbase += E.jjobs_of[v++]) {
+        const uint32_t n = E.jjobs_of[v], most = E.jpeg_max_of[v];
+        if (!n) continue;
         ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_jpeg_encode(E.d.jjobs, c->d_arena, 0, jplain, E.jpeg_max_blocks, st), "JPEG encode");
-        c->stats.frontend_launches++;
-    }
-    if (E.jjobs_opt) { // FLGPU_FEO_JPEG_OPTIMIZE: the jobs behind the plain ones, with their records and counts
-        ProfileScope ps(c, st, 2);
-        FL_HIP(c, launch_jpeg_encode_optimized(E.d.jjobs, c->d_arena, jplain, E.jjobs_opt, E.jpeg_opt_max_blocks, static_cast<uint32_t *>(c->enc.jpeg_opt.p),
-                                               static_cast<uint32_t *>(c->enc.jpeg_hist.p), c->dbg->on(DBG_JPEG_OPTIMIZE_FALLBACK), st), "JPEG encode with per-picture tables");
+        if (v == 0u) FL_HIP(c, launch_jpeg_encode(E.d.jjobs, c->d_arena, jbase, n, most, st), "JPEG encode");
+        if (v == 1u) FL_HIP(c, launch_jpeg_encode_optimized(E.d.jjobs, c->d_arena, jbase, n, most, jopt, jhist, fallback, st), "JPEG encode with per-picture tables");
+        if (v == 2u) FL_HIP(c, launch_jpeg_encode_420(E.d.jjobs, c->d_arena, jbase, n, most, st), "JPEG 4:2:0 encode");
+        if (v == 3u) FL_HIP(c, launch_jpeg_encode_420_optimized(E.d.jjobs, c->d_arena, jbase, n, most, jopt, jhist + (size_t)E.jjobs_of[1] * kJpegOptHistWords, fallback, st),
+                            "JPEG 4:2:0 encode with per-picture tables");
+        if (v >= 2u) c->jpeg_420 += n;
         c->stats.frontend_launches++;
     }
     if (!E.pjobs.empty()) {

@@ -45,6 +45,10 @@ constexpr uint32_t clamp_quality(uint32_t q) { return q < 1u ? 1u : q > 100u ? 1
 // FLGPU_FEO_SEGMENTS, which only the lossy WebP front ends know: a w x h output is coded with the option unless it fits the front end's
 // limits but not the segmented partition 0's -- then it is coded without it (no record, no class map, the unsegmented worst case)
 inline bool jpeg_optimize(const flgpu_params &p) { return p.front_end == FLGPU_FE_JPEG && (p.options & FLGPU_FEO_JPEG_OPTIMIZE); } // only FLGPU_FE_JPEG knows the bit
+inline bool jpeg_420(const flgpu_params &p) { return p.front_end == FLGPU_FE_JPEG && (p.options & FLGPU_FEO_JPEG_420); }           // likewise
+// The four launch sequences of FLGPU_FE_JPEG, in the order of their jobs: plain, _OPTIMIZE, 4:2:0, 4:2:0 + _OPTIMIZE
+constexpr uint32_t kJpegVariants = 4;
+inline uint32_t jpeg_variant(const flgpu_params &p) { return (jpeg_optimize(p) ? 1u : 0u) + (jpeg_420(p) ? 2u : 0u); }
 inline bool vp8_segments(const flgpu_params &p, uint32_t w, uint32_t h)
 {
     const std::optional<Vp8Variant> v = vp8_variant_of(p.front_end);
@@ -98,8 +102,9 @@ struct EncodeJobs {
     uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
     uint32_t vjobs_seg = 0; // how many of them are coded with FLGPU_FEO_SEGMENTS (vp8_segments): vp8_segment_kernel launches iff any is
     std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, ajob_img, vjob_img; // image of every job
-    uint32_t jpeg_max_blocks = 0;
-    uint32_t jjobs_opt = 0, jpeg_opt_max_blocks = 0; // the last jjobs_opt of jjobs carry FLGPU_FEO_JPEG_OPTIMIZE: a launch sequence of their own, behind the plain ones
+    // jjobs holds the four variants one after the other (jpeg_variant): how many jobs each has, and the largest bx * by among them
+    // (blocks; MCUs for the two 4:2:0 variants).  Each variant has a launch sequence of its own.
+    uint32_t jjobs_of[kJpegVariants] = {0, 0, 0, 0}, jpeg_max_of[kJpegVariants] = {0, 0, 0, 0};
     std::vector<FeLaunch> fe_launches;
     EncodeScratch at; // the scratch totals of the jobs so far, i.e. the next job's offsets; once all are built, the batch's totals
     struct { const FrontendJob *fjobs; const JpegJob *jjobs; const PngJob *pjobs; const WebpJob *wjobs; const WebpJob *ajobs; const Vp8Job *vjobs; } d{}; // the arrays' device copies
@@ -117,8 +122,8 @@ struct EncodeJobs {
 // Planning: the scratch picture (p, plan) needs, appended to s, and the limits that hold for the batch's totals or are not flgpu_plan_output's.
 int encode_plan_picture(const flgpu_params &p, const flgpu_plan &plan, EncodeScratch &s);
 int encode_reserve(flgpu_ctx *c, const EncodeScratch &sizes);
-// The jobs of the pictures `in` (in batch order): grouped by front end in ascending code (FLGPU_FE_JPEG with FLGPU_FEO_JPEG_OPTIMIZE: a
-// group of its own behind the plain FLGPU_FE_JPEG pictures), batch order inside a group; a job's offsets
+// The jobs of the pictures `in` (in batch order): grouped by front end in ascending code (FLGPU_FE_JPEG: four groups, jpeg_variant,
+// the plain pictures first), batch order inside a group; a job's offsets
 // into the scratch are the totals of the jobs before it.  And the planes launches, one per planar kind and one per lossy WebP group.
 void encode_build_jobs(flgpu_ctx *c, const std::vector<EncodeInput> &in, EncodeJobs &E);
 // Planar front ends, JPEG, PNG, lossless WebP, lossy WebP, in that order.

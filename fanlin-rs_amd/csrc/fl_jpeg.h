@@ -19,13 +19,13 @@ struct alignas(16) JpegUnit {
 struct alignas(16) JpegJob {
     const uint8_t *src;   // interleaved pixels, w x h x c
     uint8_t *dst;         // the JFIF stream
-    JpegUnit *units;      // scratch: [unit] the unit's record; unit = block * 3 + component
+    JpegUnit *units;      // scratch: [unit] the unit's record; unit = block * 3 + component (FLGPU_FEO_JPEG_420: MCU * 6 + slot)
     uint32_t *unit_off;   // scratch: units + 1 bit offsets
     uint32_t *acbits;     // scratch: [unit][kAcWordsPerUnit] the unit's AC code from bit 0, most significant bit first; only words
                           // kUnitAcWords and up are written and read here (the slot keeps its worst-case size and every index)
     uint32_t *result;     // [0] |= flags (FL_JPEG_RESULT_OVERFLOW), [1] = stream bytes (0 if it did not fit dst_cap)
     uint32_t w, h, c;
-    uint32_t bx, by;      // blocks per row / column
+    uint32_t bx, by;      // blocks per row / column (FLGPU_FEO_JPEG_420: MCUs of 16 x 16)
     uint32_t tab_off;     // arena word offset of the header + quantisation tables block (fl_jpeg_tables.h)
     uint32_t opt_off;     // FLGPU_FEO_JPEG_OPTIMIZE only (else 0): word offset of the picture's record in the batch's optimise scratch
     uint32_t dst_cap;     // bytes available at dst
@@ -49,5 +49,12 @@ hipError_t launch_jpeg_encode(const JpegJob *jobs, const uint32_t *arena, uint32
 // fallback: the decision always falls against the picture's tables (tests).
 hipError_t launch_jpeg_encode_optimized(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
                                         uint32_t *opt, uint32_t *hist, bool fallback, hipStream_t st);
+
+// FLGPU_FEO_JPEG_420 (fl_jpeg_420.hip): the same two sequences for pictures coded 4:2:0.  Their jobs' bx, by count 16 x 16 MCUs, a
+// picture has 6 units per MCU (Y Y Y Y Cb Cr) in units, unit_off, acbits and its optimise record, and tab_off names a header whose SOF0
+// says 2 x 2 for the first component.  max_mcus: the largest bx * by of the jobs.
+hipError_t launch_jpeg_encode_420(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_mcus, hipStream_t st);
+hipError_t launch_jpeg_encode_420_optimized(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_mcus,
+                                            uint32_t *opt, uint32_t *hist, bool fallback, hipStream_t st);
 
 } // namespace fl

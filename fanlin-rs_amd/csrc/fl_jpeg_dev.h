@@ -1,8 +1,9 @@
-// fl_jpeg_dev.h -- the device code the JPEG encoder's two translation units share: fl_jpeg.hip (jpeg_dct_quant_kernel, jpeg_pack_kernel)
-// and fl_jpeg_opt.hip (the kernels of FLGPU_FEO_JPEG_OPTIMIZE, which run the same transform, coder and packer with the picture's own
-// tables).  The latter are a translation unit of their own so that the module the two plain kernels are compiled in holds exactly
-// what it held before the option existed: their instruction streams are pinned (profiles/pr_jpeg_optimize.txt).  fl_jpeg.hip
-// describes the kernels.
+// fl_jpeg_dev.h -- the device code the JPEG encoder's translation units share: fl_jpeg.hip (jpeg_dct_quant_kernel, jpeg_pack_kernel),
+// fl_jpeg_opt.hip (the kernels of FLGPU_FEO_JPEG_OPTIMIZE, which run the same transform, coder and packer with the picture's own
+// tables) and fl_jpeg_420.hip (FLGPU_FEO_JPEG_420: its own transform and coder, this file's packer with another unit order).  The
+// options are translation units of their own so that the module the two plain kernels are compiled in holds exactly what it held
+// before the options existed: their instruction streams are pinned (profiles/pr_jpeg_optimize.txt, profiles/pr_jpeg_420.txt).
+// fl_jpeg.hip describes the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -458,17 +459,30 @@ __device__ __forceinline__ void win_or(uint32_t *win, uint32_t wbase, uint64_t g
     if (lo && W + 1 >= wbase && W + 1 < (uint64_t)wbase + kWinWords) atomicOr(&win[W + 1 - wbase], lo);
 }
 
+// The scan's unit order.  k420 = false: three units per block, Y Cb Cr, each after the same component's unit of the block before (u - 3).
+// k420 (FLGPU_FEO_JPEG_420, fl_jpeg_420.hip): six per 16 x 16 MCU, Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr; Y(0,0) follows the MCU before's
+// Y(1,1) (u - 3), the other Y units the one before (u - 1), Cb and Cr their own of the MCU before (u - 6).  In both orders a unit
+// with fewer than unit_dc_back units in front of it is its component's first: its predecessor's DC term is 0.
+template <bool k420> __device__ __forceinline__ bool unit_is_chroma(uint32_t u) { return k420 ? (u % 6u) >= 4u : (u % 3u) != 0u; }
+template <bool k420> __device__ __forceinline__ uint32_t unit_dc_back(uint32_t u)
+{
+    if constexpr (!k420) return 3u;
+    const uint32_t slot = u % 6u;
+    return slot == 0u ? 3u : slot < 4u ? 1u : 6u;
+}
+
 // s_dc: the two DC code tables (luma, chroma), kDcCodes entries each, staged in LDS -- a table entry is then an LDS read behind
 // the unit's record, not a third dependent global load
+template <bool k420 = false>
 __device__ __forceinline__ uint32_t dc_code(const uint32_t *s_dc, uint32_t u, uint32_t meta, uint32_t prev_meta, uint32_t *len)
 {
     // differential DC against the same component's previous block (encode_rgb: y_dcprev / cb_dcprev / cr_dcprev); prev_meta is
-    // the meta word of unit u - 3, or 0 for a picture's first block
+    // the meta word of unit u - unit_dc_back(u), or 0 for a picture's first block
     const int32_t dc = (int16_t)(meta & 0xffffu), prev = (int16_t)(prev_meta & 0xffffu);
     const int32_t diff = dc - prev;
     const uint32_t size = coef_size(diff);
     const uint32_t value = (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << size) - 1u);
-    const uint32_t e = s_dc[((u % 3u) ? kDcCodes : 0u) + size];
+    const uint32_t e = s_dc[(unit_is_chroma<k420>(u) ? kDcCodes : 0u) + size];
     *len = (e >> 16) + size;                                   // <= 9 + 11 or 11 + 11 bits
     return (((e & 0xffffu) << size) | value) << (32u - *len);  // left-aligned
 }
@@ -478,19 +492,22 @@ __device__ __forceinline__ uint32_t dc_code(const uint32_t *s_dc, uint32_t u, ui
 // a branch the compiler cannot count the loads in flight and waits for all of them, the ones just requested included.  What
 // such a load returned is dropped when the value is taken (take_pack_unit).
 struct PackUnit { u32x4 rec; uint32_t prev; };
+template <bool k420 = false>
 __device__ __forceinline__ PackUnit load_pack_unit(const JpegJob &jb, uint32_t u, uint32_t u_end)
 {
     const global_u32x4 *recs = (const global_u32x4 *)jb.units;
     const uint32_t uc = min(u, u_end - 1u);                    // (u_end >= 3: a picture has at least one block)
     PackUnit p;
     p.rec = recs[uc];
-    p.prev = ((const global_u32 *)(recs + (max(uc, 3u) - 3u)))[0];
+    const uint32_t back = unit_dc_back<k420>(uc);              // (clamped, never wrapped: a first unit reads unit 0)
+    p.prev = ((const global_u32 *)(recs + (max(uc, back) - back)))[0];
     return p;
 }
+template <bool k420 = false>
 __device__ __forceinline__ PackUnit take_pack_unit(PackUnit p, uint32_t u, uint32_t u_end)
 {
     if (u >= u_end) p.rec = u32x4{0u, 0u, 0u, 0u};             // no unit: no bits
-    if (u < 3u || u >= u_end) p.prev = 0u;
+    if (u < unit_dc_back<k420>(u) || u >= u_end) p.prev = 0u;
     return p;
 }
 
@@ -506,7 +523,8 @@ constexpr uint32_t kPackDepth = FL_JPEG_PACK_DEPTH;
 // differently from the kernel this was before the option existed; as a template, <false> is that kernel instruction for instruction.
 // kOwn (jpeg_pack_kernel<true>, FLGPU_FEO_JPEG_OPTIMIZE; `opt` is unused without it): the DC code tables, the header and its length are the picture's own, from its
 // record in `opt` (where the decision fell against them the record holds Annex K's, and the file is jpeg_pack_kernel's byte for byte).
-template <bool kOwn>
+// k420 (fl_jpeg_420.hip): the unit order of FLGPU_FEO_JPEG_420 -- which code table a unit takes and where its DC predecessor sits; bx, by count MCUs.
+template <bool kOwn, bool k420 = false>
 __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *__restrict__ jobs, const uint32_t *__restrict__ arena,
                                                                  uint32_t job_base, const uint32_t *__restrict__ opt)
 {
@@ -514,7 +532,7 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
     __shared__ uint32_t s_w[kPackWaves], s_carry, s_lo, s_hi, s_dc[2u * kDcCodes];
     const JpegJob jb = jobs[job_base + blockIdx.x];
     const uint32_t tid = threadIdx.x;
-    const uint32_t nunits = jb.bx * jb.by * 3u;
+    const uint32_t nunits = jb.bx * jb.by * (k420 ? 6u : 3u);
     constexpr uint32_t T = kPackThreads;
 
     // ---- bit offset of every block: DC code size (needs the previous block) + AC size, exclusive scan -- and, in the same pass,
@@ -524,7 +542,7 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
     // the records of the first kPackDepth rounds are on their way while the window is cleared
     PackUnit ahead[kPackDepth];
 #pragma unroll
-    for (uint32_t j = 0; j < kPackDepth; ++j) ahead[j] = load_pack_unit(jb, j * T + tid, nunits);
+    for (uint32_t j = 0; j < kPackDepth; ++j) ahead[j] = load_pack_unit<k420>(jb, j * T + tid, nunits);
     for (uint32_t i = tid; i < kWinWords; i += T) s_win[i] = 0u;
     const uint32_t *own = kOwn ? opt + jb.opt_off : nullptr;
     if constexpr (kOwn) { if (tid < 2u * kDcCodes) s_dc[tid] = own[kJpegOptDcLut + tid]; }
@@ -539,14 +557,14 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
             const uint32_t u = base + tid;
             // round r + kPackDepth's records are requested before round r's scan: a round waits for a load that is already
             // under way, not for a fresh round trip behind the two barriers
-            const PackUnit next = load_pack_unit(jb, u + kPackDepth * T, nunits);
-            const PackUnit cur = take_pack_unit(ahead[j], u, nunits);
+            const PackUnit next = load_pack_unit<k420>(jb, u + kPackDepth * T, nunits);
+            const PackUnit cur = take_pack_unit<k420>(ahead[j], u, nunits);
             ahead[j] = next;
             const uint32_t m = cur.rec.x;                // (0 beyond the last unit: no bits)
             const uint32_t nw = ((m >> 16) + 31u) >> 5;
             uint32_t len = 0, dl = 0, dcw = 0;
             if (u < nunits) {
-                dcw = dc_code(s_dc, u, m, cur.prev, &dl);
+                dcw = dc_code<k420>(s_dc, u, m, cur.prev, &dl);
                 len = dl + (m >> 16);
             }
             uint32_t chunk;
@@ -599,10 +617,10 @@ __global__ __launch_bounds__(kPackThreads) void jpeg_pack_kernel(const JpegJob *
         for (uint32_t ub = u_lo; ub < u_hi; ub += T / 2u) {
             const uint32_t u = ub + (tid >> 1), j = tid & 1u;
             if (u < u_hi) {
-                const PackUnit p = take_pack_unit(load_pack_unit(jb, u, u_hi), u, u_hi);
+                const PackUnit p = take_pack_unit<k420>(load_pack_unit<k420>(jb, u, u_hi), u, u_hi);
                 const uint32_t m = p.rec.x, off = jb.unit_off[u];
                 uint32_t dl;
-                const uint32_t dcw = dc_code(s_dc, u, m, p.prev, &dl);
+                const uint32_t dcw = dc_code<k420>(s_dc, u, m, p.prev, &dl);
                 if (j == 0u) win_or(s_win, wbase, off, dcw);
                 const uint32_t nw = ((m >> 16) + 31u) >> 5;
                 // words j and j + 2 of the pair's split: lane 0 takes ac[0] and ac[2], lane 1 ac[1] (unused words are zero)

@@ -280,7 +280,7 @@ void build_webp_gamma(std::vector<uint32_t> &out)
     for (int v = 0; v <= kGammaTabSize; ++v) out.push_back((uint32_t)(int)(255. * pow(scale * v, 1. / kGamma) + .5));
 }
 
-void build_jpeg_tables(uint32_t width, uint32_t height, uint32_t quality, std::vector<uint32_t> &out)
+void build_jpeg_tables(uint32_t width, uint32_t height, uint32_t quality, bool s420, std::vector<uint32_t> &out)
 {
     std::vector<uint8_t> b;
     b.reserve(kJpegTableBlockBytes);
@@ -300,7 +300,7 @@ void build_jpeg_tables(uint32_t width, uint32_t height, uint32_t quality, std::v
     b.push_back(0xFF); b.push_back(0xD8);                                                      // SOI
     segment(0xE0, {'J', 'F', 'I', 'F', 0, 1, 2, 0, 0, 1, 0, 1, 0, 0});                         // JFIF 1.2, PixelDensity::default() = 1:1 aspect
     std::vector<uint8_t> d = {8, (uint8_t)(height >> 8), (uint8_t)height, (uint8_t)(width >> 8), (uint8_t)width, 3};
-    for (int c = 0; c < 3; ++c) { d.push_back((uint8_t)(c + 1)); d.push_back(0x11); d.push_back((uint8_t)(c ? 1 : 0)); }
+    for (int c = 0; c < 3; ++c) { d.push_back((uint8_t)(c + 1)); d.push_back(c == 0 && s420 ? 0x22 : 0x11); d.push_back((uint8_t)(c ? 1 : 0)); }
     segment(0xC0, d);                                                                          // SOF0
     for (int t = 0; t < 2; ++t) {                                                              // DQT, zig-zag order
         d.assign(1, (uint8_t)t);

@@ -71,6 +71,6 @@ void build_webp_gamma(std::vector<uint32_t> &out);
 // 624) followed by the two quality-scaled quantisation tables in natural order (64 + 64 bytes) and ceil(2^32 / 2q) of each.
 // image 0.25.6 codecs/jpeg/encoder.rs: JpegEncoder::new_with_quality (table scaling), encode_image (segment order),
 // build_jfif_header / build_frame_header / build_quantization_segment / build_huffman_segment / build_scan_header.
-void build_jpeg_tables(uint32_t width, uint32_t height, uint32_t quality, std::vector<uint32_t> &out);
+void build_jpeg_tables(uint32_t width, uint32_t height, uint32_t quality, bool s420, std::vector<uint32_t> &out); // s420 (FLGPU_FEO_JPEG_420): SOF0 says 2 x 2 for Y
 
 } // namespace fl

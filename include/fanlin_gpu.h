@@ -241,6 +241,12 @@ typedef enum flgpu_front_end {
  * pay -- and today's file byte for byte where they do not.  max_out_bytes is unchanged.  It does nothing for FLGPU_FE_JFIF444, a
  * negotiated WebP or AVIF, PNG, GIF or as_is. */
 #define FLGPU_ENCODE_JPEG_OPTIMIZE 0x80000u
+/* Not a content::Format bit: a JPEG source that stays JPEG (FLGPU_FE_JPEG, FLGPU_RESULT_JPEG_STREAM) is coded with 4:2:0 chroma
+ * subsampling on the device (FLGPU_FEO_JPEG_420): Cb and Cr at half the resolution in both directions, the standard saving of JPEG
+ * files -- about a quarter fewer bytes at quality 75, half at quality 100, for chroma detail most pictures do not show.  The pixels a
+ * decoder shows differ from the 4:4:4 file's.  Alone or with FLGPU_ENCODE_JPEG_OPTIMIZE.  It does nothing for FLGPU_FE_JFIF444, a
+ * negotiated WebP or AVIF, PNG, GIF or as_is. */
+#define FLGPU_ENCODE_JPEG_420 0x200000u
 /* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
  * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
  * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
@@ -298,6 +304,18 @@ typedef struct flgpu_params {
  * device compares header + entropy-coded bytes of both codings and writes the picture's tables only if that is strictly smaller;
  * otherwise the file is FLGPU_FE_JPEG's byte for byte.  Every other front end ignores the bit. */
 #define FLGPU_FEO_JPEG_OPTIMIZE 4u
+/* FLGPU_FEO_JPEG_420, which only FLGPU_FE_JPEG knows (FLGPU_FE_JFIF444 ignores it too): the file is a baseline JPEG with sampling
+ * factors 2x2, 1x1, 1x1.  The Y, Cb, Cr bytes of every pixel are FLGPU_FE_JPEG's; the area is out_w x out_h rounded up to multiples of
+ * 16, positions past the right or bottom edge repeating the last column or row; Cb and Cr sample (i, j) is
+ * (c[2i][2j] + c[2i][2j+1] + c[2i+1][2j] + c[2i+1][2j+1] + 2) >> 2 on those bytes, replicated edge pixels included; transform, quantiser
+ * (luma table for Y, chroma table for Cb and Cr), Annex K Huffman tables, padding, stuffing and EOI are FLGPU_FE_JPEG's; one interleaved
+ * scan of 16 x 16 MCUs in raster order, each Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr; the header is FLGPU_FE_JPEG's 623 bytes with the
+ * sampling byte of SOF0's first component 0x22.  The reference never writes 4:2:0: these bytes are the library's own rule (DESIGN.md
+ * section 4), not the crate's.  With FLGPU_FEO_JPEG_OPTIMIZE as well, the counts of this scan go through that option's unchanged rule
+ * and decision.  plane_w, plane_h are multiples of 16, chroma_w, chroma_h half of them; out_bytes = 1024 + 3 * plane_w * plane_h / 2;
+ * max_out_bytes = 1024 + 2 * 208 * 6 * (plane_w / 16) * (plane_h / 16) -- for a picture of one 8 x 8 block that is LARGER than without
+ * the bit (6 units of a 16 x 16 MCU against 3), for every picture whose sides round up the same way it is half. */
+#define FLGPU_FEO_JPEG_420 8u
 
 /* Geometry decided on the host before any pixel is touched. */
 typedef struct flgpu_plan {
@@ -309,7 +327,7 @@ typedef struct flgpu_plan {
     uint32_t letterboxed;              /* 1 if overlay onto the fill colour runs (output becomes Rgba8) */
     uint32_t place_x, place_y;         /* overlay offset */
     uint32_t out_w, out_h, out_c;      /* pixel image after letterbox/blur */
-    uint32_t plane_w, plane_h;         /* front end luma plane size */
+    uint32_t plane_w, plane_h;         /* front end luma plane size (FLGPU_FE_JPEG: the coded area, multiples of 8; of 16 with FLGPU_FEO_JPEG_420) */
     uint32_t chroma_w, chroma_h;       /* front end chroma plane size */
     uint64_t pixel_bytes;              /* out_w * out_h * out_c */
     uint64_t out_bytes;                /* bytes the call writes to dst (pixels or planes); for FLGPU_FE_JPEG a planning bound
@@ -318,7 +336,7 @@ typedef struct flgpu_plan {
                                           bound, the Rgba8 bytes 4 * out_w * out_h; for FLGPU_FE_WEBP_LOSSY a planning bound, the
                                           bytes of the FLGPU_FE_WEBP420 planes */
     uint64_t max_out_bytes;            /* FLGPU_FE_JPEG: the worst case of the format (every 8x8 block of every component at its
-                                          longest code, every byte stuffed): a dst of this capacity can never be too small, as
+                                          longest code, every byte stuffed; with FLGPU_FEO_JPEG_420 six blocks per 16x16 MCU, see there): a dst of this capacity can never be too small, as
                                           JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).
                                           FLGPU_FE_PNG: the worst case of the format, every 32 KB segment of the filtered rows
                                           as stored blocks: 63 + sum over segments of (L + 5 * ceil(L / 65535) + 5 + 12).
@@ -782,6 +800,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * it handed back as pixels (a frame above 256 colours), "gif_quantized_frames" = frames above 256 colours that
  * FLGPU_ENCODE_GIF_QUANTIZE gave a table (their files count as "gif_encoded"), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
  * "jpeg_optimized" = FLGPU_FEO_JPEG_OPTIMIZE pictures whose file went out with their own tables (not those that fell back to Annex K's);
+ * "jpeg_420" = pictures coded with FLGPU_FEO_JPEG_420 (counted on the host when their launches are enqueued);
  * "blur_wtile_launches", "blur_tile_launches", "blur_generic_launches" = the blur launches (flgpu_stats.blur_launches is their sum)
  * served by the window-tile matrix-pipe kernel, by the f32 LDS-tile kernel and by the generic two passes.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB

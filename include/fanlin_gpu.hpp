@@ -110,6 +110,8 @@ public:
     // a JPEG that stays JPEG is coded with Huffman tables from the picture's own symbol counts (FLGPU_FEO_JPEG_OPTIMIZE): the same
     // pixels in a smaller file, today's file where the tables do not pay
     void encode_jpeg_optimize() { flags_ |= FLGPU_ENCODE_JPEG_OPTIMIZE; }
+    // a JPEG that stays JPEG is coded with 4:2:0 chroma subsampling (FLGPU_FEO_JPEG_420): smaller files, other pixels; alone or with the above
+    void encode_jpeg_420() { flags_ |= FLGPU_ENCODE_JPEG_420; }
     uint32_t flags() const { return flags_; }
 
 private:
