@@ -48,6 +48,8 @@ ENCODE_WEBP_LOSSY_ALPHA = 0x20000  # accept_flags bit: with ENCODE_WEBP_LOSSY, a
 ENCODE_WEBP_LOSSY_SEGMENTS = 0x40000  # accept_flags bit: with ENCODE_WEBP_LOSSY, segment-adaptive quantisers -- up to four classes of macroblocks by activity (FEO_SEGMENTS); alone, or without it, nothing
 ENCODE_JPEG_OPTIMIZE = 0x80000  # accept_flags bit: a JPEG that stays JPEG is coded with Huffman tables from the picture's own symbol counts (FEO_JPEG_OPTIMIZE); never a larger file, nothing else changes
 ENCODE_JPEG_420 = 0x200000  # accept_flags bit: a JPEG that stays JPEG is coded with 4:2:0 chroma subsampling (FEO_JPEG_420); alone or with ENCODE_JPEG_OPTIMIZE
+ENCODE_JPEG_PROGRESSIVE = 0x400000  # accept_flags bit: a JPEG that stays JPEG is written as a progressive file of five scans (FEO_JPEG_PROGRESSIVE); the same file with ENCODE_JPEG_OPTIMIZE, ignored beside ENCODE_JPEG_420
+FEO_JPEG_PROGRESSIVE = 16  # the `options` byte, FE_JPEG only: see ENCODE_JPEG_PROGRESSIVE
 FEO_JPEG_420 = 8  # the `options` byte, FE_JPEG only: see ENCODE_JPEG_420
 FEO_JPEG_OPTIMIZE = 4  # flgpu_params.reserved[0] (the header's `options` byte), FE_JPEG only: see ENCODE_JPEG_OPTIMIZE
 FEO_SEGMENTS = 2  # flgpu_params.reserved[0] (the header's `options` byte), the lossy WebP front ends only: see ENCODE_WEBP_LOSSY_SEGMENTS
@@ -175,7 +177,7 @@ EXPORTED_SYMBOLS = (
     "flgpu_png_info_of", "flgpu_decode_png", "flgpu_process_png", "flgpu_process_png_plan", "flgpu_debug_png_scanlines",
     "flgpu_png_info_of_flags", "flgpu_decode_png_flags", "flgpu_debug_png_scanlines_flags", "flgpu_debug_png_inflate_device", "flgpu_debug_png_inflate_model",
     "flgpu_webp_info_of", "flgpu_decode_webp", "flgpu_process_webp", "flgpu_process_webp_plan", "flgpu_debug_webp_residuals",
-    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs", "flgpu_debug_jpeg_optimize_tables",
+    "flgpu_vp8_info_of", "flgpu_decode_webp_lossy", "flgpu_debug_vp8_planes", "flgpu_debug_vp8_blob", "flgpu_debug_vp8_filter_costs", "flgpu_debug_jpeg_optimize_tables", "flgpu_debug_jpeg_progressive_scans",
     "flgpu_gif_info_of", "flgpu_decode_gif", "flgpu_process_gif", "flgpu_process_gif_plan", "flgpu_debug_gif_blob", "flgpu_host_alloc", "flgpu_host_free", "flgpu_ycck_to_cmyk",
     "flgpu_set_cmyk_profile", "flgpu_cmyk_bake_available", "flgpu_set_cmyk_clut", "flgpu_get_cmyk_clut",
     "flgpu_cmyk_to_rgb", "flgpu_cmyk_to_rgb_device", "flgpu_export_tables", "flgpu_copy_tables",
@@ -446,7 +448,7 @@ CMYK_GRID, CMYK_INPUT_YCCK = 17, 1
 
 def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 32), crop=False, blur_sigma=0.0,
                 grayscale=False, inverse=False, quality=75, front_end=FE_NONE, orientation=1, filter=FILTER_LANCZOS3,
-                alpha_vp8l=False, segments=False, jpeg_optimize=False, jpeg_420=False) -> flgpu_params:
+                alpha_vp8l=False, segments=False, jpeg_optimize=False, jpeg_420=False, jpeg_progressive=False) -> flgpu_params:
     p = flgpu_params()
     p.has_dims = 1 if (w is not None and h is not None) else 0
     p.w, p.h = (w or 0), (h or 0)
@@ -458,7 +460,7 @@ def make_params(w: Optional[int] = None, h: Optional[int] = None, fill=(32, 32, 
     p.orientation = orientation
     p.filter = filter
     p.reserved[0] = ((FEO_ALPHA_VP8L if alpha_vp8l else 0) | (FEO_SEGMENTS if segments else 0) | (FEO_JPEG_OPTIMIZE if jpeg_optimize else 0)
-                     | (FEO_JPEG_420 if jpeg_420 else 0))  # the options byte
+                     | (FEO_JPEG_420 if jpeg_420 else 0) | (FEO_JPEG_PROGRESSIVE if jpeg_progressive else 0))  # the options byte
     return p
 
 
@@ -585,6 +587,24 @@ def debug_jpeg_optimize_tables(counts, fallback: bool = False) -> dict:
     lib.flgpu_debug_jpeg_optimize_tables.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     _check(lib.flgpu_debug_jpeg_optimize_tables(cnt.ctypes.data, int(bool(fallback)), luts.ctypes.data, dht.ctypes.data, C.byref(n), C.byref(on)))
     return dict(luts=luts, dht=dht[:n.value].tobytes(), optimized=bool(on.value))
+
+
+def debug_jpeg_progressive_scans(coef, prefix: bytes) -> dict:
+    """flgpu_debug_jpeg_progressive_scans: FEO_JPEG_PROGRESSIVE on the host in plain loops (the rules the device runs) for the quantised
+    coefficients coef[3 * blocks][64] (unit = 3 * block + component, zig-zag) and the first 177 bytes of FE_JPEG's header ->
+    dict(counts = uint32[6][256] in file order (DC luma, DC chroma, the AC tables of scans 2-5), file = the progressive file)."""
+    lib = load_library()
+    cf = np.ascontiguousarray(coef, dtype=np.int16).reshape(-1, 64)
+    assert len(cf) % 3 == 0 and len(prefix) >= 177
+    head = np.frombuffer(bytes(prefix[:177]), np.uint8)
+    counts, n = np.zeros((6, 256), np.uint32), C.c_uint64()
+    lib.flgpu_debug_jpeg_progressive_scans.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    rc = lib.flgpu_debug_jpeg_progressive_scans(cf.ctypes.data, len(cf) // 3, head.ctypes.data, counts.ctypes.data, None, 0, C.byref(n))
+    if rc != ERR_BUFFER_TOO_SMALL:
+        _check(rc)
+    out = np.zeros(n.value, np.uint8)
+    _check(lib.flgpu_debug_jpeg_progressive_scans(cf.ctypes.data, len(cf) // 3, head.ctypes.data, counts.ctypes.data, out.ctypes.data, out.size, C.byref(n)))
+    return dict(counts=counts, file=out[:n.value].tobytes())
 
 
 def webp_info(data: bytes) -> dict:

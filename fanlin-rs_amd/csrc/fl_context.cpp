@@ -670,7 +670,7 @@ int flgpu_debug_get(flgpu_ctx *c, const char *key, int64_t *value)
         {"png_device_inflates", &flgpu_ctx::png_device_inflates}, {"png_inflate_retries", &flgpu_ctx::png_inflate_retries},
         {"webp_sources", &flgpu_ctx::webp_sources}, {"webp_file_bytes", &flgpu_ctx::webp_file_bytes}, {"webp_upload_bytes", &flgpu_ctx::webp_upload_bytes},
         {"webp_predict_ns", &flgpu_ctx::webp_predict_ns}, {"webp_pointwise_ns", &flgpu_ctx::webp_pointwise_ns}, {"webp_lossy_ns", &flgpu_ctx::webp_lossy_ns},
-        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments}, {"jpeg_optimized", &flgpu_ctx::jpeg_optimized}, {"jpeg_420", &flgpu_ctx::jpeg_420},
+        {"webp_alpha_vp8l", &flgpu_ctx::webp_alpha_vp8l}, {"webp_lossy_segments", &flgpu_ctx::webp_lossy_segments}, {"jpeg_optimized", &flgpu_ctx::jpeg_optimized}, {"jpeg_420", &flgpu_ctx::jpeg_420}, {"jpeg_progressive", &flgpu_ctx::jpeg_progressive},
         {"vp8_sources", &flgpu_ctx::vp8_sources}, {"vp8_file_bytes", &flgpu_ctx::vp8_file_bytes}, {"vp8_upload_bytes", &flgpu_ctx::vp8_upload_bytes},
         {"vp8_decode_ns", &flgpu_ctx::vp8_decode_ns},
         {"gif_sources", &flgpu_ctx::gif_sources}, {"gif_frames", &flgpu_ctx::gif_frames}, {"gif_file_bytes", &flgpu_ctx::gif_file_bytes},

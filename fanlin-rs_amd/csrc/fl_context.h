@@ -229,6 +229,7 @@ struct flgpu_ctx {
     fl::PinnedBuf h_vp8jobs;
     uint64_t vp8_sources = 0, vp8_file_bytes = 0, vp8_upload_bytes = 0, vp8_decode_ns = 0;
     uint64_t jpeg_420 = 0;                               // JPEG pictures coded with FLGPU_FEO_JPEG_420 (counted when their launches are enqueued)
+    uint64_t jpeg_progressive = 0;                       // JPEG pictures coded with FLGPU_FEO_JPEG_PROGRESSIVE (counted when their launches are enqueued)
     uint64_t jpeg_optimized = 0;                         // JPEG pictures whose file went out with their own Huffman tables (FLGPU_FEO_JPEG_OPTIMIZE; from the result words)
     uint64_t webp_lossy_segments = 0;                    // lossy WebP pictures whose frame went out segmented (FLGPU_FEO_SEGMENTS; from the result words)
     uint64_t webp_alpha_vp8l = 0;                        // lossy WebP pictures whose ALPH chunk went out as a VP8L stream (FLGPU_FEO_ALPHA_VP8L; from the result words)

@@ -4,6 +4,7 @@
 
 #include "fl_context.h"
 #include "fl_jpeg_opt_core.h"
+#include "fl_jpeg_prog_core.h"
 
 namespace fl {
 
@@ -30,6 +31,8 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan)
         // FLGPU_ERR_BUFFER_TOO_SMALL only if the finished stream really exceeds the caller's dst->capacity
         plan.out_bytes += 1024ull;
         plan.max_out_bytes = 1024ull + 2ull * kJpegMaxUnitBytes * 3ull * (plan.plane_w / 8u) * (plan.plane_h / 8u);
+        // FLGPU_FEO_JPEG_PROGRESSIVE: five headers and five padded scans, a longer DC code and a run code per scan a unit is in (see flgpu_plan)
+        if (jpeg_progressive(p)) plan.max_out_bytes = kJpegProgFixedBytes + 2ull * kJpegProgMaxUnitBytes * 3ull * (plan.plane_w / 8u) * (plan.plane_h / 8u);
         break;
     case FLGPU_FE_PNG: // the filtered rows; every segment falls back to stored blocks rather than grow (fl_png.h)
         plan.out_bytes = png_filtered_bytes(plan.out_w, plan.out_h, plan.out_c);
@@ -62,10 +65,12 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan)
 namespace {
 
 // The scratch one picture needs, appended to s, and the limits flgpu_plan_output does not hold a single picture against.
-int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize, bool s420)
+int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize, bool s420, bool progressive)
 {
     if (pl.out_w > 65535u || pl.out_h > 65535u) return FLGPU_ERR_UNSUPPORTED; // SOF0 carries u16 dimensions (the plan of such a picture is valid: refused when it is run)
-    const size_t units = s420 ? (size_t)(pl.plane_w / 16u) * (pl.plane_h / 16u) * 6u : (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u) * 3u;
+    // FLGPU_FEO_JPEG_PROGRESSIVE: four records per block, one per AC scan, where the others hold three units
+    const size_t blocks = (size_t)(pl.plane_w / 8u) * (pl.plane_h / 8u);
+    const size_t units = s420 ? (size_t)(pl.plane_w / 16u) * (pl.plane_h / 16u) * 6u : blocks * (progressive ? 4u : 3u);
     if (units * kJpegMaxUnitBytes * 8 >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED; // bit offsets are 32-bit
     s.jpeg_coef += align_up(units * sizeof(JpegUnit), 256);
     s.jpeg_off += align_up((units + 1) * sizeof(uint32_t), 256);
@@ -74,6 +79,11 @@ int jpeg_scratch(const flgpu_plan &pl, EncodeScratch &s, bool optimize, bool s42
         if ((s.jpeg_opt + jpeg_opt_bytes(units)) / 4u >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED;
         s.jpeg_opt += jpeg_opt_bytes(units);
         s.jpeg_opt_pics++;
+    }
+    if (progressive) { // the picture's record and its counts, likewise
+        if ((s.jpeg_prog + jpeg_prog_bytes(blocks)) / 4u >= ((size_t)1 << 32)) return FLGPU_ERR_UNSUPPORTED;
+        s.jpeg_prog += jpeg_prog_bytes(blocks);
+        s.jpeg_prog_pics++;
     }
     return FLGPU_OK;
 }
@@ -146,6 +156,7 @@ void add_jpeg_job(flgpu_ctx *c, EncodeJobs &E, const EncodeInput &x, const Encod
     j.bx = x.plan->plane_w / side; j.by = x.plan->plane_h / side;
     j.tab_off = x.jpeg_tab;
     if (jpeg_optimize(*x.p)) j.opt_off = (uint32_t)(at.jpeg_opt / 4u);
+    if (jpeg_progressive(*x.p)) j.opt_off = (uint32_t)(at.jpeg_prog / 4u);
     E.jjobs_of[v]++;
     E.jpeg_max_of[v] = std::max(E.jpeg_max_of[v], j.bx * j.by);
 }
@@ -235,7 +246,7 @@ void add_planes_launch(EncodeJobs &E, uint32_t kind, const std::vector<const Enc
 int encode_plan_picture(const flgpu_params &p, const flgpu_plan &plan, EncodeScratch &s)
 {
     int rc = FLGPU_OK;
-    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s, jpeg_optimize(p), jpeg_420(p));
+    if (p.front_end == FLGPU_FE_JPEG) rc = jpeg_scratch(plan, s, jpeg_optimize(p) && !jpeg_progressive(p), jpeg_420(p), jpeg_progressive(p));
     if (p.front_end == FLGPU_FE_PNG) rc = png_scratch(plan, s);
     if (p.front_end == FLGPU_FE_WEBP_LOSSLESS) rc = webpll_scratch(plan, s);
     if (const auto v = vp8_variant_of(p.front_end)) vp8_scratch(plan, s, *v, vp8_segments(p, plan.out_w, plan.out_h)); // (its limits: encode_plan_bytes)
@@ -251,6 +262,8 @@ int encode_reserve(flgpu_ctx *c, const EncodeScratch &sz)
     FL_HIP(c, b.jpeg_raw.reserve(sz.jpeg_raw), "JPEG bit-stream scratch");
     FL_HIP(c, b.jpeg_opt.reserve(sz.jpeg_opt), "JPEG per-picture table scratch");
     FL_HIP(c, b.jpeg_hist.reserve((size_t)sz.jpeg_opt_pics * kJpegOptHistWords * sizeof(uint32_t)), "JPEG symbol counts");
+    FL_HIP(c, b.jpeg_prog.reserve(sz.jpeg_prog), "progressive JPEG per-picture scratch");
+    FL_HIP(c, b.jpeg_prog_hist.reserve((size_t)sz.jpeg_prog_pics * kJpegProgHistWords * sizeof(uint32_t)), "progressive JPEG symbol counts");
     FL_HIP(c, b.png_filt.reserve(sz.png_filt), "PNG filtered-row scratch");
     FL_HIP(c, b.png_chunks.reserve((size_t)sz.png_segs * kPngSegOutBytes), "PNG chunk scratch");
     FL_HIP(c, b.png_syms.reserve((size_t)sz.png_segs * kPngSegBytes * sizeof(uint16_t)), "PNG symbol scratch");
@@ -274,7 +287,7 @@ int encode_reserve(flgpu_ctx *c, const EncodeScratch &sz)
 
 void encode_build_jobs(flgpu_ctx *c, const std::vector<EncodeInput> &in, EncodeJobs &E)
 {
-    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end; FLGPU_FE_JPEG: its four variants in jpeg_variant's order
+    std::map<uint32_t, std::vector<const EncodeInput *>> groups; // by front end; FLGPU_FE_JPEG: its five variants in jpeg_variant's order
     for (const EncodeInput &x : in) groups[kJpegVariants * x.p->front_end + jpeg_variant(*x.p)].push_back(&x);
     // E.at runs over ALL the jobs in this order: the lossy WebP groups share the lossy WebP scratch, in the families' order, and the
     // lossless WebP files share the lossless coder's with those groups' alpha planes; no other two formats touch the same total
@@ -310,7 +323,7 @@ void EncodeJobs::point_results(uint32_t *status)
 
 void EncodeBuffers::release()
 {
-    for (DeviceBuf *b : {&jpeg_coef, &jpeg_off, &jpeg_raw, &jpeg_opt, &jpeg_hist, &png_filt, &png_chunks, &png_syms, &png_recs, &webpll_res, &webpll_tok, &webpll_tiles, &webpll_pic,
+    for (DeviceBuf *b : {&jpeg_coef, &jpeg_off, &jpeg_raw, &jpeg_opt, &jpeg_hist, &jpeg_prog, &jpeg_prog_hist, &png_filt, &png_chunks, &png_syms, &png_recs, &webpll_res, &webpll_tok, &webpll_tiles, &webpll_pic,
                          &webpll_stream, &vp8_planes, &vp8_rec, &vp8_lev, &vp8_info, &vp8_sizes, &vp8_bm, &vp8_tab, &vp8_lf, &vp8_seg}) b->release();
 }
 
@@ -336,7 +349,10 @@ int encode_enqueue(flgpu_ctx *c, const EncodeJobs &E, hipStream_t st)
         if (v == 2u) FL_HIP(c, launch_jpeg_encode_420(E.d.jjobs, c->d_arena, jbase, n, most, st), "JPEG 4:2:0 encode");
         if (v == 3u) FL_HIP(c, launch_jpeg_encode_420_optimized(E.d.jjobs, c->d_arena, jbase, n, most, jopt, jhist + (size_t)E.jjobs_of[1] * kJpegOptHistWords, fallback, st),
                             "JPEG 4:2:0 encode with per-picture tables");
-        if (v >= 2u) c->jpeg_420 += n;
+        if (v == kJpegVariantProgressive) FL_HIP(c, launch_jpeg_encode_progressive(E.d.jjobs, c->d_arena, jbase, n, most, static_cast<uint32_t *>(c->enc.jpeg_prog.p),
+                                                                                  static_cast<uint32_t *>(c->enc.jpeg_prog_hist.p), st), "progressive JPEG encode");
+        if (v == 2u || v == 3u) c->jpeg_420 += n;
+        if (v == kJpegVariantProgressive) c->jpeg_progressive += n;
         c->stats.frontend_launches++;
     }
     if (!E.pjobs.empty()) {
@@ -385,6 +401,15 @@ try {
     if (on < 0) return FLGPU_ERR_INVALID_ARG;
     *optimized = on;
     return FLGPU_OK;
+} FL_ABI_CATCH
+
+// FLGPU_FEO_JPEG_PROGRESSIVE in plain loops (jpeg_prog_encode_serial): what the kernels of fl_jpeg_prog.hip compute over a batch.
+extern "C" int flgpu_debug_jpeg_progressive_scans(const int16_t *coef, uint32_t nblocks, const uint8_t *prefix, uint32_t *counts, uint8_t *file, uint64_t capacity,
+                                                  uint64_t *file_bytes)
+try {
+    if (!coef || !nblocks || !prefix || !counts || !file_bytes || (!file && capacity)) return FLGPU_ERR_INVALID_ARG;
+    if (fl::jpeg_prog_encode_serial(coef, nblocks, prefix, counts, file, capacity, file_bytes)) return FLGPU_ERR_INVALID_ARG;
+    return *file_bytes <= capacity ? FLGPU_OK : FLGPU_ERR_BUFFER_TOO_SMALL;
 } FL_ABI_CATCH
 
 // One picture through the ordinary launch sequence of a loop-filtered lossy WebP front end; then the cost words its filter launch

@@ -46,9 +46,12 @@ constexpr uint32_t clamp_quality(uint32_t q) { return q < 1u ? 1u : q > 100u ? 1
 // limits but not the segmented partition 0's -- then it is coded without it (no record, no class map, the unsegmented worst case)
 inline bool jpeg_optimize(const flgpu_params &p) { return p.front_end == FLGPU_FE_JPEG && (p.options & FLGPU_FEO_JPEG_OPTIMIZE); } // only FLGPU_FE_JPEG knows the bit
 inline bool jpeg_420(const flgpu_params &p) { return p.front_end == FLGPU_FE_JPEG && (p.options & FLGPU_FEO_JPEG_420); }           // likewise
-// The four launch sequences of FLGPU_FE_JPEG, in the order of their jobs: plain, _OPTIMIZE, 4:2:0, 4:2:0 + _OPTIMIZE
-constexpr uint32_t kJpegVariants = 4;
-inline uint32_t jpeg_variant(const flgpu_params &p) { return (jpeg_optimize(p) ? 1u : 0u) + (jpeg_420(p) ? 2u : 0u); }
+// FLGPU_FEO_JPEG_PROGRESSIVE: a progressive file -- of a 4:4:4 picture; with FLGPU_FEO_JPEG_420 the bit is ignored (include/fanlin_gpu.h)
+inline bool jpeg_progressive(const flgpu_params &p) { return p.front_end == FLGPU_FE_JPEG && (p.options & FLGPU_FEO_JPEG_PROGRESSIVE) && !jpeg_420(p); }
+// The five launch sequences of FLGPU_FE_JPEG, in the order of their jobs: plain, _OPTIMIZE, 4:2:0, 4:2:0 + _OPTIMIZE, progressive
+// (whose tables are the picture's own with or without _OPTIMIZE)
+constexpr uint32_t kJpegVariants = 5, kJpegVariantProgressive = 4;
+inline uint32_t jpeg_variant(const flgpu_params &p) { return jpeg_progressive(p) ? kJpegVariantProgressive : (jpeg_optimize(p) ? 1u : 0u) + (jpeg_420(p) ? 2u : 0u); }
 inline bool vp8_segments(const flgpu_params &p, uint32_t w, uint32_t h)
 {
     const std::optional<Vp8Variant> v = vp8_variant_of(p.front_end);
@@ -64,15 +67,16 @@ int encode_plan_bytes(const flgpu_params &p, flgpu_plan &plan);
 
 // Bytes (or records) of the encoders' scratch; while pictures are added, the running totals are their offsets.
 struct EncodeScratch {
-    size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, jpeg_opt = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
+    size_t jpeg_coef = 0, jpeg_off = 0, jpeg_raw = 0, jpeg_opt = 0, jpeg_prog = 0, png_filt = 0, wll_res = 0, wll_tok = 0, wll_stream = 0;
     size_t vp8_planes = 0, vp8_rec = 0, vp8_mbs = 0, vp8_i4_mbs = 0, vp8_lf = 0, vp8_seg = 0;
-    uint32_t jpeg_opt_pics = 0, png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
+    uint32_t jpeg_opt_pics = 0, jpeg_prog_pics = 0, png_rows = 0, png_segs = 0, wll_tiles = 0, wll_pics = 0, vp8_pics = 0, vp8_ap_pics = 0;
 };
 
 // The encoders' scratch on the device, which lives as long as the context.
 struct EncodeBuffers {
     DeviceBuf jpeg_coef, jpeg_off, jpeg_raw; // fl_jpeg.hip: unit records, bit offsets, AC bits past a record
     DeviceBuf jpeg_opt, jpeg_hist;           // fl_jpeg_opt.hip, pictures with FLGPU_FEO_JPEG_OPTIMIZE only: their records (tables, header, DC terms), their AC symbol counts
+    DeviceBuf jpeg_prog, jpeg_prog_hist;     // fl_jpeg_prog.hip, pictures with FLGPU_FEO_JPEG_PROGRESSIVE only: their records (tables, headers, DC terms, runs), their AC scans' symbol counts
     DeviceBuf png_filt, png_chunks, png_syms, png_recs; // fl_png.hip: filtered rows, segment chunks, symbols, records
     DeviceBuf webpll_res, webpll_tok, webpll_tiles, webpll_pic, webpll_stream; // fl_webpll.hip: residuals, tokens, tile records, per-picture words, bit streams
     DeviceBuf vp8_planes, vp8_rec, vp8_lev, vp8_info, vp8_sizes, vp8_bm, vp8_tab, vp8_lf, vp8_seg; // fl_vp8.hip: the front end's planes, reconstruction, levels, macroblock records, partition sizes, the I4 variants' sub-block modes, the adaptive-probability variants' tables, the loop-filtered variants' cost words and working copies, the segmented pictures' records and class maps
@@ -102,9 +106,9 @@ struct EncodeJobs {
     uint32_t vjobs_fam[kVp8Families] = {0, 0, 0, 0, 0, 0, 0, 0}; // how many of them each family has; the families follow one another (vp8_family)
     uint32_t vjobs_seg = 0; // how many of them are coded with FLGPU_FEO_SEGMENTS (vp8_segments): vp8_segment_kernel launches iff any is
     std::vector<size_t> fjob_img, jjob_img, pjob_img, wjob_img, ajob_img, vjob_img; // image of every job
-    // jjobs holds the four variants one after the other (jpeg_variant): how many jobs each has, and the largest bx * by among them
+    // jjobs holds the five variants one after the other (jpeg_variant): how many jobs each has, and the largest bx * by among them
     // (blocks; MCUs for the two 4:2:0 variants).  Each variant has a launch sequence of its own.
-    uint32_t jjobs_of[kJpegVariants] = {0, 0, 0, 0}, jpeg_max_of[kJpegVariants] = {0, 0, 0, 0};
+    uint32_t jjobs_of[kJpegVariants] = {0, 0, 0, 0, 0}, jpeg_max_of[kJpegVariants] = {0, 0, 0, 0, 0};
     std::vector<FeLaunch> fe_launches;
     EncodeScratch at; // the scratch totals of the jobs so far, i.e. the next job's offsets; once all are built, the batch's totals
     struct { const FrontendJob *fjobs; const JpegJob *jjobs; const PngJob *pjobs; const WebpJob *wjobs; const WebpJob *ajobs; const Vp8Job *vjobs; } d{}; // the arrays' device copies
@@ -122,7 +126,7 @@ struct EncodeJobs {
 // Planning: the scratch picture (p, plan) needs, appended to s, and the limits that hold for the batch's totals or are not flgpu_plan_output's.
 int encode_plan_picture(const flgpu_params &p, const flgpu_plan &plan, EncodeScratch &s);
 int encode_reserve(flgpu_ctx *c, const EncodeScratch &sizes);
-// The jobs of the pictures `in` (in batch order): grouped by front end in ascending code (FLGPU_FE_JPEG: four groups, jpeg_variant,
+// The jobs of the pictures `in` (in batch order): grouped by front end in ascending code (FLGPU_FE_JPEG: five groups, jpeg_variant,
 // the plain pictures first), batch order inside a group; a job's offsets
 // into the scratch are the totals of the jobs before it.  And the planes launches, one per planar kind and one per lossy WebP group.
 void encode_build_jobs(flgpu_ctx *c, const std::vector<EncodeInput> &in, EncodeJobs &E);

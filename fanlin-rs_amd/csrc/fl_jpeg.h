@@ -28,6 +28,7 @@ struct alignas(16) JpegJob {
     uint32_t bx, by;      // blocks per row / column (FLGPU_FEO_JPEG_420: MCUs of 16 x 16)
     uint32_t tab_off;     // arena word offset of the header + quantisation tables block (fl_jpeg_tables.h)
     uint32_t opt_off;     // FLGPU_FEO_JPEG_OPTIMIZE only (else 0): word offset of the picture's record in the batch's optimise scratch
+                          // (FLGPU_FEO_JPEG_PROGRESSIVE: in the batch's progressive scratch)
     uint32_t dst_cap;     // bytes available at dst
 };
 
@@ -56,5 +57,22 @@ hipError_t launch_jpeg_encode_optimized(const JpegJob *jobs, const uint32_t *are
 hipError_t launch_jpeg_encode_420(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_mcus, hipStream_t st);
 hipError_t launch_jpeg_encode_420_optimized(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_mcus,
                                             uint32_t *opt, uint32_t *hist, bool fallback, hipStream_t st);
+
+// FLGPU_FEO_JPEG_PROGRESSIVE (fl_jpeg_prog.hip, fl_jpeg_prog_core.h): a progressive file of five scans.  A picture's jobs' units,
+// unit_off and acbits hold four records per block, record = AC scan * blocks + block (the DC scan reads the DC terms), and opt_off names
+// its record in the progressive scratch, in words: the five scans' header lengths, the two DC and the four AC code tables
+// (length << 16 | code), the scans' header bytes (scan 0: prefix with SOF2, two DHT, SOS; scans 1-4: DHT, SOS), and behind them the
+// quantised DC terms (2 bytes per unit) and one 16-bit word per (AC scan, block): the band's flags from the statistics launch, then
+// the length of the end-of-band run the block codes (0: none).
+constexpr uint32_t kJpegProgHdrLen = 0, kJpegProgDcLut = 8, kJpegProgAcLut = 32, kJpegProgHeader = 1056, kJpegProgDcHeaderWords = 80,
+                   kJpegProgAcHeaderWords = 72, kJpegProgHeadWords = 1424;
+static_assert(kJpegProgHeader + kJpegProgDcHeaderWords + 4u * kJpegProgAcHeaderWords == kJpegProgHeadWords, "the record's head");
+constexpr uint32_t kJpegProgHistWords = 1024; // per picture, in a scratch of its own (cleared per batch): the four AC scans' symbol counts
+constexpr size_t jpeg_prog_bytes(size_t blocks) { return (kJpegProgHeadWords * 4u + blocks * (3u * 2u + 4u * 2u) + 255u) & ~(size_t)255u; }
+// max_blocks: the largest bx * by of the jobs; hist: njobs x kJpegProgHistWords words.  Launches: clear the counts, statistics (the
+// transform phase, band symbols counted in LDS, DC terms and band flags), tables (one workgroup per picture: the runs, six tables,
+// five headers), coding (the transform again, one record per AC scan and block), packing (one workgroup per picture, scan after scan).
+hipError_t launch_jpeg_encode_progressive(const JpegJob *jobs, const uint32_t *arena, uint32_t job_base, uint32_t njobs, uint32_t max_blocks,
+                                          uint32_t *prog, uint32_t *hist, hipStream_t st);
 
 } // namespace fl

@@ -213,6 +213,8 @@ try {
     if (p->front_end == FLGPU_FE_JPEG && (accept_flags & FLGPU_ENCODE_JPEG_OPTIMIZE)) p->options |= FLGPU_FEO_JPEG_OPTIMIZE;
     /* 4:2:0 chroma subsampling: likewise */
     if (p->front_end == FLGPU_FE_JPEG && (accept_flags & FLGPU_ENCODE_JPEG_420)) p->options |= FLGPU_FEO_JPEG_420;
+    /* a progressive file: likewise (the encoder ignores it beside FLGPU_FEO_JPEG_420) */
+    if (p->front_end == FLGPU_FE_JPEG && (accept_flags & FLGPU_ENCODE_JPEG_PROGRESSIVE)) p->options |= FLGPU_FEO_JPEG_PROGRESSIVE;
     /* the lossy WebP arm with both bits: whichever lossy front end the caller (or plan_request below) puts in place of the planes
        compresses the alpha plane; every other front end ignores the option */
     if (p->front_end == FLGPU_FE_WEBP420 && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY) && (accept_flags & FLGPU_ENCODE_WEBP_LOSSY_ALPHA))

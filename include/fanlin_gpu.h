@@ -247,6 +247,15 @@ typedef enum flgpu_front_end {
  * decoder shows differ from the 4:4:4 file's.  Alone or with FLGPU_ENCODE_JPEG_OPTIMIZE.  It does nothing for FLGPU_FE_JFIF444, a
  * negotiated WebP or AVIF, PNG, GIF or as_is. */
 #define FLGPU_ENCODE_JPEG_420 0x200000u
+/* Not a content::Format bit: a JPEG source that stays JPEG (FLGPU_FE_JPEG, FLGPU_RESULT_JPEG_STREAM) is written as a progressive
+ * file on the device (FLGPU_FEO_JPEG_PROGRESSIVE): the same quantised coefficients in five scans by spectral selection, so every
+ * decoder ends at the pixels of the baseline file and shows the whole picture coarsely after the first few hundred bytes.  At
+ * ordinary sizes it is also the smallest of the three codings (about 3 % below FLGPU_ENCODE_JPEG_OPTIMIZE on a 300 x 200
+ * photograph); a tiny picture grows by its four extra headers, and there is no never-larger fall-back.  With
+ * FLGPU_ENCODE_JPEG_OPTIMIZE as well the file is the same.  With FLGPU_ENCODE_JPEG_420 the bit is ignored: the 4:2:0 file stays
+ * baseline.  max_out_bytes grows (see flgpu_plan).  It does nothing for FLGPU_FE_JFIF444, a negotiated WebP or AVIF, PNG, GIF or
+ * as_is. */
+#define FLGPU_ENCODE_JPEG_PROGRESSIVE 0x400000u
 /* Not a content::Format bit: together with FLGPU_ENCODE_GIF, a frame above 256 colours is quantised on the device to a local table
  * of at most 256 entries and the file is finished (FLGPU_RESULT_GIF_STREAM) instead of returning as pixels.  The quantiser is the
  * library's own integer rule (a variance-ordered median cut), not the reference's NeuQuant: the file is valid and pinned
@@ -316,6 +325,19 @@ typedef struct flgpu_params {
  * max_out_bytes = 1024 + 2 * 208 * 6 * (plane_w / 16) * (plane_h / 16) -- for a picture of one 8 x 8 block that is LARGER than without
  * the bit (6 units of a 16 x 16 MCU against 3), for every picture whose sides round up the same way it is half. */
 #define FLGPU_FEO_JPEG_420 8u
+/* FLGPU_FEO_JPEG_PROGRESSIVE, which only FLGPU_FE_JPEG knows (FLGPU_FE_JFIF444 ignores it too): the file is a progressive JPEG
+ * (SOF2), 4:4:4, of FLGPU_FE_JPEG's quantised coefficients, by spectral selection only (Ah = Al = 0).  FLGPU_FE_JPEG's first 177
+ * bytes (SOI, APP0, SOF0, DQT, DQT) with byte 21 0xC2; scan 1: DC of Y, Cb, Cr interleaved behind DHT(class 0, destination 0) from
+ * the Y differences, DHT(0, 1) from Cb + Cr and an SOS of (1, 0x00) (2, 0x10) (3, 0x10), Ss = Se = 0; scans 2-5: Y 1-5, Cb 1-63,
+ * Cr 1-63, Y 6-63, one component each, blocks in raster order, each behind a DHT(1, 0) from the scan's own counts and its SOS; an AC
+ * scan is coded as T.81 G.1.2.2 says (end-of-band runs across blocks, at most 32,767 blocks each, no restarts); every table is
+ * FLGPU_FEO_JPEG_OPTIMIZE's rule; every scan ends as FLGPU_FE_JPEG's (ones to the byte edge, 0xFF stuffed); EOI.  The reference never
+ * writes SOF2: these bytes are the library's own rule.  There is no never-larger fall-back.  With
+ * FLGPU_FEO_JPEG_OPTIMIZE as well the file is the same, byte for byte.  With FLGPU_FEO_JPEG_420 this bit is ignored and the file is
+ * the 4:2:0 one.  max_out_bytes = 1104 + 2 * 216 * 3 * (plane_w / 8) * (plane_h / 8): five headers of at most 1,085 bytes together,
+ * EOI, a padding byte per scan, and per unit a DC code of 16 + 11 bits, 63 coefficients of 16 + 10 and a run code of 16 + 14 per AC
+ * scan it is in (two for Y) -- 1,725 bits in 216 bytes --, every byte stuffed. */
+#define FLGPU_FEO_JPEG_PROGRESSIVE 16u
 
 /* Geometry decided on the host before any pixel is touched. */
 typedef struct flgpu_plan {
@@ -336,7 +358,7 @@ typedef struct flgpu_plan {
                                           bound, the Rgba8 bytes 4 * out_w * out_h; for FLGPU_FE_WEBP_LOSSY a planning bound, the
                                           bytes of the FLGPU_FE_WEBP420 planes */
     uint64_t max_out_bytes;            /* FLGPU_FE_JPEG: the worst case of the format (every 8x8 block of every component at its
-                                          longest code, every byte stuffed; with FLGPU_FEO_JPEG_420 six blocks per 16x16 MCU, see there): a dst of this capacity can never be too small, as
+                                          longest code, every byte stuffed; with FLGPU_FEO_JPEG_420 six blocks per 16x16 MCU, with FLGPU_FEO_JPEG_PROGRESSIVE 216 bytes per unit behind 1104, see there): a dst of this capacity can never be too small, as
                                           JpegEncoder::encode_image into a Vec never fails (src/handler.rs:274-278).
                                           FLGPU_FE_PNG: the worst case of the format, every 32 KB segment of the filtered rows
                                           as stored blocks: 63 + sum over segments of (L + 5 * ceil(L / 65535) + 5 + 12).
@@ -801,6 +823,7 @@ int flgpu_reset_stats(flgpu_ctx *ctx);
  * FLGPU_ENCODE_GIF_QUANTIZE gave a table (their files count as "gif_encoded"), and with flgpu_config.profile "gif_encode_ns" = the encode kernels' HIP-event time;
  * "jpeg_optimized" = FLGPU_FEO_JPEG_OPTIMIZE pictures whose file went out with their own tables (not those that fell back to Annex K's);
  * "jpeg_420" = pictures coded with FLGPU_FEO_JPEG_420 (counted on the host when their launches are enqueued);
+ * "jpeg_progressive" = pictures coded with FLGPU_FEO_JPEG_PROGRESSIVE (likewise);
  * "blur_wtile_launches", "blur_tile_launches", "blur_generic_launches" = the blur launches (flgpu_stats.blur_launches is their sum)
  * served by the window-tile matrix-pipe kernel, by the f32 LDS-tile kernel and by the generic two passes.
  * Only "no_mfma", "force_generic", "no_wtile", "no_luma_mid", "wtile_first" and "mfma_arith" can change a result, by at most 1 LSB
@@ -872,6 +895,14 @@ int flgpu_debug_vp8_filter_costs(flgpu_ctx *ctx, const flgpu_image *src, const f
  * never-larger decision for these counts (fallback != 0: as with "jpeg_optimize_fallback"), 0 also where the segments would exceed
  * Annex K's.  Needs no device. */
 int flgpu_debug_jpeg_optimize_tables(const uint32_t *counts, int fallback, uint32_t *luts, uint8_t *dht, uint32_t *dht_bytes, int *optimized);
+
+/* FLGPU_FEO_JPEG_PROGRESSIVE alone, on the host, in plain loops (csrc/fl_jpeg_prog_core.h, the rules the kernels of fl_jpeg_prog.hip run):
+ * coef[3 * nblocks][64] = the quantised coefficients, unit = 3 * block + component, zig-zag order; prefix = the first 177 bytes of
+ * FLGPU_FE_JPEG's header.  Out: counts[6][256] = the symbol counts of the six tables in file order (DC luma, DC chroma, the AC tables
+ * of scans 2-5, end-of-band run symbols included); the file at `file` if it fits `capacity`, *file_bytes = its length either way
+ * (FLGPU_ERR_BUFFER_TOO_SMALL if it does not fit; nothing is written past capacity).  Needs no device. */
+int flgpu_debug_jpeg_progressive_scans(const int16_t *coef, uint32_t nblocks, const uint8_t *prefix, uint32_t *counts, uint8_t *file, uint64_t capacity,
+                                       uint64_t *file_bytes);
 
 /* The host half of the GIF decode front end alone (csrc/fl_gifsrc.h): the blob flgpu_process_gif uploads, all fields little-endian
  * dwords, offsets in bytes from the blob's start:

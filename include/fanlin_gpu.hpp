@@ -112,6 +112,9 @@ public:
     void encode_jpeg_optimize() { flags_ |= FLGPU_ENCODE_JPEG_OPTIMIZE; }
     // a JPEG that stays JPEG is coded with 4:2:0 chroma subsampling (FLGPU_FEO_JPEG_420): smaller files, other pixels; alone or with the above
     void encode_jpeg_420() { flags_ |= FLGPU_ENCODE_JPEG_420; }
+    // a JPEG that stays JPEG is written as a progressive file of five scans (FLGPU_FEO_JPEG_PROGRESSIVE): the baseline file's pixels, the whole picture
+    // after the first few hundred bytes; the same file with encode_jpeg_optimize(), ignored beside encode_jpeg_420()
+    void encode_jpeg_progressive() { flags_ |= FLGPU_ENCODE_JPEG_PROGRESSIVE; }
     uint32_t flags() const { return flags_; }
 
 private:

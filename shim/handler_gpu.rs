@@ -111,6 +111,8 @@ pub const ENCODE_WEBP_LOSSY_ALPHA: u32 = 0x20000; // with ENCODE_WEBP_LOSSY: the
 pub const ENCODE_WEBP_LOSSY_SEGMENTS: u32 = 0x40000; // with ENCODE_WEBP_LOSSY: segment-adaptive quantisers, up to four classes of macroblocks by activity (FEO_SEGMENTS); alone, or without it, it does nothing
 pub const ENCODE_JPEG_OPTIMIZE: u32 = 0x80000; // a JPEG that stays JPEG: Huffman tables from the picture's own symbol counts (FEO_JPEG_OPTIMIZE), never a larger file; nothing else changes
 pub const ENCODE_JPEG_420: u32 = 0x200000; // a JPEG that stays JPEG: 4:2:0 chroma subsampling (FEO_JPEG_420); smaller files, other pixels; alone or with ENCODE_JPEG_OPTIMIZE
+pub const ENCODE_JPEG_PROGRESSIVE: u32 = 0x400000; // a JPEG that stays JPEG: a progressive file of five scans (FEO_JPEG_PROGRESSIVE); the baseline file's pixels; ignored beside ENCODE_JPEG_420
+pub const FEO_JPEG_PROGRESSIVE: u8 = 16; // the options byte: honoured by FE_JPEG, ignored by every other front end
 pub const FEO_JPEG_420: u8 = 8; // the options byte: honoured by FE_JPEG, ignored by every other front end
 pub const FEO_JPEG_OPTIMIZE: u8 = 4; // flgpu_params.reserved[0], the options byte: honoured by FE_JPEG, ignored by every other front end
 pub const FEO_SEGMENTS: u8 = 2; // flgpu_params.reserved[0], the options byte: honoured by the lossy WebP front ends, ignored by every other
